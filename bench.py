@@ -9,11 +9,15 @@ pixel L1, both Adam updates) on one synthetic batch of 64 (prev_image, state, im
 fp32 accumulate, inputs resident in HBM before the timed region (BASELINE.json configs[2]).  Data-parallel over ranks
 (weak scaling: 64 images per GPU), one RCCL all-reduce of each flat gradient buffer per step.
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus
+Prints ONE JSON line (rank 0) with the driver contract fields.  A plain run sets up, warms up, times --steps steps and
+reports; the network weights and the batch are seeded, so the same arguments give the same inputs on every run.  With
+--full it also fills in
   "roofline":     in-situ HIP-event timing of the MFMA conv launches of one instrumented step: achieved
                   algorithmic TFLOP/s of the dominant kernel family vs the dense bf16 MFMA peak;
   "cpu_baseline": the CPU oracle (oracle/s2p_oracle.py, torch fp32 on the host cores) timed on a bounded sample of
                   the same workload -- a reported baseline, never the thing shipped.
+(both run after the timed steps and do not change the headline figures; without --full they are null).
+--dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -49,7 +53,38 @@ def parse():
     ap.add_argument("--serial-streams", action="store_true",
                     help="run every launch on one stream (no overlap of independent chains): the configuration in which a "
                          "kernel's own duration is measured (rocprofv3 evidence for the roofline numbers); slower end to end")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline leg and the CPU oracle baseline (each can still be "
+                         "left out with --no-roofline / --no-cpu-baseline); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 20       # elements kept of a network's flat weight buffer in --dump-outputs (a fixed, seeded sample)
+
+
+def dump_outputs(trainer, out_dir):
+    """What a caller of the timed step holds after its last step: every loss (float64 scalars), the generator's output images
+    of that step (float32 NCHW) and the updated fp32 weights of G and D -- of each network the same seeded sample of
+    DUMP_SAMPLE positions of its flat parameter buffer on every run.  About 14 MB in all at the default size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_" + k: np.asarray(float(v.detach()), dtype=np.float64) for k, v in trainer.get_latest_losses().items()}
+    arrays["generated"] = trainer.get_latest_generated().detach().float().cpu().numpy()
+    model = trainer.pix2pix_model
+    for name, net in (("netG", model.netG), ("netD", model.netD)):
+        w = net.store.master[:net.store.numel].detach().cpu()
+        if w.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(w.numel(), generator=torch.Generator().manual_seed(4321))[:DUMP_SAMPLE].sort().values
+            w = w[idx]
+        arrays[name + "_weights"] = w.numpy()
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def spade_resblk_aggregate(recs, N, HW):
@@ -260,6 +295,7 @@ def main():
                                 "--gpu_ids", str(local_rank), "--checkpoints_dir", "/tmp/s2p_bench_ckpt",
                                 "--crop_size", str(args.size)], quiet=True)
     import io, contextlib
+    torch.manual_seed(1234)         # the networks' initial weights: identical inputs from run to run (with several ranks rank 0's are broadcast)
     with contextlib.redirect_stdout(io.StringIO()):
         trainer = Pix2PixTrainer(opt)
     dp = trainer.dp
@@ -318,11 +354,15 @@ def main():
     print("[bench] timed region done: %.3f ms/step" % (elapsed / args.steps * 1e3), file=sys.stderr, flush=True)
     if not all(v == v for v in losses.values()):
         raise RuntimeError("NaN in losses: %s" % losses)
+    if args.dump_outputs and rank == 0:     # before the roofline leg, whose instrumented steps train on
+        names = dump_outputs(trainer, args.dump_outputs)
+        print("[bench] outputs of the last timed step -> %s (%d arrays)" % (args.dump_outputs, len(names)), file=sys.stderr, flush=True)
 
-    # ---- roofline leg: one instrumented eager step, events around every MFMA conv launch --------------------
+    # ---- roofline leg (--full): one instrumented eager step, events around every MFMA conv launch --------------
     roofline = None
     comm_ms = []
-    if not args.no_roofline:
+    do_roofline = args.full and not args.no_roofline
+    if do_roofline:
         # every rank runs the instrumented step (it contains the gradient all-reduces); rank 0 reports
         # three instrumented steps; a launch's time is the MEDIAN of its three samples (one sample can be lengthened by a
         # hiccup -- a single step once showed the dominant launch at 51 us against 39-42 us in every other measurement)
@@ -344,7 +384,7 @@ def main():
         for i, r in enumerate(all_recs):
             samples = [rep[i]["events"][0].elapsed_time(rep[i]["events"][1]) for rep in (reps if same else reps[:1])]
             r["ms"] = sorted(samples)[len(samples) // 2]
-    if not args.no_roofline and rank == 0:
+    if do_roofline and rank == 0:
         recs = [r for r in all_recs if r["kind"] in ("fwd", "dgrad", "wgrad")]
         print("[bench] roofline leg done (%d conv launches, %d norm launches)" % (len(recs), len(all_recs) - len(recs)),
               file=sys.stderr, flush=True)
@@ -467,7 +507,7 @@ def main():
 
     devices = sorted(set(dp.all_gather_ints(torch.cuda.current_device()))) if dp.active else None      # (a collective: every rank)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, opt.state_dim)
 
     if rank == 0:

@@ -11,11 +11,11 @@ symbol, and what matters for a given `dist.all_reduce(op=...)` is the set of fun
 
     python tests/tools/rccl_audit.py [--full] [librccl.so]      (--full: every function of the code object, ~70 s more)
 Used by tests/test_host_logic.py::test_rccl_sum_reduction_is_free_of_the_hazard_class."""
-import collections, os, re, struct, subprocess, sys
+import collections, os, re, struct, subprocess, sys, tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-CACHE = "/tmp/s2p_rccl_audit"
+CACHE = os.path.join(tempfile.gettempdir(), "s2p_rccl_audit_%d" % os.getuid())      # per user: the temp dir may be shared
 
 # the reductions the product issues (s2p_amd/parallel.py): SUM over fp32 gradients; MAX over one float64 (bench timing only)
 PRODUCT_REDUCTIONS = {"sum_f32": r"7FuncSumIfE", "minmax_f64": r"10FuncMinMaxIdE"}
