@@ -326,6 +326,29 @@ typedef struct {
 } s2p_pack_job;
 /* jobs: DEVICE array of n_jobs descriptors (caller-owned)                               */
 int s2p_pack_weights(const s2p_pack_job* jobs, int n_jobs, int max_elems, void* stream);
+/* the same packing with a per-job scale: sigma is a DEVICE array of n_jobs pointers to device fp32 scalars; job i packs
+ * src / *sigma[i] (an fp32 division, then the dtype's round-to-nearest-even cast), or src unscaled where sigma[i] is
+ * NULL (the spectral-norm operands W / sigma, SPEC.md D5s)                                                           */
+int s2p_pack_weights_scaled(const s2p_pack_job* jobs, const float* const* sigma, int n_jobs, int max_elems,
+                            void* stream);
+
+/* ---- spectral normalization (torch.nn.utils.spectral_norm: one power iteration, eps 1e-12; SPEC.md D5s) ------ */
+/* one SN weight: w fp32 master [R][K] (K = taps * channels, in the master's (tap, channel) column order); u [R],
+ * v [K] and sigma [1] are updated in place; ws: caller-owned fp32 workspace of s2p_sn_workspace_floats(R, K) floats,
+ * one per job; grad [R][K]: the projection's operand (NULL for the power iteration)                                 */
+typedef struct {
+  const float* w; float* u; float* v; float* sigma; float* ws; float* grad;
+  int32_t R, K;
+} s2p_sn_job;
+int64_t s2p_sn_workspace_floats(int R, int K);
+/* jobs: DEVICE array of n_jobs descriptors; max_R / max_K bound every job's R / K (they size the grid).
+ * training != 0: v = normalize(W^T u), u = normalize(W v), sigma = u . (W v)  (3 launches);
+ * training == 0: u and v untouched, sigma = u . (W v) (2 launches).  No atomics, fixed summation order: a job's
+ * results are bitwise independent of the other jobs in the table and reproducible call to call                     */
+int s2p_sn_power_iter(const s2p_sn_job* jobs, int n_jobs, int max_R, int max_K, int training, void* stream);
+/* grad <- (grad - <grad, w / sigma> u v^T) / sigma in place: dL/dW from dL/dW_sn with u, v held constant
+ * (2 launches: per-row-block partials of <grad, w>, then the apply)                                                 */
+int s2p_sn_project_grad(const s2p_sn_job* jobs, int n_jobs, int max_R, int max_K, void* stream);
 
 /* ---- small elementwise helpers ------------------------------------------------------ */
 /* dx = dy * act'(y)   (y = activation OUTPUT)                                           */

@@ -41,6 +41,11 @@ class PackJob(ctypes.Structure):
                 ("dtype", ctypes.c_int32)]
 
 
+class SnJob(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("u", c_void_p), ("v", c_void_p), ("sigma", c_void_p), ("ws", c_void_p), ("grad", c_void_p),
+                ("R", ctypes.c_int32), ("K", ctypes.c_int32)]
+
+
 # name -> argtypes; every entry returns int unless listed in _RESTYPE
 _P = c_void_p
 _DESC = ctypes.POINTER(ConvDesc)
@@ -105,13 +110,18 @@ SIGNATURES = {
     "s2p_adam_step_dev": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, _P],
     "s2p_adam_step_dev_part": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, c_int, _P],
     "s2p_pack_weights": [_P, c_int, c_int, _P],
+    "s2p_pack_weights_scaled": [_P, _P, c_int, c_int, _P],
+    "s2p_sn_workspace_floats": [c_int, c_int],
+    "s2p_sn_power_iter": [_P, c_int, c_int, c_int, c_int, _P],
+    "s2p_sn_project_grad": [_P, c_int, c_int, c_int, _P],
     "s2p_act_bwd": [c_int, _P, _P, c_int64, c_int, c_float, _P, _P],
     "s2p_scale": [c_int, _P, c_int64, _P, _P],
     "s2p_add": [c_int, _P, _P, _P, c_int64, _P],
     "s2p_copy_channels": [c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int64, c_int, _P],
     "s2p_image_metrics": [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P],
 }
-_RESTYPE = {"s2p_last_error": ctypes.c_char_p, "s2p_conv2d_wgrad_batched_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_workspace": ctypes.c_size_t, "s2p_conv2d_fwd_workspace": ctypes.c_size_t, "s2p_conv2d_dgrad_workspace": ctypes.c_size_t, "s2p_linear_bwd_workspace": ctypes.c_size_t, "s2p_in_stats_floats": c_int64, "s2p_in_bwd_sums_floats": c_int64}
+_RESTYPE = {"s2p_last_error": ctypes.c_char_p, "s2p_conv2d_wgrad_batched_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_workspace": ctypes.c_size_t, "s2p_conv2d_fwd_workspace": ctypes.c_size_t, "s2p_conv2d_dgrad_workspace": ctypes.c_size_t, "s2p_linear_bwd_workspace": ctypes.c_size_t, "s2p_in_stats_floats": c_int64, "s2p_in_bwd_sums_floats": c_int64,
+            "s2p_sn_workspace_floats": c_int64}
 
 _lib = None
 

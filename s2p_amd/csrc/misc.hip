@@ -685,8 +685,9 @@ extern "C" int s2p_adam_step_dev(float* p, const float* g, float* m, float* v, i
 // axis); the forward operand goes out from the registers (8-byte bf16 stores along c), the transposed backward operand through a
 // 64 x 65 LDS tile (8-byte stores along r).  (Rounds 1-2 read the master twice, the second time through 32 x 32 tiles with two
 // barriers per 1024 elements: 69 + 58 us per step for G + D.)
-template <typename T>
-__device__ void pack_one(const s2p_pack_job& j, int part, int nparts, float (*tile)[65]) {
+// SCALED: every value is divided by `den` first (s2p_pack_weights_scaled; the unscaled instantiation is the code of s2p_pack_weights)
+template <typename T, bool SCALED = false>
+__device__ void pack_one(const s2p_pack_job& j, int part, int nparts, float (*tile)[65], float den = 1.f) {
   const int tid = threadIdx.x;
   T* df = (T*)j.dst_fwd;
   T* db = (T*)j.dst_bwd;
@@ -711,6 +712,10 @@ __device__ void pack_one(const s2p_pack_job& j, int part, int nparts, float (*ti
 #pragma unroll
           for (int e = 0; e < 4; ++e) if (c + e < j.C) v[e] = sp[e];
         }
+      }
+      if constexpr (SCALED) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] / den;
       }
       if (df && r < j.R && c < j.Cpad) {                     // Cpad is a multiple of the 16-byte chunk: c + 3 < Cpad
         T* dp = df + ((long long)r * j.T + t) * j.Cpad + c;
@@ -750,24 +755,53 @@ __device__ void pack_one(const s2p_pack_job& j, int part, int nparts, float (*ti
     }
   }
 }
-__global__ __launch_bounds__(256) void pack_kernel(const s2p_pack_job* jobs) {
-  __shared__ float tile[64][65];
-  const s2p_pack_job j = jobs[blockIdx.y];
-  // the grid is sized for the largest job (one 64 x 64 tile per workgroup and pass); a smaller job uses only as many workgroups as
-  // it has tiles and the rest return at once (the jobs of one network differ by 4 orders of magnitude in size)
+// the grid is sized for the largest job (one 64 x 64 tile per workgroup and pass); a smaller job uses only as many workgroups as
+// it has tiles and the rest return at once (the jobs of one network differ by 4 orders of magnitude in size).  0: this block idles
+__device__ __forceinline__ int pack_parts(const s2p_pack_job& j) {
   const int Cw = j.dst_fwd ? (j.Cpad > j.C ? j.Cpad : j.C) : j.C;
   long long need = (long long)((j.R + 63) / 64) * ((Cw + 63) / 64) * j.T;
   if (need > (long long)gridDim.x) need = gridDim.x;
   if (need < 1) need = 1;
-  if ((long long)blockIdx.x >= need) return;
-  if (j.dtype == S2P_F32) pack_one<float>(j, blockIdx.x, (int)need, tile);
-  else pack_one<__bf16>(j, blockIdx.x, (int)need, tile);
+  return (long long)blockIdx.x >= need ? 0 : (int)need;
+}
+static inline int pack_grid(int max_elems) {     // ~ one 64 x 64 tile per workgroup
+  int parts = (max_elems + 4095) / 4096; if (parts < 1) parts = 1; if (parts > 2048) parts = 2048;
+  return parts;
+}
+__global__ __launch_bounds__(256) void pack_kernel(const s2p_pack_job* jobs) {
+  __shared__ float tile[64][65];
+  const s2p_pack_job j = jobs[blockIdx.y];
+  const int need = pack_parts(j);
+  if (!need) return;
+  if (j.dtype == S2P_F32) pack_one<float>(j, blockIdx.x, need, tile);
+  else pack_one<__bf16>(j, blockIdx.x, need, tile);
 }
 extern "C" int s2p_pack_weights(const s2p_pack_job* jobs, int n_jobs, int max_elems, void* stream) {
   if (!jobs || n_jobs <= 0) S2P_FAIL(-1, "s2p_pack_weights: bad argument");
-  int parts = (max_elems + 4095) / 4096; if (parts < 1) parts = 1; if (parts > 2048) parts = 2048;     // ~ one 64 x 64 tile per workgroup
-  hipLaunchKernelGGL(pack_kernel, dim3(parts, n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
+  hipLaunchKernelGGL(pack_kernel, dim3(pack_grid(max_elems), n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
   S2P_CHECK_LAUNCH("pack_kernel");
+  return 0;
+}
+// the same with a per-job divisor (*sigma[job], NULL: unscaled): the spectral-norm operands W / sigma
+__global__ __launch_bounds__(256) void pack_scaled_kernel(const s2p_pack_job* jobs, const float* const* sigma) {
+  __shared__ float tile[64][65];
+  const s2p_pack_job j = jobs[blockIdx.y];
+  const float* sp = sigma[blockIdx.y];
+  const int need = pack_parts(j);
+  if (!need) return;
+  if (sp) {
+    const float den = *sp;
+    if (j.dtype == S2P_F32) pack_one<float, true>(j, blockIdx.x, need, tile, den);
+    else pack_one<__bf16, true>(j, blockIdx.x, need, tile, den);
+  } else {
+    if (j.dtype == S2P_F32) pack_one<float>(j, blockIdx.x, need, tile);
+    else pack_one<__bf16>(j, blockIdx.x, need, tile);
+  }
+}
+extern "C" int s2p_pack_weights_scaled(const s2p_pack_job* jobs, const float* const* sigma, int n_jobs, int max_elems, void* stream) {
+  if (!jobs || !sigma || n_jobs <= 0) S2P_FAIL(-1, "s2p_pack_weights_scaled: bad argument");
+  hipLaunchKernelGGL(pack_scaled_kernel, dim3(pack_grid(max_elems), n_jobs), dim3(256), 0, (hipStream_t)stream, jobs, sigma);
+  S2P_CHECK_LAUNCH("pack_scaled_kernel");
   return 0;
 }
 

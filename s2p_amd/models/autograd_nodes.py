@@ -201,6 +201,7 @@ class _GLossNode(torch.autograd.Function):
         # compute_generator_loss); otherwise it goes on its side stream now, next to the (prev, fake) pass.
         dreal = pre_d
         if dreal is None:
+            model.netD.sn_forward()            # spectral norm of D (opt-in): once per D forward, after before_netD's wait
             dreal = dreal_pass(model, prev_image, real_image, OVERLAP_DREAL and not ops.SERIALIZE)
         xf = _build_d_half(model, prev_image, image_nhwc=fake)
         res, dctx = model.netD.fwd_nhwc(xf)
@@ -302,6 +303,9 @@ class _DStepNode(torch.autograd.Function):
                 grads.append(g)
             return dctx, grads
 
+        # D's spectral norm (opt-in): one power iteration for both halves; it changes sigma, hence netD.store.version, so the
+        # G step's real pass below is not reused then
+        netD.sn_forward()
         # the (prev, real) forward of this train step's G step, if it is still valid (same inputs, netD not updated since)
         cache = getattr(model, "_dreal_cache", None)
         model._dreal_cache = None

@@ -1,12 +1,25 @@
 """BaseNetwork: SPADE-lineage network base class (plugin contract of `--netG/--netD`):
 `modify_commandline_options(parser, is_train)` static hook, `cls(opt)` constructor, `init_weights(init_type,
-init_variance)`, `print_network()`.  Adds the MI355X flat parameter store hooks."""
+init_variance)`, `print_network()`.  Adds the MI355X flat parameter store hooks, and the optional spectral normalization
+(SPEC.md D5s) of chosen conv weights with torch.nn.utils.spectral_norm's checkpoint names."""
 import math
 
 import torch
 import torch.nn as nn
 
 from ...params import ParamStore
+
+SN_EPS = 1e-12
+
+
+def sn_buffers(conv):
+    """Give the conv module torch.nn.utils.spectral_norm's buffers: `weight_u` [Cout] and `weight_v` [kh*kw*Cin], both
+    normalize(randn) as torch initialises them.  v is kept in the flat master's column order (tap, channel); checkpoints
+    carry it in torch's (channel, tap) order (BaseNetwork.export_state_dict)."""
+    w = conv.weight
+    u, v = torch.randn(w.shape[0]), torch.randn(w.numel() // w.shape[0])
+    conv.register_buffer("weight_u", u / u.norm().clamp_min(SN_EPS))
+    conv.register_buffer("weight_v", v / v.norm().clamp_min(SN_EPS))
 
 
 class BaseNetwork(nn.Module):
@@ -15,6 +28,7 @@ class BaseNetwork(nn.Module):
         self.store = ParamStore()
         self.compute_dtype = torch.float32
         self.finalized = False
+        self.sn_option = None          # the option value that turns spectral norm on for this network (error messages)
 
     @staticmethod
     def modify_commandline_options(parser, is_train):
@@ -70,14 +84,57 @@ class BaseNetwork(nn.Module):
         raise NotImplementedError
 
     def load_state_dict(self, state_dict, strict=True):
-        out = super().load_state_dict(state_dict, strict=strict)
+        out = super().load_state_dict(self._sn_from_torch(state_dict), strict=strict)
         if self.finalized:
             self.store.repack()
         return out
 
     def export_state_dict(self):
-        """state_dict with plain contiguous CPU tensors (torch-layout), independent of the flat store."""
-        return {k: v.detach().cpu().contiguous().clone() for k, v in self.state_dict().items()}
+        """state_dict with plain contiguous CPU tensors (torch-layout), independent of the flat store.  A spectrally normalized
+        layer is saved under torch.nn.utils.spectral_norm's names (`weight_orig`, `weight_u`, `weight_v`, v in torch's column
+        order), so a torch module wrapped in spectral_norm loads the file as it is."""
+        sd = {k: v.detach().cpu().contiguous().clone() for k, v in self.state_dict().items()}
+        for name, m in self.sn_layers():
+            w = sd.pop(name + ".weight")
+            cout, cin, kh, kw = w.shape
+            sd[name + ".weight_orig"] = w
+            sd[name + ".weight_v"] = sd[name + ".weight_v"].view(kh, kw, cin).permute(2, 0, 1).reshape(-1).clone()
+        return sd
+
+    # ---- spectral normalization (SPEC.md D5s) -------------------------------------------------------------------
+    def sn_layers(self):
+        """(qualified name, module) of every spectrally normalized conv, in declaration order."""
+        return [(n, m) for n, m in self.named_modules() if "weight_u" in m._buffers]
+
+    def sn_forward(self):
+        """Called once per forward of the network: in training mode one power iteration, in eval mode sigma from the stored
+        u, v when the weights changed since the last refresh (after a load or an optimizer step).  No-op without SN layers."""
+        st = self.store
+        if st.sn and (self.training or st.sn_stale):
+            st.sn_refresh(self.training)
+
+    def _sn_from_torch(self, sd):
+        """torch.nn.utils.spectral_norm names -> this module's (`weight_orig` -> `weight`, v back to the master's order); a
+        checkpoint whose spectral-norm layers do not match this network's options is refused."""
+        layers = self.sn_layers()
+        orig = sorted(k[:-len(".weight_orig")] for k in sd if k.endswith(".weight_orig"))
+        what = type(self).__name__
+        if not layers:
+            if orig:
+                raise RuntimeError("the state dict holds spectrally normalized layers (%s.weight_orig, ...) but this %s was built "
+                                   "without spectral norm: pass %s" % (orig[0], what, self.sn_option))
+            return sd
+        sd = dict(sd)
+        for name, m in layers:
+            if name + ".weight_orig" not in sd:
+                raise RuntimeError("the state dict has no %s.weight_orig: it was written without spectral norm, but this %s was "
+                                   "built with %s; load it without that option" % (name, what, self.sn_option))
+            w = sd.pop(name + ".weight_orig")
+            sd[name + ".weight"] = w
+            if name + ".weight_v" in sd:
+                cout, cin, kh, kw = w.shape
+                sd[name + ".weight_v"] = sd[name + ".weight_v"].reshape(cin, kh, kw).permute(1, 2, 0).reshape(-1)
+        return sd
 
     def _require_ready(self):
         if not self.finalized:

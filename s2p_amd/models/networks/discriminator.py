@@ -13,12 +13,17 @@ import torch.nn as nn
 from ... import ops, stepgraph
 from ..._lib import ACT_LRELU, ACT_NONE, EPI_ADD, EPI_MUL_ACTGRAD, EPI_STORE
 from ...ops import ConvGeom
-from .base_network import BaseNetwork
+from .base_network import BaseNetwork, sn_buffers
 from .generator import _Conv
 from .layers import ConvLayer
 
 LRELU = 0.2
 DFWD_SIDE = True         # forward: coarser scales on a side stream under scale 0 (diagnostic switch)
+
+
+def use_sn(opt):
+    """--norm_D spectral...: spectral norm on the convs an InstanceNorm follows (SPEC.md D5s)."""
+    return getattr(opt, "norm_D", "instance").startswith("spectral")
 
 
 class NLayerDiscriminator(BaseNetwork):
@@ -39,6 +44,8 @@ class NLayerDiscriminator(BaseNetwork):
             nf_prev, nf = nf, min(nf * 2, 512)
             setattr(self, f"model{n}", _Conv(nf_prev, nf, 4, bias=False))      # InstanceNorm follows: no bias
             self.chans.append(nf)
+            if use_sn(opt):
+                sn_buffers(getattr(self, f"model{n}"))                          # --norm_D spectralinstance: the normed convs
         setattr(self, f"model{self.n_layers}", _Conv(nf, 1, 4, bias=True))
         self.chans.append(1)
 
@@ -49,6 +56,8 @@ class NLayerDiscriminator(BaseNetwork):
         for n in range(self.n_layers + 1):
             m = getattr(self, f"model{n}")
             st.add(m.weight, "conv")
+            if "weight_u" in m._buffers:
+                st.sn_add(m.weight, m, f"{prefix}model{n}")
             if m.bias is not None:
                 st.add(m.bias, "bias")
             stride = 2 if n < self.n_layers - 1 else 1
@@ -122,6 +131,7 @@ class MultiscaleDiscriminator(BaseNetwork):
         super().__init__()
         self.opt = opt
         self.num_D = opt.num_D
+        self.sn_option = "--norm_D spectralinstance"
         from . import find_network_using_name
         sub = find_network_using_name(getattr(opt, "netD_subarch", "n_layer"), "discriminator")
         for i in range(opt.num_D):
@@ -224,6 +234,7 @@ class MultiscaleDiscriminator(BaseNetwork):
         """x: fp32 NCHW [B,6,H,W] = cat(prev_image, image).  Returns List[List[Tensor]] (per scale, per layer) of fp32
         NCHW features, last entry = patch logits (inference/diagnostic API; the train step uses the fused loss nodes)."""
         self._require_ready()
+        self.sn_forward()
         from ..._lib import chunk_elems
         with torch.no_grad():
             xd = ops.nchw_to_nhwc(x, self.compute_dtype, ops.pad_to(x.shape[1], chunk_elems(self.compute_dtype)))

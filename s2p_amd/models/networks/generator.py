@@ -17,7 +17,7 @@ import torch.nn as nn
 from ... import ops, stepgraph
 from ..._lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EPI_ADD, EPI_MUL_ACTGRAD, chunk_elems
 from ...ops import ConvGeom, pad_to
-from .base_network import BaseNetwork
+from .base_network import BaseNetwork, sn_buffers
 from .layers import ConvLayer
 
 LRELU = 0.2
@@ -115,6 +115,11 @@ class S2PGenerator(BaseNetwork):
             c *= 2
         self.c_mid = c
         self.blocks = nn.ModuleList([MATResnetBlock(c, self.nhidden, self.w_dim) for _ in range(self.n_blocks)])
+        self.sn_option = "--norm_G spectralmatinstance"
+        if getattr(opt, "norm_G", "matinstance").startswith("spectral"):      # the ResBlk convs (SPEC.md D5s)
+            for blk in self.blocks:
+                sn_buffers(blk.conv_0)
+                sn_buffers(blk.conv_1)
         for i in range(self.n_down):
             setattr(self, f"up{i}", _Conv(c, c // 2, 3, bias=False, transposed=True))
             c //= 2
@@ -210,6 +215,8 @@ class S2PGenerator(BaseNetwork):
         for b, blk in enumerate(self.blocks):
             for j, cv in enumerate((blk.conv_0, blk.conv_1)):
                 st.add(cv.weight, "conv"); st.add(cv.bias, "bias")
+                if "weight_u" in cv._buffers:
+                    st.sn_add(cv.weight, cv, f"blocks.{b}.conv_{j}")
                 L[f"b{b}c{j}"] = ConvLayer(st.pack(f"blocks.{b}.conv_{j}", [cv.weight], [cv.bias], dtype=dt),
                                            ConvGeom(c, c, 3, 1, 1))
         for i in range(self.n_down):
@@ -229,6 +236,7 @@ class S2PGenerator(BaseNetwork):
     def fwd_nhwc(self, img, state, save=True):
         """img: NHWC compute-dtype [N,H,W,ce] (3 real channels), state fp32 [N,S].  Returns (out NHWC, ctx)."""
         self._require_ready()
+        self.sn_forward()                    # spectral norm (opt-in): one power iteration per training-mode forward
         L, C, nh = self.lay, self.c_mid, self.nhidden
         N, H, W, _ = img.shape
         if H % (1 << self.n_down) or W % (1 << self.n_down):

@@ -84,6 +84,8 @@ class Pix2PixModel(nn.Module):
                 # also for --continue_train: silently restarting from random weights would overwrite the run's files
                 raise FileNotFoundError("%s not found (README: put <env_type>_<epoch>.pth under --checkpoints_dir), "
                                         "or pass --random_init" % path)
+        if not opt.isTrain:
+            netG.eval()            # inference: spectral norm (if on) uses the stored u, v and never iterates
         if ckpt is not None:
             netG.load_state_dict(ckpt["netG"] if "netG" in ckpt else ckpt)
             if netD is not None and "netD" in ckpt:
@@ -170,6 +172,7 @@ class Pix2PixModel(nn.Module):
         if autograd_nodes.OVERLAP_DREAL and not ops_mod.SERIALIZE and self.before_netD is None:
             # D(prev, real): on its side stream, under the generator forward (with data parallelism netD's weight update of
             # the previous step may still be in flight here: the pass then runs inside the loss node, after the wait)
+            self.netD.sn_forward()            # D's spectral norm: once for both halves of the batch, before the first
             pre_d = autograd_nodes.dreal_pass(self, prev, real, True)
         fake = generator_apply(self.netG, prev, state)                 # NHWC compute dtype, autograd node
         L = g_losses_apply(self, fake, prev, real, pre, pre_d)

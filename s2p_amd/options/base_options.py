@@ -23,8 +23,10 @@ class BaseOptions:
         parser.add_argument("--gpu_ids", type=str, default="0", help="gpu ids: e.g. 0  0,1,2. -1 is refused (no CPU fallback)")
         parser.add_argument("--checkpoints_dir", type=str, default="./checkpoints", help="models are saved here")
         parser.add_argument("--model", type=str, default="pix2pix", help="which model to use")
-        parser.add_argument("--norm_G", type=str, default="matinstance", help="MAT (state+image modulated) instance norm")
-        parser.add_argument("--norm_D", type=str, default="instance", help="instance normalization in D")
+        parser.add_argument("--norm_G", type=str, default="matinstance", help="MAT (state+image modulated) instance norm; spectralmatinstance also applies spectral norm "
+                            "to the ResBlk convs (any value starting with 'spectral' does, as in SPADE; SPEC.md D5s)")
+        parser.add_argument("--norm_D", type=str, default="instance", help="instance normalization in D; spectralinstance also applies spectral norm to the convs "
+                            "an InstanceNorm follows (any value starting with 'spectral' does, as in SPADE; SPEC.md D5s)")
         parser.add_argument("--phase", type=str, default="train", help="train, val, test, etc")
         parser.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"],
                             help="compute dtype of the HIP kernels (fp32 accumulate either way)")

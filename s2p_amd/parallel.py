@@ -77,6 +77,9 @@ class DataParallelGroup:
         """Make every rank start from rank `src`'s parameters (C2 in SURVEY.md section 2.2)."""
         if self.active:
             dist.broadcast(store.master, src=src, group=self.group)
+            if getattr(store, "sn", None):  # spectral-norm u / v: identical on every rank from here on (deterministic kernels)
+                dist.broadcast(store.sn_u, src=src, group=self.group)
+                dist.broadcast(store.sn_v, src=src, group=self.group)
             store.repack()
 
     def barrier(self):
