@@ -107,7 +107,8 @@ int s2p_conv2d_dgrad_ws(const s2p_conv_desc* d, const void* dy, const void* w_bw
  * of up to 192 pixels (csrc/conv_planeg.hip).  Other shapes run the two calls above back to back
  * (s2p_conv2d_mat_is_fused tells which).  groups must be 1; act: none / relu / lrelu.
  * y may be NULL where the launch is fused (s2p_conv2d_mat_is_fused): the conv output itself is then not written -- a forward
- * pass that keeps nothing for a backward only needs y_mat.                                                               */
+ * pass that keeps nothing for a backward only needs y_mat.  Where the launch is not fused a call with y == NULL is refused
+ * (non-zero, s2p_last_error) before anything is launched.                                                                */
 int s2p_conv2d_fwd_mat(const s2p_conv_desc* d, const void* x, const void* w_fwd, const float* bias, const void* aux,
                        void* y, int epi, const void* gb_img, int gb_pitch, const float* gb_st, int gb_st_pitch,
                        int act, float slope, float eps, void* y_mat, int y_mat_pitch, float* stats, void* workspace,
@@ -120,7 +121,9 @@ int s2p_conv2d_fwd_mat(const s2p_conv_desc* d, const void* x, const void* w_fwd,
  * Under the conditions of s2p_conv2d_fwd_mat (on the dgrad: Cout is the contraction, Cin the produced channels) this is ONE
  * launch and dL/d(norm output) never reaches HBM (d_mid and sums may then be NULL: s2p_conv2d_mat_is_fused); otherwise it
  * is written to d_mid ([N,H,W,x_pitch]) and the norm backward runs as its own launch(es) (needs `sums`:
- * s2p_in_bwd_sums_floats(N, H*W, Cin) floats).                                                                        */
+ * s2p_in_bwd_sums_floats(N, H*W, Cin) floats).  A call without d_mid or sums that is not one launch FOR ITS ARGUMENTS (with
+ * aux the 3x3 family is two launches, which s2p_conv2d_mat_is_fused -- it has no aux argument -- cannot tell) is refused
+ * (non-zero, s2p_last_error) before anything is launched.                                                               */
 int s2p_conv2d_dgrad_mat(const s2p_conv_desc* d, const void* dy, const void* w_bwd, void* d_mid, const void* aux, const void* xn,
                          int xn_pitch, const float* stats, const void* gb_img, int gb_pitch, const float* gb_st,
                          int gb_st_pitch, int act, float slope, float eps, float* sums, void* dxn, int dxn_pitch,

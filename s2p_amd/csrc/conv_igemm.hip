@@ -15,6 +15,7 @@
 #include "conv_plane.h"
 #include "conv_planeg.h"
 #include <type_traits>
+#include <vector>
 
 #define MAX_TAPS 64
 
@@ -39,8 +40,7 @@ struct GatherArgs {
   // applies bias / activation / epilogue to the sum (fixed order: no atomics).  ws / ws_bytes: caller's scratch.
   float* part; int psplit, psteps, part_m;
   void* ws; size_t ws_bytes;
-  size_t* plan;                // non-null: dry run -- report the scratch bytes this launch would use, launch nothing
-  const PlaneMat* mat; int* mat_done;   // optional fused InstanceNorm + MAT epilogue (plane-resident kernel only): *mat_done = 1 when applied
+  size_t* plan; const PlaneMat* mat; int* mat_done;   // unused host leftovers (nobody reads them): to go with the next kernel change -- this block is a kernel argument
   unsigned x_bytes, w_bytes;   // fast path: buffer-descriptor sizes of the gathered tensor / packed weights (per group view)
   int tap[MAX_TAPS];   // (wt << 16) | ((dx & 0xff) << 8) | (dy & 0xff)
   // merged sub-pixel phases (strided dgrad / transposed fwd on the LDS-DMA kernel): blockIdx.z selects a record that
@@ -503,7 +503,6 @@ __global__ __launch_bounds__(256, 2) void conv_fast_kernel(const GatherArgs a) {
 // ------------------------------------------------------------------------------------------------
 template <typename T, int BCO, int BPIX, int WCO, int WPIX>
 static int launch_cfg(GatherArgs& a, int groups, hipStream_t st) {
-  if (a.plan) return 0;
   a.npix_tiles = cdiv(a.M, BPIX);
   a.nco_tiles = cdiv(a.Cst, BCO);
   int splits = 1;
@@ -807,10 +806,32 @@ __global__ __launch_bounds__(64) void conv_part_reduce_kernel(const GatherArgs a
   }
 }
 
+// A/B switches of the conv dispatcher (diagnostics build only: in the product library every one of them is the constant 0 / its default).
+// The environment ones are read once, at the first conv call; the numbered run-time switches (s2p_diag_set, listed in misc.hip) are
+// read at each use, because tools/ab_step.py flips them between two captures in one process.
+struct ConvSwitches {
+  int no_dma = s2p_env_set("S2P_NO_LDS_DMA");            // register-staged conv_fast_kernel instead of every LDS-DMA kernel
+  int diag = s2p_env_int("S2P_DIAG", 0);                 // timing ablation passed to the kernels (GatherArgs::diag)
+  int no_halo = s2p_env_set("S2P_NO_HALO");              // plain LDS-DMA kernel instead of the halo-resident one
+  int no_split = s2p_env_set("S2P_NO_CONV_SPLITK");
+  int split_min_steps = s2p_env_int("S2P_SPLIT_MIN_STEPS", 16);
+  int split_max_wg = s2p_env_int("S2P_SPLIT_MAX_WG", 160);
+  int no_plane = s2p_env_set("S2P_NO_PLANE");            // neither plane-resident kernel
+  int halo_extra_lds = s2p_env_int("S2P_HALO_EXTRA_LDS", 0);   // occupancy experiment
+  int no_static_taps = s2p_env_set("S2P_NO_STATIC_TAPS");
+  int halo_pipe = s2p_env_set("S2P_NO_HALO_PIPE") ? 0 : 1;     // software-pipelined halo variant (default on)
+  int no_merge = s2p_env_set("S2P_NO_PHASE_MERGE") || s2p_env_set("S2P_NO_LDS_DMA");   // one launch per sub-pixel phase
+  int no_thin_cin = s2p_env_set("S2P_NO_THIN_CIN");
+  static bool no_planeg() { return S2P_DIAG_SWITCH(0); }           // no generalised plane kernel ...
+  static bool no_planeg_3x3() { return S2P_DIAG_SWITCH(2); }       // ... not for 3x3 taps
+  static bool no_thin4() { return S2P_DIAG_SWITCH(3); }
+  static bool no_phase_fast() { return S2P_DIAG_SWITCH(10); }      // merged phases stay in blockIdx.z for the 64-row weight tile too
+};
+static const ConvSwitches& conv_switches() { static const ConvSwitches sw; return sw; }
+
 // K-split plan of a single-phase bf16 launch (1 = no split): only launches of <= 160 workgroups, >= 16 K steps per slice
 static int conv_split_plan(int nwg, int nk) {
-  static const int min_steps = s2p_env_int("S2P_SPLIT_MIN_STEPS", 16);      // A/B switch (diagnostics build only)
-  static const int max_wg = s2p_env_int("S2P_SPLIT_MAX_WG", 160);
+  const int min_steps = conv_switches().split_min_steps, max_wg = conv_switches().split_max_wg;
   if (nwg > max_wg || nk < 2 * min_steps) return 1;
   int S = 384 / nwg;
   if (S > nk / min_steps) S = nk / min_steps;
@@ -1267,30 +1288,88 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const GatherArgs a) {
   conv_epilogue<T, BCO, BPIX, TCO, TPIX>(a, acc, smem, rowoff, g, co_base, wco0, wpix0, r, h, tid);
 }
 
-template <int BCO, int BPIX, int WCO, int WPIX>
-static int launch_fast(GatherArgs& a, int groups, hipStream_t st) {
-  a.npix_tiles = cdiv(a.M, BPIX);
-  a.nco_tiles = cdiv(a.Cst, BCO);
-  dim3 grid(a.npix_tiles * a.nco_tiles, groups);
-  static const int no_dma = s2p_env_set("S2P_NO_LDS_DMA");
-  static const int diag = s2p_env_int("S2P_DIAG", 0);
-  a.diag = diag;
-  static const int no_halo = s2p_env_set("S2P_NO_HALO");        // A/B switch: plain LDS-DMA kernel
+// ================================================================================================
+// Host dispatcher.  A conv call is planned ONCE -- conv_plan_fwd / conv_plan_dgrad look at geometry, dtype, act / epi, the fused norm
+// the caller wants and the scratch it offers, and write a ConvPlan: the path of every launch, whether the norm rides in the
+// epilogue, the scratch bytes used.  Planning dereferences no tensor pointer and launches nothing.  The real call launches that plan;
+// the workspace queries return its ws_bytes; s2p_conv2d_mat_is_fused returns its `fused`.  DESIGN.md section 3.1 lists the order.
+enum class ConvPath { Thin, Thin4, ThinCin, ThinRows, Plane, PlaneG, Halo, SplitK, Dma, Fast, Phases, Generic };
+enum class HaloKind { S9_176_PIPE, S9_176, S9_320, R_176, R_320 };      // static 3x3 taps / run-time taps, positions held, pipelined
+
+struct ConvOperands {       // tensors and epilogue of one call (all NULL / zero in the queries)
+  const void* x; const void* w; const float* bias; const void* aux; const void* aux2; void* y;
+  int act; float slope; int epi, gact; float gslope;
+};
+struct NormWant { bool any, gb, bwd; };        // a fused InstanceNorm is wanted / with gamma|beta maps / in its backward form
+struct ScratchAvail { bool any; size_t bytes; };      // what the caller offers (the size queries offer "unlimited")
+static const ScratchAvail SCRATCH_UNLIMITED{true, ~(size_t)0};
+struct Scratch { void* ws; size_t bytes; };
+
+// how ONE gather-form problem (a filled GatherArgs) is launched
+struct GatherChoice {
+  ConvPath path = ConvPath::Generic;
+  bool fused = false;         // Plane / PlaneG: the wanted norm is this launch's epilogue
+  size_t ws_bytes = 0;        // SplitK: partial tiles
+  int bco = 128;              // weight-tile rows of the bf16 kernels (128 / 64)
+  HaloKind halo = HaloKind::R_320;
+  PlaneArgs plane;            // Plane / PlaneG: the kernel's argument block, complete but for the norm (copy_norm at the launch)
+  PlaneGArgs planeg;
+};
+struct GatherItem { GatherArgs a; GatherChoice c; };
+struct ConvPlan {
+  ConvPath path = ConvPath::Generic;      // Thin / Thin4 / ThinCin / ThinRows: the whole call is that kernel; otherwise `items`
+  bool fused = false;
+  size_t ws_bytes = 0;                    // maximum over the launches
+  int cout_pad = 0;                       // dgrad: channels of dy gathered
+  std::vector<GatherItem> items;          // one launch; s*s for a scatter problem that runs phase by phase
+  void add(const GatherItem& it) {
+    if (items.empty()) path = it.c.path;
+    if (it.c.ws_bytes > ws_bytes) ws_bytes = it.c.ws_bytes;
+    items.push_back(it);
+    fused = items.size() == 1 && it.c.fused;       // (the fusing kernels need ostride == 1: never a phase of several)
+  }
+};
+
+// the operand / channel / epilogue fields the three argument blocks share by name
+template <typename P>
+static void copy_conv_fields(P& p, const GatherArgs& a) {
+  p.x = a.x; p.w = a.w; p.bias = a.bias; p.aux = a.aux; p.aux2 = a.aux2; p.y = a.y;
+  p.Cin = a.Cin; p.x_pitch = a.x_pitch; p.x_gstride = a.x_gstride;
+  p.Cout = a.Cout; p.Cst = a.Cst; p.y_pitch = a.y_pitch; p.y_gstride = a.y_gstride;
+  p.w_row = a.w_row; p.w_gstride = a.w_gstride;
+  p.act = a.act; p.epi = a.epi; p.gact = a.gact; p.slope = a.slope; p.gslope = a.gslope;
+  p.x_bytes = a.x_bytes; p.w_bytes = a.w_bytes;
+}
+template <typename P>
+static void copy_norm(P& p, const PlaneMat& m) {
+  p.xn = m.xn; p.xn_pitch = m.xn_pitch; p.dgb = m.dgb; p.dgb_pitch = m.dgb_pitch;
+  p.dgbst = m.dgbst; p.dgbst_pitch = m.dgbst_pitch; p.res = m.res; p.res_pitch = m.res_pitch;
+  p.y2 = m.y2; p.y2_pitch = m.y2_pitch; p.gb = m.gb; p.gb_pitch = m.gb_pitch;
+  p.gbst = m.gbst; p.gbst_pitch = m.gbst_pitch; p.stats = m.stats;
+  p.n_act = m.act; p.n_slope = m.slope; p.eps = m.eps;
+}
+
+// ---- planning ---------------------------------------------------------------------------------------------------------------
+// bf16, 64-channel multiples: the MFMA kernels fed by LDS-DMA.  First match wins.
+static void plan_fast(GatherArgs& a, GatherChoice& c, int groups, const NormWant& want, const ScratchAvail& sc) {
+  const ConvSwitches& sw = conv_switches();
+  a.npix_tiles = cdiv(a.M, 128);
+  a.nco_tiles = cdiv(a.Cst, c.bco);
+  a.diag = sw.diag;
+  const int nwg = a.npix_tiles * a.nco_tiles;
+  const bool whole = a.ostride == 1 && a.oy0 == 0 && a.ox0 == 0 && a.Qh == a.Ho && a.Qw == a.Wo;   // one phase that is the produced grid
+  const bool planes = whole && a.M % (a.Qh * a.Qw) == 0;
   // launches that cannot fill the chip (<= 160 workgroups with a long K: PatchGAN 256->512 4x4 on 7x7 / 12x12 maps, VGG conv4_1 /
   // conv5_1 on 10x10 / 5x5 maps): K split over blockIdx.z + fixed-order reduce with the epilogue, when the caller passed a
   // scratch buffer.  One workgroup alone on a CU is bound by its LDS-DMA issue rate (~0.7 us per 32 KiB K step) whichever
-  // kernel runs it, so the K loop is spread over the idle CUs instead -- this takes precedence over the halo-resident kernel.
-  static const int no_split = s2p_env_set("S2P_NO_CONV_SPLITK");
-  int S_plan = 1;
-  if (!no_dma && !no_split && groups == 1 && a.nphase == 0 && a.ostride == 1 && a.oy0 == 0 && a.ox0 == 0 && a.Qh == a.Ho &&
-      a.Qw == a.Wo && (a.plan || a.ws))
-    S_plan = conv_split_plan((int)grid.x, a.Ktot / 64);
+  // kernel runs it, so the K loop is spread over the idle CUs instead -- this takes precedence over the halo-resident kernel
+  // (but not over the plane-resident ones).
+  int S = 1;
+  if (!sw.no_dma && !sw.no_split && groups == 1 && whole && sc.any) S = conv_split_plan(nwg, a.Ktot / 64);
   // small planes (21x21 ResBlk / VGG conv3 / gamma-beta layers and their dgrads): one workgroup per (image, 64-channel slab),
   // the whole padded plane resident in LDS (conv_plane.hip)
-  static const int no_plane = s2p_env_set("S2P_NO_PLANE");          // A/B switch (diagnostics build only)
-  if (!no_plane && !no_dma && a.nphase == 0 && a.T == 9 && a.istride == 1 && a.ostride == 1 && a.oy0 == 0 && a.ox0 == 0 &&
-      a.Qh == a.Hi && a.Qw == a.Wi && a.Ho == a.Qh && a.Wo == a.Qw && a.M % (a.Qh * a.Qw) == 0) {
-    PlaneArgs p{};
+  if (!sw.no_plane && !sw.no_dma && a.T == 9 && a.istride == 1 && planes && a.Qh == a.Hi && a.Qw == a.Wi) {
+    PlaneArgs& p = c.plane;
     bool ok = true;
     for (int t = 0; t < 9; ++t) p.wt[t] = -1;
     for (int t = 0; t < 9 && ok; ++t) {
@@ -1298,127 +1377,71 @@ static int launch_fast(GatherArgs& a, int groups, hipStream_t st) {
       if (dy < -1 || dy > 1 || dx < -1 || dx > 1 || p.wt[(dy + 1) * 3 + dx + 1] >= 0) ok = false;
       else p.wt[(dy + 1) * 3 + dx + 1] = a.tap[t] >> 16;
     }
-    if (ok) {
-      p.x = a.x; p.w = a.w; p.bias = a.bias; p.aux = a.aux; p.aux2 = a.aux2; p.y = a.y;
-      p.N = a.M / (a.Qh * a.Qw); p.H = a.Qh; p.W = a.Qw;
-      p.Cin = a.Cin; p.x_pitch = a.x_pitch; p.x_gstride = a.x_gstride;
-      p.Cout = a.Cout; p.Cst = a.Cst; p.y_pitch = a.y_pitch; p.y_gstride = a.y_gstride;
-      p.w_row = a.w_row; p.w_gstride = a.w_gstride;
-      p.act = a.act; p.epi = a.epi; p.gact = a.gact; p.slope = a.slope; p.gslope = a.gslope;
-      p.x_bytes = a.x_bytes; p.w_bytes = a.w_bytes;
-      if (s2p_conv_plane_applicable(p)) {
-        const bool fuse = a.mat && groups == 1 && a.act == S2P_ACT_NONE && a.epi != S2P_EPI_MUL_ACTGRAD && (!a.mat->xn || a.epi == S2P_EPI_STORE);
-        if (fuse) *a.mat_done = 1;
-        if (a.plan) return 0;                              // no scratch
-        if (fuse) {
-          p.xn = a.mat->xn; p.xn_pitch = a.mat->xn_pitch; p.dgb = a.mat->dgb; p.dgb_pitch = a.mat->dgb_pitch;
-          p.dgbst = a.mat->dgbst; p.dgbst_pitch = a.mat->dgbst_pitch; p.res = a.mat->res; p.res_pitch = a.mat->res_pitch;
-          p.y2 = a.mat->y2; p.y2_pitch = a.mat->y2_pitch; p.gb = a.mat->gb; p.gb_pitch = a.mat->gb_pitch;
-          p.gbst = a.mat->gbst; p.gbst_pitch = a.mat->gbst_pitch; p.stats = a.mat->stats;
-          p.n_act = a.mat->act; p.n_slope = a.mat->slope; p.eps = a.mat->eps;
-        }
-        return s2p_conv_plane_launch(p, groups, st);
-      }
+    copy_conv_fields(p, a);
+    p.N = a.M / (a.Qh * a.Qw); p.H = a.Qh; p.W = a.Qw;
+    if (ok && s2p_conv_plane_applicable(p)) {
+      c.path = ConvPath::Plane;
+      c.fused = want.any && groups == 1 && a.act == S2P_ACT_NONE && a.epi != S2P_EPI_MUL_ACTGRAD && (!want.bwd || a.epi == S2P_EPI_STORE);
+      return;
     }
   }
   // other small planes -- the PatchGAN 4x4 layers and their stride-1 dgrads (with the InstanceNorm that follows (forward) / precedes
   // (backward) the conv in the epilogue), VGG conv4_x on 10x10 maps: the generalised plane-resident kernel (conv_planeg.hip)
-  if (!no_plane && !S2P_DIAG_SWITCH(0) && !(a.T == 9 && S2P_DIAG_SWITCH(2)) && !no_dma && groups == 1 && a.nphase == 0 && a.ostride == 1 && a.oy0 == 0 && a.ox0 == 0 && a.Qh == a.Ho &&
-      a.Qw == a.Wo && a.M % (a.Qh * a.Qw) == 0 && !a.reflect) {
-    PlaneGProblem pr{a.M / (a.Qh * a.Qw), a.Hi, a.Wi, a.Ho, a.Wo, a.Cin, a.Cout, a.Cst, a.x_pitch, a.y_pitch, a.istride, a.T, a.tap, a.mat != nullptr};
-    PlaneGArgs p{};
+  if (!sw.no_plane && !sw.no_planeg() && !(a.T == 9 && sw.no_planeg_3x3()) && !sw.no_dma && groups == 1 && planes && !a.reflect) {
+    PlaneGProblem pr{a.M / (a.Qh * a.Qw), a.Hi, a.Wi, a.Ho, a.Wo, a.Cin, a.Cout, a.Cst, a.x_pitch, a.y_pitch, a.istride, a.T, a.tap, want.any};
+    PlaneGArgs& p = c.planeg;
     if (s2p_conv_planeg_setup(pr, p)) {
-      const bool fuse = a.mat && p.nbands == 1 && p.gimg == 1 && !a.mat->gb && a.act == S2P_ACT_NONE && a.epi != S2P_EPI_MUL_ACTGRAD;
-      if (fuse) *a.mat_done = 1;
-      if (a.plan) return 0;                                // no scratch
-      p.x = a.x; p.w = a.w; p.bias = a.bias; p.aux = a.aux; p.aux2 = a.aux2; p.y = a.y;
-      p.N = pr.N; p.Cin = a.Cin; p.x_pitch = a.x_pitch; p.x_gstride = a.x_gstride;
-      p.Cout = a.Cout; p.Cst = a.Cst; p.y_pitch = a.y_pitch; p.y_gstride = a.y_gstride;
-      p.w_row = a.w_row; p.w_gstride = a.w_gstride;
-      p.act = a.act; p.epi = a.epi; p.gact = a.gact; p.slope = a.slope; p.gslope = a.gslope;
-      p.x_bytes = a.x_bytes; p.w_bytes = a.w_bytes;
-      if (fuse) {
-        p.xn = a.mat->xn; p.xn_pitch = a.mat->xn_pitch; p.dgb = a.mat->dgb; p.dgb_pitch = a.mat->dgb_pitch;
-        p.dgbst = a.mat->dgbst; p.dgbst_pitch = a.mat->dgbst_pitch; p.res = a.mat->res; p.res_pitch = a.mat->res_pitch;
-        p.y2 = a.mat->y2; p.y2_pitch = a.mat->y2_pitch; p.gbst = a.mat->gbst; p.gbst_pitch = a.mat->gbst_pitch; p.stats = a.mat->stats;
-        p.n_act = a.mat->act; p.n_slope = a.mat->slope; p.eps = a.mat->eps;
-      }
-      return s2p_conv_planeg_launch(p, groups, st);
+      copy_conv_fields(p, a);
+      p.N = pr.N;
+      c.path = ConvPath::PlaneG;
+      c.fused = want.any && p.nbands == 1 && p.gimg == 1 && !want.gb && a.act == S2P_ACT_NONE && a.epi != S2P_EPI_MUL_ACTGRAD;
+      return;
     }
   }
-  if constexpr (BCO == 128 && BPIX == 128) {
-    if (S_plan <= 1 && !no_dma && !no_halo && a.istride == 1 && a.ostride == 1 && a.Qh == a.Hi && a.Qw == a.Wi && a.Ho == a.Qh &&
-        a.Wo == a.Qw && a.T >= 4) {
-      if (a.plan) return 0;                              // halo-resident kernels: no scratch
-      int lo = 0, hi = 0;
-      for (int t = 0; t < a.T; ++t) {
-        int off = (int)(signed char)(a.tap[t] & 0xff) * a.Wi + (int)(signed char)((a.tap[t] >> 8) & 0xff);
-        if (-off > lo) lo = -off;
-        if (off > hi) hi = off;
-      }
+  // stride-1 "same" convs with the 128-row weight tile that are not K-split: the pixel tile and its halo resident in LDS
+  if (c.bco == 128 && S <= 1 && !sw.no_dma && !sw.no_halo && a.istride == 1 && a.ostride == 1 && a.Qh == a.Hi && a.Qw == a.Wi &&
+      a.Ho == a.Qh && a.Wo == a.Qw && a.T >= 4) {
+    int lo = 0, hi = 0;
+    for (int t = 0; t < a.T; ++t) {
+      int off = (int)(signed char)(a.tap[t] & 0xff) * a.Wi + (int)(signed char)((a.tap[t] >> 8) & 0xff);
+      if (-off > lo) lo = -off;
+      if (off > hi) hi = off;
+    }
+    const int npos = 128 + lo + hi;
+    const bool s9 = a.T == 9 && !sw.no_static_taps;
+    if (npos <= 320) {
       a.halo_lo = lo; a.halo_hi = hi;
-      const int npos = BPIX + lo + hi;
-      static const int extra_lds = s2p_env_int("S2P_HALO_EXTRA_LDS", 0);   // occupancy experiment
-      static const int no_ts = s2p_env_set("S2P_NO_STATIC_TAPS");
-      static const int pipe = (s2p_env_set("S2P_NO_HALO_PIPE") ? 0 : 1);         // A/B switch: software-pipelined variant (default on)
-      if (a.T == 9 && !no_ts && pipe && npos <= 176 && a.Cin % 64 == 0) {
-        hipLaunchKernelGGL((conv_halo_kernel<176, true, 9, true>), grid, dim3(256), extra_lds, st, a); S2P_CHECK_LAUNCH("conv_halo_kernel"); return 0;
-      }
-      if (a.T == 9 && !no_ts) {
-        if (npos <= 176) { hipLaunchKernelGGL((conv_halo_kernel<176, true, 9>), grid, dim3(256), extra_lds, st, a); S2P_CHECK_LAUNCH("conv_halo_kernel"); return 0; }
-        if (npos <= 320) { hipLaunchKernelGGL((conv_halo_kernel<320, false, 9>), grid, dim3(256), 0, st, a); S2P_CHECK_LAUNCH("conv_halo_kernel"); return 0; }
-      }
-      if (npos <= 176) { hipLaunchKernelGGL((conv_halo_kernel<176, true>), grid, dim3(256), extra_lds, st, a); S2P_CHECK_LAUNCH("conv_halo_kernel"); return 0; }
-      if (npos <= 320) { hipLaunchKernelGGL((conv_halo_kernel<320, false>), grid, dim3(256), 0, st, a); S2P_CHECK_LAUNCH("conv_halo_kernel"); return 0; }
+      c.path = ConvPath::Halo;
+      if (npos <= 176) c.halo = s9 ? (sw.halo_pipe && a.Cin % 64 == 0 ? HaloKind::S9_176_PIPE : HaloKind::S9_176) : HaloKind::R_176;
+      else c.halo = s9 ? HaloKind::S9_320 : HaloKind::R_320;
+      return;
     }
   }
-  if (S_plan > 1) {
+  if (S > 1) {
     const int nk = a.Ktot / 64;
-    {
-      a.psteps = cdiv(nk, S_plan); a.psplit = cdiv(nk, a.psteps);
-      a.part_m = a.npix_tiles * BPIX;
-      const size_t need = (size_t)a.psplit * a.Cst * a.part_m * sizeof(float);
-      if (a.plan) { if (need > *a.plan) *a.plan = need; return 0; }
-      if (a.psplit > 1 && need <= a.ws_bytes) {
-        a.part = (float*)a.ws;
-        grid.z = a.psplit;
-        hipLaunchKernelGGL((conv_dma_kernel<BCO, BPIX, WCO, WPIX>), grid, dim3(256), 0, st, a);
-        S2P_CHECK_LAUNCH("conv_dma_kernel(split)");
-        const long long n = (long long)(a.part_m / 4) * ((a.Cst + 7) / 8);
-        hipLaunchKernelGGL(conv_part_reduce_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, a);
-        S2P_CHECK_LAUNCH("conv_part_reduce_kernel");
-        return 0;
-      }
-      a.psplit = 1; a.part = nullptr;
-    }
+    a.psteps = cdiv(nk, S); a.psplit = cdiv(nk, a.psteps);
+    a.part_m = a.npix_tiles * 128;
+    const size_t need = (size_t)a.psplit * a.Cst * a.part_m * sizeof(float);
+    if (a.psplit > 1 && need <= sc.bytes) { c.path = ConvPath::SplitK; c.ws_bytes = need; return; }
+    a.psplit = 1;                                        // the caller's buffer is too small: unsplit
   }
-  if (a.plan) return 0;
-  if (no_dma) hipLaunchKernelGGL((conv_fast_kernel<BCO, BPIX, WCO, WPIX>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((conv_dma_kernel<BCO, BPIX, WCO, WPIX>), grid, dim3(256), 0, st, a);
-  S2P_CHECK_LAUNCH("conv_fast_kernel");
-  return 0;
+  c.path = sw.no_dma ? ConvPath::Fast : ConvPath::Dma;
 }
 
-template <typename T>
-static int launch_gather(GatherArgs& a, int groups, long long x_elems, hipStream_t st) {
-  if (a.M <= 0) return 0;
-  if constexpr (sizeof(T) == 2) {
-    const long long xb = x_elems * 2, wb = (long long)a.Cout * a.w_row * 2;
-    if (a.Cin % 64 == 0 && !a.reflect && a.T > 0 && xb < (1ll << 31) && wb < (1ll << 31) && a.Cst > 32) {
-      a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-      if (a.Cst > 64) return launch_fast<128, 128, 2, 2>(a, groups, st);
-      return launch_fast<64, 128, 2, 2>(a, groups, st);
-    }
+// one gather-form problem: `a` holds operands, geometry and taps
+static GatherItem plan_gather(const GatherArgs& a_in, bool bf16, int groups, long long x_elems, const NormWant& want, const ScratchAvail& sc) {
+  GatherItem it{a_in, {}};
+  GatherArgs& a = it.a;
+  const long long xb = x_elems * 2, wb = (long long)a.Cout * a.w_row * 2;
+  if (bf16 && a.Cin % 64 == 0 && !a.reflect && a.T > 0 && xb < (1ll << 31) && wb < (1ll << 31) && a.Cst > 32) {
+    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
+    it.c.bco = a.Cst > 64 ? 128 : 64;
+    plan_fast(a, it.c, groups, want, sc);
   }
-  if (a.Cst > 64) return launch_cfg<T, 128, 128, 2, 2>(a, groups, st);
-  if (a.Cst > 32) return launch_cfg<T, 64, 128, 2, 2>(a, groups, st);
-  return launch_cfg<T, 32, 256, 1, 4>(a, groups, st);
+  return it;                                             // otherwise ConvPath::Generic (conv_gather_kernel, either dtype)
 }
 
 static int pack_tap(int dy, int dx, int wt) { return (wt << 16) | ((dx & 0xff) << 8) | (dy & 0xff); }
-
-// caller's scratch for K-split launches (ws may be null), or a dry run that only reports the bytes needed (plan)
-struct Scratch { void* ws; size_t bytes; size_t* plan; const PlaneMat* mat; int* mat_done; };
 
 // geometry of one generic problem: gathered tensor (Hi,Wi,Ci,xpitch,xg), produced tensor (Ho,Wo,Co,Cst,ypitch,yg)
 struct Geo {
@@ -1434,117 +1457,98 @@ static inline long long gathered_elems(const Geo& G) {
   return (G.groups > 1 && G.xg >= G.xp) ? one + (long long)(G.groups - 1) * G.xg : one;
 }
 
-// "gather" orientation: out(oy) = sum_k in(oy*stride + k - pad)   (conv fwd, convT dgrad)
-template <typename T>
-static int run_gather(const Geo& G, const void* x, const void* w, const float* bias, const void* aux,
-                      const void* aux2, void* y,
-                      int act, float slope, int epi, int gact, float gslope, hipStream_t st, const Scratch& sc) {
+// the part of the argument block that does not depend on the phase: operands, tensors, epilogue.  The callers add the produced
+// sub-grid (Qh, Qw, M, oy0, ox0), the strides, the taps and `reflect`.
+static GatherArgs gather_base(const Geo& G, const ConvOperands& op) {
   GatherArgs a{};
-  a.ws = sc.ws; a.ws_bytes = sc.bytes; a.plan = sc.plan; a.mat = sc.mat; a.mat_done = sc.mat_done;
-  a.x = x; a.w = w; a.bias = bias; a.aux = aux; a.aux2 = aux2; a.y = y;
-  a.Hi = G.Hi; a.Wi = G.Wi; a.Qh = G.Ho; a.Qw = G.Wo; a.M = G.N * G.Ho * G.Wo;
+  a.x = op.x; a.w = op.w; a.bias = op.bias; a.aux = op.aux; a.aux2 = op.aux2; a.y = op.y;
+  a.Hi = G.Hi; a.Wi = G.Wi; a.Ho = G.Ho; a.Wo = G.Wo;
   a.Cin = G.Ci; a.x_pitch = G.xp; a.x_gstride = G.xg;
   a.Cout = G.Co; a.Cst = G.Cst; a.y_pitch = G.yp; a.y_gstride = G.yg;
-  a.Ho = G.Ho; a.Wo = G.Wo; a.istride = G.stride; a.ostride = 1; a.oy0 = 0; a.ox0 = 0;
-  a.T = G.KH * G.KW; a.Ktot = a.T * G.Ci; a.w_row = G.w_row; a.w_gstride = G.w_gstride;
-  a.reflect = G.reflect; a.act = act; a.epi = epi; a.slope = slope; a.gact = gact; a.gslope = gslope;
+  a.w_row = G.w_row; a.w_gstride = G.w_gstride;
+  a.act = op.act; a.epi = op.epi; a.slope = op.slope; a.gact = op.gact; a.gslope = op.gslope;
+  return a;
+}
+
+// taps of output phase (py, px) of a scatter problem; returns the count, -1 when there are more than `cap`
+static int phase_taps(const Geo& G, int py, int px, int* tap, int cap) {
+  const int s = G.stride;
+  int t = 0;
+  for (int ky = 0; ky < G.KH; ++ky) {
+    if ((py + G.pad - ky) % s != 0) continue;
+    for (int kx = 0; kx < G.KW; ++kx) {
+      if ((px + G.pad - kx) % s != 0) continue;
+      if (t >= cap) return -1;
+      tap[t++] = pack_tap((py + G.pad - ky) / s, (px + G.pad - kx) / s, ky * G.KW + kx);
+    }
+  }
+  return t;
+}
+
+// "gather" orientation: out(oy) = sum_k in(oy*stride + k - pad)   (conv fwd, convT dgrad)
+static int plan_gather_problem(const Geo& G, bool bf16, const ConvOperands& op, const NormWant& want, const ScratchAvail& sc, ConvPlan& P) {
+  GatherArgs a = gather_base(G, op);
+  a.Qh = G.Ho; a.Qw = G.Wo; a.M = G.N * G.Ho * G.Wo;
+  a.istride = G.stride; a.ostride = 1;
+  a.T = G.KH * G.KW; a.Ktot = a.T * G.Ci; a.reflect = G.reflect;
   if (a.T > MAX_TAPS) S2P_FAIL(-2, "conv: more than %d taps", MAX_TAPS);
   for (int ky = 0; ky < G.KH; ++ky)
     for (int kx = 0; kx < G.KW; ++kx) a.tap[ky * G.KW + kx] = pack_tap(ky - G.pad, kx - G.pad, ky * G.KW + kx);
-  return launch_gather<T>(a, G.groups, gathered_elems(G), st);
+  if (a.M > 0) P.add(plan_gather(a, bf16, G.groups, gathered_elems(G), want, sc));
+  return 0;
 }
 
 // "scatter" orientation expressed per output phase: out(oy) = sum_k in((oy + pad - k)/stride)
 // (conv_transpose fwd, strided/unstrided conv dgrad)
-template <typename T>
-static int run_scatter(const Geo& G, const void* x, const void* w, const float* bias, const void* aux,
-                       const void* aux2, void* y,
-                       int act, float slope, int epi, int gact, float gslope, hipStream_t st, const Scratch& sc) {
+static int plan_scatter_problem(const Geo& G, bool bf16, const ConvOperands& op, const NormWant& want, const ScratchAvail& sc, ConvPlan& P) {
+  const ConvSwitches& sw = conv_switches();
   const int s = G.stride;
-  if constexpr (sizeof(T) == 2) {
-    // all s*s phases in ONE launch of the LDS-DMA kernel (blockIdx.z = phase) when that kernel applies
-    static const int no_merge = (s2p_env_set("S2P_NO_PHASE_MERGE") || s2p_env_set("S2P_NO_LDS_DMA"));
-    const long long xb = gathered_elems(G) * 2, wb = (long long)G.Co * G.w_row * 2;
-    if (!no_merge && s * s <= MAX_PHASES && s > 1 && G.Ci % 64 == 0 && xb < (1ll << 31) && wb < (1ll << 31) && G.Cst > 32) {
-      GatherArgs a{};
-      a.x = x; a.w = w; a.bias = bias; a.aux = aux; a.aux2 = aux2; a.y = y;
-      a.Hi = G.Hi; a.Wi = G.Wi;
-      a.Cin = G.Ci; a.x_pitch = G.xp; a.x_gstride = G.xg;
-      a.Cout = G.Co; a.Cst = G.Cst; a.y_pitch = G.yp; a.y_gstride = G.yg;
-      a.Ho = G.Ho; a.Wo = G.Wo; a.istride = 1; a.ostride = s;
-      a.w_row = G.w_row; a.w_gstride = G.w_gstride;
-      a.reflect = 0; a.act = act; a.epi = epi; a.slope = slope; a.gact = gact; a.gslope = gslope;
-      a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-      static const int diag = s2p_env_int("S2P_DIAG", 0);
-      a.diag = diag;
-      bool ok = true;
-      int np = 0, max_npt = 0;
-      for (int py = 0; py < s && ok; ++py)
-        for (int px = 0; px < s && ok; ++px) {
-          GatherArgs::Phase& P = a.ph[np];
-          P.Qh = (G.Ho - py + s - 1) / s; P.Qw = (G.Wo - px + s - 1) / s;
-          if (P.Qh <= 0 || P.Qw <= 0) continue;
-          P.M = G.N * P.Qh * P.Qw; P.oy0 = py; P.ox0 = px;
-          int t = 0;
-          for (int ky = 0; ky < G.KH; ++ky) {
-            if ((py + G.pad - ky) % s != 0) continue;
-            for (int kx = 0; kx < G.KW; ++kx) {
-              if ((px + G.pad - kx) % s != 0) continue;
-              if (t >= PHASE_TAPS) { ok = false; break; }
-              P.tap[t++] = pack_tap((py + G.pad - ky) / s, (px + G.pad - kx) / s, ky * G.KW + kx);
-            }
-            if (!ok) break;
-          }
-          if (t == 0) ok = false;                      // a phase without taps still has to store zeros / bias: generic path
-          P.T = t; P.Ktot = t * G.Ci;
-          P.npix_tiles = cdiv(P.M, 128);
-          if (P.npix_tiles > max_npt) max_npt = P.npix_tiles;
-          ++np;
-        }
-      if (ok && np > 0) {
-        if (sc.plan) return 0;
-        a.nphase = np;
-        const int BCO = a.Cst > 64 ? 128 : 64;
-        a.nco_tiles = cdiv(a.Cst, BCO);
-        dim3 grid(max_npt * a.nco_tiles, G.groups, np);
-        // phase-fastest 1-D grid (see conv_dma_kernel) for the 64-row weight tile: HBM reads of the decoder's 128 -> 64 transposed conv
-        // 117 -> 30 MB (= its input once) at the same duration, the 64 -> 128 stride-2 dgrad 55 -> 33 MB and 6 % faster; the 128-row tile
-        // keeps the phase in blockIdx.z (measured: 41 -> 48 us on the 128 -> 256 stride-2 dgrad with the phases interleaved)
-        a.phase_fast = (BCO == 64 && !S2P_DIAG_SWITCH(10)) ? 1 : 0;
-        if (a.phase_fast) grid = dim3(((max_npt * a.nco_tiles + 7) / 8) * 8 * np, G.groups, 1);
-        if (BCO == 128) hipLaunchKernelGGL((conv_dma_kernel<128, 128, 2, 2>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv_dma_kernel<64, 128, 2, 2>), grid, dim3(256), 0, st, a);
-        S2P_CHECK_LAUNCH("conv_dma_kernel(phases)");
-        return 0;
+  GatherArgs base = gather_base(G, op);
+  base.istride = 1; base.ostride = s;
+  const long long xb = gathered_elems(G) * 2, wb = (long long)G.Co * G.w_row * 2;
+  // all s*s phases in ONE launch of the LDS-DMA kernel (blockIdx.z = phase) when that kernel applies
+  if (bf16 && !sw.no_merge && s * s <= MAX_PHASES && s > 1 && G.Ci % 64 == 0 && xb < (1ll << 31) && wb < (1ll << 31) && G.Cst > 32) {
+    GatherItem it{base, {}};
+    GatherArgs& a = it.a;
+    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
+    a.diag = sw.diag;
+    bool ok = true;
+    int np = 0;
+    for (int py = 0; py < s && ok; ++py)
+      for (int px = 0; px < s && ok; ++px) {
+        GatherArgs::Phase& ph = a.ph[np];
+        ph.Qh = (G.Ho - py + s - 1) / s; ph.Qw = (G.Wo - px + s - 1) / s;
+        if (ph.Qh <= 0 || ph.Qw <= 0) continue;
+        ph.M = G.N * ph.Qh * ph.Qw; ph.oy0 = py; ph.ox0 = px;
+        ph.T = phase_taps(G, py, px, ph.tap, PHASE_TAPS);
+        if (ph.T <= 0) { ok = false; break; }            // too many taps; or none -- that phase still has to store zeros / bias: generic path
+        ph.Ktot = ph.T * G.Ci;
+        ph.npix_tiles = cdiv(ph.M, 128);
+        ++np;
       }
+    if (ok && np > 0) {
+      a.nphase = np;
+      it.c.path = ConvPath::Phases;
+      it.c.bco = a.Cst > 64 ? 128 : 64;
+      a.nco_tiles = cdiv(a.Cst, it.c.bco);
+      // phase-fastest 1-D grid (see conv_dma_kernel) for the 64-row weight tile: HBM reads of the decoder's 128 -> 64 transposed conv
+      // 117 -> 30 MB (= its input once) at the same duration, the 64 -> 128 stride-2 dgrad 55 -> 33 MB and 6 % faster; the 128-row tile
+      // keeps the phase in blockIdx.z (measured: 41 -> 48 us on the 128 -> 256 stride-2 dgrad with the phases interleaved)
+      a.phase_fast = (it.c.bco == 64 && !sw.no_phase_fast()) ? 1 : 0;
+      P.add(it);
+      return 0;
     }
   }
   for (int py = 0; py < s; ++py)
     for (int px = 0; px < s; ++px) {
-      GatherArgs a{};
-      a.ws = sc.ws; a.ws_bytes = sc.bytes; a.plan = sc.plan; a.mat = sc.mat; a.mat_done = sc.mat_done;
-      a.x = x; a.w = w; a.bias = bias; a.aux = aux; a.aux2 = aux2; a.y = y;
-      a.Hi = G.Hi; a.Wi = G.Wi;
+      GatherArgs a = base;
       a.Qh = (G.Ho - py + s - 1) / s; a.Qw = (G.Wo - px + s - 1) / s;
       if (a.Qh <= 0 || a.Qw <= 0) continue;
-      a.M = G.N * a.Qh * a.Qw;
-      a.Cin = G.Ci; a.x_pitch = G.xp; a.x_gstride = G.xg;
-      a.Cout = G.Co; a.Cst = G.Cst; a.y_pitch = G.yp; a.y_gstride = G.yg;
-      a.Ho = G.Ho; a.Wo = G.Wo; a.istride = 1; a.ostride = s; a.oy0 = py; a.ox0 = px;
-      a.w_row = G.w_row; a.w_gstride = G.w_gstride;
-      a.reflect = 0; a.act = act; a.epi = epi; a.slope = slope; a.gact = gact; a.gslope = gslope;
-      int t = 0;
-      for (int ky = 0; ky < G.KH; ++ky) {
-        if ((py + G.pad - ky) % s != 0) continue;
-        for (int kx = 0; kx < G.KW; ++kx) {
-          if ((px + G.pad - kx) % s != 0) continue;
-          if (t >= MAX_TAPS) S2P_FAIL(-2, "conv: more than %d taps", MAX_TAPS);
-          a.tap[t++] = pack_tap((py + G.pad - ky) / s, (px + G.pad - kx) / s, ky * G.KW + kx);
-        }
-      }
-      a.T = t; a.Ktot = t * G.Ci;
-      int rc = launch_gather<T>(a, G.groups, gathered_elems(G), st);
-      if (rc) return rc;
+      a.M = G.N * a.Qh * a.Qw; a.oy0 = py; a.ox0 = px;
+      a.T = phase_taps(G, py, px, a.tap, MAX_TAPS);
+      if (a.T < 0) S2P_FAIL(-2, "conv: more than %d taps", MAX_TAPS);
+      a.Ktot = a.T * G.Ci;
+      if (a.M > 0) P.add(plan_gather(a, bf16, G.groups, gathered_elems(G), want, sc));
     }
   return 0;
 }
@@ -1563,25 +1567,18 @@ static int check_desc(const s2p_conv_desc* d, const char* who) {
   return 0;
 }
 
-static int conv_fwd_impl(const s2p_conv_desc* d, const void* x, const void* w_fwd, const float* bias, const void* aux,
-                         void* y, int act, float slope, int epi, const Scratch& sc, void* stream) {
+// forward: the thin kernels first (each takes the whole call), then the generic problem
+static int conv_plan_fwd(const s2p_conv_desc* d, const ConvOperands& op, const NormWant& want, const ScratchAvail& sc, ConvPlan& P) {
   int rc = check_desc(d, "s2p_conv2d_fwd");
   if (rc) return rc;
-  S2P_CHECK_SLOPE("s2p_conv2d_fwd", act, slope);
-  if (sc.mat) S2P_CHECK_SLOPE("s2p_conv2d_fwd_mat", sc.mat->act, sc.mat->slope);
-  if (!sc.plan) {
-    if (!x || !w_fwd || (!y && !sc.mat)) S2P_FAIL(-1, "s2p_conv2d_fwd: null pointer");      // (y == NULL: s2p_conv2d_fwd_mat checked that the launch is fused)
-    if (epi != S2P_EPI_STORE && !aux) S2P_FAIL(-1, "s2p_conv2d_fwd: epi needs aux");
+  const ConvSwitches& sw = conv_switches();
+  if (op.epi == S2P_EPI_STORE && s2p_thin_applicable(d)) { P.path = ConvPath::Thin; return 0; }
+  if (!sw.no_thin4() && s2p_thin4_fwd_applicable(d, op.act, op.epi)) {      // 7x7, <= 4 real input channels (the generator's stem)
+    const size_t need = s2p_thin4_fwd_ws_bytes(d);
+    if (sc.any && sc.bytes >= need) { P.path = ConvPath::Thin4; P.ws_bytes = need; return 0; }      // no scratch: the next path
   }
-  hipStream_t st = (hipStream_t)stream;
-  int ce = d->dtype == S2P_F32 ? 4 : 8;
-  if (epi == S2P_EPI_STORE && s2p_thin_applicable(d)) return sc.plan ? 0 : s2p_thin_fwd(d, x, w_fwd, bias, y, act, slope, st);
-  if (!S2P_DIAG_SWITCH(3) && s2p_thin4_fwd_applicable(d, act, epi)) {      // 7x7, <= 4 real input channels (the generator's stem)
-    if (sc.plan) { const size_t need = s2p_thin4_fwd_ws_bytes(d); if (need > *sc.plan) *sc.plan = need; return 0; }
-    if (sc.ws && sc.bytes >= s2p_thin4_fwd_ws_bytes(d)) return s2p_thin4_fwd(d, x, w_fwd, bias, y, act, slope, sc.ws, sc.bytes, st);
-  }
-  static const int no_cin = s2p_env_set("S2P_NO_THIN_CIN");          // A/B switch (diagnostics build only)
-  if (!no_cin && s2p_thin_cin_fwd_applicable(d, act, epi)) return sc.plan ? 0 : s2p_thin_cin_fwd(d, x, w_fwd, bias, y, act, slope, st);
+  if (!sw.no_thin_cin && s2p_thin_cin_fwd_applicable(d, op.act, op.epi)) { P.path = ConvPath::ThinCin; return 0; }
+  const int ce = d->dtype == S2P_F32 ? 4 : 8;
   Geo G{d->N, d->H, d->W, d->Cin, d->x_pitch, d->x_gstride, d->Ho, d->Wo, d->Cout,
         /*Cst*/ d->groups == 1 ? ((d->Cout + ce - 1) / ce * ce <= d->y_pitch ? (d->Cout + ce - 1) / ce * ce : d->Cout)
                                : d->Cout,
@@ -1589,89 +1586,200 @@ static int conv_fwd_impl(const s2p_conv_desc* d, const void* x, const void* w_fw
         (long long)d->Cout * d->KH * d->KW * d->Cin, d->KH * d->KW * d->Cin};
   if (d->transposed) {
     if (d->reflect) S2P_FAIL(-1, "s2p_conv2d_fwd: reflect + transposed unsupported");
-    return d->dtype == S2P_F32 ? run_scatter<float>(G, x, w_fwd, bias, aux, nullptr, y, act, slope, epi, 0, 0.f, st, sc)
-                               : run_scatter<__bf16>(G, x, w_fwd, bias, aux, nullptr, y, act, slope, epi, 0, 0.f, st, sc);
+    return plan_scatter_problem(G, d->dtype == S2P_BF16, op, want, sc, P);
   }
-  return d->dtype == S2P_F32 ? run_gather<float>(G, x, w_fwd, bias, aux, nullptr, y, act, slope, epi, 0, 0.f, st, sc)
-                             : run_gather<__bf16>(G, x, w_fwd, bias, aux, nullptr, y, act, slope, epi, 0, 0.f, st, sc);
+  return plan_gather_problem(G, d->dtype == S2P_BF16, op, want, sc, P);
+}
+
+// dgrad: gathered tensor = dy (grid Ho x Wo, channels Cout), produced tensor = dx (grid H x W, channels Cin).
+// With reflect padding the produced grid is the PADDED one, (H+2p) x (W+2p): fold it with s2p_reflect_pad_bwd.
+static int conv_plan_dgrad(const s2p_conv_desc* d, const ConvOperands& op, const NormWant& want, const ScratchAvail& sc, ConvPlan& P) {
+  int rc = check_desc(d, "s2p_conv2d_dgrad");
+  if (rc) return rc;
+  const int ce = d->dtype == S2P_F32 ? 4 : 8;
+  const int cout_pad = P.cout_pad = (d->Cout + ce - 1) / ce * ce;       // channels of dy actually gathered
+  if (cout_pad > d->y_pitch) S2P_FAIL(-1, "s2p_conv2d_dgrad: dy pitch %d < padded Cout %d", d->y_pitch, cout_pad);
+  if (!ConvSwitches::no_thin4() && op.epi == S2P_EPI_STORE && s2p_thin4_dgrad_applicable(d, cout_pad)) {      // 7x7, <= 4 output channels (the generator's output conv)
+    const size_t need = s2p_thin4_dgrad_ws_bytes(d);
+    if (sc.any && sc.bytes >= need) { P.path = ConvPath::Thin4; P.ws_bytes = need; return 0; }      // no scratch: the next path
+  }
+  // thin input (<= 8 channels), stride 1: the adjoint is a thin-Cout conv over dy (row-streaming kernel, thin_rows.hip)
+  if (op.epi == S2P_EPI_STORE && s2p_thin_rows_dgrad_applicable(d, cout_pad)) { P.path = ConvPath::ThinRows; return 0; }
+  int H = d->H, W = d->W, pad = d->pad;
+  if (d->reflect) { H += 2 * pad; W += 2 * pad; pad = 0; }
+  Geo G{d->N, d->Ho, d->Wo, cout_pad, d->y_pitch, d->y_gstride, H, W, d->Cin, d->Cin,
+        d->x_pitch, d->x_gstride, d->KH, d->KW, d->stride, pad, 0, d->groups,
+        (long long)d->Cin * d->KH * d->KW * cout_pad, d->KH * d->KW * cout_pad};
+  if (d->transposed) return plan_gather_problem(G, d->dtype == S2P_BF16, op, want, sc, P);   // adjoint of a scatter is a gather
+  return plan_scatter_problem(G, d->dtype == S2P_BF16, op, want, sc, P);
+}
+
+// ---- launching --------------------------------------------------------------------------------------------------------------
+template <int BCO>
+static int launch_bf16(GatherArgs& a, const GatherChoice& c, int groups, void* ws, hipStream_t st) {
+  const int extra_lds = conv_switches().halo_extra_lds;
+  dim3 grid(a.npix_tiles * a.nco_tiles, groups);
+  switch (c.path) {
+    case ConvPath::Halo:
+      if constexpr (BCO == 128) {
+        switch (c.halo) {
+          case HaloKind::S9_176_PIPE: hipLaunchKernelGGL((conv_halo_kernel<176, true, 9, true>), grid, dim3(256), extra_lds, st, a); break;
+          case HaloKind::S9_176: hipLaunchKernelGGL((conv_halo_kernel<176, true, 9>), grid, dim3(256), extra_lds, st, a); break;
+          case HaloKind::S9_320: hipLaunchKernelGGL((conv_halo_kernel<320, false, 9>), grid, dim3(256), 0, st, a); break;
+          case HaloKind::R_176: hipLaunchKernelGGL((conv_halo_kernel<176, true>), grid, dim3(256), extra_lds, st, a); break;
+          case HaloKind::R_320: hipLaunchKernelGGL((conv_halo_kernel<320, false>), grid, dim3(256), 0, st, a); break;
+        }
+        S2P_CHECK_LAUNCH("conv_halo_kernel");
+      }
+      return 0;
+    case ConvPath::SplitK: {
+      a.part = (float*)ws;
+      grid.z = a.psplit;
+      hipLaunchKernelGGL((conv_dma_kernel<BCO, 128, 2, 2>), grid, dim3(256), 0, st, a);
+      S2P_CHECK_LAUNCH("conv_dma_kernel(split)");
+      const long long n = (long long)(a.part_m / 4) * ((a.Cst + 7) / 8);
+      hipLaunchKernelGGL(conv_part_reduce_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, a);
+      S2P_CHECK_LAUNCH("conv_part_reduce_kernel");
+      return 0;
+    }
+    case ConvPath::Fast:
+      hipLaunchKernelGGL((conv_fast_kernel<BCO, 128, 2, 2>), grid, dim3(256), 0, st, a);
+      S2P_CHECK_LAUNCH("conv_fast_kernel");
+      return 0;
+    default:
+      hipLaunchKernelGGL((conv_dma_kernel<BCO, 128, 2, 2>), grid, dim3(256), 0, st, a);
+      S2P_CHECK_LAUNCH("conv_dma_kernel");
+      return 0;
+  }
+}
+
+template <typename T>
+static int launch_generic(GatherArgs& a, int groups, hipStream_t st) {
+  if (a.Cst > 64) return launch_cfg<T, 128, 128, 2, 2>(a, groups, st);
+  if (a.Cst > 32) return launch_cfg<T, 64, 128, 2, 2>(a, groups, st);
+  return launch_cfg<T, 32, 256, 1, 4>(a, groups, st);
+}
+
+// One launch of a planned call; `mat`: the norm operands where the launch is fused.  (hipcc lays the kernel templates out in the code
+// object in the order this function first names them -- fp32 generic, phases, the bf16 tile kernels, bf16 generic, the order they
+// have always had; keeping it keeps the device code byte-identical across host-only changes.)
+static int launch_item(GatherItem& it, bool bf16, int groups, const PlaneMat* mat, void* ws, hipStream_t st) {
+  if (!bf16) return launch_generic<float>(it.a, groups, st);      // fp32 is always ConvPath::Generic
+  switch (it.c.path) {
+    case ConvPath::Plane:
+      if (it.c.fused) copy_norm(it.c.plane, *mat);
+      return s2p_conv_plane_launch(it.c.plane, groups, st);
+    case ConvPath::PlaneG:
+      if (it.c.fused) copy_norm(it.c.planeg, *mat);
+      return s2p_conv_planeg_launch(it.c.planeg, groups, st);
+    case ConvPath::Phases: {                                        // all sub-pixel phases as one launch of the LDS-DMA kernel
+      GatherArgs& a = it.a;
+      int max_npt = 0;
+      for (int i = 0; i < a.nphase; ++i) if (a.ph[i].npix_tiles > max_npt) max_npt = a.ph[i].npix_tiles;
+      const dim3 grid = a.phase_fast ? dim3(((max_npt * a.nco_tiles + 7) / 8) * 8 * a.nphase, groups, 1) : dim3(max_npt * a.nco_tiles, groups, a.nphase);
+      if (it.c.bco == 128) hipLaunchKernelGGL((conv_dma_kernel<128, 128, 2, 2>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((conv_dma_kernel<64, 128, 2, 2>), grid, dim3(256), 0, st, a);
+      S2P_CHECK_LAUNCH("conv_dma_kernel(phases)");
+      return 0;
+    }
+    case ConvPath::Generic: break;
+    default: return it.c.bco == 128 ? launch_bf16<128>(it.a, it.c, groups, ws, st) : launch_bf16<64>(it.a, it.c, groups, ws, st);
+  }
+  return launch_generic<__bf16>(it.a, groups, st);
+}
+static int launch_items(ConvPlan& P, bool bf16, int groups, const PlaneMat* mat, const Scratch& sc, hipStream_t st) {
+  for (GatherItem& it : P.items) {
+    const int rc = launch_item(it, bf16, groups, mat, sc.ws, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// mat != NULL (s2p_conv2d_fwd_mat): *fused tells the caller whether the norm went with the conv; y may be NULL only then
+static int conv_fwd_impl(const s2p_conv_desc* d, const ConvOperands& op, const PlaneMat* mat, bool* fused, const Scratch& sc, void* stream) {
+  S2P_CHECK_SLOPE("s2p_conv2d_fwd", op.act, op.slope);
+  if (mat) S2P_CHECK_SLOPE("s2p_conv2d_fwd_mat", mat->act, mat->slope);
+  ConvPlan P;
+  int rc = conv_plan_fwd(d, op, NormWant{mat != nullptr, mat && mat->gb, false}, ScratchAvail{sc.ws != nullptr, sc.bytes}, P);
+  if (rc) return rc;
+  if (!op.x || !op.w || (!op.y && !mat)) S2P_FAIL(-1, "s2p_conv2d_fwd: null pointer");
+  if (op.epi != S2P_EPI_STORE && !op.aux) S2P_FAIL(-1, "s2p_conv2d_fwd: epi needs aux");
+  if (!op.y && !P.fused) S2P_FAIL(-1, "s2p_conv2d_fwd_mat: y == NULL needs the fused launch (s2p_conv2d_mat_is_fused)");
+  if (fused) *fused = P.fused;
+  hipStream_t st = (hipStream_t)stream;
+  switch (P.path) {
+    case ConvPath::Thin: return s2p_thin_fwd(d, op.x, op.w, op.bias, op.y, op.act, op.slope, st);
+    case ConvPath::Thin4: return s2p_thin4_fwd(d, op.x, op.w, op.bias, op.y, op.act, op.slope, sc.ws, sc.bytes, st);
+    case ConvPath::ThinCin: return s2p_thin_cin_fwd(d, op.x, op.w, op.bias, op.y, op.act, op.slope, st);
+    default: return launch_items(P, d->dtype == S2P_BF16, d->groups, mat, sc, st);
+  }
 }
 
 extern "C" int s2p_conv2d_fwd(const s2p_conv_desc* d, const void* x, const void* w_fwd, const float* bias,
                               const void* aux, void* y, int act, float slope, int epi, void* stream) {
-  return conv_fwd_impl(d, x, w_fwd, bias, aux, y, act, slope, epi, Scratch{nullptr, 0, nullptr}, stream);
+  return conv_fwd_impl(d, ConvOperands{x, w_fwd, bias, aux, nullptr, y, act, slope, epi, 0, 0.f}, nullptr, nullptr, Scratch{nullptr, 0}, stream);
 }
 extern "C" int s2p_conv2d_fwd_ws(const s2p_conv_desc* d, const void* x, const void* w_fwd, const float* bias,
                                  const void* aux, void* y, int act, float slope, int epi, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  return conv_fwd_impl(d, x, w_fwd, bias, aux, y, act, slope, epi, Scratch{workspace, workspace_bytes, nullptr}, stream);
+  return conv_fwd_impl(d, ConvOperands{x, w_fwd, bias, aux, nullptr, y, act, slope, epi, 0, 0.f}, nullptr, nullptr,
+                       Scratch{workspace, workspace_bytes}, stream);
 }
 extern "C" int s2p_conv2d_fwd_mat(const s2p_conv_desc* d, const void* x, const void* w_fwd, const float* bias, const void* aux,
                                   void* y, int epi, const void* gb_img, int gb_pitch, const float* gb_st, int gb_st_pitch,
                                   int act, float slope, float eps, void* y_mat, int y_mat_pitch, float* stats, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   if (!d || !y_mat || !stats) S2P_FAIL(-1, "s2p_conv2d_fwd_mat: null pointer");
-  // y == NULL: the conv output itself is not wanted (a forward pass without a backward: it is written only for the backward's sake) --
-  // allowed where conv and norm are ONE launch, which then skips that store
-  if (!y && !s2p_conv2d_mat_is_fused(d, 0, gb_img != nullptr))
-    S2P_FAIL(-1, "s2p_conv2d_fwd_mat: y == NULL needs the fused launch (s2p_conv2d_mat_is_fused)");
   if (act != S2P_ACT_NONE && act != S2P_ACT_RELU && act != S2P_ACT_LRELU) S2P_FAIL(-1, "s2p_conv2d_fwd_mat: activation must be none / relu / lrelu");
   if (d->groups != 1 || d->transposed) S2P_FAIL(-1, "s2p_conv2d_fwd_mat: groups == 1, not transposed");
   PlaneMat m{y_mat, y_mat_pitch, gb_img, gb_pitch, gb_st, gb_st_pitch, stats, act, slope, eps, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0};
-  int done = 0;
-  int rc = conv_fwd_impl(d, x, w_fwd, bias, aux, y, S2P_ACT_NONE, 0.f, epi, Scratch{workspace, workspace_bytes, nullptr, &m, &done}, stream);
-  if (rc || done) return rc;
-  if (!y) S2P_FAIL(-1, "s2p_conv2d_fwd_mat: y == NULL but the launch was not fused");
-  // shapes the plane-resident kernel does not take: the conv above + the norm as its own launch(es)
+  // y == NULL: the conv output itself is not wanted (a forward pass without a backward: it is written only for the backward's sake) --
+  // allowed where conv and norm are ONE launch, which then skips that store; refused (before any launch) otherwise
+  bool fused = false;
+  int rc = conv_fwd_impl(d, ConvOperands{x, w_fwd, bias, aux, nullptr, y, S2P_ACT_NONE, 0.f, epi, 0, 0.f}, &m, &fused,
+                         Scratch{workspace, workspace_bytes}, stream);
+  if (rc || fused) return rc;
+  // shapes the plane-resident kernels do not take: the conv above + the norm as its own launch(es)
   return s2p_in_norm_fwd(d->dtype, y, d->N, d->Ho * d->Wo, d->Cout, d->y_pitch, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope,
                          eps, y_mat, y_mat_pitch, stats, stream);
 }
 extern "C" size_t s2p_conv2d_fwd_workspace(const s2p_conv_desc* d, int epi) {
-  size_t need = 0;
-  if (conv_fwd_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, S2P_ACT_NONE, 0.f, epi, Scratch{nullptr, 0, &need}, nullptr)) return 0;
-  return need;
+  ConvPlan P;
+  if (conv_plan_fwd(d, ConvOperands{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, S2P_ACT_NONE, 0.f, epi, 0, 0.f}, NormWant{}, SCRATCH_UNLIMITED, P)) return 0;
+  return P.ws_bytes;
 }
 
-// dgrad: gathered tensor = dy (grid Ho x Wo, channels Cout), produced tensor = dx (grid H x W, channels Cin).
-// With reflect padding the produced grid is the PADDED one, (H+2p) x (W+2p): fold it with s2p_reflect_pad_bwd.
-static int conv_dgrad_impl(const s2p_conv_desc* d, const void* dy, const void* w_bwd, const void* aux, const void* aux2,
-                           void* dx, int epi, int aux_act, float slope, const Scratch& sc, void* stream) {
-  int rc = check_desc(d, "s2p_conv2d_dgrad");
+// must_fuse (s2p_conv2d_dgrad_mat without the scratch of its two-launch form): refuse, before any launch, unless the norm backward
+// goes with the dgrad
+static int conv_dgrad_impl(const s2p_conv_desc* d, const ConvOperands& op, const PlaneMat* mat, bool must_fuse, bool* fused, const Scratch& sc,
+                           void* stream) {
+  ConvPlan P;
+  int rc = conv_plan_dgrad(d, op, NormWant{mat != nullptr, mat && mat->gb, true}, ScratchAvail{sc.ws != nullptr, sc.bytes}, P);
   if (rc) return rc;
-  if (!sc.plan) {
-    if (!dy || !w_bwd || !dx) S2P_FAIL(-1, "s2p_conv2d_dgrad: null pointer");
-    if (epi != S2P_EPI_STORE && !aux) S2P_FAIL(-1, "s2p_conv2d_dgrad: epi needs aux");
-  }
+  if (!op.x || !op.w || !op.y) S2P_FAIL(-1, "s2p_conv2d_dgrad: null pointer");
+  if (op.epi != S2P_EPI_STORE && !op.aux) S2P_FAIL(-1, "s2p_conv2d_dgrad: epi needs aux");
+  if (must_fuse && !P.fused)
+    S2P_FAIL(-1, "s2p_conv2d_dgrad_mat: dgrad and norm backward are two launches for these arguments (s2p_conv2d_mat_is_fused; an aux "
+                 "gradient fuses only on the 4x4 family): d_mid and sums are required");
+  if (fused) *fused = P.fused;
   hipStream_t st = (hipStream_t)stream;
-  int ce = d->dtype == S2P_F32 ? 4 : 8;
-  int cout_pad = (d->Cout + ce - 1) / ce * ce;       // channels of dy actually gathered
-  if (cout_pad > d->y_pitch) S2P_FAIL(-1, "s2p_conv2d_dgrad: dy pitch %d < padded Cout %d", d->y_pitch, cout_pad);
-  if (!S2P_DIAG_SWITCH(3) && epi == S2P_EPI_STORE && s2p_thin4_dgrad_applicable(d, cout_pad)) {      // 7x7, <= 4 output channels (the generator's output conv)
-    if (sc.plan) { const size_t need = s2p_thin4_dgrad_ws_bytes(d); if (need > *sc.plan) *sc.plan = need; return 0; }
-    if (sc.ws && sc.bytes >= s2p_thin4_dgrad_ws_bytes(d)) return s2p_thin4_dgrad(d, dy, w_bwd, dx, cout_pad, sc.ws, sc.bytes, st);
+  switch (P.path) {
+    case ConvPath::Thin4: return s2p_thin4_dgrad(d, op.x, op.w, op.y, P.cout_pad, sc.ws, sc.bytes, st);
+    case ConvPath::ThinRows: return s2p_thin_rows_dgrad(d, op.x, op.w, op.y, P.cout_pad, st);
+    default: return launch_items(P, d->dtype == S2P_BF16, d->groups, mat, sc, st);
   }
-  // thin input (<= 8 channels), stride 1: the adjoint is a thin-Cout conv over dy (row-streaming kernel, thin_rows.hip)
-  if (epi == S2P_EPI_STORE && s2p_thin_rows_dgrad_applicable(d, cout_pad))
-    return sc.plan ? 0 : s2p_thin_rows_dgrad(d, dy, w_bwd, dx, cout_pad, st);
-  int H = d->H, W = d->W, pad = d->pad;
-  if (d->reflect) { H += 2 * pad; W += 2 * pad; pad = 0; }
-  Geo G{d->N, d->Ho, d->Wo, cout_pad, d->y_pitch, d->y_gstride, H, W, d->Cin, d->Cin,
-        d->x_pitch, d->x_gstride, d->KH, d->KW, d->stride, pad, 0, d->groups,
-        (long long)d->Cin * d->KH * d->KW * cout_pad, d->KH * d->KW * cout_pad};
-  if (d->transposed)   // adjoint of a scatter is a gather
-    return d->dtype == S2P_F32 ? run_gather<float>(G, dy, w_bwd, nullptr, aux, aux2, dx, S2P_ACT_NONE, 0.f, epi, aux_act, slope, st, sc)
-                               : run_gather<__bf16>(G, dy, w_bwd, nullptr, aux, aux2, dx, S2P_ACT_NONE, 0.f, epi, aux_act, slope, st, sc);
-  return d->dtype == S2P_F32 ? run_scatter<float>(G, dy, w_bwd, nullptr, aux, aux2, dx, S2P_ACT_NONE, 0.f, epi, aux_act, slope, st, sc)
-                             : run_scatter<__bf16>(G, dy, w_bwd, nullptr, aux, aux2, dx, S2P_ACT_NONE, 0.f, epi, aux_act, slope, st, sc);
 }
 
 extern "C" int s2p_conv2d_dgrad(const s2p_conv_desc* d, const void* dy, const void* w_bwd, const void* aux,
                                 const void* aux2, void* dx, int epi, int aux_act, float slope, void* stream) {
-  return conv_dgrad_impl(d, dy, w_bwd, aux, aux2, dx, epi, aux_act, slope, Scratch{nullptr, 0, nullptr}, stream);
+  return conv_dgrad_impl(d, ConvOperands{dy, w_bwd, nullptr, aux, aux2, dx, S2P_ACT_NONE, 0.f, epi, aux_act, slope}, nullptr, false, nullptr,
+                         Scratch{nullptr, 0}, stream);
 }
 extern "C" int s2p_conv2d_dgrad_ws(const s2p_conv_desc* d, const void* dy, const void* w_bwd, const void* aux,
                                    const void* aux2, void* dx, int epi, int aux_act, float slope, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-  return conv_dgrad_impl(d, dy, w_bwd, aux, aux2, dx, epi, aux_act, slope, Scratch{workspace, workspace_bytes, nullptr}, stream);
+  return conv_dgrad_impl(d, ConvOperands{dy, w_bwd, nullptr, aux, aux2, dx, S2P_ACT_NONE, 0.f, epi, aux_act, slope}, nullptr, false, nullptr,
+                         Scratch{workspace, workspace_bytes}, stream);
 }
 extern "C" int s2p_conv2d_dgrad_mat(const s2p_conv_desc* d, const void* dy, const void* w_bwd, void* d_mid, const void* aux, const void* xn,
                                     int xn_pitch, const float* stats, const void* gb_img, int gb_pitch, const float* gb_st,
@@ -1684,15 +1792,12 @@ extern "C" int s2p_conv2d_dgrad_mat(const s2p_conv_desc* d, const void* dy, cons
   if (d->Cin != d->x_pitch) S2P_FAIL(-1, "s2p_conv2d_dgrad_mat: the produced tensor must be dense (x_pitch %d != Cin %d)", d->x_pitch, d->Cin);
   PlaneMat m{dxn, dxn_pitch, gb_img, gb_pitch, gb_st, gb_st_pitch, const_cast<float*>(stats), act, slope, eps,
              xn, xn_pitch, dgb_img, dgb_pitch, dgb_st, dgb_st_pitch, res, res_pitch};
-  if (!d_mid || !sums) {                  // scratch of the two-launch form left out: the caller relies on the fused kernel
-    if (!s2p_conv2d_mat_is_fused(d, 1, gb_img != nullptr))
-      S2P_FAIL(-1, "s2p_conv2d_dgrad_mat: this shape runs as two launches and needs d_mid and sums (s2p_conv2d_mat_is_fused)");
-  }
-  int done = 0;
-  int rc = conv_dgrad_impl(d, dy, w_bwd, aux, nullptr, d_mid ? d_mid : dxn, aux ? S2P_EPI_ADD : S2P_EPI_STORE, S2P_ACT_NONE, 0.f,
-                           Scratch{workspace, workspace_bytes, nullptr, &m, &done}, stream);
-  if (rc || done) return rc;
-  if (!d_mid || !sums) S2P_FAIL(-1, "s2p_conv2d_dgrad_mat: not fused for these arguments (an aux gradient fuses only on the 4x4 family): d_mid and sums are required");
+  // d_mid / sums (scratch of the two-launch form) left out: the caller relies on the fused kernel, which does not store the dgrad
+  bool fused = false;
+  int rc = conv_dgrad_impl(d, ConvOperands{dy, w_bwd, nullptr, aux, nullptr, d_mid ? d_mid : dxn, S2P_ACT_NONE, 0.f,
+                                           aux ? S2P_EPI_ADD : S2P_EPI_STORE, S2P_ACT_NONE, 0.f},
+                           &m, !d_mid || !sums, &fused, Scratch{workspace, workspace_bytes}, stream);
+  if (rc || fused) return rc;
   // shapes the plane-resident kernels do not take: the dgrad above wrote d_mid; the norm backward as its own launch(es)
   return s2p_in_norm_bwd_res(d->dtype, d_mid, d->x_pitch, xn, d->N, d->H * d->W, d->Cin, xn_pitch, stats, gb_img, gb_pitch, gb_st,
                              gb_st_pitch, act, slope, eps, sums, dxn, dxn_pitch, dgb_img, dgb_pitch, dgb_st, dgb_st_pitch, res,
@@ -1700,16 +1805,15 @@ extern "C" int s2p_conv2d_dgrad_mat(const s2p_conv_desc* d, const void* dy, cons
 }
 extern "C" int s2p_conv2d_mat_is_fused(const s2p_conv_desc* d, int dgrad, int has_gb) {
   if (!d || d->groups != 1 || d->transposed || d->reflect) return 0;
-  static const char dummy[16] = {0};
-  PlaneMat m{};
-  m.y2 = (void*)dummy; m.gb = has_gb ? dummy : nullptr; m.xn = dgrad ? dummy : nullptr;
-  int done = 0; size_t need = 0;
-  const int rc = dgrad ? conv_dgrad_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, S2P_EPI_STORE, S2P_ACT_NONE, 0.f, Scratch{nullptr, 0, &need, &m, &done}, nullptr)
-                       : conv_fwd_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, S2P_ACT_NONE, 0.f, S2P_EPI_STORE, Scratch{nullptr, 0, &need, &m, &done}, nullptr);
-  return rc == 0 && done ? 1 : 0;
+  const ConvOperands op{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, S2P_ACT_NONE, 0.f, S2P_EPI_STORE, S2P_ACT_NONE, 0.f};
+  const NormWant want{true, has_gb != 0, dgrad != 0};
+  ConvPlan P;
+  const int rc = dgrad ? conv_plan_dgrad(d, op, want, SCRATCH_UNLIMITED, P) : conv_plan_fwd(d, op, want, SCRATCH_UNLIMITED, P);
+  return rc == 0 && P.fused ? 1 : 0;
 }
 extern "C" size_t s2p_conv2d_dgrad_workspace(const s2p_conv_desc* d) {
-  size_t need = 0;
-  if (conv_dgrad_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, S2P_EPI_STORE, S2P_ACT_NONE, 0.f, Scratch{nullptr, 0, &need}, nullptr)) return 0;
-  return need;
+  ConvPlan P;
+  if (conv_plan_dgrad(d, ConvOperands{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, S2P_ACT_NONE, 0.f, S2P_EPI_STORE, S2P_ACT_NONE, 0.f},
+                      NormWant{}, SCRATCH_UNLIMITED, P)) return 0;
+  return P.ws_bytes;
 }

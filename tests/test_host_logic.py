@@ -101,6 +101,179 @@ def test_fused_norm_dispatch_is_host_logic():
         assert fused(*a) == 0, a
 
 
+def _step_conv_descs():
+    """(name, ConvDesc) of every conv launch geometry of the bs-64 84x84 bf16 train step (generator, both discriminator scales, VGG19)
+    and of the generator forward of the bs-16 256x256 rollout.  The layers come from the networks' own constructors (`lay`); only the
+    way a tensor's size travels from layer to layer is restated here (ConvGeom.out_hw, the pools' rounding)."""
+    from s2p_amd.models.networks.loss import VGG19, VGG_CFG
+    from s2p_amd.ops import pad_to
+    bf = torch.bfloat16
+    opt = TrainOptions().parse(["--gpu_ids", "0"], quiet=True)
+    netG, netD, vgg = networks.define_G(opt), networks.define_D(opt), VGG19()
+    for net in (netG, netD, vgg):
+        net._declare_packs(bf)
+    out = []
+
+    def add(name, lay, N, H, W, x_pitch=None, y_pitch=None, geom=None):
+        g = geom or lay.geom
+        cp = lay.cin_pad(bf)
+        xp = x_pitch or cp * g.groups
+        yp = y_pitch or pad_to(g.cout * g.groups, 8)
+        out.append((name, g.desc(bf, N, H, W, cp, xp, yp)))
+        return g.out_hw(H, W)
+
+    def generator(tag, N, S):
+        L = netG.lay
+        q = S >> netG.n_down
+        add(tag + "shared", L["shared"], N, q, q)
+        gb = L["gb"]
+        add(tag + "gb", gb, N, q, q)
+        gm = ops.ConvGeom(gb.geom.cin, gb.geom.cout, 3, 1, 1, groups=gb.geom.groups, x_gstride=gb.geom.x_gstride,
+                          y_gstride=N * q * q * gb.geom.cout)           # ConvLayer._group_major: one whole tensor per group
+        add(tag + "gb_group_major", gb, N, q, q, y_pitch=gb.geom.cout, geom=gm)
+        hw = (S, S)
+        names = ["stem"] + ["down%d" % i for i in range(netG.n_down)] + ["b%dc%d" % (b, j) for b in range(netG.n_blocks) for j in (0, 1)] \
+            + ["up%d" % i for i in range(netG.n_down)] + ["out"]
+        assert sorted(names + ["shared", "gb"]) == sorted(k for k, l in L.items() if l.geom.k > 1)
+        for n in names:
+            hw = add(tag + n, L[n], N, *hw)
+        assert hw == (S, S)
+
+    generator("G84/", 64, 84)
+    generator("G256/", 16, 256)
+    S = 84
+    for i, sub in enumerate(netD.subnets()):
+        hw = (S, S)
+        for n, lay in enumerate(sub.lay):
+            hw = add("D%d/model%d" % (i, n), lay, 64, *hw)
+        S = (S - 1) // 2 + 1                                            # ops.avgpool_fwd
+    hw = (84, 84)
+    for item in VGG_CFG:
+        if item == "P":
+            hw = (hw[0] // 2, hw[1] // 2)                               # ops.maxpool_fwd
+        else:
+            hw = add("VGG/" + item[0], vgg.lay[item[0]], 64, *hw)
+    return out
+
+
+def _conv_host_queries(d):
+    import ctypes
+    L = _lib.lib()
+    r = ctypes.byref(d)
+    return (int(L.s2p_conv2d_fwd_workspace(r, _lib.EPI_STORE)), int(L.s2p_conv2d_fwd_workspace(r, _lib.EPI_ADD)),
+            int(L.s2p_conv2d_dgrad_workspace(r)),
+            "".join(str(int(L.s2p_conv2d_mat_is_fused(r, dgrad, gb))) for dgrad in (0, 1) for gb in (0, 1)))
+
+
+# (fwd workspace bytes with EPI_STORE, with EPI_ADD, dgrad workspace bytes, s2p_conv2d_mat_is_fused for (forward, no gamma|beta),
+# (forward, gamma|beta), (backward, no gamma|beta), (backward, gamma|beta)) -- recorded before the dispatcher was split into
+# "select a path" and "launch it"
+_CONV_PIN = {
+    "G84/shared": (0, 0, 0, "0000"),
+    "G84/gb": (0, 0, 0, "0000"),
+    "G84/gb_group_major": (0, 0, 0, "0000"),
+    "G84/stem": (4268048, 0, 0, "0000"),
+    "G84/down0": (0, 0, 0, "0000"),
+    "G84/down1": (0, 0, 0, "0000"),
+    "G84/b0c0": (0, 0, 0, "1111"),
+    "G84/b0c1": (0, 0, 0, "1111"),
+    "G84/b1c0": (0, 0, 0, "1111"),
+    "G84/b1c1": (0, 0, 0, "1111"),
+    "G84/b2c0": (0, 0, 0, "1111"),
+    "G84/b2c1": (0, 0, 0, "1111"),
+    "G84/b3c0": (0, 0, 0, "1111"),
+    "G84/b3c1": (0, 0, 0, "1111"),
+    "G84/b4c0": (0, 0, 0, "1111"),
+    "G84/b4c1": (0, 0, 0, "1111"),
+    "G84/b5c0": (0, 0, 0, "1111"),
+    "G84/b5c1": (0, 0, 0, "1111"),
+    "G84/up0": (0, 0, 0, "0000"),
+    "G84/up1": (0, 0, 0, "0000"),
+    "G84/out": (0, 0, 4845584, "0000"),
+    "G256/shared": (0, 0, 0, "0000"),
+    "G256/gb": (0, 0, 0, "0000"),
+    "G256/gb_group_major": (0, 0, 0, "0000"),
+    "G256/stem": (8882192, 0, 0, "0000"),
+    "G256/down0": (0, 0, 0, "0000"),
+    "G256/down1": (0, 0, 0, "0000"),
+    "G256/b0c0": (0, 0, 0, "0000"),
+    "G256/b0c1": (0, 0, 0, "0000"),
+    "G256/b1c0": (0, 0, 0, "0000"),
+    "G256/b1c1": (0, 0, 0, "0000"),
+    "G256/b2c0": (0, 0, 0, "0000"),
+    "G256/b2c1": (0, 0, 0, "0000"),
+    "G256/b3c0": (0, 0, 0, "0000"),
+    "G256/b3c1": (0, 0, 0, "0000"),
+    "G256/b4c0": (0, 0, 0, "0000"),
+    "G256/b4c1": (0, 0, 0, "0000"),
+    "G256/b5c0": (0, 0, 0, "0000"),
+    "G256/b5c1": (0, 0, 0, "0000"),
+    "G256/up0": (0, 0, 0, "0000"),
+    "G256/up1": (0, 0, 0, "0000"),
+    "G256/out": (0, 0, 9290768, "0000"),
+    "D0/model0": (0, 0, 0, "0000"),
+    "D0/model1": (0, 0, 0, "0000"),
+    "D0/model2": (0, 0, 0, "1000"),
+    "D0/model3": (0, 0, 0, "1010"),
+    "D0/model4": (0, 0, 0, "0000"),
+    "D1/model0": (0, 0, 0, "0000"),
+    "D1/model1": (0, 0, 0, "1000"),
+    "D1/model2": (0, 0, 0, "1000"),
+    "D1/model3": (0, 0, 0, "1010"),
+    "D1/model4": (0, 0, 0, "0000"),
+    "VGG/conv1_1": (0, 0, 0, "0000"),
+    "VGG/conv1_2": (0, 0, 0, "0000"),
+    "VGG/conv2_1": (0, 0, 0, "0000"),
+    "VGG/conv2_2": (0, 0, 0, "0000"),
+    "VGG/conv3_1": (0, 0, 0, "1111"),
+    "VGG/conv3_2": (0, 0, 0, "1111"),
+    "VGG/conv3_3": (0, 0, 0, "1111"),
+    "VGG/conv3_4": (0, 0, 0, "1111"),
+    "VGG/conv4_1": (0, 0, 0, "1010"),
+    "VGG/conv4_2": (0, 0, 0, "1010"),
+    "VGG/conv4_3": (0, 0, 0, "1010"),
+    "VGG/conv4_4": (0, 0, 0, "1010"),
+    "VGG/conv5_1": (0, 0, 0, "0000"),
+}
+
+
+def test_conv_dispatch_answers_are_pinned_for_the_train_step_and_the_rollout():
+    """The host-side answers of the conv dispatcher (scratch bytes forward / backward, conv + norm as one launch or two) for every conv
+    geometry of the train step and the rollout forward, against a literal table: a change of the path selection shows up here
+    without a GPU."""
+    got = {name: _conv_host_queries(d) for name, d in _step_conv_descs()}
+    assert sorted(got) == sorted(_CONV_PIN)
+    assert {k: v for k, v in got.items() if v != _CONV_PIN[k]} == {}
+
+
+def _mat_refusal_args():
+    import ctypes
+    buf = (ctypes.c_char * 64)()                   # never dereferenced: the refusal comes before any launch
+    return ctypes.addressof(buf), buf
+
+
+def test_fwd_mat_without_y_is_refused_where_conv_and_norm_are_two_launches():
+    import ctypes
+    L = _lib.lib()
+    p, _keep = _mat_refusal_args()
+    d = ops.ConvGeom(64, 128, 4, 2, 2).desc(torch.bfloat16, 64, 43, 43, 64, 64, 128)
+    assert L.s2p_conv2d_mat_is_fused(ctypes.byref(d), 0, 0) == 0
+    rc = L.s2p_conv2d_fwd_mat(ctypes.byref(d), p, p, None, None, None, _lib.EPI_STORE, None, 0, None, 0, _lib.ACT_LRELU, 0.2, 1e-5,
+                              p, 128, p, None, 0, None)
+    assert rc != 0 and b"y == NULL" in L.s2p_last_error()
+
+
+def test_dgrad_mat_without_d_mid_is_refused_where_dgrad_and_norm_are_two_launches():
+    import ctypes
+    L = _lib.lib()
+    p, _keep = _mat_refusal_args()
+    d = ops.ConvGeom(128, 256, 4, 2, 2).desc(torch.bfloat16, 64, 22, 22, 128, 128, 256)
+    assert L.s2p_conv2d_mat_is_fused(ctypes.byref(d), 1, 0) == 0
+    rc = L.s2p_conv2d_dgrad_mat(ctypes.byref(d), p, p, None, None, p, 128, p, None, 0, None, 0, _lib.ACT_LRELU, 0.2, 1e-5, p, p, 128,
+                                None, 0, None, 0, None, 0, None, 0, None)
+    assert rc != 0 and b"d_mid" in L.s2p_last_error()
+
+
 def test_struct_layouts_match_header():
     import ctypes
     assert ctypes.sizeof(_lib.ConvDesc) == 20 * 4
