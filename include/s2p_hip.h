@@ -159,7 +159,8 @@ typedef struct { const void* x; const void* dy; float* dw; float* db; } s2p_wgra
 size_t s2p_conv2d_wgrad_batched_workspace(const s2p_conv_desc* d, int n_jobs, int cin_real, int cout_real);
 int s2p_conv2d_wgrad_batched(const s2p_conv_desc* d, const s2p_wgrad_job* jobs, int n_jobs, int cin_real,
                              int cout_real, void* workspace, size_t workspace_bytes, void* stream);
-/* adjoint of F.pad(mode='reflect'): dx[N,H,W,C] = fold(dxp[N,H+2p,W+2p,C])              */
+/* adjoint of F.pad(mode='reflect'): dx[N,H,W,C] = fold(dxp[N,H+2p,W+2p,C]).  C is the NHWC pitch (a multiple of the
+ * 16-byte chunk), dxp and dx 16-byte aligned, pad < H and pad < W (as F.pad requires).   */
 int s2p_reflect_pad_bwd(int dtype, const void* dxp, int N, int H, int W, int C, int pad, void* dx,
                         void* stream);
 /* db[c] += sum over pixels of dy[p][c]  (bias gradient; fp32 accumulate into db)        */
@@ -200,6 +201,8 @@ int s2p_in_bwd_reduce(int dtype, const void* da, int da_pitch, const void* x, in
                       int pitch, const float* stats, const void* gb_img, int gb_pitch,
                       const float* gb_st, int gb_st_pitch, int act, float slope, float eps,
                       float* sums, void* stream);
+/* (the backward entry points take act none / relu / lrelu / tanh: the derivative is formed from the activation's
+ * output, which swish does not allow -- S2P_ACT_SWISH and unknown ids are refused)       */
 int s2p_in_bwd_apply(int dtype, const void* da, int da_pitch, const void* x, int N, int HW, int C,
                      int pitch, const float* stats, const void* gb_img, int gb_pitch,
                      const float* gb_st, int gb_st_pitch, int act, float slope, float eps,
@@ -233,7 +236,8 @@ int s2p_linear_fwd(const float* x, int M, int K, int x_pitch, const float* w, in
 /* Backward given dy = dL/dy and the layer OUTPUT y (needed when act != NONE; dpre = dy * act'(y)):
  *   dw[N][dw_row] += dpre^T . x (columns < k_real), db[N] += sum_m dpre (db may be NULL),
  *   dx[M][dx_pitch] = dpre . w  (dx may be NULL; needs w_bwd [K][wb_row], the transpose of w).
- * No atomics: fixed summation order.  workspace: s2p_linear_bwd_workspace(M,K,N) bytes (0 for N < 2048). */
+ * No atomics: fixed summation order.  workspace: s2p_linear_bwd_workspace(M,K,N) bytes (0 for N < 2048).
+ * act: none / relu / lrelu; anything else is refused (the forward also takes tanh and swish).              */
 size_t s2p_linear_bwd_workspace(int M, int K, int N);
 int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int dy_pitch, const float* y, int y_pitch, int M,
                    int K, int k_real, int N, const float* w_bwd, int wb_row, int act, float slope, float* dw,
@@ -241,19 +245,28 @@ int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int dy_pitch, c
                    void* stream);
 
 /* ---- pooling / resize / layout ---------------------------------------------------- */
+/* Common to the entry points from here to the small elementwise helpers at the end: a negative size and an unknown dtype are
+ * refused; a call that covers no element (a size of 0) returns 0 without a launch and without looking at its pointers;
+ * otherwise NULL tensors are refused.  Alignment: where stated below the kernel moves whole 16-byte chunks and an unaligned
+ * pointer is refused; the avg-pool, s2p_l1_loss and s2p_add take any element-aligned pointer (per-element form).
+ * Every refusal happens before anything is launched (non-zero return, s2p_last_error).                                   */
 /* F.avg_pool2d(k=3,s=2,p=1,count_include_pad=False) and its backward                   */
 int s2p_avgpool3x3s2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream);
 int s2p_avgpool3x3s2_bwd(int dtype, const void* dy, int N, int H, int W, int C, void* dx,
                          int accumulate, void* stream);
-/* F.max_pool2d(2,2) (floor) and backward fused with the producer's ReLU mask            */
+/* F.max_pool2d(2,2) (floor) and backward fused with the producer's ReLU mask: x is a ReLU output (negative values and
+ * -0.0 count as 0), dx = dy at the FIRST maximum of each window in (row, column) order if that maximum is > 0, else 0;
+ * rows / columns of an odd H / W outside every window get 0.  C a multiple of the 16-byte chunk, all pointers 16-byte
+ * aligned.                                                                              */
 int s2p_maxpool2x2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream);
 int s2p_maxpool2x2_bwd(int dtype, const void* dy, const void* x, int N, int H, int W, int C,
                        void* dx, void* stream);
 /* F.interpolate(mode='nearest') on NHWC                                                 */
 int s2p_resize_nearest(int dtype, const void* x, int N, int H, int W, int C, void* y, int Ho, int Wo,
                        void* stream);
-/* fp32 NCHW [N,C,H,W]  ->  NHWC dtype with channel pitch (zero pad), written at channel
- * offset c_off; and back.                                                               */
+/* fp32 NCHW [N,C,H,W]  ->  NHWC dtype with channel pitch, written at channel offset c_off (c_off + C <= y_pitch);
+ * zero_pad != 0: every other channel of the pitch is written as zero (y 16-byte aligned if the pitch is a whole number
+ * of chunks), zero_pad == 0: the other channels are left untouched.  And back (accumulate != 0: y += ...).              */
 int s2p_nchw_to_nhwc(int dtype, const float* x, int N, int C, int H, int W, void* y, int y_pitch,
                      int c_off, int zero_pad, void* stream);
 int s2p_nhwc_to_nchw(int dtype, const void* x, int x_pitch, int c_off, int N, int C, int H, int W,
@@ -267,13 +280,13 @@ int s2p_nhwc_to_u8(int dtype, const void* x, int x_pitch, int64_t pixels, int C,
 int s2p_cast(int src_dtype, const void* src, int dst_dtype, void* dst, int64_t n, void* stream);
 
 /* ---- losses (forward value + gradient seed in one pass) ---------------------------- */
-/* loss_out[0] += scale * sum|a-b| ; if grad_a: grad_a = (accumulate? grad_a:0) + scale*sign(a-b)
- * a,b: `count` elements each (dtype)                                                    */
+/* loss_out[0] += scale * sum|a-b| ; if grad_a: grad_a = (accumulate? grad_a:0) + scale*sign(a-b)  (sign(0) = 0)
+ * a,b: `count` elements each (dtype); any alignment (16-byte chunks only when a, b and grad_a are all aligned) */
 int s2p_l1_loss(int dtype, const void* a, const void* b, int64_t count, float scale,
                 float* loss_out, void* grad_a, int accumulate, void* stream);
 /* n_jobs (<= S2P_L1_MAX_JOBS) such terms in one launch (the feature-matching maps of all PatchGAN scales, the VGG taps);
  * `jobs` is a HOST array (copied into the kernel arguments).  Pointers 16-byte aligned, counts a multiple of the 16-byte
- * chunk (8 bf16 / 4 fp32); grad_a is overwritten (no accumulate form).                                              */
+ * chunk (8 bf16 / 4 fp32), an empty job is refused; grad_a is overwritten (no accumulate form).                      */
 #define S2P_L1_MAX_JOBS 16
 typedef struct { const void* a; const void* b; void* grad_a; int64_t count; float scale; float* loss_out; } s2p_l1_job;
 int s2p_l1_loss_multi(int dtype, const s2p_l1_job* jobs, int n_jobs, void* stream);
@@ -284,7 +297,8 @@ int s2p_l1_loss_multi(int dtype, const s2p_l1_job* jobs, int n_jobs, void* strea
 int s2p_hinge_loss(int dtype, const void* x, int64_t count, int mode, float scale,
                    float* loss_out, void* grad_x, void* stream);
 /* the same on an NHWC map x [pixels][pitch] whose channel 0 is the logit (the discriminator heads' output layout);
- * grad_x (same layout, may be NULL): gradient in channel 0, zeros in the other channels                              */
+ * grad_x (same layout, may be NULL): gradient in channel 0, zeros in the other channels.  pitch a multiple of the 16-byte
+ * chunk, grad_x 16-byte aligned                                                                                       */
 int s2p_hinge_loss_strided(int dtype, const void* x, int64_t pixels, int pitch, int mode, float scale,
                            float* loss_out, void* grad_x, void* stream);
 
@@ -304,7 +318,9 @@ int s2p_ensemble_head(const float* raw, int raw_pitch, const float* xin, int x_p
                       void* stream);
 
 /* ---- optimizer + weight packing ---------------------------------------------------- */
-/* torch.optim.Adam step on flat fp32 buffers; g is multiplied by grad_scale first.      */
+/* torch.optim.Adam step on flat fp32 buffers; g is multiplied by grad_scale first.  All three forms move 16-byte groups:
+ * p, g, m, v must be 16-byte aligned (a sub-range of a flat buffer starts at a multiple of 4 elements), else the call is
+ * refused; n need not be a multiple of 4 (the last 1..3 elements go one by one); n == 0 is a no-op (no tick either).  */
 int s2p_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                   float beta2, float eps, int step, float grad_scale, void* stream);
 /* same update with the step counter in DEVICE memory (incremented on the device first), so the launch
@@ -354,7 +370,8 @@ int s2p_sn_power_iter(const s2p_sn_job* jobs, int n_jobs, int max_R, int max_K, 
 int s2p_sn_project_grad(const s2p_sn_job* jobs, int n_jobs, int max_R, int max_K, void* stream);
 
 /* ---- small elementwise helpers ------------------------------------------------------ */
-/* dx = dy * act'(y)   (y = activation OUTPUT)                                           */
+/* dx = dy * act'(y)   (y = activation OUTPUT; act none / relu / lrelu / tanh -- swish' cannot be formed from the
+ * output: S2P_ACT_SWISH and unknown ids are refused, as they are for aux_act of s2p_conv2d_dgrad) */
 int s2p_act_bwd(int dtype, const void* dy, const void* y, int64_t n, int act, float slope, void* dx,
                 void* stream);
 /* x *= *scale  (device fp32 scalar: applies an upstream grad_output without a host sync) */
@@ -362,7 +379,7 @@ int s2p_scale(int dtype, void* x, int64_t n, const float* scale, void* stream);
 /* out = a + b (n elements; out may alias a or b)                                         */
 int s2p_add(int dtype, const void* a, const void* b, void* out, int64_t n, void* stream);
 /* dst[p][dst_off+c] (+)= src[p][src_off+c] for c<C, p<pixels  (torch.cat(dim=1) on NHWC and
- * its backward slice)                                                                   */
+ * its backward slice); src_off + C <= src_pitch and dst_off + C <= dst_pitch             */
 int s2p_copy_channels(int dtype, const void* src, int src_pitch, int src_off, void* dst,
                       int dst_pitch, int dst_off, int C, int64_t pixels, int accumulate, void* stream);
 

@@ -1753,6 +1753,7 @@ extern "C" size_t s2p_conv2d_fwd_workspace(const s2p_conv_desc* d, int epi) {
 // goes with the dgrad
 static int conv_dgrad_impl(const s2p_conv_desc* d, const ConvOperands& op, const PlaneMat* mat, bool must_fuse, bool* fused, const Scratch& sc,
                            void* stream) {
+  if (op.epi == S2P_EPI_MUL_ACTGRAD) S2P_CHECK_ACT_FROM_OUT("s2p_conv2d_dgrad (aux_act)", op.gact);
   ConvPlan P;
   int rc = conv_plan_dgrad(d, op, NormWant{mat != nullptr, mat && mat->gb, true}, ScratchAvail{sc.ws != nullptr, sc.bytes}, P);
   if (rc) return rc;

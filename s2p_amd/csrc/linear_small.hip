@@ -330,6 +330,8 @@ extern "C" int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int 
                               void* stream) {
   int rc = lin_check("s2p_linear_bwd", M, K, N, x_pitch); if (rc) return rc;
   if (!x || !dy || !dw || dy_pitch % 4 || N % 4) S2P_FAIL(-1, "s2p_linear_bwd: bad arguments (N and pitches must be multiples of 4)");
+  if (act != S2P_ACT_NONE && act != S2P_ACT_RELU && act != S2P_ACT_LRELU)      // (lin_actgrad has these three cases only)
+    S2P_FAIL(-1, "s2p_linear_bwd: activation %d has no backward here (none / relu / lrelu only)", act);
   if (act != S2P_ACT_NONE && (!y || y_pitch % 4)) S2P_FAIL(-1, "s2p_linear_bwd: the activation output is needed");
   if (dx && (!w_bwd || wb_row % 4)) S2P_FAIL(-1, "s2p_linear_bwd: dx needs w_bwd");
   hipStream_t st = (hipStream_t)stream;

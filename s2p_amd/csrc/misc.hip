@@ -17,6 +17,16 @@ static inline int grid_for(long long total, int cap = 4096) {
 #define GRID_STRIDE(idx, total) \
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < (total); idx += (long long)gridDim.x * 256)
 
+// ---- argument checks of the element-wise entry points (all of them before any launch) ---------------------------------------------
+// A negative size or an unknown dtype is refused.  A call that covers no element is a successful no-op: nothing is launched and no
+// pointer is looked at (an empty tensor may well have a null data pointer).  Otherwise null pointers are refused, and so are pointers
+// that are not 16-byte aligned wherever the kernel moves whole 16-byte chunks unconditionally (include/s2p_hip.h says which).
+#define S2P_REQUIRE(cond, ...) do { if (!(cond)) S2P_FAIL(-1, __VA_ARGS__); } while (0)
+static inline bool is_dtype(int dtype) { return dtype == S2P_F32 || dtype == S2P_BF16; }
+static inline bool host_al16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
+
 // ---- positional encoding ---------------------------------------------------------------------------
 __global__ void posenc_kernel(const float* s, int N, int S, int L, float* out, int pitch) {
   long long total = (long long)N * pitch;
@@ -34,8 +44,9 @@ __global__ void posenc_kernel(const float* s, int N, int S, int L, float* out, i
   }
 }
 extern "C" int s2p_posenc_fwd(const float* state, int N, int S, int L, float* out, int out_pitch, void* stream) {
+  if (N < 0 || S < 1 || L < 0 || L > 30 || out_pitch < S * (1 + 2 * L)) S2P_FAIL(-1, "s2p_posenc_fwd: bad N/S/L/pitch");
+  if (N == 0) return 0;
   if (!state || !out) S2P_FAIL(-1, "s2p_posenc_fwd: null pointer");
-  if (out_pitch < S * (1 + 2 * L) || L > 30) S2P_FAIL(-1, "s2p_posenc_fwd: bad pitch/L");
   hipLaunchKernelGGL(posenc_kernel, dim3(grid_for((long long)N * out_pitch)), dim3(256), 0, (hipStream_t)stream,
                      state, N, S, L, out, out_pitch);
   S2P_CHECK_LAUNCH("posenc_kernel");
@@ -119,6 +130,10 @@ __global__ void avgpool_bwd_kernel(const T* dy, int N, int H, int W, int C, T* d
   }
 }
 extern "C" int s2p_avgpool3x3s2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_avgpool3x3s2_fwd: bad dtype");
+  S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0, "s2p_avgpool3x3s2_fwd: negative size");
+  if ((long long)N * H * W * C == 0) return 0;
+  S2P_REQUIRE(x && y, "s2p_avgpool3x3s2_fwd: null pointer");
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int ce = dtype == S2P_F32 ? 4 : 8;
   const bool chunks = C % ce == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
@@ -135,6 +150,10 @@ extern "C" int s2p_avgpool3x3s2_fwd(int dtype, const void* x, int N, int H, int 
   return 0;
 }
 extern "C" int s2p_avgpool3x3s2_bwd(int dtype, const void* dy, int N, int H, int W, int C, void* dx, int accumulate, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_avgpool3x3s2_bwd: bad dtype");
+  S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0, "s2p_avgpool3x3s2_bwd: negative size");
+  if ((long long)N * H * W * C == 0) return 0;
+  S2P_REQUIRE(dy && dx, "s2p_avgpool3x3s2_bwd: null pointer");
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int ce = dtype == S2P_F32 ? 4 : 8;
   const bool chunks = C % ce == 0 && (((uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
@@ -241,9 +260,14 @@ __global__ void maxpool_bwd_kernel(const T* dy, const T* x, int N, int H, int W,
   }
 }
 extern "C" int s2p_maxpool2x2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_maxpool2x2_fwd: bad dtype");
+  S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0, "s2p_maxpool2x2_fwd: negative size");
   int Ho = H / 2, Wo = W / 2, ce = dtype == S2P_F32 ? 4 : 8;
   if (C % ce) S2P_FAIL(-1, "s2p_maxpool2x2_fwd: C must be a multiple of %d", ce);
   long long total = (long long)N * Ho * Wo * (C / ce);
+  if (total == 0) return 0;
+  S2P_REQUIRE(x && y, "s2p_maxpool2x2_fwd: null pointer");
+  S2P_REQUIRE(host_al16(x, y), "s2p_maxpool2x2_fwd: x and y must be 16-byte aligned");
   if (dtype == S2P_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, N, H, W, C, (float*)y, Ho, Wo);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(maxpool_fwd_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, N, H, W, C, (__bf16*)y, Ho, Wo);
   else S2P_FAIL(-1, "s2p_maxpool2x2_fwd: bad dtype");
@@ -251,9 +275,14 @@ extern "C" int s2p_maxpool2x2_fwd(int dtype, const void* x, int N, int H, int W,
   return 0;
 }
 extern "C" int s2p_maxpool2x2_bwd(int dtype, const void* dy, const void* x, int N, int H, int W, int C, void* dx, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_maxpool2x2_bwd: bad dtype");
+  S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0, "s2p_maxpool2x2_bwd: negative size");
   int Ho = H / 2, Wo = W / 2, ce = dtype == S2P_F32 ? 4 : 8;
   if (C % ce) S2P_FAIL(-1, "s2p_maxpool2x2_bwd: C must be a multiple of %d", ce);
   long long total = (long long)N * H * W * (C / ce);
+  if (total == 0) return 0;
+  S2P_REQUIRE(x && dx && (dy || (long long)Ho * Wo == 0), "s2p_maxpool2x2_bwd: null pointer");
+  S2P_REQUIRE(host_al16(dy, x, dx), "s2p_maxpool2x2_bwd: dy, x and dx must be 16-byte aligned");
   if (dtype == S2P_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)x, N, H, W, C, (float*)dx, Ho, Wo);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(maxpool_bwd_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy, (const __bf16*)x, N, H, W, C, (__bf16*)dx, Ho, Wo);
   else S2P_FAIL(-1, "s2p_maxpool2x2_bwd: bad dtype");
@@ -275,7 +304,12 @@ __global__ void resize_kernel(const T* x, int N, int H, int W, int C, T* y, int 
   }
 }
 extern "C" int s2p_resize_nearest(int dtype, const void* x, int N, int H, int W, int C, void* y, int Ho, int Wo, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_resize_nearest: bad dtype");
+  S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0 && Ho >= 0 && Wo >= 0, "s2p_resize_nearest: negative size");
   long long total = (long long)N * Ho * Wo * C;
+  if (total == 0) return 0;
+  S2P_REQUIRE(H > 0 && W > 0, "s2p_resize_nearest: empty input plane");
+  S2P_REQUIRE(x && y, "s2p_resize_nearest: null pointer");
   if (dtype == S2P_F32) hipLaunchKernelGGL(resize_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, N, H, W, C, (float*)y, Ho, Wo);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(resize_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, N, H, W, C, (__bf16*)y, Ho, Wo);
   else S2P_FAIL(-1, "s2p_resize_nearest: bad dtype");
@@ -327,8 +361,14 @@ __global__ void nhwc_to_nchw_kernel(const T* x, int pitch, int c_off, int N, int
   }
 }
 extern "C" int s2p_nchw_to_nhwc(int dtype, const float* x, int N, int C, int H, int W, void* y, int y_pitch, int c_off, int zero_pad, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_nchw_to_nhwc: bad dtype");
+  S2P_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0 && c_off >= 0 && y_pitch >= 0, "s2p_nchw_to_nhwc: negative size");
   if (c_off + C > y_pitch) S2P_FAIL(-1, "s2p_nchw_to_nhwc: channels exceed pitch");
   long long total = (long long)N * H * W;                                   // one thread per pixel
+  if (total == 0 || (zero_pad ? y_pitch : C) == 0) return 0;
+  S2P_REQUIRE(y && (x || C == 0), "s2p_nchw_to_nhwc: null pointer");
+  // zero_pad with a pitch of whole chunks stores 16 bytes at a time
+  S2P_REQUIRE(!(zero_pad && y_pitch % (dtype == S2P_F32 ? 4 : 8) == 0) || host_al16(y), "s2p_nchw_to_nhwc: y must be 16-byte aligned");
   if (dtype == S2P_F32) hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, N, C, H, W, (float*)y, y_pitch, c_off, zero_pad);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, N, C, H, W, (__bf16*)y, y_pitch, c_off, zero_pad);
   else S2P_FAIL(-1, "s2p_nchw_to_nhwc: bad dtype");
@@ -336,7 +376,12 @@ extern "C" int s2p_nchw_to_nhwc(int dtype, const float* x, int N, int C, int H, 
   return 0;
 }
 extern "C" int s2p_nhwc_to_nchw(int dtype, const void* x, int x_pitch, int c_off, int N, int C, int H, int W, float* y, int accumulate, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_nhwc_to_nchw: bad dtype");
+  S2P_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0 && c_off >= 0, "s2p_nhwc_to_nchw: negative size");
+  S2P_REQUIRE(c_off + C <= x_pitch, "s2p_nhwc_to_nchw: channels exceed pitch");
   long long total = (long long)N * C * H * W;
+  if (total == 0) return 0;
+  S2P_REQUIRE(x && y, "s2p_nhwc_to_nchw: null pointer");
   if (dtype == S2P_F32) hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, x_pitch, c_off, N, C, H, W, y, accumulate);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, x_pitch, c_off, N, C, H, W, y, accumulate);
   else S2P_FAIL(-1, "s2p_nhwc_to_nchw: bad dtype");
@@ -349,6 +394,10 @@ __global__ void cast_kernel(const S* s, D* d, long long n) {
   GRID_STRIDE(idx, n) d[idx] = from_f32<D>(to_f32(s[idx]));
 }
 extern "C" int s2p_cast(int sd, const void* src, int dd, void* dst, int64_t n, void* stream) {
+  S2P_REQUIRE(is_dtype(sd) && is_dtype(dd), "s2p_cast: bad dtype");
+  S2P_REQUIRE(n >= 0, "s2p_cast: negative size");
+  if (n == 0) return 0;
+  S2P_REQUIRE(src && dst, "s2p_cast: null pointer");
   dim3 g(grid_for(n)), b(256); hipStream_t st = (hipStream_t)stream;
   if (sd == S2P_F32 && dd == S2P_BF16) hipLaunchKernelGGL((cast_kernel<float, __bf16>), g, b, 0, st, (const float*)src, (__bf16*)dst, (long long)n);
   else if (sd == S2P_BF16 && dd == S2P_F32) hipLaunchKernelGGL((cast_kernel<__bf16, float>), g, b, 0, st, (const __bf16*)src, (float*)dst, (long long)n);
@@ -392,9 +441,16 @@ __global__ void reflect_fold_kernel(const T* dxp, int N, int H, int W, int C, in
   }
 }
 extern "C" int s2p_reflect_pad_bwd(int dtype, const void* dxp, int N, int H, int W, int C, int pad, void* dx, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_reflect_pad_bwd: bad dtype");
+  S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0 && pad >= 0, "s2p_reflect_pad_bwd: negative size");
   const int ce = dtype == S2P_F32 ? 4 : 8;
   if (C % ce) S2P_FAIL(-1, "s2p_reflect_pad_bwd: C (the NHWC pitch) must be a multiple of %d", ce);
   long long total = (long long)N * H * W * (C / ce);
+  if (total == 0) return 0;
+  // (reflection needs pad < H, W as F.pad does; the kernel folds at most one reflection per side and axis)
+  S2P_REQUIRE(pad < H && pad < W, "s2p_reflect_pad_bwd: pad %d must be smaller than H %d and W %d", pad, H, W);
+  S2P_REQUIRE(dxp && dx, "s2p_reflect_pad_bwd: null pointer");
+  S2P_REQUIRE(host_al16(dxp, dx), "s2p_reflect_pad_bwd: dxp and dx must be 16-byte aligned");
   if (dtype == S2P_F32) hipLaunchKernelGGL(reflect_fold_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)dxp, N, H, W, C, pad, (float*)dx);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(reflect_fold_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dxp, N, H, W, C, pad, (__bf16*)dx);
   else S2P_FAIL(-1, "s2p_reflect_pad_bwd: bad dtype");
@@ -444,6 +500,9 @@ __global__ void l1_loss_kernel(const T* a, const T* b, long long count, float sc
   block_atomic_add(s * scale, loss);
 }
 extern "C" int s2p_l1_loss(int dtype, const void* a, const void* b, int64_t count, float scale, float* loss_out, void* grad_a, int accumulate, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_l1_loss: bad dtype");
+  S2P_REQUIRE(count >= 0, "s2p_l1_loss: negative count");
+  if (count == 0) return 0;
   if (!a || !b || !loss_out) S2P_FAIL(-1, "s2p_l1_loss: null pointer");
   // every workgroup ends in ONE atomicAdd on the same loss word, and same-address atomics retire at ~13 ns each on
   // MI355X (2048 workgroups = a 29 us floor): 512 workgroups of 16-byte loads still saturate HBM
@@ -536,7 +595,10 @@ __global__ void hinge_kernel(const T* x, long long count, int mode, float scale,
   block_atomic_add(s * scale, loss);
 }
 extern "C" int s2p_hinge_loss(int dtype, const void* x, int64_t count, int mode, float scale, float* loss_out, void* grad_x, void* stream) {
-  if (!x || !loss_out || mode < 0 || mode > 2) S2P_FAIL(-1, "s2p_hinge_loss: bad argument");
+  S2P_REQUIRE(is_dtype(dtype), "s2p_hinge_loss: bad dtype");
+  S2P_REQUIRE(count >= 0 && mode >= 0 && mode <= 2, "s2p_hinge_loss: bad count / mode");
+  if (count == 0) return 0;
+  if (!x || !loss_out) S2P_FAIL(-1, "s2p_hinge_loss: null pointer");
   dim3 g(grid_for(count, 256));                         // same-address atomic per workgroup: keep the grid small
   if (dtype == S2P_F32) hipLaunchKernelGGL(hinge_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, (const float*)x, (long long)count, mode, scale, loss_out, (float*)grad_x);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(hinge_kernel<__bf16>, g, dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, (long long)count, mode, scale, loss_out, (__bf16*)grad_x);
@@ -570,9 +632,13 @@ __global__ void hinge_strided_kernel(const T* x, long long pixels, int pitch, in
 }
 extern "C" int s2p_hinge_loss_strided(int dtype, const void* x, int64_t pixels, int pitch, int mode, float scale, float* loss_out,
                                       void* grad_x, void* stream) {
-  if (!x || !loss_out || mode < 0 || mode > 2) S2P_FAIL(-1, "s2p_hinge_loss_strided: bad argument");
+  S2P_REQUIRE(is_dtype(dtype), "s2p_hinge_loss_strided: bad dtype");
+  S2P_REQUIRE(pixels >= 0 && mode >= 0 && mode <= 2, "s2p_hinge_loss_strided: bad pixels / mode");
   const int ce = dtype == S2P_F32 ? 4 : 8;
   if (pitch < ce || pitch % ce) S2P_FAIL(-1, "s2p_hinge_loss_strided: pitch must be a multiple of %d", ce);
+  if (pixels == 0) return 0;
+  if (!x || !loss_out) S2P_FAIL(-1, "s2p_hinge_loss_strided: null pointer");
+  S2P_REQUIRE(host_al16(grad_x), "s2p_hinge_loss_strided: grad_x must be 16-byte aligned");      // whole chunks are stored
   dim3 g(grid_for(pixels, 256));                        // same-address atomic per workgroup: keep the grid small
   if (dtype == S2P_F32) hipLaunchKernelGGL(hinge_strided_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, (const float*)x, (long long)pixels, pitch, mode, scale, loss_out, (float*)grad_x);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(hinge_strided_kernel<__bf16>, g, dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, (long long)pixels, pitch, mode, scale, loss_out, (__bf16*)grad_x);
@@ -607,8 +673,10 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long l
   }
 }
 extern "C" int s2p_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream) {
-  if (!p || !g || !m || !v || step < 1) S2P_FAIL(-1, "s2p_adam_step: bad argument");
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) S2P_FAIL(-1, "s2p_adam_step: buffers must be 16-byte aligned");
+  S2P_REQUIRE(n >= 0 && step >= 1, "s2p_adam_step: bad n / step");
+  if (n == 0) return 0;
+  if (!p || !g || !m || !v) S2P_FAIL(-1, "s2p_adam_step: null pointer");
+  if (!host_al16(p, g, m, v)) S2P_FAIL(-1, "s2p_adam_step: buffers must be 16-byte aligned");
   double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   long long n4 = (n + 3) / 4;
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, (long long)n,
@@ -665,8 +733,11 @@ __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, lo
   }
 }
 extern "C" int s2p_adam_step_dev_part(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int* step_dev, float grad_scale, int tick, void* stream) {
-  if (!p || !g || !m || !v || !step_dev) S2P_FAIL(-1, "s2p_adam_step_dev: bad argument");
-  if (n <= 0) return 0;
+  S2P_REQUIRE(n >= 0, "s2p_adam_step_dev: negative n");
+  if (n == 0) return 0;                                       // (no tick either: an empty range is no part of a step)
+  if (!p || !g || !m || !v || !step_dev) S2P_FAIL(-1, "s2p_adam_step_dev: null pointer");
+  // the kernel moves 16-byte groups of p, g, m, v: a sub-range of the flat buffers must start at a multiple of 4 elements
+  if (!host_al16(p, g, m, v)) S2P_FAIL(-1, "s2p_adam_step_dev: buffers must be 16-byte aligned");
   long long n4 = (n + 3) / 4;
   if (tick) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev);
   hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, (long long)n,
@@ -811,6 +882,12 @@ __global__ void act_bwd_kernel(const T* dy, const T* y, long long n, int act, fl
   GRID_STRIDE(idx, n) dx[idx] = from_f32<T>(to_f32(dy[idx]) * act_grad_from_out(to_f32(y[idx]), act, slope));
 }
 extern "C" int s2p_act_bwd(int dtype, const void* dy, const void* y, int64_t n, int act, float slope, void* dx, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_act_bwd: bad dtype");
+  S2P_CHECK_ACT_FROM_OUT("s2p_act_bwd", act);
+  S2P_REQUIRE(n >= 0, "s2p_act_bwd: negative size");
+  if (n == 0) return 0;
+  S2P_REQUIRE(dy && dx && (y || act == S2P_ACT_NONE), "s2p_act_bwd: null pointer");
+  if (!y) y = dy;                                             // (act none: the kernel reads y without using it)
   if (dtype == S2P_F32) hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)y, (long long)n, act, slope, (float*)dx);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(act_bwd_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy, (const __bf16*)y, (long long)n, act, slope, (__bf16*)dx);
   else S2P_FAIL(-1, "s2p_act_bwd: bad dtype");
@@ -824,6 +901,10 @@ __global__ void scale_kernel(T* x, long long n, const float* scale) {
   GRID_STRIDE(idx, n) x[idx] = from_f32<T>(to_f32(x[idx]) * s);
 }
 extern "C" int s2p_scale(int dtype, void* x, int64_t n, const float* scale, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_scale: bad dtype");
+  S2P_REQUIRE(n >= 0, "s2p_scale: negative size");
+  if (n == 0) return 0;
+  S2P_REQUIRE(x && scale, "s2p_scale: null pointer");
   if (dtype == S2P_F32) hipLaunchKernelGGL(scale_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (float*)x, (long long)n, scale);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(scale_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (__bf16*)x, (long long)n, scale);
   else S2P_FAIL(-1, "s2p_scale: bad dtype");
@@ -847,6 +928,10 @@ __global__ void add_kernel(const T* a, const T* b, T* out, long long n) {
     out[idx] = from_f32<T>(to_f32(a[idx]) + to_f32(b[idx]));
 }
 extern "C" int s2p_add(int dtype, const void* a, const void* b, void* out, int64_t n, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_add: bad dtype");
+  S2P_REQUIRE(n >= 0, "s2p_add: negative size");
+  if (n == 0) return 0;
+  S2P_REQUIRE(a && b && out, "s2p_add: null pointer");
   if (dtype == S2P_F32) hipLaunchKernelGGL(add_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)out, (long long)n);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(add_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)a, (const __bf16*)b, (__bf16*)out, (long long)n);
   else S2P_FAIL(-1, "s2p_add: bad dtype");
@@ -866,7 +951,12 @@ __global__ void copy_channels_kernel(const T* src, int sp, int so, T* dst, int d
 }
 extern "C" int s2p_copy_channels(int dtype, const void* src, int src_pitch, int src_off, void* dst, int dst_pitch, int dst_off,
                                  int C, int64_t pixels, int accumulate, void* stream) {
+  S2P_REQUIRE(is_dtype(dtype), "s2p_copy_channels: bad dtype");
+  S2P_REQUIRE(pixels >= 0 && C >= 0 && src_off >= 0 && dst_off >= 0, "s2p_copy_channels: negative size");
+  S2P_REQUIRE(src_off + C <= src_pitch && dst_off + C <= dst_pitch, "s2p_copy_channels: channels exceed pitch");
   long long total = (long long)pixels * C;
+  if (total == 0) return 0;
+  S2P_REQUIRE(src && dst, "s2p_copy_channels: null pointer");
   if (dtype == S2P_F32) hipLaunchKernelGGL(copy_channels_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)src, src_pitch, src_off, (float*)dst, dst_pitch, dst_off, C, (long long)pixels, accumulate);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(copy_channels_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)src, src_pitch, src_off, (__bf16*)dst, dst_pitch, dst_off, C, (long long)pixels, accumulate);
   else S2P_FAIL(-1, "s2p_copy_channels: bad dtype");
@@ -899,8 +989,11 @@ __global__ void nhwc_to_u8_kernel(const T* x, int pitch, long long pixels, int C
   }
 }
 extern "C" int s2p_u8_to_nhwc(int dtype, const void* x, int64_t pixels, int C, void* y, int y_pitch, void* stream) {
-  if (!x || !y || C > y_pitch) S2P_FAIL(-1, "s2p_u8_to_nhwc: bad argument");
+  S2P_REQUIRE(is_dtype(dtype), "s2p_u8_to_nhwc: bad dtype");
+  S2P_REQUIRE(pixels >= 0 && C >= 0 && C <= y_pitch, "s2p_u8_to_nhwc: bad pixels / C / pitch");
   long long total = (long long)pixels * y_pitch;
+  if (total == 0) return 0;
+  if (!y || (!x && C)) S2P_FAIL(-1, "s2p_u8_to_nhwc: null pointer");
   if (dtype == S2P_F32) hipLaunchKernelGGL(u8_to_nhwc_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)x, (long long)pixels, C, (float*)y, y_pitch);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(u8_to_nhwc_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)x, (long long)pixels, C, (__bf16*)y, y_pitch);
   else S2P_FAIL(-1, "s2p_u8_to_nhwc: bad dtype");
@@ -908,8 +1001,11 @@ extern "C" int s2p_u8_to_nhwc(int dtype, const void* x, int64_t pixels, int C, v
   return 0;
 }
 extern "C" int s2p_nhwc_to_u8(int dtype, const void* x, int x_pitch, int64_t pixels, int C, void* y, void* stream) {
-  if (!x || !y || C > x_pitch) S2P_FAIL(-1, "s2p_nhwc_to_u8: bad argument");
+  S2P_REQUIRE(is_dtype(dtype), "s2p_nhwc_to_u8: bad dtype");
+  S2P_REQUIRE(pixels >= 0 && C >= 0 && C <= x_pitch, "s2p_nhwc_to_u8: bad pixels / C / pitch");
   long long total = (long long)pixels * C;
+  if (total == 0) return 0;
+  if (!x || !y) S2P_FAIL(-1, "s2p_nhwc_to_u8: null pointer");
   if (dtype == S2P_F32) hipLaunchKernelGGL(nhwc_to_u8_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, x_pitch, (long long)pixels, C, (unsigned char*)y);
   else if (dtype == S2P_BF16) hipLaunchKernelGGL(nhwc_to_u8_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, x_pitch, (long long)pixels, C, (unsigned char*)y);
   else S2P_FAIL(-1, "s2p_nhwc_to_u8: bad dtype");

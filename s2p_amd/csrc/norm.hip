@@ -758,6 +758,7 @@ extern "C" int s2p_in_bwd_reduce(int dtype, const void* da, int da_pitch, const 
                                  const float* gb_st, int gb_st_pitch, int act, float slope, float eps,
                                  float* sums, void* stream) {
   int rc = norm_check("s2p_in_bwd_reduce", dtype, C, pitch, gb_pitch, da_pitch); if (rc) return rc;
+  S2P_CHECK_ACT_FROM_OUT("s2p_in_bwd_reduce", act);
   NormArgs a{}; a.x = x; a.da = da; a.stats = stats; a.gb = gb_img; a.gbst = gb_st; a.sums = sums;
   a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.da_pitch = da_pitch; a.gb_pitch = gb_pitch;
   a.gbst_pitch = gb_st_pitch; a.act = act; a.slope = slope; a.eps = eps;
@@ -770,6 +771,7 @@ extern "C" int s2p_in_bwd_apply(int dtype, const void* da, int da_pitch, const v
                                 const float* sums, void* dx, int dx_pitch, void* dgb_img, int dgb_pitch,
                                 float* dgb_st, int dgb_st_pitch, void* stream) {
   int rc = norm_check("s2p_in_bwd_apply", dtype, C, pitch, gb_pitch, da_pitch); if (rc) return rc;
+  S2P_CHECK_ACT_FROM_OUT("s2p_in_bwd_apply", act);
   if (dx_pitch % (dtype == S2P_F32 ? 4 : 8) || dgb_pitch % (dtype == S2P_F32 ? 4 : 8))
     S2P_FAIL(-1, "s2p_in_bwd_apply: bad output pitch");
   if (dgb_st && dgb_st_pitch < 2 * C) S2P_FAIL(-1, "s2p_in_bwd_apply: dgb_st pitch < 2*C");
@@ -795,6 +797,7 @@ extern "C" int s2p_in_norm_bwd_res(int dtype, const void* da, int da_pitch, cons
                                    int act, float slope, float eps, float* sums, void* dx, int dx_pitch, void* dgb_img,
                                    int dgb_pitch, float* dgb_st, int dgb_st_pitch, const void* res, int res_pitch, void* stream) {
   int rc = norm_check("s2p_in_norm_bwd", dtype, C, pitch, gb_pitch, da_pitch); if (rc) return rc;
+  S2P_CHECK_ACT_FROM_OUT("s2p_in_norm_bwd", act);
   if (res && (res_pitch != dx_pitch || dx_pitch != C)) S2P_FAIL(-1, "s2p_in_norm_bwd_res: res must have the layout of dx (pitch == C)");
   const int maxhw = dtype == S2P_F32 ? 256 : 512;
   const bool simple_act = act == S2P_ACT_NONE || act == S2P_ACT_RELU || act == S2P_ACT_LRELU;

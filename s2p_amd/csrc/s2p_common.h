@@ -42,6 +42,11 @@ void s2p_set_error(const char* fmt, ...);
 // leaky-relu slopes above 1 are rejected by the forward entry points: the kernels compute  max(v, v * slope)  (lrelu_ns below)
 #define S2P_CHECK_SLOPE(who, act, slope) do { if ((act) == S2P_ACT_LRELU && !((slope) <= 1.f)) \
     S2P_FAIL(-1, "%s: leaky-relu slope %g > 1 is not supported", who, (double)(slope)); } while (0)
+// backward entry points that form the activation's derivative from its OUTPUT (act_grad_from_out below; the fused epilogues of the
+// conv / norm kernels do the same) refuse what that function has no case for: swish' is not a function of swish(x), and an unknown
+// id must not fall through to "derivative 1"
+#define S2P_CHECK_ACT_FROM_OUT(who, act) do { if ((act) != S2P_ACT_NONE && (act) != S2P_ACT_RELU && (act) != S2P_ACT_LRELU && \
+    (act) != S2P_ACT_TANH) S2P_FAIL(-1, "%s: no derivative from the output for activation %d (none / relu / lrelu / tanh only)", who, (int)(act)); } while (0)
 #define S2P_CHECK_LAUNCH(name) do { hipError_t e_ = hipGetLastError(); \
     if (e_ != hipSuccess) { s2p_set_error("%s: launch failed: %s", name, hipGetErrorString(e_)); \
       return -(int)e_ - 1000; } } while (0)

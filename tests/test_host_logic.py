@@ -392,6 +392,28 @@ def test_flat_param_store_layout_on_cpu():
     assert sum(n for r in bk[:-1] for _, n in r) >= 0.66 * (st.numel - netG.early_grad_offset)
 
 
+def test_flat_adam_ranges_are_16_byte_aligned():
+    """s2p_adam_step_dev / _dev_part move 16-byte groups and refuse a range that does not start on one (include/s2p_hip.h).  Every range
+    the parameter stores of G and D hand them -- the whole flat buffer, and the head [0, start) / tail [start, end) split of
+    adam_step_early at the generator's early_grad_offset -- starts at a multiple of 4 floats inside an allocation padded to one."""
+    opt = TrainOptions().parse(["--gpu_ids", "0"], quiet=True)
+    netG, netD = networks.define_G(opt), networks.define_D(opt)
+    for net in (netG, netD):
+        net._declare_packs(torch.bfloat16)
+        st = net.store
+        st.finalize(torch.device("cpu"))
+        for buf in (st.master, st.grad, st.m, st.v):
+            assert buf.numel() % 4 == 0 and buf.numel() >= st.numel and buf.data_ptr() % 16 == 0
+    start = netG.early_grad_offset
+    st = netG.store
+    assert 0 < start < st.numel and start % 4 == 0
+    for buf in (st.master, st.grad, st.m, st.v):
+        assert buf[start:].data_ptr() % 16 == 0 and buf[:start].data_ptr() % 16 == 0
+    # the split refuses an offset that would misalign the tail before anything is launched
+    with pytest.raises(AssertionError):
+        st.adam_step_early(start + 1, 2e-4, 0.0, 0.9)
+
+
 def test_dataset_and_checkpoint_naming(tmp_path):
     from s2p_amd.data import S2PDataset, images_to_tensor, tensor_to_images
     opt = TrainOptions().parse(["--dataroot", os.path.join(ROOT, "datasets"), "--env_type", "cheetah", "--gpu_ids", "0"], quiet=True)
