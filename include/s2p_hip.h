@@ -29,7 +29,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: only the entry points declared here are exported */
 #pragma GCC visibility push(default)
 
-#define S2P_VERSION 124
+#define S2P_VERSION 125
 
 enum { S2P_F32 = 0, S2P_BF16 = 1 };
 enum { S2P_ACT_NONE = 0, S2P_ACT_RELU = 1, S2P_ACT_LRELU = 2, S2P_ACT_TANH = 3, S2P_ACT_SWISH = 4 };
@@ -148,6 +148,10 @@ size_t s2p_conv2d_wgrad_workspace(const s2p_conv_desc* d, int cin_real, int cout
 int s2p_conv2d_wgrad_ws(const s2p_conv_desc* d, const void* x, const void* dy, float* dw, float* db,
                         int cin_real, int cout_real, int64_t dw_gstride, int splitk, void* workspace,
                         size_t workspace_bytes, void* stream);
+/* Scratch size with which s2p_conv2d_wgrad_ws is free of atomics for fp32 tensors as well (groups == 1; `splitk` as passed to the
+ * launch): every K split stores a partial image of dw (and partial channel sums for db), added in split order.  For bf16 it
+ * equals s2p_conv2d_wgrad_workspace.  A call with the smaller scratch of s2p_conv2d_wgrad_workspace runs fp32 as before.  */
+size_t s2p_conv2d_wgrad_det_workspace(const s2p_conv_desc* d, int cin_real, int cout_real, int splitk);
 /* Batched weight gradient: n_jobs (<= 16) convolutions of the SAME geometry `d` (groups must be 1; a grouped conv is
  * passed as one job per group with offset pointers and the tensors' pitches in d->x_pitch / d->y_pitch) in ONE launch.
  * `jobs` is a HOST array (copied into the kernel arguments: safe under hipGraph capture).  dw / db are ACCUMULATED into,
@@ -166,6 +170,11 @@ int s2p_reflect_pad_bwd(int dtype, const void* dxp, int N, int H, int W, int C, 
 /* db[c] += sum over pixels of dy[p][c]  (bias gradient; fp32 accumulate into db)        */
 int s2p_channel_sum(int dtype, const void* dy, int64_t pixels, int C, int pitch, float* db,
                     void* stream);
+/* the same without atomics: per-block partial sums in a caller-owned scratch of s2p_channel_sum_workspace(pixels, C) bytes and
+ * a fixed-order reduce (bitwise reproducible); a NULL / short scratch runs s2p_channel_sum                               */
+size_t s2p_channel_sum_workspace(int64_t pixels, int C);
+int s2p_channel_sum_ws(int dtype, const void* dy, int64_t pixels, int C, int pitch, float* db, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- instance norm + MAT/SPADE modulation (replaces F.instance_norm + the elementwise
  *      `normalized * (1 + gamma) + beta` + activation of the SPADE-lineage norm) -------- */
@@ -243,6 +252,66 @@ int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int dy_pitch, c
                    int K, int k_real, int N, const float* w_bwd, int wb_row, int act, float slope, float* dw,
                    int dw_row, float* db, float* dx, int dx_pitch, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* ---- SLAC latent model: Gaussian heads, KL and likelihood terms (SPEC.md N3b; reference rlkit/torch/slac/network/
+ *      latent.py:29-52, 239-311 and slac/utils.py:66-69; csrc/gauss.hip).  All fp32 except the image likelihood's mu / dmu.
+ * Common to these entry points: every tensor argument comes with its own row pitch in ELEMENTS (pass the pointer already
+ * offset to the first column), so a slice of a [B,S+1,288] sequence buffer is read or written in place; a negative size is
+ * refused, a size of 0 is a successful no-op that looks at no pointer, NULL for a required tensor and a pitch shorter than the
+ * row are refused before anything is launched (non-zero, s2p_last_error).  No atomics and a fixed summation order everywhere
+ * except the loss word of s2p_gauss_ll_image (stated there).                                                              */
+/* Gaussian head (replaces torch.chunk + F.softplus + `mean + randn_like(std) * std`): raw [M][raw_pitch >= 2 D] is the last
+ * linear's output [mean | raw_std];  mean[m][d] = raw[m][d],  std = softplus(raw[m][D + d]) + 1e-5  (softplus evaluated as
+ * max(r, 0) + log1p(exp(-|r|)): no overflow, never 0),  and with eps:  z = z2 = mean + eps * std.  Any of mean, std, z, z2 may
+ * be NULL (at least one is not); z / z2 need eps.                                                                         */
+int s2p_gauss_head_fwd(const float* raw, int raw_pitch, int M, int D, const float* eps, int eps_pitch, float* mean,
+                       int mean_pitch, float* std, int std_pitch, float* z, int z_pitch, float* z2, int z2_pitch,
+                       void* stream);
+/* draw[m][0:D] = dmean + dz + dz2,  draw[m][D:2D] = (dstd + (dz + dz2) * eps) * sigmoid(raw[m][D:2D]);  any of dmean, dstd,
+ * dz, dz2 may be NULL (= 0; dz and dz2 are the gradients arriving at the two copies of the sample); dz / dz2 need eps.    */
+int s2p_gauss_head_bwd(const float* raw, int raw_pitch, int M, int D, const float* eps, int eps_pitch, const float* dmean,
+                       int dmean_pitch, const float* dstd, int dstd_pitch, const float* dz, int dz_pitch, const float* dz2,
+                       int dz2_pitch, float* draw, int draw_pitch, void* stream);
+/* s2p_linear_fwd with an additive input:  y = act(x[M][K] . w[N][w_row]^T + add[M][add_pitch] + bias)  (add, bias may be
+ * NULL; y may be the add buffer itself).  For a first layer whose input is a concatenation of which only some columns
+ * change per time step: the other columns' product is one batched s2p_linear_fwd over all time steps, passed here as add.
+ * K, x_pitch, w_row multiples of 4 floats, x and w 16-byte aligned; columns [N, n_store) of y are written as zeros.       */
+int s2p_linear_add_fwd(const float* x, int M, int K, int x_pitch, const float* w, int w_row, const float* bias, int N,
+                       const float* add, int add_pitch, int act, float slope, float* y, int y_pitch, int n_store,
+                       void* stream);
+/* Its backward, every output optional (at least one), dpre = dy * act'(y) (act none / relu / lrelu, y = the layer OUTPUT):
+ *   dadd[M][dadd_pitch] = dpre                       (the additive term's gradient, and what a weight-gradient pass that is
+ *                                                    batched over all time steps after the chain takes as its dy)
+ *   dw[N][dw_row] += dpre^T x (columns < k_real), db[N] += sum_m dpre     (s2p_linear_bwd's pass: N, pitches multiples of 4;
+ *                                                    db needs dw)
+ *   dx[M][dx_pitch] = dpre . w  or, with dx_accumulate != 0,  dx += dpre . w  (w_bwd [K][wb_row >= N] = the transpose of w;
+ *                                                    N, dy_pitch, wb_row multiples of 4, dy / y / w_bwd 16-byte aligned)  */
+int s2p_linear_add_bwd(const float* x, int x_pitch, const float* dy, int dy_pitch, const float* y, int y_pitch, int M,
+                       int K, int k_real, int N, const float* w_bwd, int wb_row, int act, float slope, float* dw,
+                       int dw_row, float* db, float* dx, int dx_pitch, int dx_accumulate, float* dadd, int dadd_pitch,
+                       void* stream);
+/* KL(p || q) of diagonal Gaussians, value and all four gradients in one pass (slac/utils.py:66-69):
+ *   loss[0] += scale * sum 0.5 ((sp/sq)^2 + ((mp-mq)/sq)^2 - 1 - log (sp/sq)^2),  d* = scale * dKL/d*  (overwritten; any NULL).
+ * p: [B][T][p_pitch >= D].  const_first == 0: q is [B][T][q_pitch]; const_first != 0: q is [B][T-1][q_pitch] and holds the
+ * steps 1..T-1, step 0 is compared with the constant N(0, I) (no gradient, nothing materialised).  dmu_p / dstd_p share
+ * dp_pitch and p's row order, dmu_q / dstd_q share dq_pitch and q's.  One workgroup, plain add into loss.                 */
+int s2p_gauss_kl(const float* mu_p, const float* std_p, int p_pitch, const float* mu_q, const float* std_q, int q_pitch,
+                 int B, int T, int D, int const_first, float scale, float* loss, float* dmu_p, float* dstd_p,
+                 int dp_pitch, float* dmu_q, float* dstd_q, int dq_pitch, void* stream);
+/* Masked Gaussian negative log-likelihood of n scalars (the reward term, latent.py:303-310):
+ *   nll_i = 0.5 ((target_i - mu_i) / (std_i + 1e-8))^2 + log std_i + 0.5 log 2 pi,  loss[0] += scale * sum (1 - done_i) nll_i,
+ *   dmu[i], dstd[i] = scale (1 - done_i) d nll_i / d*  (contiguous, overwritten; may be NULL).  mu / std element i at
+ *   i * pitch; target, done (NULL: no mask) contiguous.  One workgroup, plain add into loss.                             */
+int s2p_gauss_ll(const float* mu, int mu_pitch, const float* std, int std_pitch, const float* target, const float* done,
+                 int64_t n, float scale, float* loss, float* dmu, float* dstd, void* stream);
+/* The same for images with a constant sigma (latent.py:296-300).  mu: NHWC [N][HW][pitch] in `dtype` (the decoder's output:
+ * pitch a multiple of the 16-byte chunk, 16-byte aligned); target: fp32 NCHW [N][C][HW] (target_u8 == 0) or uint8 NHWC
+ * [N][HW][C] read as u8 / 255 (target_u8 != 0) -- always at full precision, never from a compute-dtype copy;
+ * dmu (may be NULL): scale * d nll / d mu in mu's layout and dtype, channels [C, pitch) written as zeros.
+ * loss[0] += scale * sum nll ends in ONE fp32 atomicAdd per workgroup (as s2p_l1_loss): the value may differ in its last
+ * bits from call to call, dmu does not.                                                                                   */
+int s2p_gauss_ll_image(int dtype, const void* mu, int pitch, const void* target, int target_u8, int N, int C, int HW,
+                       float sigma, float scale, float* loss, void* dmu, void* stream);
 
 /* ---- pooling / resize / layout ---------------------------------------------------- */
 /* Common to the entry points from here to the small elementwise helpers at the end: a negative size and an unknown dtype are

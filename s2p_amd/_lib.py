@@ -65,6 +65,9 @@ SIGNATURES = {
     "s2p_conv2d_dgrad_ws": [_DESC, _P, _P, _P, _P, _P, c_int, c_int, c_float, _P, ctypes.c_size_t, _P],
     "s2p_conv2d_wgrad": [_DESC, _P, _P, _P, _P, c_int, c_int, c_int64, c_int, _P],
     "s2p_conv2d_wgrad_workspace": [_DESC, c_int, c_int],
+    "s2p_conv2d_wgrad_det_workspace": [_DESC, c_int, c_int, c_int],
+    "s2p_channel_sum_workspace": [c_int64, c_int],
+    "s2p_channel_sum_ws": [c_int, _P, c_int64, c_int, c_int, _P, _P, ctypes.c_size_t, _P],
     "s2p_conv2d_wgrad_ws": [_DESC, _P, _P, _P, _P, c_int, c_int, c_int64, c_int, _P, ctypes.c_size_t, _P],
     "s2p_conv2d_wgrad_batched_workspace": [_DESC, c_int, c_int, c_int],
     "s2p_conv2d_wgrad_batched": [_DESC, ctypes.POINTER(WgradJob), c_int, c_int, c_int, _P, ctypes.c_size_t, _P],
@@ -89,6 +92,14 @@ SIGNATURES = {
     "s2p_linear_bwd_workspace": [c_int, c_int, c_int],
     "s2p_linear_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int, _P, _P,
                        c_int, _P, ctypes.c_size_t, _P],
+    "s2p_gauss_head_fwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P],
+    "s2p_gauss_head_bwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P],
+    "s2p_linear_add_fwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_float, _P, c_int, c_int, _P],
+    "s2p_linear_add_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int, _P, _P,
+                           c_int, c_int, _P, c_int, _P],
+    "s2p_gauss_kl": [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int, _P, _P, c_int, _P],
+    "s2p_gauss_ll": [_P, c_int, _P, c_int, _P, _P, c_int64, c_float, _P, _P, _P, _P],
+    "s2p_gauss_ll_image": [c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, _P],
     "s2p_posenc_fwd": [_P, c_int, c_int, c_int, _P, c_int, _P],
     "s2p_avgpool3x3s2_fwd": [c_int, _P, c_int, c_int, c_int, c_int, _P, _P],
     "s2p_avgpool3x3s2_bwd": [c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P],
@@ -120,7 +131,7 @@ SIGNATURES = {
     "s2p_copy_channels": [c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int64, c_int, _P],
     "s2p_image_metrics": [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P],
 }
-_RESTYPE = {"s2p_last_error": ctypes.c_char_p, "s2p_conv2d_wgrad_batched_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_workspace": ctypes.c_size_t, "s2p_conv2d_fwd_workspace": ctypes.c_size_t, "s2p_conv2d_dgrad_workspace": ctypes.c_size_t, "s2p_linear_bwd_workspace": ctypes.c_size_t, "s2p_in_stats_floats": c_int64, "s2p_in_bwd_sums_floats": c_int64,
+_RESTYPE = {"s2p_last_error": ctypes.c_char_p, "s2p_conv2d_wgrad_det_workspace": ctypes.c_size_t, "s2p_channel_sum_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_batched_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_workspace": ctypes.c_size_t, "s2p_conv2d_fwd_workspace": ctypes.c_size_t, "s2p_conv2d_dgrad_workspace": ctypes.c_size_t, "s2p_linear_bwd_workspace": ctypes.c_size_t, "s2p_in_stats_floats": c_int64, "s2p_in_bwd_sums_floats": c_int64,
             "s2p_sn_workspace_floats": c_int64}
 
 _lib = None
@@ -148,7 +159,7 @@ def lib():
             fn = getattr(L, name)          # AttributeError if the export is missing
             fn.argtypes = args
             fn.restype = _RESTYPE.get(name, c_int)
-        if L.s2p_version() < 121:
+        if L.s2p_version() < 125:
             raise RuntimeError("libs2p_hip.so is older than this package")
         _lib = L
     return _lib

@@ -882,3 +882,10 @@ extern "C" int s2p_channel_sum(int dtype, const void* dy, int64_t pixels, int C,
                                void* stream) {
   return s2p_channel_sum_det(dtype, dy, pixels, C, pitch, db, nullptr, 0, stream);
 }
+// the same without atomics: partial sums in a caller-owned scratch of s2p_channel_sum_workspace(pixels, C) bytes + a fixed-order
+// reduce (a NULL / short scratch falls back to the atomics of s2p_channel_sum)
+extern "C" size_t s2p_channel_sum_workspace(int64_t pixels, int C) { return s2p_channel_sum_ws_bytes(pixels, C); }
+extern "C" int s2p_channel_sum_ws(int dtype, const void* dy, int64_t pixels, int C, int pitch, float* db, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  return s2p_channel_sum_det(dtype, dy, pixels, C, pitch, db, workspace, workspace_bytes, stream);
+}

@@ -191,7 +191,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         int arow = a_tile * BT + wa0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (arow < a.Ca_real) atomicAdd(dWg + (size_t)arow * a.dw_row + col, acc[i][j][e]);
+        if (arow >= a.Ca_real) continue;
+        // deterministic mode (groups == 1): split z stores its partial dW image [Ca_real][dw_row]; s2p_partial_reduce adds the
+        // images to dW in split order
+        if (a.part) a.part[((size_t)split * a.Ca_real + arow) * a.dw_row + col] = acc[i][j][e];
+        else atomicAdd(dWg + (size_t)arow * a.dw_row + col, acc[i][j][e]);
       }
   }
 }
@@ -620,6 +624,33 @@ extern "C" size_t s2p_conv2d_wgrad_workspace(const s2p_conv_desc* d, int cin_rea
   return g > sg ? g : sg;
 }
 
+// K split of the register-staged kernel (fp32): the launch and the scratch query below must agree
+static void wgrad_reg_splits(const s2p_conv_desc* d, int splitk, int& splits, int& steps_per_split) {
+  const int ce = d->dtype == S2P_F32 ? 4 : 8, BT = d->dtype == S2P_F32 ? 64 : 128, T = d->KH * d->KW;
+  const int cout_pad = (d->Cout + ce - 1) / ce * ce;
+  const int Ca = d->transposed ? d->Cin : cout_pad, Cb = d->transposed ? cout_pad : d->Cin;
+  const long long M = d->transposed ? (long long)d->N * d->H * d->W : (long long)d->N * d->Ho * d->Wo;
+  const int total_steps = cdiv(M, 32);
+  if (splitk <= 0) {   // aim at ~2 blocks per CU
+    int tiles = cdiv(Ca, BT) * cdiv(T * Cb, BT) * d->groups;
+    splitk = (512 + tiles - 1) / tiles;
+    if (splitk > total_steps) splitk = total_steps;
+    if (splitk < 1) splitk = 1;
+  }
+  steps_per_split = cdiv(total_steps, splitk);
+  splits = cdiv(total_steps, steps_per_split);
+}
+static size_t wgrad_reg_part_bytes(const s2p_conv_desc* d, int cin_real, int cout_real, int splitk) {
+  int splits, sps; wgrad_reg_splits(d, splitk, splits, sps);
+  return ws_align((size_t)splits * cin_real * cout_real * d->KH * d->KW * sizeof(float));
+}
+// Scratch with which s2p_conv2d_wgrad_ws is free of atomics for fp32 tensors too (splitk as passed to the launch)
+extern "C" size_t s2p_conv2d_wgrad_det_workspace(const s2p_conv_desc* d, int cin_real, int cout_real, int splitk) {
+  if (!d) return 0;
+  if (d->dtype != S2P_F32 || d->groups != 1 || d->KH * d->KW > 64) return s2p_conv2d_wgrad_workspace(d, cin_real, cout_real);
+  return wgrad_reg_part_bytes(d, cin_real, cout_real, splitk) + wgrad_bias_ws_bytes(d, cout_real);
+}
+
 extern "C" int s2p_conv2d_wgrad(const s2p_conv_desc* d, const void* x, const void* dy, float* dw, float* db,
                                 int cin_real, int cout_real, int64_t dw_gstride, int splitk, void* stream) {
   return s2p_conv2d_wgrad_ws(d, x, dy, dw, db, cin_real, cout_real, dw_gstride, splitk, nullptr, 0, stream);
@@ -738,22 +769,27 @@ extern "C" int s2p_conv2d_wgrad_ws(const s2p_conv_desc* d, const void* x, const 
       a.tap[ky * d->KW + kx] = (((kx - d->pad) & 0xff) << 8) | ((ky - d->pad) & 0xff);
   const int BT = d->dtype == S2P_F32 ? 64 : 128;
   a.na_tiles = cdiv(a.Ca, BT); a.nb_tiles = cdiv(a.NB, BT);
-  const int total_steps = cdiv(a.M, 32);
-  if (splitk <= 0) {   // aim at ~2 blocks per CU
-    int tiles = a.na_tiles * a.nb_tiles * d->groups;
-    splitk = (512 + tiles - 1) / tiles;
-    if (splitk > total_steps) splitk = total_steps;
-    if (splitk < 1) splitk = 1;
-  }
-  a.steps_per_split = cdiv(total_steps, splitk);
-  a.splitk = cdiv(total_steps, a.steps_per_split);
+  // fp32, one group, with the scratch of s2p_conv2d_wgrad_det_workspace: per-split partial images of dW (and partial channel sums
+  // for db) + fixed-order reduces -- no atomics, bitwise reproducible.  Any other call: fp32 atomics, as before.
+  const size_t part_bytes = wgrad_reg_part_bytes(d, cin_real, cout_real, splitk);
+  const bool det = d->dtype == S2P_F32 && d->groups == 1 && workspace &&
+                   workspace_bytes >= part_bytes + wgrad_bias_ws_bytes(d, cout_real);
+  wgrad_reg_splits(d, splitk, a.splitk, a.steps_per_split);
   dim3 grid(a.na_tiles * a.nb_tiles, d->groups, a.splitk);
   if (db) {
-    int rc = s2p_channel_sum(d->dtype, dy, (int64_t)d->N * d->Ho * d->Wo, cout_real * d->groups, d->y_pitch, db, stream);
+    int rc = s2p_channel_sum_det(d->dtype, dy, (int64_t)d->N * d->Ho * d->Wo, cout_real * d->groups, d->y_pitch, db,
+                                 det ? (char*)workspace + part_bytes : nullptr, det ? wgrad_bias_ws_bytes(d, cout_real) : 0, stream);
     if (rc) return rc;
   }
+  a.part = det ? (float*)workspace : nullptr;
   if (d->dtype == S2P_F32) hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(wgrad_kernel<__bf16>, grid, dim3(256), 0, st, a);
   S2P_CHECK_LAUNCH("wgrad_kernel");
+  if (det) {
+    const long long n = (long long)a.Ca_real * a.dw_row;
+    if (n >= (1ll << 31)) S2P_FAIL(-2, "s2p_conv2d_wgrad: dW too large");
+    s2p_partial_reduce(a.part, a.splitk, n, (int)n, dw, st);
+    S2P_CHECK_LAUNCH("s2p_partial_reduce_kernel(wgrad)");
+  }
   return 0;
 }

@@ -236,12 +236,16 @@ def conv_dgrad_mat(geom, dy, w_bwd, xn, cin_pad, stats, gb, gb_off, gb_st, st_of
     return dxn
 
 
-def conv_wgrad(geom, x, dy, dw, cin_pad, cin_real, cout_real, dw_gstride=0, splitk=0, db=None):
+def conv_wgrad(geom, x, dy, dw, cin_pad, cin_real, cout_real, dw_gstride=0, splitk=0, db=None, deterministic=False):
     """dw += wgrad (cudnn_convolution_backward_weight equivalent); dw is an fp32 view in channels-last layout.
-    The K-split partial sums go through a scratch buffer and are added in a fixed order (s2p_conv2d_wgrad_ws): no atomics."""
+    The K-split partial sums go through a scratch buffer and are added in a fixed order (s2p_conv2d_wgrad_ws): no atomics
+    for bf16; `deterministic` asks for the larger scratch with which fp32 tensors take the same route."""
     N, H, W, xp = x.shape
     d = geom.desc(x.dtype, N, H, W, cin_pad, xp, dy.shape[3])
-    need = lib().s2p_conv2d_wgrad_workspace(ctypes.byref(d), cin_real, cout_real)
+    if deterministic:
+        need = lib().s2p_conv2d_wgrad_det_workspace(ctypes.byref(d), cin_real, cout_real, splitk)
+    else:
+        need = lib().s2p_conv2d_wgrad_workspace(ctypes.byref(d), cin_real, cout_real)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
     pr = _Prof("wgrad", geom, N, H, W, x.dtype)
     check(lib().s2p_conv2d_wgrad_ws(ctypes.byref(d), ptr(x), ptr(dy), ptr(dw), ptr(db), cin_real, cout_real, dw_gstride, splitk,
@@ -273,9 +277,15 @@ def conv_wgrad_batched(geom, jobs, cin_pad, cin_real, cout_real):
     pr.done()
 
 
-def channel_sum(dy, C, db):
-    """db += dy.sum over pixels (bias gradient)."""
+def channel_sum(dy, C, db, deterministic=False):
+    """db += dy.sum over pixels (bias gradient); `deterministic`: partial sums in a scratch + fixed-order reduce, no atomics."""
     pixels = dy.shape[0] * dy.shape[1] * dy.shape[2]
+    if deterministic:
+        need = lib().s2p_channel_sum_workspace(pixels, C)
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dy.device)
+        check(lib().s2p_channel_sum_ws(dtype_id(dy.dtype), ptr(dy), pixels, C, dy.shape[3], ptr(db), ptr(ws), need, stream()),
+              "s2p_channel_sum_ws")
+        return
     check(lib().s2p_channel_sum(dtype_id(dy.dtype), ptr(dy), pixels, C, dy.shape[3], ptr(db), stream()),
           "s2p_channel_sum")
 
@@ -548,3 +558,92 @@ def nhwc_to_u8(x, C, out=None):
     y = out if out is not None else torch.empty((N, H, W, C), dtype=torch.uint8, device=x.device)
     check(lib().s2p_nhwc_to_u8(dtype_id(x.dtype), ptr(x), xp, N * H * W, C, ptr(y), stream()), "s2p_nhwc_to_u8")
     return y
+
+
+# ---- SLAC latent model (csrc/gauss.hip).  Arguments are 2-D fp32 VIEWS (unit stride in the last dimension): the row pitch is the
+# view's stride, so a slice of a [B,S+1,288] sequence buffer is read or written in place -- no cat / chunk / stack copy.
+def _view2(t):
+    if t is None:
+        return None, 0
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError("a 2-D fp32 view with unit stride in its last dimension is needed")
+    return ptr(t), (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def linear_fwd_into(x, w, bias, N, y, act=ACT_NONE, slope=0.2, add=None):
+    """y[:, :] = act(x @ w[:N].T + add + bias); x [M,K] view (K a multiple of 4), w [>=N, w_row], y [M, n_store >= N] view
+    (columns >= N written as zeros).  With `add` ([M, >= N] view) the launch is s2p_linear_add_fwd, else s2p_linear_fwd."""
+    (xp, xs), (yp, ys) = _view2(x), _view2(y)
+    M, K = x.shape
+    if add is None:
+        check(lib().s2p_linear_fwd(xp, M, K, xs, ptr(w), w.shape[-1], ptr(bias), N, act, slope, yp, ys, y.shape[1], stream()),
+              "s2p_linear_fwd")
+    else:
+        ap, as_ = _view2(add)
+        check(lib().s2p_linear_add_fwd(xp, M, K, xs, ptr(w), w.shape[-1], ptr(bias), N, ap, as_, act, slope, yp, ys, y.shape[1],
+                                       stream()), "s2p_linear_add_fwd")
+    return y
+
+
+def linear_add_bwd(dy, y, N, act, slope=0.2, x=None, k_real=0, dw=None, db=None, w_bwd=None, dx=None, accumulate=False, dadd=None):
+    """Backward of linear_fwd_into given dy ([M, >= N] view) and the layer output y (None with ACT_NONE); dpre = dy * act'(y).
+    dw [N, k_real] += dpre.T @ x, db += dpre.sum(0) (needs x);  dx (view [M, K]) = or += dpre @ w (needs w_bwd [K, >= N]);
+    dadd (view) = dpre.  Every output is optional."""
+    (dyp, dys), (yp, ys), (xp, xs), (dxp, dxs), (dap, das) = _view2(dy), _view2(y), _view2(x), _view2(dx), _view2(dadd)
+    M = dy.shape[0]
+    K = x.shape[1] if x is not None else dx.shape[1] if dx is not None else 4
+    check(lib().s2p_linear_add_bwd(xp, xs, dyp, dys, yp, ys, M, K, k_real, N, ptr(w_bwd), w_bwd.shape[-1] if w_bwd is not None else 0,
+                                   act, slope, ptr(dw), dw.shape[-1] if dw is not None else 0, ptr(db), dxp, dxs, int(accumulate),
+                                   dap, das, stream()), "s2p_linear_add_bwd")
+    return dx
+
+
+def gauss_head_fwd(raw, D, eps=None, mean=None, std=None, z=None, z2=None):
+    """raw [M, >= 2D] = [mean | raw_std] -> mean, std = softplus + 1e-5, z = z2 = mean + eps * std, each into its own view."""
+    views = [_view2(t) for t in (raw, eps, mean, std, z, z2)]
+    (rp, rs), (ep, es), (mp, ms), (sp, ss), (zp, zs), (z2p, z2s) = views
+    check(lib().s2p_gauss_head_fwd(rp, rs, raw.shape[0], D, ep, es, mp, ms, sp, ss, zp, zs, z2p, z2s, stream()), "s2p_gauss_head_fwd")
+
+
+def gauss_head_bwd(raw, D, draw, eps=None, dmean=None, dstd=None, dz=None, dz2=None):
+    """draw[:, :2D] = [dmean + dz + dz2 | (dstd + (dz + dz2) * eps) * sigmoid(raw_std)]."""
+    views = [_view2(t) for t in (raw, eps, dmean, dstd, dz, dz2, draw)]
+    (rp, rs), (ep, es), (mp, ms), (sp, ss), (zp, zs), (z2p, z2s), (dp, ds) = views
+    check(lib().s2p_gauss_head_bwd(rp, rs, raw.shape[0], D, ep, es, mp, ms, sp, ss, zp, zs, z2p, z2s, dp, ds, stream()),
+          "s2p_gauss_head_bwd")
+
+
+def gauss_kl(mu_p, std_p, mu_q, std_q, B, T, scale, loss, const_first=True, want_grad=True):
+    """loss[0] += scale * sum KL(p || q); p [B*T, D] rows (b, t), q [B*(T-1), D] rows (b, t-1) (t = 0: N(0, I)) or [B*T, D].
+    Returns (dmu_p, dstd_p, dmu_q, dstd_q), already scaled, or None."""
+    D = mu_p.shape[1]
+    g = [torch.empty_like(t) for t in (mu_p, std_p, mu_q, std_q)] if want_grad else [None] * 4
+    check(lib().s2p_gauss_kl(ptr(mu_p), ptr(std_p), mu_p.stride(0), ptr(mu_q), ptr(std_q), mu_q.stride(0) if mu_q is not None else 0, B, T,
+                             D, int(const_first), scale, ptr(loss), ptr(g[0]), ptr(g[1]), D, ptr(g[2]), ptr(g[3]), D, stream()),
+          "s2p_gauss_kl")
+    return g if want_grad else None
+
+
+def gauss_ll(mu, std, target, done, scale, loss, want_grad=True):
+    """loss[0] += scale * sum (1 - done) * nll(target | mu, std); mu, std [n, 1] views, target / done contiguous [n]."""
+    n = mu.shape[0]
+    dmu = torch.empty(n, dtype=torch.float32, device=mu.device) if want_grad else None
+    dstd = torch.empty(n, dtype=torch.float32, device=mu.device) if want_grad else None
+    check(lib().s2p_gauss_ll(ptr(mu), mu.stride(0), ptr(std), std.stride(0), ptr(target), ptr(done), n, scale, ptr(loss), ptr(dmu),
+                             ptr(dstd), stream()), "s2p_gauss_ll")
+    return dmu, dstd
+
+
+def gauss_ll_image(mu, target, C, sigma, scale, loss, want_grad=True):
+    """mu: NHWC [N,H,W,pitch] (compute dtype); target: fp32 NCHW [N,C,H,W] or uint8 NHWC [N,H,W,C] (read as u8 / 255).
+    loss[0] += scale * sum nll; returns dmu (layout and dtype of mu, padded channels zero) or None."""
+    N, H, W, pitch = mu.shape
+    u8 = target.dtype == torch.uint8
+    if not u8 and target.dtype != torch.float32:
+        raise TypeError("the image target is fp32 NCHW or uint8 NHWC")
+    if target.numel() != N * C * H * W or not target.is_contiguous() or not mu.is_contiguous():
+        raise ValueError("image likelihood: target / mu shape or layout")
+    dmu = torch.empty_like(mu) if want_grad else None
+    check(lib().s2p_gauss_ll_image(dtype_id(mu.dtype), ptr(mu), pitch, ptr(target), int(u8), N, C, H * W, sigma, scale, ptr(loss),
+                                   ptr(dmu), stream()), "s2p_gauss_ll_image")
+    return dmu

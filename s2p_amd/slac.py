@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import ACT_LRELU, EPI_MUL_ACTGRAD, chunk_elems
+from ._lib import ACT_LRELU, ACT_NONE, EPI_MUL_ACTGRAD, chunk_elems
 from .ops import ConvGeom, pad_to
 
 ENCODER_100 = [("conv", 3, 32, 5, 2, 2, 0), ("conv", 32, 64, 3, 2, 1, 0), ("conv", 64, 128, 3, 2, 1, 0),
@@ -62,10 +62,10 @@ class _StackFn(torch.autograd.Function):
             dw = torch.zeros((rows, k * k, cols), dtype=torch.float32, device=dev)
             db = torch.zeros(cout, dtype=torch.float32, device=dev)
             if tr:                                                       # scatter form: bias gradient is a plain channel sum
-                ops.conv_wgrad(geom, x_i, d, dw, cin_pad, cin, cout)
-                ops.channel_sum(d, cout, db)
-            else:
-                ops.conv_wgrad(geom, x_i, d, dw, cin_pad, cin, cout, db=db)
+                ops.conv_wgrad(geom, x_i, d, dw, cin_pad, cin, cout, deterministic=True)
+                ops.channel_sum(d, cout, db, deterministic=True)
+            else:                                                        # (deterministic: no atomics in fp32 either)
+                ops.conv_wgrad(geom, x_i, d, dw, cin_pad, cin, cout, db=db, deterministic=True)
             grads[2 * i] = dw.reshape(rows, k, k, cols).permute(0, 3, 1, 2).contiguous()
             grads[2 * i + 1] = db
             if i > 0:                                                    # x_i = lrelu(pre_{i-1}): fold its derivative in
@@ -189,3 +189,427 @@ class Decoder(_Stack):
         y = self.run(h)                                            # [B*S,100,100,pitch]
         img = _ToNchw.apply(y, 3).reshape(B, S, 3, y.shape[1], y.shape[2])
         return img, torch.full_like(img, self.std)
+
+
+# ---- the latent model (SPEC.md N3b; reference latent.py:174-311) ---------------------------------------------------------
+Z1, Z2, HID, FEAT = 32, 256, 256, 256
+_LOG_STD_MIN = 1e-5
+
+
+def _f32(shape, dev, zero=False):
+    return (torch.zeros if zero else torch.empty)(shape, dtype=torch.float32, device=dev)
+
+
+class _Lin(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin))
+        self.bias = nn.Parameter(torch.zeros(cout))
+        nn.init.xavier_uniform_(self.weight, gain=1.0)
+
+
+class Gaussian(nn.Module):
+    """Linear -> LeakyReLU(0.2) -> Linear -> LeakyReLU(0.2) -> Linear(2D); mean | raw = chunk, std = softplus(raw) + 1e-5
+    (latent.py:29-52).  Parameters under the reference's keys `net.{0,2,4}.{weight,bias}`.  `groups` splits the first layer's
+    input columns into separately packed operands (the chain part and the part hoisted out of the chain)."""
+
+    def __init__(self, input_dim, output_dim, hidden_units=(256, 256), groups=None):
+        super().__init__()
+        if tuple(hidden_units) != (HID, HID):
+            raise NotImplementedError("only hidden_units=(256, 256) is built")
+        self.input_dim, self.D = input_dim, output_dim
+        self.N = 2 * output_dim
+        self.Npad = pad_to(self.N, 4)
+        self.groups = groups if groups is not None else [[(0, input_dim)]]
+        self.net = nn.Module()
+        self.net.add_module("0", _Lin(input_dim, HID))
+        self.net.add_module("2", _Lin(HID, HID))
+        self.net.add_module("4", _Lin(HID, self.N))
+        self._pack_key, self._packed = None, None
+
+    def layer_params(self):
+        out = []
+        for i in (0, 2, 4):
+            m = self.net._modules[str(i)]
+            out += [m.weight, m.bias]
+        return out
+
+    def packed(self):
+        """fp32 GEMM operands: per first-layer column group (w [256][Kpad], its transpose [Kpad][256], K); w2 / w3 and their
+        transposes, the last layer padded to a multiple of 4 rows.  Re-packed only when a parameter changed."""
+        ps = self.layer_params()
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if key == self._pack_key:
+            return self._packed
+        with torch.no_grad():
+            w1, b1, w2, b2, w3, b3 = [p.detach().float() for p in ps]
+            g1 = []
+            for cols in self.groups:
+                w = torch.cat([w1[:, a:b] for a, b in cols], dim=1)
+                k = w.shape[1]
+                wp = _f32((HID, pad_to(k, 4)), w.device, zero=True)
+                wp[:, :k] = w
+                g1.append((wp, wp.t().contiguous(), k))
+            w3p = _f32((self.Npad, HID), w3.device, zero=True)
+            w3p[:self.N] = w3
+            b3p = _f32((self.Npad,), w3.device, zero=True)
+            b3p[:self.N] = b3
+            out = dict(g1=g1, b1=b1.contiguous(), w2=w2.contiguous(), w2t=w2.t().contiguous(), b2=b2.contiguous(), w3=w3p,
+                       w3t=w3p.t().contiguous(), b3=b3p)
+        self._pack_key, self._packed = key, out
+        return out
+
+    def unpack_dw1(self, dws):
+        """Gradients of the packed first-layer groups -> the gradient of net.0.weight (reference column order)."""
+        dw = torch.empty_like(self.net._modules["0"].weight)
+        for cols, g in zip(self.groups, dws):
+            o = 0
+            for a, b in cols:
+                dw[:, a:b] = g[:, o:o + b - a]
+                o += b - a
+        return dw
+
+
+def _mlp_tail_fwd(g, pk, h1, h2, raw):
+    """Layers 2 and 3 on a first-layer output h1 (views [M, 256]); raw: [M, Npad]."""
+    ops.linear_fwd_into(h1, pk["w2"], pk["b2"], HID, h2, ACT_LRELU, SLOPE)
+    ops.linear_fwd_into(h2, pk["w3"], pk["b3"], g.Npad, raw)
+
+
+def _mlp_tail_dgrad(g, pk, draw, h2, dh2, h1, dh1):
+    """dL/dh2 and dL/dh1 from dL/draw: the two launches of the backward that ARE sequential (weight gradients are not)."""
+    ops.linear_add_bwd(draw, None, g.Npad, ACT_NONE, w_bwd=pk["w3t"], dx=dh2)
+    ops.linear_add_bwd(dh2, h2, HID, ACT_LRELU, SLOPE, w_bwd=pk["w2t"], dx=dh1)
+
+
+def _mlp_tail_wgrad(g, pk, draw, h2, dh2, h1, dev):
+    """Weight / bias gradients of layers 2 and 3 over all rows in one launch each (s2p_linear_bwd's wgrad pass)."""
+    dw3, db3 = _f32((g.Npad, HID), dev, True), _f32((g.Npad,), dev, True)
+    dw2, db2 = _f32((HID, HID), dev, True), _f32((HID,), dev, True)
+    ops.linear_add_bwd(draw, None, g.Npad, ACT_NONE, x=h2, k_real=HID, dw=dw3, db=db3)
+    ops.linear_add_bwd(dh2, h2, HID, ACT_LRELU, SLOPE, x=h1, k_real=HID, dw=dw2, db=db2)
+    return dw2, db2, dw3[:g.N], db3[:g.N]
+
+
+def _mlp_fwd(g, pk, x, M, dev):
+    h1, h2, raw = _f32((M, HID), dev), _f32((M, HID), dev), _f32((M, g.Npad), dev)
+    ops.linear_fwd_into(x, pk["g1"][0][0], pk["b1"], HID, h1, ACT_LRELU, SLOPE)
+    _mlp_tail_fwd(g, pk, h1, h2, raw)
+    return h1, h2, raw
+
+
+def _mlp_bwd(g, pk, x, h1, h2, draw, dev, need_dx=True):
+    """Whole backward of an MLP that is not inside the chain (all rows known): -> (grads of the 6 parameters, dx)."""
+    M = x.shape[0]
+    dh2, dh1 = _f32((M, HID), dev), _f32((M, HID), dev)
+    _mlp_tail_dgrad(g, pk, draw, h2, dh2, h1, dh1)
+    dw2, db2, dw3, db3 = _mlp_tail_wgrad(g, pk, draw, h2, dh2, h1, dev)
+    w1, w1t, k = pk["g1"][0]
+    dw1, db1 = _f32((HID, k), dev, True), _f32((HID,), dev, True)
+    dx = _f32((M, w1.shape[1]), dev) if need_dx else None
+    ops.linear_add_bwd(dh1, h1, HID, ACT_LRELU, SLOPE, x=x, k_real=k, dw=dw1, db=db1, w_bwd=w1t, dx=dx)
+    return [g.unpack_dw1([dw1]), db1, dw2, db2, dw3, db3], dx
+
+
+class _GaussFn(torch.autograd.Function):
+    """A Gaussian head on rows that are all known up front (z1_prior, reward): x [M, Kpad] -> mean, std [M, D]."""
+
+    @staticmethod
+    def forward(ctx, x, g, *params):
+        dev, M = x.device, x.shape[0]
+        pk = g.packed()
+        h1, h2, raw = _mlp_fwd(g, pk, x, M, dev)
+        mean, std = _f32((M, g.D), dev), _f32((M, g.D), dev)
+        ops.gauss_head_fwd(raw, g.D, mean=mean, std=std)
+        ctx.g, ctx.pk = g, pk
+        ctx.saved = (x, h1, h2, raw) if torch.is_grad_enabled() or any(ctx.needs_input_grad) else None
+        return mean, std
+
+    @staticmethod
+    def backward(ctx, dmean, dstd):
+        g, pk = ctx.g, ctx.pk
+        x, h1, h2, raw = ctx.saved
+        dev = x.device
+        draw = _f32(raw.shape, dev, True)
+        ops.gauss_head_bwd(raw, g.D, draw, dmean=dmean.contiguous(), dstd=dstd.contiguous())
+        grads, dx = _mlp_bwd(g, pk, x, h1, h2, draw, dev, need_dx=ctx.needs_input_grad[0])
+        ctx.saved = None
+        return (dx, None) + tuple(grads)
+
+
+class _PosteriorFn(torch.autograd.Function):
+    """The reparameterised posterior chain (latent.py:250-281) as ONE autograd node over HIP launches.
+    feat [B,T,256], action [B,T-1,A], noise [B,T,288] (keep: the caller's grad mode; activations are saved only then) -> z1_mean [B,T,32], z1_std [B,T,32], z [B,T,288] (z1 | z2).
+    Per time step the chain is 8 launches forward (2 x (3 layers + head)) and 8 backward (2 x (head + 3 dgrads)): the
+    feature / action columns of the two first layers are one batched GEMM before the chain, every weight gradient and the
+    feature / action gradients are batched launches after it."""
+
+    @staticmethod
+    def forward(ctx, feat, action, noise, model, keep, *params):
+        dev = feat.device
+        B, T, _ = feat.shape
+        S, A = T - 1, action.shape[2]
+        gi1, gi2, g1, g2 = model.z1_posterior_init, model.z2_prior_init, model.z1_posterior, model.z2_prior
+        pi1, pi2, p1, p2 = gi1.packed(), gi2.packed(), g1.packed(), g2.packed()
+        Tn = max(S, 1) if keep else 1                                  # time slots of the saved activations
+        slot = (lambda t: t - 1) if keep else (lambda t: 0)
+        z = _f32((B, T, Z1 + Z2), dev)
+        mean, std = _f32((B, T, Z1), dev), _f32((B, T, Z1), dev)
+        # t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
+        xz = _f32((Tn, B, Z1 + Z2), dev)                               # [slot(t)] = z1(t) | z2(t-1): the chain's input rows
+        a0 = _mlp_fwd(gi1, pi1, feat[:, 0], B, dev)
+        ops.gauss_head_fwd(a0[2], Z1, eps=noise[:, 0, :Z1], mean=mean[:, 0], std=std[:, 0], z=z[:, 0, :Z1])
+        b0 = _mlp_fwd(gi2, pi2, z[:, 0, :Z1], B, dev)
+        ops.gauss_head_fwd(b0[2], Z2, eps=noise[:, 0, Z1:], z=z[:, 0, Z1:], z2=xz[0][:, Z1:] if S > 0 else None)
+        sv = None
+        if S > 0:
+            # what does not depend on the chain: feat(t) | a(t-1) -> the row term of z1_posterior's first layer, a(t-1) -> z2_posterior's
+            ka, kb = p1["g1"][1][0].shape[1], p2["g1"][1][0].shape[1]
+            xa, xb = _f32((S, B, ka), dev, True), _f32((S, B, kb), dev, True)
+            xa[:, :, :FEAT] = feat[:, 1:].transpose(0, 1)
+            xa[:, :, FEAT:FEAT + A] = action.transpose(0, 1)
+            xb[:, :, :A] = action.transpose(0, 1)
+            ra, rb = _f32((S * B, HID), dev), _f32((S * B, HID), dev)
+            ops.linear_fwd_into(xa.view(S * B, ka), p1["g1"][1][0], None, HID, ra)
+            ops.linear_fwd_into(xb.view(S * B, kb), p2["g1"][1][0], None, HID, rb)
+            h1a, h2a, rawa = _f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g1.Npad), dev)
+            h1b, h2b, rawb = _f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g2.Npad), dev)
+            for t in range(1, T):
+                s, r = slot(t), slice((t - 1) * B, t * B)
+                # q(z1(t) | feat(t), z2(t-1), a(t-1))
+                ops.linear_fwd_into(xz[s][:, Z1:], p1["g1"][0][0], p1["b1"], HID, h1a[s], ACT_LRELU, SLOPE, add=ra[r])
+                _mlp_tail_fwd(g1, p1, h1a[s], h2a[s], rawa[s])
+                ops.gauss_head_fwd(rawa[s], Z1, eps=noise[:, t, :Z1], mean=mean[:, t], std=std[:, t], z=z[:, t, :Z1], z2=xz[s][:, :Z1])
+                # q(z2(t) | z1(t), z2(t-1), a(t-1))
+                ops.linear_fwd_into(xz[s], p2["g1"][0][0], p2["b1"], HID, h1b[s], ACT_LRELU, SLOPE, add=rb[r])
+                _mlp_tail_fwd(g2, p2, h1b[s], h2b[s], rawb[s])
+                ops.gauss_head_fwd(rawb[s], Z2, eps=noise[:, t, Z1:], z=z[:, t, Z1:], z2=xz[slot(t + 1)][:, Z1:] if t < S else None)
+            sv = (xa, xb, h1a, h2a, rawa, h1b, h2b, rawb)
+        ctx.model, ctx.packs, ctx.A = model, (pi1, pi2, p1, p2), A
+        ctx.saved = (feat, noise, z, xz, a0, b0, sv) if keep else None
+        model.chain_state_bytes = sum(t.numel() * 4 for t in (xz,) + a0 + b0 + (sv or ())) if keep else 0
+        return mean, std, z
+
+    @staticmethod
+    def backward(ctx, dmean, dstd, dz):
+        model, A = ctx.model, ctx.A
+        pi1, pi2, p1, p2 = ctx.packs
+        gi1, gi2, g1, g2 = model.z1_posterior_init, model.z2_prior_init, model.z1_posterior, model.z2_prior
+        feat, noise, z, xz, a0, b0, sv = ctx.saved
+        dev = feat.device
+        B, T, _ = feat.shape
+        S = T - 1
+        dmean = dmean.contiguous() if dmean is not None else _f32((B, T, Z1), dev, True)
+        dstd = dstd.contiguous() if dstd is not None else _f32((B, T, Z1), dev, True)
+        dz = dz.contiguous() if dz is not None else _f32((B, T, Z1 + Z2), dev, True)
+        g_chain, dfeat, daction = [None] * 12, _f32((B, T, FEAT), dev), None
+        dxz = None
+        if S > 0:
+            xa, xb, h1a, h2a, rawa, h1b, h2b, rawb = sv
+            dxz = _f32((S, B, Z1 + Z2), dev)                           # gradient at z1(t) | z2(t-1), slot t - 1
+            drawa, dh2a, dh1a = _f32((S, B, g1.Npad), dev), _f32((S, B, HID), dev), _f32((S, B, HID), dev)
+            drawb, dh2b, dh1b = _f32((S, B, g2.Npad), dev), _f32((S, B, HID), dev), _f32((S, B, HID), dev)
+            for t in range(S, 0, -1):
+                s = t - 1
+                ops.gauss_head_bwd(rawb[s], Z2, drawb[s], eps=noise[:, t, Z1:], dz=dz[:, t, Z1:], dz2=dxz[t][:, Z1:] if t < S else None)
+                _mlp_tail_dgrad(g2, p2, drawb[s], h2b[s], dh2b[s], h1b[s], dh1b[s])
+                ops.linear_add_bwd(dh1b[s], h1b[s], HID, ACT_LRELU, SLOPE, w_bwd=p2["g1"][0][1], dx=dxz[s])
+                ops.gauss_head_bwd(rawa[s], Z1, drawa[s], eps=noise[:, t, :Z1], dmean=dmean[:, t], dstd=dstd[:, t], dz=dz[:, t, :Z1],
+                                   dz2=dxz[s][:, :Z1])
+                _mlp_tail_dgrad(g1, p1, drawa[s], h2a[s], dh2a[s], h1a[s], dh1a[s])
+                ops.linear_add_bwd(dh1a[s], h1a[s], HID, ACT_LRELU, SLOPE, w_bwd=p1["g1"][0][1], dx=dxz[s][:, Z1:], accumulate=True)
+        # t = 0
+        drb0 = _f32(b0[2].shape, dev)
+        ops.gauss_head_bwd(b0[2], Z2, drb0, eps=noise[:, 0, Z1:], dz=dz[:, 0, Z1:], dz2=dxz[0][:, Z1:] if S > 0 else None)
+        g_i2, dz10 = _mlp_bwd(gi2, pi2, z[:, 0, :Z1], b0[0], b0[1], drb0, dev)
+        dra0 = _f32(a0[2].shape, dev)
+        ops.gauss_head_bwd(a0[2], Z1, dra0, eps=noise[:, 0, :Z1], dmean=dmean[:, 0], dstd=dstd[:, 0], dz=dz[:, 0, :Z1], dz2=dz10)
+        g_i1, dfeat0 = _mlp_bwd(gi1, pi1, feat[:, 0], a0[0], a0[1], dra0, dev)
+        dfeat[:, 0] = dfeat0
+        if S > 0:
+            # after the chain: every weight gradient of the two chain MLPs, and the feature / action gradients, over all S*B rows
+            M = S * B
+            f2 = lambda t: t.view(M, t.shape[-1])
+            for j, (g, p, dr, h2, dh2, h1, dh1, xrow, xchain) in enumerate((
+                    (g1, p1, drawa, h2a, dh2a, h1a, dh1a, xa, f2(xz)[:, Z1:]), (g2, p2, drawb, h2b, dh2b, h1b, dh1b, xb, f2(xz)))):
+                dw2, db2, dw3, db3 = _mlp_tail_wgrad(g, p, f2(dr), f2(h2), f2(dh2), f2(h1), dev)
+                (wz, wzt, kz), (wr, wrt, kr) = p["g1"]
+                dwz, dwr, db1 = _f32((HID, kz), dev, True), _f32((HID, kr), dev, True), _f32((HID,), dev, True)
+                ops.linear_add_bwd(f2(dh1), f2(h1), HID, ACT_LRELU, SLOPE, x=xchain, k_real=kz, dw=dwz, db=db1)
+                dxr = _f32((M, wr.shape[1]), dev)
+                ops.linear_add_bwd(f2(dh1), f2(h1), HID, ACT_LRELU, SLOPE, x=f2(xrow), k_real=kr, dw=dwr, w_bwd=wrt, dx=dxr)
+                g_chain[6 * j:6 * j + 6] = [g.unpack_dw1([dwz, dwr]), db1, dw2, db2, dw3, db3]
+                dxr = dxr.view(S, B, -1).transpose(0, 1)
+                if j == 0:
+                    dfeat[:, 1:] = dxr[:, :, :FEAT]
+                    daction = dxr[:, :, FEAT:FEAT + A].contiguous()
+                else:
+                    daction = daction + dxr[:, :, :A]
+        else:
+            g_chain = [torch.zeros_like(q) for q in g1.layer_params() + g2.layer_params()]
+        ctx.saved = None
+        need = ctx.needs_input_grad
+        return (dfeat if need[0] else None, daction if need[1] else None, None, None, None) + tuple(g_i1) + tuple(g_i2) + tuple(g_chain)
+
+
+class _KlFn(torch.autograd.Function):
+    """loss_kld = KL(posterior || prior).mean(0).sum() with the N(0, I) prior of t = 0 built in; value and gradients in one launch."""
+
+    @staticmethod
+    def forward(ctx, mu_p, std_p, mu_q, std_q, B, T):
+        loss = _f32((1,), mu_p.device, True)
+        keep = torch.is_grad_enabled() or any(ctx.needs_input_grad)
+        ctx.shapes = (mu_p.shape, mu_q.shape)
+        ctx.g = ops.gauss_kl(mu_p.reshape(B * T, -1), std_p.reshape(B * T, -1), mu_q, std_q, B, T, 1.0 / B, loss, want_grad=keep)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        go = go.reshape(1).float().contiguous()
+        g, ctx.g = ctx.g, None
+        sp, sq = ctx.shapes
+        return tuple(ops.scale_(t, go).reshape(s) for t, s in zip(g, (sp, sp, sq, sq))) + (None, None)
+
+
+class _RewardLlFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu, std, reward, done, B):
+        loss = _f32((1,), mu.device, True)
+        keep = torch.is_grad_enabled() or any(ctx.needs_input_grad)
+        ctx.g = ops.gauss_ll(mu, std, reward, done, 1.0 / B, loss, want_grad=keep)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        go = go.reshape(1).float().contiguous()
+        (dmu, dstd), ctx.g = ctx.g, None
+        return ops.scale_(dmu, go).reshape(-1, 1), ops.scale_(dstd, go).reshape(-1, 1), None, None, None
+
+
+class _ImageLlFn(torch.autograd.Function):
+    """loss_image on the decoder's NHWC output; the gradient is produced in that layout and dtype in the same pass."""
+
+    @staticmethod
+    def forward(ctx, y, target, sigma, B):
+        loss = _f32((1,), y.device, True)
+        keep = torch.is_grad_enabled() or any(ctx.needs_input_grad)
+        ctx.g = ops.gauss_ll_image(y, target, 3, sigma, 1.0 / B, loss, want_grad=keep)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        g, ctx.g = ctx.g, None
+        return ops.scale_(g, go.reshape(1).float().contiguous()), None, None, None
+
+
+def create_feature_actions(feature_, action_):
+    """fa(t) = (feat(1:t), a(1:t-1)) and fa(t+1), flattened per sample (slac/utils.py:7-18)."""
+    N = feature_.size(0)
+    f, n_f = feature_[:, :-1].reshape(N, -1), feature_[:, 1:].reshape(N, -1)
+    a, n_a = action_[:, :-1].reshape(N, -1), action_[:, 1:].reshape(N, -1)
+    return torch.cat([f, a], dim=-1), torch.cat([n_f, n_a], dim=-1)
+
+
+class LatentModel(nn.Module):
+    """SLAC's stochastic latent variable model (latent.py:174-311) on HIP: the call surface, state_dict keys and parameter
+    aliasing (`z2_posterior_init` is `z2_prior_init`, `z2_posterior` is `z2_prior`) of the reference, so its `latent.pth`
+    loads with strict=True and torch.optim.Adam(model.parameters()) trains it.  The Gaussian heads are fp32; `dtype` is
+    the compute dtype of the two conv stacks.  `noise` ([B,S+1,288], the eps of z1(t) | z2(t)) makes a call reproducible."""
+
+    def __init__(self, state_shape=(3, 100, 100), action_shape=(6,), feature_dim=256, z1_dim=32, z2_dim=256,
+                 hidden_units=(256, 256), image_size=100, dtype=torch.float32, device="cuda:0"):
+        super().__init__()
+        if (image_size, feature_dim, z1_dim, z2_dim, tuple(hidden_units)) != (100, FEAT, Z1, Z2, (HID, HID)) or \
+                tuple(state_shape) != (3, 100, 100):
+            raise NotImplementedError("only image_size=100, feature_dim=256, z1_dim=32, z2_dim=256, hidden_units=(256, 256) is built")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("the SLAC latent model runs on a HIP device only (no CPU fallback)")
+        A = self.action_dim = int(action_shape[0])
+        self.z2_prior_init = Gaussian(Z1, Z2)                                              # p(z2(0) | z1(0))
+        self.z1_prior = Gaussian(Z2 + A, Z1)                                               # p(z1(t+1) | z2(t), a(t))
+        self.z2_prior = Gaussian(Z1 + Z2 + A, Z2, groups=[[(0, Z1 + Z2)], [(Z1 + Z2, Z1 + Z2 + A)]])
+        self.z1_posterior_init = Gaussian(FEAT, Z1)                                        # q(z1(0) | feat(0))
+        self.z2_posterior_init = self.z2_prior_init
+        self.z1_posterior = Gaussian(FEAT + Z2 + A, Z1, groups=[[(FEAT, FEAT + Z2)], [(0, FEAT), (FEAT + Z2, FEAT + Z2 + A)]])
+        self.z2_posterior = self.z2_prior
+        self.reward = Gaussian(2 * (Z1 + Z2) + A, 1)                                       # p(r(t) | z(t), a(t), z(t+1))
+        self.encoder = Encoder(state_shape[0], feature_dim, image_size, dtype=dtype, device=dev)
+        self.decoder = Decoder(Z1 + Z2, state_shape[0], std=float(0.1 ** 0.5), image_size=image_size, dtype=dtype, device=dev)
+        for st in (self.encoder, self.decoder):                                            # initialize_weight of the reference
+            for i, p in enumerate(st.layer_params()):
+                if i % 2 == 0:
+                    nn.init.xavier_uniform_(p, gain=1.0)
+        self.to(dev)
+        self.chain_state_bytes = 0              # bytes the last sample_posterior kept for its backward (0 under no_grad)
+
+    @property
+    def device(self):
+        return self.encoder.device
+
+    def _chain_params(self):
+        return (self.z1_posterior_init.layer_params() + self.z2_prior_init.layer_params() + self.z1_posterior.layer_params() +
+                self.z2_prior.layer_params())
+
+    def _posterior(self, features_, actions_, noise):
+        dev = self.device
+        features_ = features_.to(dev, torch.float32).contiguous()
+        actions_ = actions_.to(dev, torch.float32).contiguous()
+        B, T, _ = features_.shape
+        if actions_.shape[:2] != (B, T - 1) or actions_.shape[2] != self.action_dim or features_.shape[2] != FEAT:
+            raise ValueError("features_ [B,S+1,256] and actions_ [B,S,A] are needed")
+        if noise is None:
+            noise = torch.randn((B, T, Z1 + Z2), dtype=torch.float32, device=dev)
+        noise = noise.to(dev, torch.float32).contiguous()
+        if noise.shape != (B, T, Z1 + Z2):
+            raise ValueError("noise is [B,S+1,z1_dim+z2_dim]")
+        return _PosteriorFn.apply(features_, actions_, noise, self, torch.is_grad_enabled(), *self._chain_params())
+
+    def sample_posterior(self, features_, actions_, noise=None):
+        mean, std, z = self._posterior(features_, actions_, noise)
+        return mean, std, z[..., :Z1], z[..., Z1:]
+
+    def _prior(self, actions_, z2_post_):
+        B, S, A = actions_.shape
+        x = _f32((B, S, pad_to(Z2 + A, 4)), self.device, True)
+        x = torch.cat([z2_post_[:, :S], actions_, x[..., Z2 + A:]], dim=-1).reshape(B * S, -1)
+        return _GaussFn.apply(x, self.z1_prior, *self.z1_prior.layer_params())          # [B*S, 32] each
+
+    def sample_prior(self, actions_, z2_post_):
+        actions_ = actions_.to(self.device, torch.float32)
+        B, S, _ = actions_.shape
+        mean, std = self._prior(actions_, z2_post_)
+        m0, s0 = _f32((B, 1, Z1), self.device, True), torch.ones((B, 1, Z1), dtype=torch.float32, device=self.device)
+        return torch.cat([m0, mean.reshape(B, S, Z1)], dim=1), torch.cat([s0, std.reshape(B, S, Z1)], dim=1)
+
+    def calculate_loss(self, state_, action_, reward_, done_, noise=None):
+        dev = self.device
+        B, T = state_.shape[:2]
+        S = T - 1
+        action_ = action_.to(dev, torch.float32).contiguous()
+        reward_ = reward_.to(dev, torch.float32).reshape(B * S).contiguous()
+        done_ = done_.to(dev, torch.float32).reshape(B * S).contiguous()
+        feature_ = self.encoder(state_)
+        z1_mean_post_, z1_std_post_, z_ = self._posterior(feature_, action_, noise)
+        z1_mean_pri_, z1_std_pri_ = self._prior(action_, z_[..., Z1:])
+        loss_kld = _KlFn.apply(z1_mean_post_, z1_std_post_, z1_mean_pri_, z1_std_pri_, B, T)
+        # image term: straight on the decoder's NHWC output, target at full precision
+        y = self.decoder.run(z_.reshape(B * T, 1, 1, Z1 + Z2).to(self.decoder.dtype).contiguous())
+        if state_.dtype == torch.uint8:
+            target = state_.reshape(B * T, *state_.shape[2:]).to(dev).contiguous()
+        else:
+            target = state_.reshape(B * T, *state_.shape[2:]).to(dev, torch.float32).contiguous()
+        loss_image = _ImageLlFn.apply(y, target, self.decoder.std, B)
+        # reward term
+        pad = _f32((B, S, pad_to(2 * (Z1 + Z2) + self.action_dim, 4) - 2 * (Z1 + Z2) - self.action_dim), dev, True)
+        x = torch.cat([z_[:, :-1], action_, z_[:, 1:], pad], dim=-1).reshape(B * S, -1)
+        r_mean, r_std = _GaussFn.apply(x, self.reward, *self.reward.layer_params())
+        loss_reward = _RewardLlFn.apply(r_mean, r_std, reward_, done_, B)
+        return loss_kld, loss_image, loss_reward
+
+    def save_model(self, save_dir):
+        """encoder.pth and latent.pth with the reference's keys (slac/algo.py:145-150)."""
+        import os
+        os.makedirs(save_dir, exist_ok=True)
+        torch.save(self.encoder.state_dict(), os.path.join(save_dir, "encoder.pth"))
+        torch.save(self.state_dict(), os.path.join(save_dir, "latent.pth"))
