@@ -49,11 +49,6 @@ struct GatherArgs {
   struct Phase { int Qh, Qw, M, oy0, ox0, T, Ktot, npix_tiles; int tap[PHASE_TAPS]; } ph[MAX_PHASES];
 };
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) { f(std::integral_constant<int, B>{}); static_for<B + 1, E>(f); }
-}
-
 template <typename T> struct Mma;
 template <> struct Mma<__bf16> { static constexpr int BK = 32; };
 template <> struct Mma<float> { static constexpr int BK = 16; };
@@ -1070,7 +1065,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const GatherArgs a) {
       const char* hb = hbase + (slab & 1) * HALO;
       const char* hb_next = hbase + ((slab + 1) & 1) * HALO;
       const bool more_slabs = slab + 1 < nslab;
-      static_for<0, 2 * TS>([&](auto uc) {               // u = 2 * tap + half (compile time: register sets and taps are static)
+      s2p_static_for<0, 2 * TS>([&](auto uc) {           // u = 2 * tap + half (compile time: register sets and taps are static)
         constexpr int u = decltype(uc)::value;
         // (1) DMA of half-step hs + 3
         constexpr int u3 = u + 3;

@@ -24,11 +24,6 @@
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void pl_static_for(F&& f) {
-  if constexpr (B < E) { f(std::integral_constant<int, B>{}); pl_static_for<B + 1, E>(f); }
-}
-
 // DMA with the uniform part of the source offset in an SGPR (soffset).  An invalid lane carries voffset = 0x80000000 and returns
 // zeros whatever the scalar part is.  The scalar part COUNTS in the range check on gfx950 (measured in round 4: a group offset
 // beyond num_records in soffset zero-filled valid lanes), so num_records must cover base + voffset + soffset of every valid lane:
@@ -259,8 +254,8 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
 #pragma unroll
         for (int j = 0; j < PB; ++j) fb[j] = junk;
       }
-      pl_static_for<0, 4>([&](auto ic) { read_a(uc{}, ic, fa); });
-      pl_static_for<0, PB>([&](auto jc) { read_b(uc{}, jc, fb); });
+      s2p_static_for<0, 4>([&](auto ic) { read_a(uc{}, ic, fa); });
+      s2p_static_for<0, PB>([&](auto jc) { read_b(uc{}, jc, fb); });
     }
     if constexpr ((DIAG & 16) != 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
     if constexpr ((DIAG & 128) != 0) ph[1] = __builtin_amdgcn_s_memrealtime();
@@ -280,7 +275,7 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
                    last ? pi * 4 * a.gb_pitch * 2 : (k2 + 2) * 64);
         }
       };
-      pl_static_for<0, 9>([&](auto Uc) {
+      s2p_static_for<0, 9>([&](auto Uc) {
         constexpr int U = decltype(Uc)::value;
         constexpr int u = 2 * U + SET;
         typedef std::integral_constant<int, u + 2> un;           // the step whose fragments are fetched now
@@ -898,14 +893,14 @@ __global__ __launch_bounds__(512) void conv_plane_pair_kernel(const PlaneArgs a)
   __builtin_amdgcn_s_barrier();                                 // ... for every wave
   __builtin_amdgcn_sched_barrier(0);
   bf16x8 fa[4], fb[PB];
-  pl_static_for<0, 4>([&](auto ic) { read_a(I0{}, ic, fa); });
-  pl_static_for<0, PB>([&](auto jc) { read_b(I0{}, jc, fb); });
+  s2p_static_for<0, 4>([&](auto ic) { read_a(I0{}, ic, fa); });
+  s2p_static_for<0, PB>([&](auto jc) { read_b(I0{}, jc, fb); });
   // K step u of an 18-step iteration (two half-slabs): MFMAs of step u on the fragments in registers; between them the
   // fragment reads of step u + 1, the weight piece of step u + 3 (ring stage (u + 3) % 6, last read in step u - 4) and, in
   // steps 0..3 / 9..12, one piece of the plane of the next-but-one / next half-slab (buffer 1 is free from step 17 of the
   // previous iteration and needed by the reads of step 8; buffer 0 is free from step 8 and needed in step 17).
   for (int k2 = 0; k2 < nhs; k2 += 2) {
-    pl_static_for<0, 18>([&](auto uc) {
+    s2p_static_for<0, 18>([&](auto uc) {
       constexpr int u = decltype(uc)::value;
       typedef std::integral_constant<int, u + 1> un;
       constexpr int up = (u + 17) % 18;                         // previous step: what it issued may still be in flight

@@ -14,10 +14,6 @@
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void pg_static_for(F&& f) {
-  if constexpr (B < E) { f(std::integral_constant<int, B>{}); pg_static_for<B + 1, E>(f); }
-}
 __device__ __forceinline__ void pg_dma16(i32x4 rsrc, unsigned lds_dst, int voffset, int soffset) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
                :: "v"(voffset), "s"(rsrc), "s"(lds_dst), "s"(soffset) : "memory", "m0");
@@ -250,19 +246,19 @@ __global__ __launch_bounds__(512, ((PB <= 3 && (TY == 3 || PG_OCC4_ALL)) ? 4 : 2
     bf16x8 fa[4], fb[PB];
     {
       typedef std::integral_constant<int, SET> vc;
-      pg_static_for<0, 4>([&](auto ic) { read_a(vc{}, ic, fa); });
-      pg_static_for<0, PB>([&](auto jc) { read_b(vc{}, jc, fb); });
+      s2p_static_for<0, 4>([&](auto ic) { read_a(vc{}, ic, fa); });
+      s2p_static_for<0, PB>([&](auto jc) { read_b(vc{}, jc, fb); });
     }
     for (int k2 = 0; k2 < nhs; k2 += 2) {                       // two half-slabs = NSTEP K steps = NTAP pair-steps per iteration
-      pg_static_for<0, NTAP>([&](auto Uc) {
+      s2p_static_for<0, NTAP>([&](auto Uc) {
         constexpr int U = decltype(Uc)::value;
         constexpr int u = 2 * U + SET;
         typedef std::integral_constant<int, u + 2> vn;           // the step whose fragments are fetched now
         sync_top(Uc);
         bf16x8 na[4], nb[PB];
-        pg_static_for<0, PB>([&](auto jc) {
+        s2p_static_for<0, PB>([&](auto jc) {
           constexpr int j = decltype(jc)::value;
-          pg_static_for<j * RPS, ((j + 1) * RPS < NRD ? (j + 1) * RPS : NRD)>([&](auto rc) {
+          s2p_static_for<j * RPS, ((j + 1) * RPS < NRD ? (j + 1) * RPS : NRD)>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
             if constexpr (r < 4) read_a(vn{}, std::integral_constant<int, r>{}, na);
             else read_b(vn{}, std::integral_constant<int, r - 4>{}, nb);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 #include "../../include/s2p_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -178,6 +179,19 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// compute units of the current device (256 where there is none to ask: the workspace queries answer without a GPU)
+inline int s2p_num_cus() {
+  static int ncu = 0;
+  if (!ncu) { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev); ncu = hipGetDeviceProperties(&pr, dev) == hipSuccess ? pr.multiProcessorCount : 256; }
+  return ncu;
+}
+
+// f(integral_constant<int, B>) ... f(integral_constant<int, E - 1>): a loop whose index is a compile-time constant in the body
+template <int B, int E, typename F>
+__device__ __forceinline__ void s2p_static_for(F&& f) {
+  if constexpr (B < E) { f(std::integral_constant<int, B>{}); s2p_static_for<B + 1, E>(f); }
+}
 
 // ---- hand-issued LDS-DMA (buffer_load_dwordx4 ... lds) ---------------------------------------------------------
 // Issued from inline asm so that hipcc does not see the LDS write: with the builtin, hipcc inserts `s_waitcnt vmcnt(0)`

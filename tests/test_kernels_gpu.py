@@ -488,6 +488,12 @@ def test_leaky_relu_slope_above_one_is_rejected(hip_device):
     (2, 128, 64, 21, 21, 2, False),     # the ResBlk grid
     (4, 64, 64, 5, 5, 1, True),         # one job per group of a grouped conv (channel-offset pointers, wide pitches)
     (1, 64, 64, 30, 36, 2, False),      # wider image: 192-row X window variant
+    # the remaining instantiations of wgrad_slab_kernel<window rows, tabulated raster>.  Window rows = 64 + 2 * (W + 2) rounded up to
+    # 32 (128 / 192 / 256 select the kernel); the raster is tabulated up to (H + 1) * (W + 1) = 768 positions
+    (1, 64, 64, 40, 20, 1, False),      # <128, false>: 41 * 21 = 861 positions, window 64 + 44 = 108 -> 128
+    (1, 64, 64, 20, 31, 2, False),      # <192, true>:  21 * 32 = 672, window 64 + 66 = 130 -> 160 (W = 30 is exactly 128)
+    (1, 64, 64, 8, 63, 2, False),       # <256, true>:  9 * 64 = 576, halo 65, window 64 + 130 = 194 -> 224 (W = 62 is exactly 192)
+    (1, 64, 64, 16, 63, 1, False),      # <256, false>: 17 * 64 = 1088
 ])
 def test_conv_wgrad_batched_slab(hip_device, case):
     """s2p_conv2d_wgrad_batched (csrc/wgrad_slab.hip): padded-raster slab kernel + fixed-order partial reduction against
@@ -593,6 +599,11 @@ def test_conv_small_map_splitk(hip_device, case):
     (256, 512, 4, 1, 2, False, 12, 12, 3),     # PatchGAN 4x4 stride 1, pad 2: two classes of 8 taps, dY one row / column larger than x
     (128, 192, 4, 2, 2, False, 9, 13, 5),      # ... three co tiles x two ci slabs per class, a raster of 6 x 8 positions, ragged split
     (64, 64, 4, 1, 2, False, 5, 9, 7),         # ... one tile per class, fewer raster blocks than the split target
+    # ... rasters beyond the 768 tabulated positions: the (n, row, column) address state of wgrad_slabg_kernel (splits for 256 CUs)
+    (128, 256, 4, 1, 2, False, 27, 27, 6),     # dY 28x28, raster 29 x 29 = 841; two classes of 8 taps, span 64 + 60 = 124 (4 window
+                                               # pieces); 6 * 841 positions = 79 blocks, 512 / 16 = 32 splits -> 27 of 3, the last of 1
+    (128, 256, 4, 2, 2, False, 56, 56, 4),     # parity planes 28x28, dY 29x29, raster 29 x 29; four classes of 4 taps, span 64 + 30 = 94
+                                               # (3 pieces); 53 blocks, 512 / 32 = 16 splits -> 14 of 4, the last of 1
 ])
 def test_conv_wgrad_split_units_deterministic(hip_device, case):
     """s2p_conv2d_wgrad_ws: the K-split units of the LDS-DMA weight-gradient kernel store partial tiles and a second
