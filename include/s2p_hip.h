@@ -386,6 +386,43 @@ int s2p_ensemble_head(const float* raw, int raw_pitch, const float* xin, int x_p
                       float rew_std, float* next_obs, float* reward, float* disagreement, float* aleatoric,
                       void* stream);
 
+/* ---- ensemble state-dynamics TRAINING (SPEC.md N2b; reference gaussian_ensemble.py:21-96; csrc/ensemble_train.hip).
+ * All fp32 on v_mfma_f32_32x32x2_f32, group = ensemble member, every entry point ONE launch for all members, no atomics, fixed
+ * summation order (two identical calls give bitwise identical results).
+ * Layouts: activations [B][pitch >= G*N], group g at columns g*N (what s2p_ensemble_head reads); weights, biases and their
+ * gradients PACKED [E][N][K] / [E][N] -- K = the input width padded to a multiple of 4, i.e. the TRANSPOSE of the reference's
+ * [E, in, out] (the layout the grouped conv forward consumes).  `member` is a HOST array of G slot indices in [0, E) (copied
+ * into the kernel arguments; NULL: 0..G-1): group g uses slot member[g] of the [E] arrays, the activations are compact in g.
+ * x: group g, row m at x + g * x_gstride + m * x_pitch (x_gstride 0: every member reads the same [B][K] input; B * x_pitch: a
+ * per-member [G][B][K] batch; N_prev with x_pitch = G * N_prev: the previous layer's activations).
+ * Argument checking as stated above s2p_gauss_head_fwd: negative sizes, a required NULL tensor, a short pitch are refused
+ * before any launch; a size of 0 (G, B or N) is a successful no-op that looks at no pointer.  1 <= G <= E <= 8.
+ * K, N, the pitches and x_gstride multiples of 4 floats; x, w, dpre 16-byte aligned.                                          */
+/* pre[m][g*N+n] = sum_k x[g][m][k] w[e][n][k] + bias[e][n];  act = pre * sigmoid(pre).  pre and/or act (at least one): the
+ * backward of Swish needs pre, the next layer reads act.                                                                      */
+int s2p_ensemble_linear_fwd(const float* x, int64_t x_gstride, int x_pitch, const float* w, const float* bias,
+                            const int32_t* member, int G, int E, int B, int K, int N, float* pre, float* act, int y_pitch,
+                            void* stream);
+/* From dpre [B][dpre_pitch] of a layer: dw[e][n][k] = sum_m dpre[m][g*N+n] x[g][m][k] (packed orientation, OVERWRITTEN for the
+ * listed members, other slots untouched), db[e][n] = sum_m dpre, and with dprev != NULL
+ * dprev[m][g*K+k] = (sum_n dpre[m][g*N+n] w[e][n][k]) * swish'(pre_prev[m][g*K+k])  (pre_prev, dprev share prev_pitch).
+ * Rows are summed in row order by one wave per tile at any B: there is no row split, hence no workspace.                  */
+int s2p_ensemble_linear_bwd(const float* x, int64_t x_gstride, int x_pitch, const float* dpre, int dpre_pitch,
+                            const float* w, const int32_t* member, int G, int E, int B, int K, int N, float* dw, float* db,
+                            const float* pre_prev, float* dprev, int prev_pitch, void* stream);
+/* Fused Gaussian NLL head.  raw [B][raw_pitch >= G*2D] (group g: mu | logstd), xin / target with a group stride like x above
+ * (0: shared by the groups), bounds [D].  mu = raw_mu (+ xin for the D-1 obs outputs, 'local' mode), ls = soft_clamp(raw_ls),
+ * nll = 0.5 ((target - mu) / exp(ls))^2 + ls + 0.5 log 2 pi.  Outputs, each optional:
+ *   sums [2G]: sum nll per group, then sum (mu - target)^2 per group;   loss[0] = scale * sum nll + bound_reg * sum_d (max - min)
+ *   draw [B][draw_pitch] = scale * d sum nll / d raw (both soft-clamp factors included)
+ *   dmin_logstd / dmax_logstd [D] (together) = scale * d sum nll / d bound -/+ bound_reg
+ *   mean / std [G][B][D] (the forward alone: target may then be NULL).
+ * The caller owns the scaling: scale = 1 / (G B D), bound_reg = 0.01 / D give the loss of SPEC.md N2b.  2 <= D <= 33.     */
+int s2p_ensemble_nll(const float* raw, int raw_pitch, const float* xin, int64_t x_gstride, int x_pitch, const float* target,
+                     int64_t t_gstride, int t_pitch, int B, int G, int D, const float* min_logstd, const float* max_logstd,
+                     float scale, float bound_reg, float* sums, float* loss, float* draw, int draw_pitch, float* dmin_logstd,
+                     float* dmax_logstd, float* mean, float* std, void* stream);
+
 /* ---- optimizer + weight packing ---------------------------------------------------- */
 /* torch.optim.Adam step on flat fp32 buffers; g is multiplied by grad_scale first.  All three forms move 16-byte groups:
  * p, g, m, v must be 16-byte aligned (a sub-range of a flat buffer starts at a multiple of 4 elements), else the call is

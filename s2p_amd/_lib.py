@@ -118,6 +118,12 @@ SIGNATURES = {
     "s2p_adam_step": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int, c_float, _P],
     "s2p_ensemble_head": [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, _P,
                           _P, _P, _P],
+    "s2p_ensemble_linear_fwd": [_P, c_int64, c_int, _P, _P, ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_int, c_int, c_int, _P, _P,
+                                c_int, _P],
+    "s2p_ensemble_linear_bwd": [_P, c_int64, c_int, _P, c_int, _P, ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_int, c_int, c_int,
+                                _P, _P, _P, _P, c_int, _P],
+    "s2p_ensemble_nll": [_P, c_int, _P, c_int64, c_int, _P, c_int64, c_int, c_int, c_int, c_int, _P, _P, c_float, c_float,
+                         _P, _P, _P, c_int, _P, _P, _P, _P, _P],
     "s2p_adam_step_dev": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, _P],
     "s2p_adam_step_dev_part": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, c_int, _P],
     "s2p_pack_weights": [_P, c_int, c_int, _P],
