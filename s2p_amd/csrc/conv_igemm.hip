@@ -40,7 +40,6 @@ struct GatherArgs {
   // applies bias / activation / epilogue to the sum (fixed order: no atomics).  ws / ws_bytes: caller's scratch.
   float* part; int psplit, psteps, part_m;
   void* ws; size_t ws_bytes;
-  size_t* plan; const PlaneMat* mat; int* mat_done;   // unused host leftovers (nobody reads them): to go with the next kernel change -- this block is a kernel argument
   unsigned x_bytes, w_bytes;   // fast path: buffer-descriptor sizes of the gathered tensor / packed weights (per group view)
   int tap[MAX_TAPS];   // (wt << 16) | ((dx & 0xff) << 8) | (dy & 0xff)
   // merged sub-pixel phases (strided dgrad / transposed fwd on the LDS-DMA kernel): blockIdx.z selects a record that
@@ -1307,7 +1306,7 @@ struct GatherChoice {
   size_t ws_bytes = 0;        // SplitK: partial tiles
   int bco = 128;              // weight-tile rows of the bf16 kernels (128 / 64)
   HaloKind halo = HaloKind::R_320;
-  PlaneArgs plane;            // Plane / PlaneG: the kernel's argument block, complete but for the norm (copy_norm at the launch)
+  PlaneArgs plane;            // Plane / PlaneG: the kernel's argument block, complete but for the norm block `nm` (filled at the launch)
   PlaneGArgs planeg;
 };
 struct GatherItem { GatherArgs a; GatherChoice c; };
@@ -1334,14 +1333,6 @@ static void copy_conv_fields(P& p, const GatherArgs& a) {
   p.w_row = a.w_row; p.w_gstride = a.w_gstride;
   p.act = a.act; p.epi = a.epi; p.gact = a.gact; p.slope = a.slope; p.gslope = a.gslope;
   p.x_bytes = a.x_bytes; p.w_bytes = a.w_bytes;
-}
-template <typename P>
-static void copy_norm(P& p, const PlaneMat& m) {
-  p.xn = m.xn; p.xn_pitch = m.xn_pitch; p.dgb = m.dgb; p.dgb_pitch = m.dgb_pitch;
-  p.dgbst = m.dgbst; p.dgbst_pitch = m.dgbst_pitch; p.res = m.res; p.res_pitch = m.res_pitch;
-  p.y2 = m.y2; p.y2_pitch = m.y2_pitch; p.gb = m.gb; p.gb_pitch = m.gb_pitch;
-  p.gbst = m.gbst; p.gbst_pitch = m.gbst_pitch; p.stats = m.stats;
-  p.n_act = m.act; p.n_slope = m.slope; p.eps = m.eps;
 }
 
 // ---- planning ---------------------------------------------------------------------------------------------------------------
@@ -1658,14 +1649,14 @@ static int launch_generic(GatherArgs& a, int groups, hipStream_t st) {
 // One launch of a planned call; `mat`: the norm operands where the launch is fused.  (hipcc lays the kernel templates out in the code
 // object in the order this function first names them -- fp32 generic, phases, the bf16 tile kernels, bf16 generic, the order they
 // have always had; keeping it keeps the device code byte-identical across host-only changes.)
-static int launch_item(GatherItem& it, bool bf16, int groups, const PlaneMat* mat, void* ws, hipStream_t st) {
+static int launch_item(GatherItem& it, bool bf16, int groups, const PlaneNorm* mat, void* ws, hipStream_t st) {
   if (!bf16) return launch_generic<float>(it.a, groups, st);      // fp32 is always ConvPath::Generic
   switch (it.c.path) {
     case ConvPath::Plane:
-      if (it.c.fused) copy_norm(it.c.plane, *mat);
+      if (it.c.fused) it.c.plane.nm = *mat;
       return s2p_conv_plane_launch(it.c.plane, groups, st);
     case ConvPath::PlaneG:
-      if (it.c.fused) copy_norm(it.c.planeg, *mat);
+      if (it.c.fused) it.c.planeg.nm = *mat;
       return s2p_conv_planeg_launch(it.c.planeg, groups, st);
     case ConvPath::Phases: {                                        // all sub-pixel phases as one launch of the LDS-DMA kernel
       GatherArgs& a = it.a;
@@ -1682,7 +1673,7 @@ static int launch_item(GatherItem& it, bool bf16, int groups, const PlaneMat* ma
   }
   return launch_generic<__bf16>(it.a, groups, st);
 }
-static int launch_items(ConvPlan& P, bool bf16, int groups, const PlaneMat* mat, const Scratch& sc, hipStream_t st) {
+static int launch_items(ConvPlan& P, bool bf16, int groups, const PlaneNorm* mat, const Scratch& sc, hipStream_t st) {
   for (GatherItem& it : P.items) {
     const int rc = launch_item(it, bf16, groups, mat, sc.ws, st);
     if (rc) return rc;
@@ -1691,9 +1682,9 @@ static int launch_items(ConvPlan& P, bool bf16, int groups, const PlaneMat* mat,
 }
 
 // mat != NULL (s2p_conv2d_fwd_mat): *fused tells the caller whether the norm went with the conv; y may be NULL only then
-static int conv_fwd_impl(const s2p_conv_desc* d, const ConvOperands& op, const PlaneMat* mat, bool* fused, const Scratch& sc, void* stream) {
+static int conv_fwd_impl(const s2p_conv_desc* d, const ConvOperands& op, const PlaneNorm* mat, bool* fused, const Scratch& sc, void* stream) {
   S2P_CHECK_SLOPE("s2p_conv2d_fwd", op.act, op.slope);
-  if (mat) S2P_CHECK_SLOPE("s2p_conv2d_fwd_mat", mat->act, mat->slope);
+  if (mat) S2P_CHECK_SLOPE("s2p_conv2d_fwd_mat", mat->n_act, mat->n_slope);
   ConvPlan P;
   int rc = conv_plan_fwd(d, op, NormWant{mat != nullptr, mat && mat->gb, false}, ScratchAvail{sc.ws != nullptr, sc.bytes}, P);
   if (rc) return rc;
@@ -1727,7 +1718,7 @@ extern "C" int s2p_conv2d_fwd_mat(const s2p_conv_desc* d, const void* x, const v
   if (!d || !y_mat || !stats) S2P_FAIL(-1, "s2p_conv2d_fwd_mat: null pointer");
   if (act != S2P_ACT_NONE && act != S2P_ACT_RELU && act != S2P_ACT_LRELU) S2P_FAIL(-1, "s2p_conv2d_fwd_mat: activation must be none / relu / lrelu");
   if (d->groups != 1 || d->transposed) S2P_FAIL(-1, "s2p_conv2d_fwd_mat: groups == 1, not transposed");
-  PlaneMat m{y_mat, y_mat_pitch, gb_img, gb_pitch, gb_st, gb_st_pitch, stats, act, slope, eps, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0};
+  PlaneNorm m{y_mat, y_mat_pitch, gb_img, gb_pitch, gb_st, gb_st_pitch, stats, act, slope, eps, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0};
   // y == NULL: the conv output itself is not wanted (a forward pass without a backward: it is written only for the backward's sake) --
   // allowed where conv and norm are ONE launch, which then skips that store; refused (before any launch) otherwise
   bool fused = false;
@@ -1746,7 +1737,7 @@ extern "C" size_t s2p_conv2d_fwd_workspace(const s2p_conv_desc* d, int epi) {
 
 // must_fuse (s2p_conv2d_dgrad_mat without the scratch of its two-launch form): refuse, before any launch, unless the norm backward
 // goes with the dgrad
-static int conv_dgrad_impl(const s2p_conv_desc* d, const ConvOperands& op, const PlaneMat* mat, bool must_fuse, bool* fused, const Scratch& sc,
+static int conv_dgrad_impl(const s2p_conv_desc* d, const ConvOperands& op, const PlaneNorm* mat, bool must_fuse, bool* fused, const Scratch& sc,
                            void* stream) {
   if (op.epi == S2P_EPI_MUL_ACTGRAD) S2P_CHECK_ACT_FROM_OUT("s2p_conv2d_dgrad (aux_act)", op.gact);
   ConvPlan P;
@@ -1786,8 +1777,8 @@ extern "C" int s2p_conv2d_dgrad_mat(const s2p_conv_desc* d, const void* dy, cons
   if (act != S2P_ACT_NONE && act != S2P_ACT_RELU && act != S2P_ACT_LRELU) S2P_FAIL(-1, "s2p_conv2d_dgrad_mat: activation must be none / relu / lrelu");
   if (d->groups != 1 || d->transposed || d->reflect) S2P_FAIL(-1, "s2p_conv2d_dgrad_mat: groups == 1, not transposed, zero padding");
   if (d->Cin != d->x_pitch) S2P_FAIL(-1, "s2p_conv2d_dgrad_mat: the produced tensor must be dense (x_pitch %d != Cin %d)", d->x_pitch, d->Cin);
-  PlaneMat m{dxn, dxn_pitch, gb_img, gb_pitch, gb_st, gb_st_pitch, const_cast<float*>(stats), act, slope, eps,
-             xn, xn_pitch, dgb_img, dgb_pitch, dgb_st, dgb_st_pitch, res, res_pitch};
+  PlaneNorm m{dxn, dxn_pitch, gb_img, gb_pitch, gb_st, gb_st_pitch, const_cast<float*>(stats), act, slope, eps,
+              xn, xn_pitch, dgb_img, dgb_pitch, dgb_st, dgb_st_pitch, res, res_pitch};
   // d_mid / sums (scratch of the two-launch form) left out: the caller relies on the fused kernel, which does not store the dgrad
   bool fused = false;
   int rc = conv_dgrad_impl(d, ConvOperands{dy, w_bwd, nullptr, aux, nullptr, d_mid ? d_mid : dxn, S2P_ACT_NONE, 0.f,

@@ -2,9 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// optional fused InstanceNorm + MAT epilogue (see PlaneArgs)
-struct PlaneMat {
-  void* y2; int y2_pitch; const void* gb; int gb_pitch; const float* gbst; int gbst_pitch; float* stats; int act; float slope, eps;
+// The fused InstanceNorm + MAT epilogue of the plane-resident kernels (PlaneArgs / PlaneGArgs embed it; the two s2p_conv2d_*_mat entry
+// points fill it).  Forward form (y2 != NULL, xn == NULL; groups must be 1): y2 = n_act(xhat * (1 + g_img + g_st) + b_img + b_st) with
+// the statistics of the conv output y (after the residual epilogue); stats is written in norm.hip's format.  BACKWARD form (xn != NULL;
+// the launch is the dgrad of the conv the norm fed): the conv result is dL/d(norm output) and is not stored (y unused); y2 = dL/d(xn)
+// + res, dgb / dgbst = d(gamma | beta) of the image map / the state affine; stats is read (the forward's).
+struct PlaneNorm {
+  void* y2; int y2_pitch;
+  const void* gb; int gb_pitch;      // [N, HW, gb_pitch]: gamma at channel 0, beta at channel Cout (may be NULL)
+  const float* gbst; int gbst_pitch; // fp32 [N][gbst_pitch]: gamma at [0, Cout), beta at [Cout, 2 Cout) (may be NULL)
+  float* stats; int n_act; float n_slope, eps;
   const void* xn; int xn_pitch; void* dgb; int dgb_pitch; float* dgbst; int dgbst_pitch; const void* res; int res_pitch;   // backward form
 };
 
@@ -19,16 +26,7 @@ struct PlaneArgs {
   int act, epi, gact;
   float slope, gslope;
   unsigned x_bytes, w_bytes;
-  // fused InstanceNorm + MAT modulation of the OUTPUT plane (y2 != NULL; groups must be 1): y2 = n_act(xhat * (1 + g_img + g_st)
-  // + b_img + b_st) with the statistics of y (after the residual epilogue); stats is written in norm.hip's format
-  void* y2; int y2_pitch;
-  const void* gb; int gb_pitch;      // [N, HW, gb_pitch]: gamma at channel 0, beta at channel Cout (may be NULL)
-  const float* gbst; int gbst_pitch; // fp32 [N][gbst_pitch]: gamma at [0, Cout), beta at [Cout, 2 Cout) (may be NULL)
-  float* stats; int n_act; float n_slope, eps;
-  // fused BACKWARD of that norm (xn != NULL; this launch is the dgrad of the conv the norm fed): the conv result is
-  // dL/d(norm output) and is not stored (y unused); y2 = dL/d(xn) + res, dgb / dgbst = d(gamma | beta) of the image map /
-  // the state affine; stats is read (the forward's)
-  const void* xn; int xn_pitch; void* dgb; int dgb_pitch; float* dgbst; int dgbst_pitch; const void* res; int res_pitch;
+  PlaneNorm nm;                      // all zero: plain conv
   int nco, gxcd;                     // set by the launcher: Cout / 64; grouped launch with (group, image half) units dealt to the XCDs
   int diag;                          // timing ablations (diagnostics build only)
 };

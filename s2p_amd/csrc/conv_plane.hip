@@ -20,18 +20,8 @@
 // 16 larger MFMAs of twice the cycles) and 4 KiB of weight writes for 448 px (there: 16 KiB for 128 px).
 #include "s2p_common.h"
 #include "conv_plane.h"
+#include "conv_plane_epi.h"
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-
-// DMA with the uniform part of the source offset in an SGPR (soffset).  An invalid lane carries voffset = 0x80000000 and returns
-// zeros whatever the scalar part is.  The scalar part COUNTS in the range check on gfx950 (measured in round 4: a group offset
-// beyond num_records in soffset zero-filled valid lanes), so num_records must cover base + voffset + soffset of every valid lane:
-// here the scalar part is a channel offset inside a pixel row / a tap offset inside a weight row, both inside the records.
-__device__ __forceinline__ void pl_dma16(i32x4 rsrc, unsigned lds_dst, int voffset, int soffset) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-               :: "v"(voffset), "s"(rsrc), "s"(lds_dst), "s"(soffset) : "memory", "m0");
-}
 
 namespace {
 constexpr int PL_NPOS = 512;                 // padded-raster positions per plane buffer
@@ -39,7 +29,6 @@ constexpr int PL_CPS = PL_NPOS * 32;         // bytes between the two 16-channel
 constexpr int PL_PBUF = 2 * PL_CPS;          // one half-slab plane buffer (32 KiB)
 constexpr int PL_WST = 4096;                 // one weight stage: [2 pairs][64 co][32 B]
 constexpr int PL_RING = 6;
-constexpr int PL_ERS = 144;                  // epilogue staging row: 64 co x 2 B + 16
 }
 
 // DIAG: timing ablations, instantiated only in the diagnostics build; a bit mask: 1 no in-loop DMA, 2 no MFMAs, 4 no fragment
@@ -68,7 +57,7 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
   constexpr int NT = 4 * PB;                                   // accumulator tiles per wave
   constexpr int MERGE = 4 * NT * 1024;
   constexpr int MAIN = 2 * PL_PBUF + PL_RING * PL_WST;
-  constexpr int EPI = BPIX * PL_ERS;
+  constexpr int EPI = BPIX * PE_ERS;
   constexpr int SMEM = GST ? 163840 : (MERGE > MAIN ? (MERGE > EPI ? MERGE : EPI) : (MAIN > EPI ? MAIN : EPI));
   constexpr int XOFF = GST ? PL_PBUF : 0;                      // GST: exchange / staging / scratch region = buffer 1 + ring (56 KB)
   constexpr int GB_B = MAIN;                                   // GST: gamma|beta rows 0..287
@@ -137,14 +126,14 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
   // (l >> 3) & 1, chunk l & 7; the half holds beta iff half != row parity.  Wave w issues pieces w + 8 j.
   i32x4 grs = xrs; int gvo = 0;
   if constexpr (GST != 0) {
-    grs = s2p_make_rsrc(a.gb, (unsigned)a.N * (unsigned)HW * (unsigned)a.gb_pitch * 2u);
+    grs = s2p_make_rsrc(a.nm.gb, (unsigned)a.N * (unsigned)HW * (unsigned)a.nm.gb_pitch * 2u);
     const int rl = lane >> 4, isb = ((lane >> 3) ^ rl) & 1;
-    gvo = (int)((((unsigned)img * HW + rl) * a.gb_pitch + isb * a.Cout + co_base + (lane & 7) * 8) * 2u);
+    gvo = (int)((((unsigned)img * HW + rl) * a.nm.gb_pitch + isb * a.Cout + co_base + (lane & 7) * 8) * 2u);
   }
   auto issue_g = [&](int pi) {
     if constexpr (GST != 0) {
       const unsigned dst = pi < GB_ROWS_B / 4 ? (unsigned)(GB_B + pi * 1024) : (unsigned)((pi - GB_ROWS_B / 4) * 1024);
-      pl_dma16(grs, p_lds + dst, gvo, pi * 4 * a.gb_pitch * 2);     // (host: H * W >= 384, every staged row exists)
+      s2p_dma16_so(grs, p_lds + dst, gvo, pi * 4 * a.nm.gb_pitch * 2);     // (host: H * W >= 384, every staged row exists)
     }
   };
   const int nhs = a.Cin / 32;                                   // half-slabs (host guarantees Cin % 64 == 0)
@@ -152,10 +141,10 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
     const int so = hs * 64;
 #pragma unroll
     for (int k = k0; k < k0 + 2; ++k)
-      pl_dma16(xrs, p_lds + (unsigned)(buf * PL_PBUF) + hdst[k], hs < nhs ? hv[k] : (int)OOB, so);
+      s2p_dma16_so(xrs, p_lds + (unsigned)(buf * PL_PBUF) + hdst[k], hs < nhs ? hv[k] : (int)OOB, so);
   };
   auto issue_w = [&](int stage, int tap_off, int hs) {
-    pl_dma16(wrs, w_lds + (unsigned)(stage * PL_WST) + wdst, hs < nhs ? wv : (int)OOB, tap_off + hs * 64);
+    s2p_dma16_so(wrs, w_lds + (unsigned)(stage * PL_WST) + wdst, hs < nhs ? wv : (int)OOB, tap_off + hs * 64);
   };
 
   // ---- prologue: plane of half-slab 0 + the first three weight stages of this wave's set --------------------------------
@@ -183,11 +172,11 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
 #pragma unroll
     for (int j = 0; j < PB; ++j) asm volatile("" : "+v"(bB[j]));
   }
-  f32x4v acc[4][PB];
+  f32x4 acc[4][PB];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < PB; ++j) acc[i][j] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < PB; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   // Software pipeline, identical in both wave sets: in pair-step U a wave runs the 28 MFMAs of its K step u on fragments
   // that are already in registers, and BETWEEN them issues the 11 fragment reads of its next step (u + 2) and its LDS-DMA
@@ -271,8 +260,8 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
           i32x4 rs;
 #pragma unroll
           for (int c = 0; c < 4; ++c) rs[c] = last ? grs[c] : xrs[c];
-          pl_dma16(rs, p_lds + (last ? (unsigned)((pi - GB_ROWS_B / 4) * 1024) : hdst[k]), last ? gvo : hv[k],
-                   last ? pi * 4 * a.gb_pitch * 2 : (k2 + 2) * 64);
+          s2p_dma16_so(rs, p_lds + (last ? (unsigned)((pi - GB_ROWS_B / 4) * 1024) : hdst[k]), last ? gvo : hv[k],
+                   last ? pi * 4 * a.nm.gb_pitch * 2 : (k2 + 2) * 64);
         }
       };
       s2p_static_for<0, 9>([&](auto Uc) {
@@ -343,14 +332,14 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
   Chunk<T> pre_g[T_MAXR - T_KG0], pre_b[T_MAXR - T_KG0], pre_x[MAT == 2 ? T_MAXR : 1], pre_a[MAT == 1 ? T_MAXR : 1];
   if constexpr (GST != 0) {
     const int ch = tid & 7, r0 = tid >> 3, lc = co_base + ch * 8;
-    const T* gbb = (const T*)a.gb + (size_t)img * HW * a.gb_pitch + lc;
+    const T* gbb = (const T*)a.nm.gb + (size_t)img * HW * a.nm.gb_pitch + lc;
 #pragma unroll
     for (int k = T_KG0; k < T_MAXR; ++k) {
       const int row = r0 + 64 * k;
       pre_g[k - T_KG0].raw = (u32x4){0u, 0u, 0u, 0u}; pre_b[k - T_KG0].raw = pre_g[k - T_KG0].raw;
       if (row < HW) {
-        pre_g[k - T_KG0].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch);
-        pre_b[k - T_KG0].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch + a.Cout);
+        pre_g[k - T_KG0].raw = *(const u32x4*)(gbb + (size_t)row * a.nm.gb_pitch);
+        pre_b[k - T_KG0].raw = *(const u32x4*)(gbb + (size_t)row * a.nm.gb_pitch + a.Cout);
       }
     }
     if constexpr (MAT == 1) {                                  // ... and the residual / producer tensor of the conv's own epilogue (conv_1 + skip)
@@ -365,12 +354,12 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
       }
     }
     if constexpr (MAT == 2) {
-      const T* xb = (const T*)a.xn + (size_t)img * HW * a.xn_pitch + lc;
+      const T* xb = (const T*)a.nm.xn + (size_t)img * HW * a.nm.xn_pitch + lc;
 #pragma unroll
       for (int k = 0; k < T_MAXR; ++k) {
         const int row = r0 + 64 * k;
         pre_x[k].raw = (u32x4){0u, 0u, 0u, 0u};
-        if (row < HW) pre_x[k].raw = *(const u32x4*)(xb + (size_t)row * a.xn_pitch);
+        if (row < HW) pre_x[k].raw = *(const u32x4*)(xb + (size_t)row * a.nm.xn_pitch);
       }
     }
   }
@@ -386,376 +375,51 @@ __global__ __launch_bounds__(512) void conv_plane_kernel(const PlaneArgs a) {
     return;
   }
 
-  // ---- add the two partial accumulators of a wave pair through LDS: the pair exchanges halves (set 0 ends up with the sums
-  //      of co blocks 0-1, set 1 with co blocks 2-3), so all eight waves share the epilogue -----------------------------------
-  // staging row of pixel px, 16-byte chunk c (8 channels): 144-byte rows, or (GST) 128-byte rows with the chunk index XOR px & 7
-  auto srow = [&](int px, int c) -> char* {
-    if constexpr (GST != 0) return smem + XOFF + px * 128 + ((c ^ (px & 7)) << 4);
-    else return smem + px * PL_ERS + c * 16;
-  };
+  // ---- add the two partial accumulators of a wave pair through LDS, stage the plane as [pixel][co] rows (144-byte rows, or (GST)
+  //      128-byte swizzled rows in the exchange region), then the store loop / the fused norm tail: conv_plane_epi.h ------------------
+  typedef std::conditional_t<GST != 0, PeRowsSwz128, PeRows144> Rows;
+  const Rows srow{smem + XOFF};
   auto finish = [&](auto ibc) {
     constexpr int IB = decltype(ibc)::value;                    // first co block this wave keeps; it hands over the other two
-    if constexpr (GST == 0) {
-      char* mb = smem + (size_t)(wq * NT) * 1024 + lane * 16;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < PB; ++j) *(f32x4v*)(mb + ((2 - IB + i) * PB + j) * 1024) = acc[2 - IB + i][j];
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < PB; ++j) acc[IB + i][j] += *(const f32x4v*)(mb + ((IB + i) * PB + j) * 1024);
-      __syncthreads();                                          // the staging rows below overlap the exchange area
-    } else {
+    if constexpr (GST == 0) pe_exchange<PB, IB>(acc, smem, wq, lane);
+    else {
       // two rounds of one co block per wave: a wave pair shares 2 x 7 KB; set 0 writes slot 1 and reads slot 0, set 1 the reverse
       char* mb = smem + XOFF + (size_t)(wq * 2 * PB) * 1024 + lane * 16;
       constexpr int WS = IB == 0 ? 1 : 0, RS = 1 - WS;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
 #pragma unroll
-        for (int j = 0; j < PB; ++j) *(f32x4v*)(mb + (WS * PB + j) * 1024) = acc[2 - IB + i][j];
+        for (int j = 0; j < PB; ++j) *(f32x4*)(mb + (WS * PB + j) * 1024) = acc[2 - IB + i][j];
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < PB; ++j) acc[IB + i][j] += *(const f32x4v*)(mb + (RS * PB + j) * 1024);
+        for (int j = 0; j < PB; ++j) acc[IB + i][j] += *(const f32x4*)(mb + (RS * PB + j) * 1024);
         __syncthreads();                                        // (the last one: the staging rows below overlap the exchange area)
       }
     }
     if constexpr ((DIAG & 128) != 0) ph[3] = __builtin_amdgcn_s_memrealtime();
-    // bias + activation in registers, then [pixel][co] staging rows (transpose through LDS)
-    const float* bias = a.bias ? a.bias + (size_t)g * a.Cout + co_base : nullptr;
-    float bv[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bv[i][e] = bias ? bias[16 * (IB + i) + 4 * q + e] : 0.f;
-    // the activation selector is resolved ONCE (a uniform branch around the whole pass), never per element
-    auto stage_out = [&](auto f) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < PB; ++j) {
-          const int px = (wq * PB + j) * 16 + l15;
-          const f32x4v v = acc[IB + i][j];
-          bf16x4 o = {(__bf16)f(v[0] + bv[i][0]), (__bf16)f(v[1] + bv[i][1]), (__bf16)f(v[2] + bv[i][2]), (__bf16)f(v[3] + bv[i][3])};
-          *(bf16x4*)(srow(px, 2 * (IB + i) + (q >> 1)) + (q & 1) * 8) = o;
-        }
-    };
-    if (a.act == S2P_ACT_TANH) stage_out([](float v) { return tanhf(v); });
-    else if (a.act == S2P_ACT_SWISH) stage_out([](float v) { return v / (1.f + expf(-v)); });
-    else if (a.act == S2P_ACT_NONE) stage_out([](float v) { return v; });        // (dgrads, gamma/beta conv: the pass is VALU-bound)
-    else {
-      const float ns = a.act == S2P_ACT_RELU ? 0.f : a.slope;                    // relu / lrelu
-      stage_out([ns](float v) { return lrelu_ns(v, ns); });
-    }
+    pe_stage_out<PB, 2, IB>(acc, a.bias ? a.bias + (size_t)g * a.Cout + co_base : nullptr, a.act, a.slope, wq, q, l15, srow);
   };
   if (set == 0) finish(std::integral_constant<int, 0>{}); else finish(std::integral_constant<int, 2>{});
   __syncthreads();
   if constexpr ((DIAG & 128) != 0) ph[4] = __builtin_amdgcn_s_memrealtime();
   T* yg = (T*)a.y + (size_t)g * a.y_gstride;
-  const T* auxg = a.aux ? (const T*)a.aux + (size_t)g * a.y_gstride : nullptr;
-  const T* aux2g = a.aux2 ? (const T*)a.aux2 + (size_t)g * a.y_gstride : nullptr;
-  const bool epi_add = a.epi == S2P_EPI_ADD;
-  const bool g_tanh = a.gact == S2P_ACT_TANH;
-  const float gneg = a.gact == S2P_ACT_RELU ? 0.f : (a.gact == S2P_ACT_LRELU ? a.gslope : 1.f);
-  // one (pixel row, 8-channel chunk) item of the output: staged value (+ residual / producer-activation-gradient epilogue)
-  auto out_chunk = [&](int row, int ch, size_t go, const Chunk<T>* pre = nullptr) {      // pre: aux chunk already in registers
-    Chunk<T> c;
-    c.raw = *(const u32x4*)srow(row, ch);
-    if (a.epi != S2P_EPI_STORE) {
-      Chunk<T> x, x2;
-      if (pre) x = *pre; else x.raw = *(const u32x4*)(auxg + go);
-      x2.raw = (u32x4){0u, 0u, 0u, 0u};
-      if (aux2g) x2.raw = *(const u32x4*)(aux2g + go);
-      float ov[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = c.get(e), xv = x.get(e);
-        const float f = g_tanh ? 1.f - xv * xv : (xv > 0.f ? 1.f : gneg);
-        ov[e] = epi_add ? v + xv : (v + x2.get(e)) * f;
-      }
-      c.pack(ov);
-    }
-    return c;
-  };
+  // MAT == 2 keeps this kernel's behaviour of not reading aux in the backward form: the plan fuses the norm backward only onto a
+  // dgrad without an epilogue of its own (a 3x3 dgrad with an aux gradient runs as two launches), so the tail sees EPI_STORE
+  const PeOut eo(a.aux, a.aux2, (size_t)g * a.y_gstride, MAT == 2 ? S2P_EPI_STORE : a.epi, a.gact, a.gslope);
   if constexpr (MAT == 0) {
     for (int idx = tid; idx < HW * 8; idx += 512) {
       const int row = idx >> 3, ch = idx & 7;
       const size_t go = ((size_t)img * HW + row) * a.y_pitch + co_base + ch * 8;
-      *(u32x4*)(yg + go) = out_chunk(row, ch, go).raw;
+      *(u32x4*)(yg + go) = pe_out_chunk(eo, srow, row, ch, go).raw;
     }
-  } else if constexpr (MAT == 1) {
-    // ---- fused InstanceNorm + MAT modulation (norm.hip: in_fused_fwd_kernel) on the plane this workgroup owns ------------
-    // Thread (row lane r = tid >> 3, chunk ch = tid & 7) holds the rows r, r + 64, ... of its 8 channels: the conv output
-    // (as stored: bf16) stays in registers, the statistics are the exact two-pass ones (mean, then centred second moment),
-    // summed in a fixed order (lanes, then waves), and the modulated tensor is written from the same registers.
-    constexpr int MAXR = BPIX / 64;
-    const int ch = tid & 7, r0 = tid >> 3;
-    const T* gbb = a.gb ? (const T*)a.gb + (size_t)img * HW * a.gb_pitch + co_base + ch * 8 : nullptr;
-    constexpr int KG0 = GST ? GB_ROWS / 64 : 0;                  // rows r0 + 64 k, k < KG0: gamma | beta are staged in LDS
-    static_assert(!GST || KG0 == T_KG0, "row groups staged in LDS");
-    Chunk<T> xv[MAXR], gv[MAXR - KG0], bv[MAXR - KG0];
-#pragma unroll
-    for (int k = KG0; k < MAXR; ++k) {                           // gamma / beta first: their latency runs under the rest
-      const int row = r0 + 64 * k;
-      if constexpr (GST != 0) { gv[k - KG0] = pre_g[k - KG0]; bv[k - KG0] = pre_b[k - KG0]; }     // (requested behind the loop)
-      else {
-        gv[k - KG0].raw = (u32x4){0u, 0u, 0u, 0u}; bv[k - KG0].raw = gv[k - KG0].raw;
-        if (gbb && row < HW) {
-          gv[k - KG0].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch);
-          bv[k - KG0].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch + a.Cout);
-        }
-      }
-    }
-    // GST: LDS address of this thread's gamma chunk of row r0 (beta: ^ 128); row r0 + 64 k is 64 rows = 16 KB further (r0 + 64 k
-    // keeps r0's parity), rows from 288 on live in plane buffer 0
-    auto gst_row = [&](int k) -> int {
-      const int row = r0 + 64 * k;
-      return (row < GB_ROWS_B ? GB_B + row * 256 : (row - GB_ROWS_B) * 256) + ((r0 & 1) << 7) + ch * 16;
-    };
-    // The plane stays in registers UNPACKED from here on (56 floats: the accumulators are dead): round 4 kept it packed and paid
-    // three unpack passes; with the centred values kept from the second pass, the maximum form of the activation and paired
-    // bf16 conversions the tail is ~330 VALU instructions per wave shorter (of 1 320)
-    float xf[MAXR][8];
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) {
-      const int row = r0 + 64 * k;
-      xv[k].raw = (u32x4){0u, 0u, 0u, 0u};
-      if (row < HW) {
-        const size_t go = ((size_t)img * HW + row) * a.y_pitch + co_base + ch * 8;
-        if constexpr (GST != 0) xv[k] = out_chunk(row, ch, go, &pre_a[k]); else xv[k] = out_chunk(row, ch, go);
-        if (a.y) *(u32x4*)(yg + go) = xv[k].raw;                  // (y == NULL: the caller keeps only the modulated tensor -- a forward without a backward)
-      }
-      xv[k].unpack(xf[k]);                                        // rows beyond HW hold zeros
-    }
-    __syncthreads();                                            // the staging rows are dead: LDS is scratch from here on
-    float* red = (float*)(smem + XOFF);                         // [8 waves][64]
-    float* cst = red + 8 * 64;                                  // [4][64]: plane sum / M2, then 1 + gamma_st, beta_st
-    auto plane_sum = [&](float (&v)[8], int slot) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-#pragma unroll
-        for (int o = 8; o < 64; o <<= 1) v[e] += __shfl_xor(v[e], o, 64);
-      }
-      __syncthreads();
-      if (lane < 8) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[wave * 64 + lane * 8 + e] = v[e];
-      }
-      __syncthreads();
-      if (tid < 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) t += red[w * 64 + tid];
-        cst[slot * 64 + tid] = t;
-      }
-      __syncthreads();
-    };
-    const float inv = 1.f / (float)HW;
-    float sacc[8], mean[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      sacc[e] = 0.f;
-#pragma unroll
-      for (int k = 0; k < MAXR; ++k) sacc[e] += xf[k][e];
-    }
-    plane_sum(sacc, 0);
-    // rows r0 + 64 k with k < KFULL exist in every thread (GST: the host requires HW >= 384): no bounds select on their squares
-    constexpr int KFULL = GST ? 6 : 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      mean[e] = cst[ch * 8 + e] * inv;
-      sacc[e] = 0.f;
-#pragma unroll
-      for (int k = 0; k < MAXR; ++k) {
-        const float d = xf[k][e] - mean[e];
-        xf[k][e] = d;                                             // the centred value is what the last pass needs
-        if (k < KFULL) sacc[e] = __builtin_fmaf(d, d, sacc[e]);
-        else sacc[e] += (r0 + 64 * k < HW) ? d * d : 0.f;
-      }
-    }
-    plane_sum(sacc, 1);
-    if (tid < 64) {
-      const int c = co_base + tid;
-      float* o = a.stats + 4 + ((size_t)img * a.Cout + c) * 2;     // norm.hip format: 4-word header, then [N][C][1 split]{mean, M2}
-      o[0] = cst[tid] * inv; o[1] = cst[64 + tid];
-      if (c == 0 && img == 0) *(i32x4*)a.stats = (i32x4){1, HW, 0, 0};
-      cst[2 * 64 + tid] = a.gbst ? 1.f + a.gbst[(size_t)img * a.gbst_pitch + c] : 1.f;
-      cst[3 * 64 + tid] = a.gbst ? a.gbst[(size_t)img * a.gbst_pitch + a.Cout + c] : 0.f;
-    }
-    __syncthreads();
-    float rstd[8], gs[8], bs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      rstd[e] = 1.f / sqrtf(cst[64 + ch * 8 + e] * inv + a.eps);
-      gs[e] = cst[2 * 64 + ch * 8 + e]; bs[e] = cst[3 * 64 + ch * 8 + e];
-    }
-    const float nns = a.n_act == S2P_ACT_RELU ? 0.f : (a.n_act == S2P_ACT_LRELU ? a.n_slope : 1.f);   // none / relu / lrelu (host)
-    T* y2 = (T*)a.y2 + (size_t)img * HW * a.y2_pitch + co_base + ch * 8;
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) {
-      const int row = r0 + 64 * k;
-      if (row >= HW) break;
-      Chunk<T> o0, gk, bk;
-      if (k < KG0) { const int go = gst_row(k); gk.raw = *(const u32x4*)(smem + go); bk.raw = *(const u32x4*)(smem + (go ^ 128)); }
-      else { gk = gv[k < KG0 ? 0 : k - KG0]; bk = bv[k < KG0 ? 0 : k - KG0]; }
-      float ov[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float gg = gs[e] + gk.get(e), bb = bs[e] + bk.get(e);
-        const float xh = xf[k][e] * rstd[e];                      // (x - mean) * rstd
-        const float yv = __builtin_fmaf(xh, gg, bb);              // (norm.hip: mat_value)
-        ov[e] = lrelu_ns(yv, nns);
-      }
-      o0.pack(ov);
-      *(u32x4*)(y2 + (size_t)row * a.y2_pitch) = o0.raw;
-    }
-  }
-  if constexpr (MAT == 2) {
-    // ---- fused backward of InstanceNorm + MAT modulation + activation (norm.hip: in_fused_bwd_kernel) ---------------------
-    // This launch is the dgrad of the conv that CONSUMED the norm's output, so the staged plane is dL/d(norm output) for the
-    // (image, 64-channel slab) this workgroup owns; it never goes to HBM.  Thread (row lane r0 = tid >> 3, chunk ch = tid & 7)
-    // loads the norm INPUT xn, gamma and beta of its rows, forms the four plane sums (lanes, then waves: fixed order) and
-    // writes dL/d(xn) (+ the skip gradient `res`), d(gamma_img | beta_img) and the state-affine gradient.
-    constexpr int MAXR = BPIX / 64;
-    const int ch = tid & 7, r0 = tid >> 3, lc = co_base + ch * 8;
-    const T* xb = (const T*)a.xn + (size_t)img * HW * a.xn_pitch + lc;
-    const T* gbb = a.gb ? (const T*)a.gb + (size_t)img * HW * a.gb_pitch + lc : nullptr;
-    constexpr int KG0 = GST ? GB_ROWS / 64 : 0;                  // rows r0 + 64 k, k < KG0: gamma | beta are staged in LDS
-    Chunk<T> xv[MAXR], gv[MAXR - KG0], bv[MAXR - KG0], dv[MAXR];
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) {
-      const int row = r0 + 64 * k;
-      xv[k].raw = (u32x4){0u, 0u, 0u, 0u}; dv[k].raw = xv[k].raw;
-      if (k >= KG0) { gv[k < KG0 ? 0 : k - KG0].raw = xv[k].raw; bv[k < KG0 ? 0 : k - KG0].raw = xv[k].raw; }
-      if constexpr (GST != 0) {                                  // xn and the seventh row group's gamma | beta: requested behind the loop
-        xv[k] = pre_x[k];
-        if (k >= KG0) { gv[k < KG0 ? 0 : k - KG0] = pre_g[k < KG0 ? 0 : k - KG0]; bv[k < KG0 ? 0 : k - KG0] = pre_b[k < KG0 ? 0 : k - KG0]; }
-        if (row < HW) dv[k].raw = *(const u32x4*)srow(row, ch);
-      } else if (row < HW) {
-        xv[k].raw = *(const u32x4*)(xb + (size_t)row * a.xn_pitch);
-        if (k >= KG0 && gbb) { gv[k < KG0 ? 0 : k - KG0].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch); bv[k < KG0 ? 0 : k - KG0].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch + a.Cout); }
-        dv[k].raw = *(const u32x4*)srow(row, ch);                // rows beyond HW stay zero: they add nothing to the sums
-      }
-    }
-    auto gst_row = [&](int k) -> int {                          // (see the forward tail)
-      const int row = r0 + 64 * k;
-      return (row < GB_ROWS_B ? GB_B + row * 256 : (row - GB_ROWS_B) * 256) + ((r0 & 1) << 7) + ch * 16;
-    };
-    // gamma | beta chunk of this thread's row r0 + 64 k: from the staged rows (a masked row reads some other row: its dv is zero)
-    auto load_gb = [&](int k, Chunk<T>& gk, Chunk<T>& bk) {
-      if (k < KG0) { const int go = gst_row(k); gk.raw = *(const u32x4*)(smem + go); bk.raw = *(const u32x4*)(smem + (go ^ 128)); }
-      else { gk = gv[k < KG0 ? 0 : k - KG0]; bk = bv[k < KG0 ? 0 : k - KG0]; }
-    };
-    __syncthreads();                                            // the staging rows are dead: LDS is scratch from here on
-    float* red = (float*)(smem + XOFF);                         // [4 sums][8 waves][64]
-    float* cst = red + 4 * 8 * 64;                              // [6][64]: mean, rstd, 1 + gamma_st, beta_st, s1 / HW, s2 / HW
-    if (tid < 64) {
-      const int c = co_base + tid;
-      // merge the per-split partial moments (norm.hip: mean_rstd; S = 1 when a fused forward kernel wrote them)
-      const int S = ((const int*)a.stats)[0], rows = ((const int*)a.stats)[1];
-      const float* pm = a.stats + 4 + ((size_t)img * a.Cout + c) * S * 2;
-      const float inv = 1.f / (float)HW;
-      const float m0 = pm[0];
-      float m = 0.f;
-      for (int b = 1; b < S; ++b) { int nb = HW - b * rows; if (nb > rows) nb = rows; m += (float)nb * (pm[2 * b] - m0); }
-      m = m0 + m * inv;
-      float M2 = 0.f;
-      for (int b = 0; b < S; ++b) { int nb = HW - b * rows; if (nb > rows) nb = rows; const float dd = pm[2 * b] - m; M2 += pm[2 * b + 1] + (float)nb * dd * dd; }
-      cst[tid] = m; cst[64 + tid] = 1.f / sqrtf(M2 * inv + a.eps);
-      cst[2 * 64 + tid] = a.gbst ? 1.f + a.gbst[(size_t)img * a.gbst_pitch + c] : 1.f;
-      cst[3 * 64 + tid] = a.gbst ? a.gbst[(size_t)img * a.gbst_pitch + a.Cout + c] : 0.f;
-    }
-    __syncthreads();
-    const float gneg = a.n_act == S2P_ACT_RELU ? 0.f : (a.n_act == S2P_ACT_LRELU ? a.n_slope : 1.f);
-    // ---- pass 1: the four plane sums.  Rows outermost (one read of the gamma | beta chunk per row); every sum adds its rows in
-    // ascending order.  The normalised input xh and the gradient dy behind the activation stay in registers for pass 2 (112 floats:
-    // the accumulators are dead) -- round 4 recomputed both there from the packed chunks and a 64-bit mask of the activation
-    // branches: 40 VALU instructions per element over the two passes, now ~23
-    float xhf[MAXR][8], dyf[MAXR][8];
-    {
-      float mm[8], rr[8], g1[8], b1[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const int cl = ch * 8 + e; mm[e] = cst[cl]; rr[e] = cst[64 + cl]; g1[e] = cst[128 + cl]; b1[e] = cst[192 + cl]; }
-      float q0[8], q1[8], q2[8], q3[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { q0[e] = 0.f; q1[e] = 0.f; q2[e] = 0.f; q3[e] = 0.f; }
-#pragma unroll
-      for (int k = 0; k < MAXR; ++k) {
-        Chunk<T> gk, bk;
-        load_gb(k, gk, bk);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float gg = g1[e] + gk.get(e), bb = b1[e] + bk.get(e);
-          const float xh = (xv[k].get(e) - mm[e]) * rr[e];
-          const float yv = __builtin_fmaf(xh, gg, bb);          // (norm.hip: mat_value -- the forward's rounding)
-          const float dvv = dv[k].get(e);
-          const float dy = yv > 0.f ? dvv : dvv * gneg;
-          const float dxh = dy * gg;
-          xhf[k][e] = xh; dyf[k][e] = dy;
-          q0[e] += dxh; q1[e] += dxh * xh; q2[e] += dy * xh; q3[e] += dy;
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int cl = ch * 8 + e;
-#pragma unroll
-        for (int o = 8; o < 64; o <<= 1) {
-          q0[e] += __shfl_xor(q0[e], o, 64); q1[e] += __shfl_xor(q1[e], o, 64); q2[e] += __shfl_xor(q2[e], o, 64); q3[e] += __shfl_xor(q3[e], o, 64);
-        }
-        if (lane < 8) { red[(0 * 8 + wave) * 64 + cl] = q0[e]; red[(1 * 8 + wave) * 64 + cl] = q1[e]; red[(2 * 8 + wave) * 64 + cl] = q2[e]; red[(3 * 8 + wave) * 64 + cl] = q3[e]; }
-      }
-    }
-    __syncthreads();
-    if (tid < 64) {
-      float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) { t0 += red[(0 * 8 + w) * 64 + tid]; t1 += red[(1 * 8 + w) * 64 + tid]; t2 += red[(2 * 8 + w) * 64 + tid]; t3 += red[(3 * 8 + w) * 64 + tid]; }
-      const float inv = 1.f / (float)HW;
-      cst[4 * 64 + tid] = t0 * inv; cst[5 * 64 + tid] = t1 * inv;
-      const int c = co_base + tid;
-      if (a.dgbst) {
-        a.dgbst[(size_t)img * a.dgbst_pitch + c] = t2;
-        a.dgbst[(size_t)img * a.dgbst_pitch + a.Cout + c] = t3;
-      }
-    }
-    __syncthreads();
-    // ---- pass 2: outputs
-    T* dxo = (T*)a.y2 + (size_t)img * HW * a.y2_pitch + lc;
-    T* dgo = a.dgb ? (T*)a.dgb + (size_t)img * HW * a.dgb_pitch + lc : nullptr;
-    const T* rsb = a.res ? (const T*)a.res + (size_t)img * HW * a.res_pitch + lc : nullptr;
-    float rr2[8], g12[8], s1v[8], s2v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const int cl = ch * 8 + e; rr2[e] = cst[64 + cl]; g12[e] = cst[128 + cl]; s1v[e] = cst[256 + cl]; s2v[e] = cst[320 + cl]; }
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) {
-      const int row = r0 + 64 * k;
-      if (row >= HW) break;
-      Chunk<T> o0, o1, o2, gk, bk;
-      load_gb(k, gk, bk);
-      float v0[8], v1[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float gg = g12[e] + gk.get(e);
-        const float xh = xhf[k][e], dy = dyf[k][e];
-        const float dxh = dy * gg;
-        v0[e] = rr2[e] * (dxh - s1v[e] - xh * s2v[e]);
-        v1[e] = dy * xh;
-      }
-      if (rsb) {                                                // skip-connection gradient folded into the store (fp32 add, one rounding)
-        Chunk<T> rv; rv.raw = *(const u32x4*)(rsb + (size_t)row * a.res_pitch);
-        // (round 4 rounded dx to bf16 before the add: o0.get(e) + rv.get(e); kept, bit for bit)
-        o0.pack(v0);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v0[e] = o0.get(e) + rv.get(e);
-      }
-      o0.pack(v0); o1.pack(v1); o2.pack(dyf[k]);
-      *(u32x4*)(dxo + (size_t)row * a.y2_pitch) = o0.raw;
-      if (dgo) {
-        *(u32x4*)(dgo + (size_t)row * a.dgb_pitch) = o1.raw;
-        *(u32x4*)(dgo + (size_t)row * a.dgb_pitch + a.Cout) = o2.raw;
-      }
-    }
+  } else {
+    static_assert(!GST || GB_ROWS / 64 == T_KG0, "row groups staged in LDS");
+    const PeTail t{tid, lane, wave, img, co_base, a.Cout, HW, (size_t)img * HW, smem + XOFF, a.y ? yg : nullptr, a.y_pitch, &a.nm};
+    std::conditional_t<GST != 0, PeGbStaged<T_KG0, GB_B, GB_ROWS_B>, PeGbGlobal<T_MAXR>> gb;
+    if constexpr (GST != 0) { gb.smem = smem; gb.tid = tid; gb.pre_g = pre_g; gb.pre_b = pre_b; gb.pre_x = pre_x; gb.pre_a = pre_a; }
+    // rows r0 + 64 k with k < 6 exist in every thread of the staged form (the host requires HW >= 384)
+    if constexpr (MAT == 1) pe_norm_fwd<T_MAXR, GST ? 6 : 0>(t, eo, srow, gb);
+    else pe_norm_bwd<T_MAXR, false>(t, eo, srow, gb);
   }
   if constexpr ((DIAG & 128) != 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -781,7 +445,7 @@ __global__ __launch_bounds__(512) void conv_plane_pair_kernel(const PlaneArgs a)
   constexpr int BPIX = 4 * PB * 16;
   constexpr int RINGB = PL_RING * PL_WST;                      // one set's weight ring
   constexpr int MAIN = 2 * PL_PBUF + 2 * RINGB;
-  constexpr int EPI = BPIX * PL_ERS;                           // one set's staging rows
+  constexpr int EPI = BPIX * PE_ERS;                           // one set's staging rows
   constexpr int SMEM = 2 * EPI > MAIN ? 2 * EPI : MAIN;
   __shared__ __attribute__((aligned(1024))) char smem[SMEM];
   char* const pbase = smem;
@@ -843,10 +507,10 @@ __global__ __launch_bounds__(512) void conv_plane_pair_kernel(const PlaneArgs a)
   for (int t = 0; t < 9; ++t) wto[t] = a.wt[t] * a.Cin * 2;
   const int nhs = a.Cin / 32;
   auto issue_plane1 = [&](int buf, int hs, int k) {
-    pl_dma16(xrs, p_lds + (unsigned)(buf * PL_PBUF) + hdst[k], hs < nhs ? hv[k] : (int)OOB, hs * 64);
+    s2p_dma16_so(xrs, p_lds + (unsigned)(buf * PL_PBUF) + hdst[k], hs < nhs ? hv[k] : (int)OOB, hs * 64);
   };
   auto issue_w = [&](int stage, int tap_off, int hs) {
-    pl_dma16(wrs, w_lds + (unsigned)(stage * PL_WST) + wdst, hs < nhs ? wv : (int)OOB, tap_off + hs * 64);
+    s2p_dma16_so(wrs, w_lds + (unsigned)(stage * PL_WST) + wdst, hs < nhs ? wv : (int)OOB, tap_off + hs * 64);
   };
   // prologue: the plane of half-slab 0, the weight stages of K steps 0, 1, 2
 #pragma unroll
@@ -866,11 +530,11 @@ __global__ __launch_bounds__(512) void conv_plane_pair_kernel(const PlaneArgs a)
     }
   }
   const int bA = (q >> 1) * 2048 + l15 * 32 + (q & 1) * 16;
-  f32x4v acc[4][PB];
+  f32x4 acc[4][PB];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < PB; ++j) acc[i][j] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < PB; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   auto read_a = [&](auto uc, auto ic, bf16x8 (&fa)[4]) {
     constexpr int u = decltype(uc)::value % 18, i = decltype(ic)::value;
     fa[i] = *(const bf16x8*)(wbase + (u % PL_RING) * PL_WST + i * 512 + bA);
@@ -943,61 +607,15 @@ __global__ __launch_bounds__(512) void conv_plane_pair_kernel(const PlaneArgs a)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
   // ---- epilogue: every wave stages its 28 tiles into its set's [pixel][co] rows; then 16-B stores of both slabs --------
-  {
-    char* stg = smem + set * EPI;
-    const float* bias = a.bias ? a.bias + (size_t)g * a.Cout + co_base : nullptr;
-    float bv[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bv[i][e] = bias ? bias[16 * i + 4 * q + e] : 0.f;
-    auto stage_out = [&](auto f) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < PB; ++j) {
-          const int px = (wq * PB + j) * 16 + l15;
-          const f32x4v v = acc[i][j];
-          bf16x4 o = {(__bf16)f(v[0] + bv[i][0]), (__bf16)f(v[1] + bv[i][1]), (__bf16)f(v[2] + bv[i][2]), (__bf16)f(v[3] + bv[i][3])};
-          *(bf16x4*)(stg + px * PL_ERS + (16 * i + 4 * q) * 2) = o;
-        }
-    };
-    if (a.act == S2P_ACT_TANH) stage_out([](float v) { return tanhf(v); });
-    else if (a.act == S2P_ACT_SWISH) stage_out([](float v) { return v / (1.f + expf(-v)); });
-    else if (a.act == S2P_ACT_NONE) stage_out([](float v) { return v; });        // (dgrads, gamma/beta conv: the pass is VALU-bound)
-    else {
-      const float ns = a.act == S2P_ACT_RELU ? 0.f : a.slope;
-      stage_out([ns](float v) { return lrelu_ns(v, ns); });
-    }
-  }
+  pe_stage_out<PB, 4, 0>(acc, a.bias ? a.bias + (size_t)g * a.Cout + co_base : nullptr, a.act, a.slope, wq, q, l15, PeRows144{smem + set * EPI});
   __syncthreads();
   {
     T* yg = (T*)a.y + (size_t)g * a.y_gstride;
-    const T* auxg = a.aux ? (const T*)a.aux + (size_t)g * a.y_gstride : nullptr;
-    const T* aux2g = a.aux2 ? (const T*)a.aux2 + (size_t)g * a.y_gstride : nullptr;
-    const bool epi_add = a.epi == S2P_EPI_ADD;
-    const bool g_tanh = a.gact == S2P_ACT_TANH;
-    const float gneg = a.gact == S2P_ACT_RELU ? 0.f : (a.gact == S2P_ACT_LRELU ? a.gslope : 1.f);
+    const PeOut eo(a.aux, a.aux2, (size_t)g * a.y_gstride, a.epi, a.gact, a.gslope);
     for (int idx = tid; idx < HW * 16; idx += 512) {            // (row, 16 chunks of 8 channels: the two slabs side by side)
       const int row = idx >> 4, ch16 = idx & 15, sl = ch16 >> 3, ch = ch16 & 7;
-      Chunk<T> c;
-      c.raw = *(const u32x4*)(smem + sl * EPI + row * PL_ERS + ch * 16);
       const size_t go = ((size_t)img * HW + row) * a.y_pitch + (2 * cpair + sl) * 64 + ch * 8;
-      if (a.epi != S2P_EPI_STORE) {
-        Chunk<T> x, x2;
-        x.raw = *(const u32x4*)(auxg + go);
-        x2.raw = (u32x4){0u, 0u, 0u, 0u};
-        if (aux2g) x2.raw = *(const u32x4*)(aux2g + go);
-        float ov[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float v = c.get(e), xv = x.get(e);
-          const float f = g_tanh ? 1.f - xv * xv : (xv > 0.f ? 1.f : gneg);
-          ov[e] = epi_add ? v + xv : (v + x2.get(e)) * f;
-        }
-        c.pack(ov);
-      }
-      *(u32x4*)(yg + go) = c.raw;
+      *(u32x4*)(yg + go) = pe_out_chunk(eo, PeRows144{smem + sl * EPI}, row, ch, go).raw;
     }
   }
 }
@@ -1021,7 +639,7 @@ int s2p_conv_plane_launch(PlaneArgs& a, int groups, hipStream_t st) {
 #undef PL_DIAG_CASE
 #endif
   // several tiles per CU and an even slab count: two slabs per workgroup from one resident plane (no accumulator exchange)
-  if (!a.y2 && (a.nco & 1) == 0 && (long long)a.N * a.nco * groups > 256 && !s2p_env_set("S2P_NO_PLANE_PAIR")) {
+  if (!a.nm.y2 && (a.nco & 1) == 0 && (long long)a.N * a.nco * groups > 256 && !s2p_env_set("S2P_NO_PLANE_PAIR")) {
     dim3 gp(a.N * (a.nco / 2), groups);
     // (group, image half) units on XCDs: 2 * groups units over 8 XCDs, whole units per XCD, the grid's x extent a multiple of 8
     a.gxcd = (groups > 1 && (2 * groups) % 8 == 0 && a.N % 2 == 0 && gp.x % 8 == 0 && !S2P_DIAG_SWITCH(17)) ? 1 : 0;
@@ -1030,13 +648,13 @@ int s2p_conv_plane_launch(PlaneArgs& a, int groups, hipStream_t st) {
     return 0;
   }
   // gamma|beta maps present and at least four loop iterations (Cin >= 256): the maps' rows are staged by LDS-DMA under the K loop
-  const bool gst = a.y2 && a.gb && a.Cin >= 256 && a.H * a.W >= 384 && (long long)a.N * a.H * a.W * a.gb_pitch * 2 < (1ll << 31) && !S2P_DIAG_SWITCH(7);
-  if (a.y2 && a.xn) {
+  const bool gst = a.nm.y2 && a.nm.gb && a.Cin >= 256 && a.H * a.W >= 384 && (long long)a.N * a.H * a.W * a.nm.gb_pitch * 2 < (1ll << 31) && !S2P_DIAG_SWITCH(7);
+  if (a.nm.y2 && a.nm.xn) {
     if (gst) hipLaunchKernelGGL((conv_plane_kernel<7, 22, 0, 2, 1>), grid, dim3(512), 0, st, a);
     else hipLaunchKernelGGL((conv_plane_kernel<7, 22, 0, 2>), grid, dim3(512), 0, st, a);
     S2P_CHECK_LAUNCH("conv_plane_kernel(mat bwd)"); return 0;
   }
-  if (a.y2) {
+  if (a.nm.y2) {
     if (gst) hipLaunchKernelGGL((conv_plane_kernel<7, 22, 0, 1, 1>), grid, dim3(512), 0, st, a);
     else hipLaunchKernelGGL((conv_plane_kernel<7, 22, 0, 1>), grid, dim3(512), 0, st, a);
     S2P_CHECK_LAUNCH("conv_plane_kernel(mat)"); return 0;

@@ -7,6 +7,7 @@
 // with the padded row width a run-time value and the InstanceNorm (+ LeakyReLU) forward / backward in the epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "conv_plane.h"
 
 struct PlaneGArgs {
   const void* x; const void* w; const float* bias; const void* aux; const void* aux2; void* y;
@@ -23,13 +24,7 @@ struct PlaneGArgs {
   int act, epi, gact;
   float slope, gslope;
   unsigned x_bytes, w_bytes;
-  // fused InstanceNorm forward of the OUTPUT plane (y2 != NULL, xn == NULL) / backward of the norm that fed this dgrad's forward
-  // conv (xn != NULL): see conv_plane.h; gamma / beta maps are optional (plain InstanceNorm when NULL)
-  void* y2; int y2_pitch;
-  const void* gb; int gb_pitch;
-  const float* gbst; int gbst_pitch;
-  float* stats; int n_act; float n_slope, eps;
-  const void* xn; int xn_pitch; void* dgb; int dgb_pitch; float* dgbst; int dgbst_pitch; const void* res; int res_pitch;
+  PlaneNorm nm;                      // fused InstanceNorm forward / backward (conv_plane.h); gamma / beta maps are not instantiated here
   int nco, img_xcd;               // set by the launcher: Cout / 64; all row bands of an image on one XCD
   int R, nbands;                     // produced rows per workgroup and bands per image (R = Ho, 1: the whole plane)
   int shape;                         // index of the instantiated tile shape (set by s2p_conv_planeg_setup)

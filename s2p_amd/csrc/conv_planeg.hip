@@ -10,21 +10,14 @@
 //     The LDS-DMA's per-lane source address does the space-to-depth; a "half-slab" is one parity x 32 channels.
 #include "s2p_common.h"
 #include "conv_planeg.h"
+#include "conv_plane_epi.h"
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-
-__device__ __forceinline__ void pg_dma16(i32x4 rsrc, unsigned lds_dst, int voffset, int soffset) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-               :: "v"(voffset), "s"(rsrc), "s"(lds_dst), "s"(soffset) : "memory", "m0");
-}
 
 #ifndef PG_OCC4_ALL
 #define PG_OCC4_ALL 0      // 1 (timing builds): also the 4x4 / parity-form 192-pixel shapes are limited to 128 VGPRs (two workgroups per CU; spills)
 #endif
 namespace {
 constexpr int PG_WST = 4096;                 // one weight stage: [2 pairs][64 co][32 B]
-constexpr int PG_ERS = 144;                  // epilogue staging row: 64 co x 2 B + 16
 
 // plane prefetch schedule of an iteration of T pair-steps (compile time).  Buffer 0 holds the even half-slabs (steps [0, T) of an
 // iteration), buffer 1 the odd ones (steps [T, 2T)); the fragments of step v are read in pair-step (v - 2) / 2.
@@ -76,7 +69,7 @@ __global__ __launch_bounds__(512, ((PB <= 3 && (TY == 3 || PG_OCC4_ALL)) ? 4 : 2
   constexpr int NT = 4 * PB;
   constexpr int MERGE = 4 * NT * 1024;
   constexpr int MAIN = 2 * PBUF + RING * PG_WST;
-  constexpr int EPI = BPIX * PG_ERS;
+  constexpr int EPI = BPIX * PE_ERS;
   constexpr int SMEM = MERGE > MAIN ? (MERGE > EPI ? MERGE : EPI) : (MAIN > EPI ? MAIN : EPI);
   __shared__ __attribute__((aligned(1024))) char smem[SMEM];
   char* const pbase = smem;
@@ -169,7 +162,7 @@ __global__ __launch_bounds__(512, ((PB <= 3 && (TY == 3 || PG_OCC4_ALL)) ? 4 : 2
       if constexpr (S2D) { const int pp = hs / ncg; v = ((hm[k] >> pp) & 1) ? hv[k] : (int)OOB; }
       else v = hm[k] ? hv[k] : (int)OOB;
     }
-    pg_dma16(xrs, p_lds + (unsigned)(buf * PBUF) + hdst[k], v, hs < nhs ? plane_soff(hs) : 0);
+    s2p_dma16_so(xrs, p_lds + (unsigned)(buf * PBUF) + hdst[k], v, hs < nhs ? plane_soff(hs) : 0);
   };
   // weights of raster tap t of half-slab hs
   auto issue_w = [&](int stage, int t, int hs) {
@@ -178,7 +171,7 @@ __global__ __launch_bounds__(512, ((PB <= 3 && (TY == 3 || PG_OCC4_ALL)) ? 4 : 2
       if constexpr (S2D) { const int pp = hs / ncg, cg = hs - pp * ncg; so = a.wt[pp * 4 + t] * cin2 + cg * 64; }
       else so = a.wt[t] * cin2 + hs * 64;
     }
-    pg_dma16(wrs, w_lds + (unsigned)(stage * PG_WST) + wdst, hs < nhs ? wv : (int)OOB, so);
+    s2p_dma16_so(wrs, w_lds + (unsigned)(stage * PG_WST) + wdst, hs < nhs ? wv : (int)OOB, so);
   };
 
   // ---- prologue: plane of half-slab 0 (and 1 when the schedule prefetches buffer 1 a whole iteration ahead) + the first RING / 2
@@ -206,11 +199,11 @@ __global__ __launch_bounds__(512, ((PB <= 3 && (TY == 3 || PG_OCC4_ALL)) ? 4 : 2
     }
   }
   const int bA = (q >> 1) * 2048 + l15 * 32 + (q & 1) * 16;
-  f32x4v acc[4][PB];
+  f32x4 acc[4][PB];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < PB; ++j) acc[i][j] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < PB; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   auto read_a = [&](auto vc, auto ic, bf16x8 (&fa)[4]) {
     constexpr int v = decltype(vc)::value % NSTEP, i = decltype(ic)::value;
@@ -283,300 +276,30 @@ __global__ __launch_bounds__(512, ((PB <= 3 && (TY == 3 || PG_OCC4_ALL)) ? 4 : 2
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // ---- add the two partial accumulators of a wave pair through LDS (set 0 keeps co blocks 0-1, set 1 co blocks 2-3), then
-  //      bias + activation in registers and [pixel][co] staging rows (transpose through LDS) -------------------------------------
+  // ---- add the two partial accumulators of a wave pair through LDS (set 0 keeps co blocks 0-1, set 1 co blocks 2-3), stage the plane
+  //      as [pixel][co] rows, then the store loop / the fused norm tail of the plane: conv_plane_epi.h -------------------------------
+  const PeRows144 srow{smem};
   auto finish = [&](auto ibc) {
     constexpr int IB = decltype(ibc)::value;
-    char* mb = smem + (size_t)(wq * NT) * 1024 + lane * 16;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < PB; ++j) *(f32x4v*)(mb + ((2 - IB + i) * PB + j) * 1024) = acc[2 - IB + i][j];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < PB; ++j) acc[IB + i][j] += *(const f32x4v*)(mb + ((IB + i) * PB + j) * 1024);
-    __syncthreads();                                            // the staging rows below overlap the exchange area
-    const float* bias = a.bias ? a.bias + (size_t)g * a.Cout + co_base : nullptr;
-    float bv[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bv[i][e] = bias ? bias[16 * (IB + i) + 4 * q + e] : 0.f;
-    auto stage_out = [&](auto f) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < PB; ++j) {
-          const int px = (wq * PB + j) * 16 + l15;
-          const f32x4v v = acc[IB + i][j];
-          bf16x4 o = {(__bf16)f(v[0] + bv[i][0]), (__bf16)f(v[1] + bv[i][1]), (__bf16)f(v[2] + bv[i][2]), (__bf16)f(v[3] + bv[i][3])};
-          *(bf16x4*)(smem + px * PG_ERS + (16 * (IB + i) + 4 * q) * 2) = o;
-        }
-    };
-    if (a.act == S2P_ACT_TANH) stage_out([](float v) { return tanhf(v); });
-    else if (a.act == S2P_ACT_SWISH) stage_out([](float v) { return v / (1.f + expf(-v)); });
-    else if (a.act == S2P_ACT_NONE) stage_out([](float v) { return v; });
-    else {
-      const float ns = a.act == S2P_ACT_RELU ? 0.f : a.slope;
-      stage_out([ns](float v) { return lrelu_ns(v, ns); });
-    }
+    pe_exchange<PB, IB>(acc, smem, wq, lane);
+    pe_stage_out<PB, 2, IB>(acc, a.bias ? a.bias + (size_t)g * a.Cout + co_base : nullptr, a.act, a.slope, wq, q, l15, srow);
   };
   if (set == 0) finish(std::integral_constant<int, 0>{}); else finish(std::integral_constant<int, 2>{});
   __syncthreads();
   T* yg = (T*)a.y + (size_t)g * a.y_gstride;
-  const T* auxg = a.aux ? (const T*)a.aux + (size_t)g * a.y_gstride : nullptr;
-  const T* aux2g = a.aux2 ? (const T*)a.aux2 + (size_t)g * a.y_gstride : nullptr;
-  const bool epi_add = a.epi == S2P_EPI_ADD;
-  const bool g_tanh = a.gact == S2P_ACT_TANH;
-  const float gneg = a.gact == S2P_ACT_RELU ? 0.f : (a.gact == S2P_ACT_LRELU ? a.gslope : 1.f);
-  // one (pixel row, 8-channel chunk) item of the output: staged value (+ residual / producer-activation-gradient epilogue)
-  auto out_chunk = [&](int row, int ch, size_t go) {
-    Chunk<T> c;
-    c.raw = *(const u32x4*)(smem + row * PG_ERS + ch * 16);
-    if (a.epi != S2P_EPI_STORE) {
-      Chunk<T> x, x2;
-      x.raw = *(const u32x4*)(auxg + go);
-      x2.raw = (u32x4){0u, 0u, 0u, 0u};
-      if (aux2g) x2.raw = *(const u32x4*)(aux2g + go);
-      float ov[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = c.get(e), xv = x.get(e);
-        const float f = g_tanh ? 1.f - xv * xv : (xv > 0.f ? 1.f : gneg);
-        ov[e] = epi_add ? v + xv : (v + x2.get(e)) * f;
-      }
-      c.pack(ov);
-    }
-    return c;
-  };
-  constexpr int MAXR = BPIX / 64;
+  const PeOut eo(a.aux, a.aux2, (size_t)g * a.y_gstride, a.epi, a.gact, a.gslope);
   if constexpr (MAT == 0) {
     for (int idx = tid; idx < HW * 8; idx += 512) {
       const int row = idx >> 3, ch = idx & 7;
       const size_t go = (pix0 + row) * a.y_pitch + co_base + ch * 8;
-      *(u32x4*)(yg + go) = out_chunk(row, ch, go).raw;
-    }
-  } else if constexpr (MAT == 1) {
-    // ---- fused InstanceNorm (+ MAT modulation) + activation of the plane this workgroup owns (conv_plane.hip, MAT == 1) ---------
-    const int ch = tid & 7, r0 = tid >> 3;
-    const T* gbb = (GB && a.gb) ? (const T*)a.gb + pix0 * a.gb_pitch + co_base + ch * 8 : nullptr;
-    Chunk<T> xv[MAXR], gv[GB ? MAXR : 1], bv[GB ? MAXR : 1];
-    if constexpr (GB) {
-#pragma unroll
-      for (int k = 0; k < MAXR; ++k) {
-        const int row = r0 + 64 * k;
-        gv[k].raw = (u32x4){0u, 0u, 0u, 0u}; bv[k].raw = gv[k].raw;
-        if (gbb && row < HW) {
-          gv[k].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch);
-          bv[k].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch + a.Cout);
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) {
-      const int row = r0 + 64 * k;
-      xv[k].raw = (u32x4){0u, 0u, 0u, 0u};
-      if (row < HW) {
-        const size_t go = (pix0 + row) * a.y_pitch + co_base + ch * 8;
-        xv[k] = out_chunk(row, ch, go);
-        if (a.y) *(u32x4*)(yg + go) = xv[k].raw;                  // (y == NULL: only the normalised tensor is wanted)
-      }
-    }
-    // the plane unpacked ONCE, the centred values kept from the second pass for the third (conv_plane.hip, MAT == 1; round 5)
-    float xf[MAXR][8];
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) xv[k].unpack(xf[k]);
-    __syncthreads();                                            // the staging rows are dead: LDS is scratch from here on
-    float* red = (float*)smem;                                  // [8 waves][64]
-    float* cst = (float*)smem + 8 * 64;                         // [4][64]: plane sum / M2, then 1 + gamma_st, beta_st
-    auto plane_sum = [&](float (&v)[8], int slot) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-#pragma unroll
-        for (int o = 8; o < 64; o <<= 1) v[e] += __shfl_xor(v[e], o, 64);
-      }
-      __syncthreads();
-      if (lane < 8) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[wave * 64 + lane * 8 + e] = v[e];
-      }
-      __syncthreads();
-      if (tid < 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) t += red[w * 64 + tid];
-        cst[slot * 64 + tid] = t;
-      }
-      __syncthreads();
-    };
-    const float inv = 1.f / (float)HW;
-    float sacc[8], mean[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      sacc[e] = 0.f;
-#pragma unroll
-      for (int k = 0; k < MAXR; ++k) sacc[e] += xf[k][e];          // rows beyond HW hold zeros
-    }
-    plane_sum(sacc, 0);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      mean[e] = cst[ch * 8 + e] * inv;
-      sacc[e] = 0.f;
-#pragma unroll
-      for (int k = 0; k < MAXR; ++k) {
-        const float d = xf[k][e] - mean[e];
-        xf[k][e] = d;
-        sacc[e] += (r0 + 64 * k < HW) ? d * d : 0.f;
-      }
-    }
-    plane_sum(sacc, 1);
-    if (tid < 64) {
-      const int c = co_base + tid;
-      float* o = a.stats + 4 + ((size_t)img * a.Cout + c) * 2;     // norm.hip format: 4-word header, then [N][C][1 split]{mean, M2}
-      o[0] = cst[tid] * inv; o[1] = cst[64 + tid];
-      if (c == 0 && img == 0) *(i32x4*)a.stats = (i32x4){1, HW, 0, 0};
-      cst[2 * 64 + tid] = a.gbst ? 1.f + a.gbst[(size_t)img * a.gbst_pitch + c] : 1.f;
-      cst[3 * 64 + tid] = a.gbst ? a.gbst[(size_t)img * a.gbst_pitch + a.Cout + c] : 0.f;
-    }
-    __syncthreads();
-    float rstd[8], gs[8], bs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      rstd[e] = 1.f / sqrtf(cst[64 + ch * 8 + e] * inv + a.eps);
-      gs[e] = cst[2 * 64 + ch * 8 + e]; bs[e] = cst[3 * 64 + ch * 8 + e];
-    }
-    const float nns = a.n_act == S2P_ACT_RELU ? 0.f : (a.n_act == S2P_ACT_LRELU ? a.n_slope : 1.f);
-    T* y2 = (T*)a.y2 + pix0 * a.y2_pitch + co_base + ch * 8;
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) {
-      const int row = r0 + 64 * k;
-      if (row >= HW) break;
-      Chunk<T> o0;
-      float ov[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float gg = gs[e] + (GB ? gv[k].get(e) : 0.f), bb = bs[e] + (GB ? bv[k].get(e) : 0.f);
-        const float xh = xf[k][e] * rstd[e];                      // (x - mean) * rstd
-        const float yv = __builtin_fmaf(xh, gg, bb);              // (norm.hip: mat_value)
-        ov[e] = lrelu_ns(yv, nns);
-      }
-      o0.pack(ov);
-      *(u32x4*)(y2 + (size_t)row * a.y2_pitch) = o0.raw;
+      *(u32x4*)(yg + go) = pe_out_chunk(eo, srow, row, ch, go).raw;
     }
   } else {
-    // ---- fused backward of InstanceNorm (+ MAT modulation) + activation (conv_plane.hip, MAT == 2): the staged plane (+ the aux
-    //      gradient of EPI_ADD, e.g. a feature-matching tap) is dL/d(norm output) for this (image, slab); it never goes to HBM --------
-    const int ch = tid & 7, r0 = tid >> 3, lc = co_base + ch * 8;
-    const T* xb = (const T*)a.xn + pix0 * a.xn_pitch + lc;
-    const T* gbb = (GB && a.gb) ? (const T*)a.gb + pix0 * a.gb_pitch + lc : nullptr;
-    Chunk<T> xv[MAXR], gv[GB ? MAXR : 1], bv[GB ? MAXR : 1], dv[MAXR];
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) {
-      const int row = r0 + 64 * k;
-      xv[k].raw = (u32x4){0u, 0u, 0u, 0u}; dv[k].raw = xv[k].raw;
-      if constexpr (GB) { gv[k].raw = xv[k].raw; bv[k].raw = xv[k].raw; }
-      if (row < HW) {
-        xv[k].raw = *(const u32x4*)(xb + (size_t)row * a.xn_pitch);
-        if constexpr (GB) {
-          if (gbb) { gv[k].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch); bv[k].raw = *(const u32x4*)(gbb + (size_t)row * a.gb_pitch + a.Cout); }
-        }
-        dv[k] = out_chunk(row, ch, (pix0 + row) * a.y_pitch + lc);      // rows beyond HW stay zero: they add nothing to the sums
-      }
-    }
-    __syncthreads();                                            // the staging rows are dead: LDS is scratch from here on
-    float* red = (float*)smem;                                  // [4 sums][8 waves][64]
-    float* cst = (float*)smem + 4 * 8 * 64;                     // [6][64]: mean, rstd, 1 + gamma_st, beta_st, s1 / HW, s2 / HW
-    if (tid < 64) {
-      const int c = co_base + tid;
-      const int S = ((const int*)a.stats)[0], rows = ((const int*)a.stats)[1];
-      const float* pm = a.stats + 4 + ((size_t)img * a.Cout + c) * S * 2;
-      const float inv = 1.f / (float)HW;
-      const float m0 = pm[0];
-      float m = 0.f;
-      for (int b = 1; b < S; ++b) { int nb = HW - b * rows; if (nb > rows) nb = rows; m += (float)nb * (pm[2 * b] - m0); }
-      m = m0 + m * inv;
-      float M2 = 0.f;
-      for (int b = 0; b < S; ++b) { int nb = HW - b * rows; if (nb > rows) nb = rows; const float dd = pm[2 * b] - m; M2 += pm[2 * b + 1] + (float)nb * dd * dd; }
-      cst[tid] = m; cst[64 + tid] = 1.f / sqrtf(M2 * inv + a.eps);
-      cst[2 * 64 + tid] = a.gbst ? 1.f + a.gbst[(size_t)img * a.gbst_pitch + c] : 1.f;
-      cst[3 * 64 + tid] = a.gbst ? a.gbst[(size_t)img * a.gbst_pitch + a.Cout + c] : 0.f;
-    }
-    __syncthreads();
-    const float nneg = a.n_act == S2P_ACT_RELU ? 0.f : (a.n_act == S2P_ACT_LRELU ? a.n_slope : 1.f);
-    // the normalised input xh and the gradient dy behind the activation stay in registers for the output pass (conv_plane.hip,
-    // MAT == 2; round 5: 40 -> ~23 VALU instructions per element over the two passes)
-    float xhf[MAXR][8], dyf[MAXR][8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int cl = ch * 8 + e;
-      const float m = cst[cl], r = cst[64 + cl], g1 = cst[128 + cl], b1 = cst[192 + cl];
-      float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-#pragma unroll
-      for (int k = 0; k < MAXR; ++k) {
-        const float gg = g1 + (GB ? gv[k].get(e) : 0.f), bb = b1 + (GB ? bv[k].get(e) : 0.f);
-        const float xh = (xv[k].get(e) - m) * r;
-        const float yv = __builtin_fmaf(xh, gg, bb);            // (norm.hip: mat_value -- the forward's rounding)
-        const float dvv = dv[k].get(e);
-        const float dy = yv > 0.f ? dvv : dvv * nneg;
-        const float dxh = dy * gg;
-        xhf[k][e] = xh; dyf[k][e] = dy;
-        q0 += dxh; q1 += dxh * xh; q2 += dy * xh; q3 += dy;
-      }
-#pragma unroll
-      for (int o = 8; o < 64; o <<= 1) {
-        q0 += __shfl_xor(q0, o, 64); q1 += __shfl_xor(q1, o, 64); q2 += __shfl_xor(q2, o, 64); q3 += __shfl_xor(q3, o, 64);
-      }
-      if (lane < 8) { red[(0 * 8 + wave) * 64 + cl] = q0; red[(1 * 8 + wave) * 64 + cl] = q1; red[(2 * 8 + wave) * 64 + cl] = q2; red[(3 * 8 + wave) * 64 + cl] = q3; }
-    }
-    __syncthreads();
-    if (tid < 64) {
-      float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) { t0 += red[(0 * 8 + w) * 64 + tid]; t1 += red[(1 * 8 + w) * 64 + tid]; t2 += red[(2 * 8 + w) * 64 + tid]; t3 += red[(3 * 8 + w) * 64 + tid]; }
-      const float inv = 1.f / (float)HW;
-      cst[4 * 64 + tid] = t0 * inv; cst[5 * 64 + tid] = t1 * inv;
-      const int c = co_base + tid;
-      if (a.dgbst) {
-        a.dgbst[(size_t)img * a.dgbst_pitch + c] = t2;
-        a.dgbst[(size_t)img * a.dgbst_pitch + a.Cout + c] = t3;
-      }
-    }
-    __syncthreads();
-    T* dxo = (T*)a.y2 + pix0 * a.y2_pitch + lc;
-    T* dgo = a.dgb ? (T*)a.dgb + pix0 * a.dgb_pitch + lc : nullptr;
-    const T* rsb = a.res ? (const T*)a.res + pix0 * a.res_pitch + lc : nullptr;
-    float rr2[8], g12[8], s1v[8], s2v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const int cl = ch * 8 + e; rr2[e] = cst[64 + cl]; g12[e] = cst[128 + cl]; s1v[e] = cst[256 + cl]; s2v[e] = cst[320 + cl]; }
-#pragma unroll
-    for (int k = 0; k < MAXR; ++k) {
-      const int row = r0 + 64 * k;
-      if (row >= HW) break;
-      Chunk<T> o0, o1, o2;
-      float v0[8], v1[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float gg = g12[e] + (GB ? gv[k].get(e) : 0.f);
-        const float xh = xhf[k][e], dy = dyf[k][e];
-        const float dxh = dy * gg;
-        v0[e] = rr2[e] * (dxh - s1v[e] - xh * s2v[e]);
-        v1[e] = dy * xh;
-      }
-      o0.pack(v0); o1.pack(v1); o2.pack(dyf[k]);
-      if (rsb) {                                                // (added to the ROUNDED dx, as before)
-        Chunk<T> rv; rv.raw = *(const u32x4*)(rsb + (size_t)row * a.res_pitch);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v0[e] = o0.get(e) + rv.get(e);
-        o0.pack(v0);
-      }
-      *(u32x4*)(dxo + (size_t)row * a.y2_pitch) = o0.raw;
-      if (dgo) {
-        *(u32x4*)(dgo + (size_t)row * a.dgb_pitch) = o1.raw;
-        *(u32x4*)(dgo + (size_t)row * a.dgb_pitch + a.Cout) = o2.raw;
-      }
-    }
+    constexpr int MAXR = BPIX / 64;
+    const PeTail t{tid, lane, wave, img, co_base, a.Cout, HW, pix0, smem, a.y ? yg : nullptr, a.y_pitch, &a.nm};
+    std::conditional_t<GB, PeGbGlobal<MAXR>, PeGbNone> gb;
+    if constexpr (MAT == 1) pe_norm_fwd<MAXR, 0>(t, eo, srow, gb);
+    else pe_norm_bwd<MAXR, true>(t, eo, srow, gb);
   }
 }
 
@@ -691,17 +414,17 @@ bool s2p_conv_planeg_setup(const PlaneGProblem& p, PlaneGArgs& a) {
 template <int TY, int TX, int PB, int NPB, bool S2D>
 static void pg_launch_shape(const PlaneGArgs& a, dim3 grid, hipStream_t st) {
   constexpr int RING = (2 * TY * TX) % 8 == 0 ? 8 : 6;          // divides the K steps of an iteration
-  if (a.y2 && a.xn) hipLaunchKernelGGL((conv_planeg_kernel<TY, TX, PB, NPB, RING, 2, S2D, false>), grid, dim3(512), 0, st, a);
-  else if (a.y2) hipLaunchKernelGGL((conv_planeg_kernel<TY, TX, PB, NPB, RING, 1, S2D, false>), grid, dim3(512), 0, st, a);
+  if (a.nm.y2 && a.nm.xn) hipLaunchKernelGGL((conv_planeg_kernel<TY, TX, PB, NPB, RING, 2, S2D, false>), grid, dim3(512), 0, st, a);
+  else if (a.nm.y2) hipLaunchKernelGGL((conv_planeg_kernel<TY, TX, PB, NPB, RING, 1, S2D, false>), grid, dim3(512), 0, st, a);
   else hipLaunchKernelGGL((conv_planeg_kernel<TY, TX, PB, NPB, RING, 0, S2D, false>), grid, dim3(512), 0, st, a);
 }
 
 int s2p_conv_planeg_launch(PlaneGArgs& a, int groups, hipStream_t st) {
   a.nco = a.Cout / 64;
   a.img_xcd = (a.N % 8 == 0 && a.nbands > 1 && !S2P_DIAG_SWITCH(15)) ? 1 : 0;      // all bands of an image on one XCD (see the kernel)
-  if (a.gb) S2P_FAIL(-1, "conv_planeg: gamma / beta maps are not instantiated for this kernel family");
-  if (a.nbands > 1 && a.y2) S2P_FAIL(-1, "conv_planeg: the fused norm needs the whole plane in one workgroup");
-  if (a.gimg > 1 && (a.y2 || a.nbands > 1 || a.N % a.gimg)) S2P_FAIL(-1, "conv_planeg: several images per plane exclude the fused norm and row bands");
+  if (a.nm.gb) S2P_FAIL(-1, "conv_planeg: gamma / beta maps are not instantiated for this kernel family");
+  if (a.nbands > 1 && a.nm.y2) S2P_FAIL(-1, "conv_planeg: the fused norm needs the whole plane in one workgroup");
+  if (a.gimg > 1 && (a.nm.y2 || a.nbands > 1 || a.N % a.gimg)) S2P_FAIL(-1, "conv_planeg: several images per plane exclude the fused norm and row bands");
   dim3 grid((a.N / a.gimg) * a.nbands * a.nco, groups);
   if (a.shape == 0) pg_launch_shape<4, 4, 1, 128, false>(a, grid, st);
   else if (a.shape == 1) pg_launch_shape<4, 4, 3, 256, false>(a, grid, st);

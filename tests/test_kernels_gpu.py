@@ -736,11 +736,20 @@ def test_instance_norm_backward_with_fused_residual(hip_device, dtype, HW):
     assert err < tol, err
 
 
+def _mat_is_fused(geom, dtype, N, H, W, cin, cout, dgrad):
+    """s2p_conv2d_mat_is_fused for a conv with gamma|beta maps: does the norm go with the conv / the dgrad in one launch?"""
+    d = geom.desc(dtype, N, H, W, cin, cin, cout)
+    return lib().s2p_conv2d_mat_is_fused(ctypes.byref(d), dgrad, 1) == 1
+
+
 @pytest.mark.parametrize("dtype,shape", [
     (torch.bfloat16, (8, 128, 128, 21, 21)),     # plane-resident kernel: conv + residual + IN + MAT + LeakyReLU in ONE launch
     (torch.bfloat16, (3, 64, 192, 19, 20)),      # ... N % 8 != 0, three co slabs, 380-px plane
     (torch.bfloat16, (2, 64, 64, 9, 7)),         # small plane: conv launch + norm launch behind the same entry point
     (torch.float32, (2, 16, 32, 21, 21)),        # fp32 parity path: two launches
+    (torch.bfloat16, (3, 256, 64, 20, 20)),      # Cin >= 256, 400 px >= 384: gamma|beta staged in LDS; the seventh row group exists for 16 row lanes
+    (torch.bfloat16, (2, 256, 256, 20, 20)),     # ... with the residual chunk requested behind the loop, four slabs
+    (torch.bfloat16, (2, 256, 64, 19, 20)),      # ... 380 px < 384: the other side of that boundary (maps through registers)
 ])
 @pytest.mark.parametrize("residual", [False, True])
 def test_conv_fwd_mat_fused(hip_device, dtype, shape, residual):
@@ -759,6 +768,8 @@ def test_conv_fwd_mat_fused(hip_device, dtype, shape, residual):
     if dtype == torch.bfloat16:
         x = x.bfloat16().float(); w = w.bfloat16().float(); gb = gb.bfloat16().float()
     geom = ops.ConvGeom(cin, cout, 3, 1, 1)
+    if cin == 256:                                   # the staged-map cases: the conv and the norm must be ONE launch
+        assert _mat_is_fused(geom, dtype, N, H, W, cin, cout, dgrad=0)
     xd = nhwc(x, cin, dtype, dev)
     wf = pack_fwd(w, cin, dtype, dev)
     gbd = nhwc(gb, 2 * cout + 16, dtype, dev)
@@ -801,6 +812,8 @@ def test_conv_fwd_mat_fused(hip_device, dtype, shape, residual):
     (torch.bfloat16, (3, 192, 64, 19, 20)),      # ... N % 8 != 0, 380-px plane, three input-channel slabs produced
     (torch.bfloat16, (2, 64, 64, 9, 7)),         # small plane: two launches behind the same entry point
     (torch.float32, (2, 16, 32, 21, 21)),        # fp32 parity path: two launches
+    (torch.bfloat16, (3, 64, 256, 20, 20)),      # K = cout >= 256, 400 px: gamma|beta staged in LDS, backward form
+    (torch.bfloat16, (2, 64, 256, 19, 20)),      # ... 380 px: the maps through registers
 ])
 @pytest.mark.parametrize("with_res", [False, True])
 def test_conv_dgrad_mat_fused(hip_device, dtype, shape, with_res):
@@ -818,6 +831,8 @@ def test_conv_dgrad_mat_fused(hip_device, dtype, shape, with_res):
     if dtype == torch.bfloat16:
         xn = xn.bfloat16().float(); w = w.bfloat16().float(); gb = gb.bfloat16().float(); dy = dy.bfloat16().float(); res = res.bfloat16().float()
     geom = ops.ConvGeom(C, cout, 3, 1, 1)
+    if cout == 256:
+        assert _mat_is_fused(geom, dtype, N, H, W, C, cout, dgrad=1)
     xnd = nhwc(xn, C, dtype, dev)
     wb = pack_bwd(w, C, cout, dtype, dev)
     gbd = nhwc(gb, 2 * C + 16, dtype, dev)
@@ -969,6 +984,15 @@ def test_conv_planeg_4x4_stride1(hip_device, shape):
         d_mid = ops.conv_dgrad(geom, dyd, wb, tuple(xd.shape), cin, aux=tapd if with_tap else None, epi=EPI_ADD if with_tap else EPI_STORE)
         dx2 = ops.in_bwd(d_mid, xnd, cin, st_n, act=ACT_LRELU, slope=0.2)
         assert rel_err(dxn.float().cpu(), dx2.float().cpu().double()) < 1e-2
+        if shape == (3, 64, 128, 7, 7) and not with_tap:       # ... and ONE more call with the skip gradient `res` folded into the store
+            res = r(N, cin, H, W)
+            resd = nhwc(res, cin, dtype, dev)
+            dxr = ops.conv_dgrad_mat(geom, dyd, wb, xnd, cin, st_n, None, 0, None, 0, ACT_LRELU, 0.2, None, 0, None, 0,
+                                     res=resd)
+            dx3 = ops.in_bwd(d_mid, xnd, cin, st_n, act=ACT_LRELU, slope=0.2, res=resd)
+            torch.cuda.synchronize()
+            assert rel_err(dxr.float().cpu(), dx3.float().cpu().double()) < 1e-2
+            assert rel_err(nchw(dxr, cin)[pick], xr.grad + res[pick].double()) < TOL[dtype]
 
 
 @pytest.mark.parametrize("shape", [(8, 512, 512, 10, 10), (3, 256, 512, 10, 10), (5, 64, 128, 9, 11), (64, 512, 512, 10, 10),
