@@ -15,6 +15,10 @@ _SO = os.path.join(_HERE, "csrc", "libs2p_hip.so")     # (tools/uselib.py points
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SWISH = 0, 1, 2, 3, 4
 EPI_STORE, EPI_ADD, EPI_MUL_ACTGRAD = 0, 1, 2
+# s2p_conv2d_path: the dispatcher's path of a conv problem; for PATH_HALO the kernel variant is in bits 8 and up (halo_path)
+(PATH_THIN, PATH_THIN4, PATH_THIN_CIN, PATH_THIN_ROWS, PATH_PLANE, PATH_PLANEG, PATH_HALO, PATH_SPLITK, PATH_DMA, PATH_PHASES,
+ PATH_GENERIC) = range(11)
+HALO_S9_176_PIPE, HALO_S9_176, HALO_S9_320, HALO_R_176, HALO_R_320 = range(5)
 
 c_int, c_float, c_void_p, c_int64 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64
 
@@ -61,6 +65,7 @@ SIGNATURES = {
     "s2p_conv2d_dgrad_mat": [_DESC, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_float, c_float, _P, _P, c_int, _P, c_int,
                              _P, c_int, _P, c_int, _P, ctypes.c_size_t, _P],
     "s2p_conv2d_mat_is_fused": [_DESC, c_int, c_int],
+    "s2p_conv2d_path": [_DESC, c_int, c_int],
     "s2p_conv2d_dgrad_workspace": [_DESC],
     "s2p_conv2d_dgrad_ws": [_DESC, _P, _P, _P, _P, _P, c_int, c_int, c_float, _P, ctypes.c_size_t, _P],
     "s2p_conv2d_wgrad": [_DESC, _P, _P, _P, _P, c_int, c_int, c_int64, c_int, _P],
@@ -169,6 +174,11 @@ def lib():
             raise RuntimeError("libs2p_hip.so is older than this package")
         _lib = L
     return _lib
+
+
+def halo_path(kind):
+    """The s2p_conv2d_path answer for the halo-resident kernel in variant `kind` (HALO_*)."""
+    return PATH_HALO | (kind << 8)
 
 
 def check(rc, what):

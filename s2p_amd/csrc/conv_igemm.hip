@@ -170,6 +170,94 @@ __device__ __forceinline__ void conv_epilogue(const GatherArgs& a, f32x16 (&acc)
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Pieces the tile kernels below share: each kernel keeps its own staging and K loop.
+constexpr unsigned DMA_OOB = 0x80000000u;      // a byte offset past the range of every buffer descriptor: the load returns zeros
+
+// XCD-aware tile order: blocks b, b+8, ... share an XCD (observed round-robin); give each XCD a contiguous run of tiles so blocks
+// that share a pixel tile (all co tiles of it) hit the same L2.  Returns the tile's first weight row and first GEMM pixel.
+template <int BCO, int BPIX>
+__device__ __forceinline__ void tile_of_block(int bid, int nblk, int nco_tiles, int& co_base, int& pix_base) {
+  const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, k = bid >> 3;
+  bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
+  co_base = bid % nco_tiles * BCO; pix_base = bid / nco_tiles * BPIX;
+}
+
+// GEMM pixel m -> (image, row, column) of the produced sub-grid Qh x Qw, without integer divisions
+struct PixelSplit {
+  int QQ, Qw; double rcpQQ, rcpQw;
+  __device__ __forceinline__ PixelSplit(int Qh, int Qw_) : QQ(Qh * Qw_), Qw(Qw_), rcpQQ(s2p_rcp_f64(QQ)), rcpQw(s2p_rcp_f64(Qw_)) {}
+  __device__ __forceinline__ void operator()(int m, int& n, int& qy, int& qx) const {
+    int rr;
+    n = divmod_rcp(m, QQ, rcpQQ, rr); qy = divmod_rcp(rr, Qw, rcpQw, qx);
+  }
+};
+
+// rowoff[i]: output pixel index of the tile's i-th GEMM pixel (-1 past the end of the problem), read by conv_epilogue
+template <int BPIX>
+__device__ __forceinline__ void fill_rowoff(int* rowoff, const GatherArgs& a, const PixelSplit& split, int pix_base, int M, int oy0, int ox0) {
+  const int tid = threadIdx.x, m = pix_base + tid;
+  if (tid < BPIX) {
+    int off = -1, n, qy, qx;
+    if (m < M) { split(m, n, qy, qx); off = ((n * a.Ho + qy * a.ostride + oy0) * a.Wo + qx * a.ostride + ox0); }
+    rowoff[tid] = off;
+  }
+}
+
+template <int TCO, int TPIX>
+__device__ __forceinline__ void clear_acc(f32x16 (&acc)[TCO][TPIX]) {
+#pragma unroll
+  for (int i = 0; i < TCO; ++i)
+#pragma unroll
+    for (int j = 0; j < TPIX; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+
+// one K = 16 sub-step of a wave's tile: TCO x TPIX MFMAs on fragments already in registers
+template <int TCO, int TPIX>
+__device__ __forceinline__ void mfma_tile(f32x16 (&acc)[TCO][TPIX], const bf16x8 (&af)[TCO], const bf16x8 (&bf)[TPIX]) {
+#pragma unroll
+  for (int i = 0; i < TCO; ++i)
+#pragma unroll
+    for (int j = 0; j < TPIX; ++j)
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+}
+
+// LDS-DMA kernels: buffer descriptors of group g's gathered tensor / packed weights (hardware range check: an invalid gather is an
+// out-of-range offset that returns zeros), and this lane's source byte offset for weight row `row` of the tile -- the 16-byte chunk
+// XOR-swizzled for 128-byte LDS rows, chunk' = chunk ^ ((row >> 1) & 7) -- or DMA_OOB past Cout
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_x_rsrc(const GatherArgs& a, int g) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.x + (size_t)g * a.x_gstride), 0,
+                                           a.x_bytes - (unsigned)g * (unsigned)a.x_gstride * 2u, 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_w_rsrc(const GatherArgs& a, int g) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.w + (size_t)g * a.w_gstride), 0, a.w_bytes, 0x00020000);
+}
+__device__ __forceinline__ unsigned w_row_dma_byte(const GatherArgs& a, int co_base, int row, int pc) {
+  const int c = pc ^ ((row >> 1) & 7), co = co_base + row;
+  return co < a.Cout ? (unsigned)(co * a.w_row * 2 + c * 16) : DMA_OOB;
+}
+typedef __attribute__((address_space(3))) void* lds_ptr;
+
+// One BK = 64 step of a wave's tile from XOR-swizzled 128-byte LDS rows: all 4 x (TCO + TPIX) fragment reads are issued before the
+// first MFMA (the waits become counted lgkmcnt(N): reading per sub-step exposes the LDS latency four times per step).  wrow: the
+// lane's first weight row, swizzle `swr`; baddr(s, j): address of the lane's B fragment j for sub-step s
+template <int TCO, int TPIX, typename BAddr>
+__device__ __forceinline__ void mma_step_swizzled(f32x16 (&acc)[TCO][TPIX], const char* wrow, int swr, int h, BAddr&& baddr) {
+  bf16x8 af[4][TCO], bf[4][TPIX];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+#pragma unroll
+    for (int i = 0; i < TCO; ++i) af[s][i] = *(const bf16x8*)(wrow + i * 32 * 128 + (((2 * s + h) ^ swr) * 16));
+#pragma unroll
+    for (int j = 0; j < TPIX; ++j) bf[s][j] = *(const bf16x8*)baddr(s, j);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) mfma_tile(acc, af[s], bf[s]);
+}
+
 template <typename T, int BCO, int BPIX, int WCO, int WPIX>
 __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const GatherArgs a) {
   constexpr int CE = DT<T>::CE;
@@ -182,38 +270,16 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const GatherArgs a)
   constexpr int EPI = BPIX * ERS;
   constexpr int MAIN = (2 * STAGE > EPI ? 2 * STAGE : EPI);
   __shared__ __attribute__((aligned(16))) char smem[MAIN + BPIX * 4 + MAX_TAPS * 4];
-  int* rowoff = (int*)(smem + MAIN);
-  int* taps = rowoff + BPIX;
+  int *rowoff = (int*)(smem + MAIN), *taps = rowoff + BPIX;
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int g = blockIdx.y;
-
-  // XCD-aware tile order: blocks b, b+8, ... share an XCD (observed round-robin); give each XCD a
-  // contiguous run of tiles so blocks that share a pixel tile (all co tiles of it) hit the same L2.
-  int nblk = a.npix_tiles * a.nco_tiles;
-  int bid = blockIdx.x;
-  {
-    int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, k = bid >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
-  const int co_tile = bid % a.nco_tiles, pix_tile = bid / a.nco_tiles;
-  const int co_base = co_tile * BCO, pix_base = pix_tile * BPIX;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5, g = blockIdx.y;
+  int co_base, pix_base;
+  tile_of_block<BCO, BPIX>(blockIdx.x, a.npix_tiles * a.nco_tiles, a.nco_tiles, co_base, pix_base);
 
   if (tid < MAX_TAPS) taps[tid] = a.tap[tid];
-  const int QQ = a.Qh * a.Qw;
-  const double rcpQQ = s2p_rcp_f64(QQ), rcpQw = s2p_rcp_f64(a.Qw);
-  if (tid < BPIX) {
-    int m = pix_base + tid;
-    int off = -1;
-    if (m < a.M) {
-      int rr, qx;
-      const int n = divmod_rcp(m, QQ, rcpQQ, rr), qy = divmod_rcp(rr, a.Qw, rcpQw, qx);
-      off = ((n * a.Ho + qy * a.ostride + a.oy0) * a.Wo + qx * a.ostride + a.ox0);
-    }
-    rowoff[tid] = off;
-  }
+  const PixelSplit split(a.Qh, a.Qw);
+  fill_rowoff<BPIX>(rowoff, a, split, pix_base, a.M, a.oy0, a.ox0);
 
   // ---- per-thread staging assignment -------------------------------------------------------
   const int jc = tid & 3;          // 16-byte chunk column inside the 64-byte K row
@@ -222,8 +288,7 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const GatherArgs a)
   const int kt0 = a.splitk > 1 ? (int)blockIdx.z * a.ksteps : 0;
   const int kt1 = a.splitk > 1 ? (kt0 + a.ksteps < nk_all ? kt0 + a.ksteps : nk_all) : nk_all;
   int kk = kt0 * BK + jc * CE;     // linear k of this thread's chunk
-  int k_tap, k_c;                  // (tap, channel) of this thread's chunk, advanced by BK per step
-  k_tap = kk / a.Cin; k_c = kk - k_tap * a.Cin;
+  int k_tap = kk / a.Cin, k_c = kk - k_tap * a.Cin;      // (tap, channel) of this thread's chunk, advanced by BK per step
   // pixel rows handled by this thread
   int p_py[NLP], p_px[NLP], p_base[NLP];
   bool p_ok[NLP];
@@ -231,9 +296,8 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const GatherArgs a)
   for (int i = 0; i < NLP; ++i) {
     int m = pix_base + r0 + 64 * i;
     p_ok[i] = m < a.M;
-    int mm = p_ok[i] ? m : 0;
-    int rr, qx;
-    const int n = divmod_rcp(mm, QQ, rcpQQ, rr), qy = divmod_rcp(rr, a.Qw, rcpQw, qx);
+    int n, qy, qx;
+    split(p_ok[i] ? m : 0, n, qy, qx);
     p_py[i] = qy * a.istride; p_px[i] = qx * a.istride; p_base[i] = n * a.Hi;
   }
   const T* xg = (const T*)a.x + (size_t)g * a.x_gstride;
@@ -288,20 +352,11 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const GatherArgs a)
   };
 
   f32x16 acc[TCO][TPIX];
-#pragma unroll
-  for (int i = 0; i < TCO; ++i)
-#pragma unroll
-    for (int j = 0; j < TPIX; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
+  clear_acc(acc);
   const int wco0 = (wave / WPIX) * (TCO * 32);
   const int wpix0 = (wave % WPIX) * (TPIX * 32);
 
-  if (nk > 0) {
-    load_global();
-    store_lds(0);
-  }
+  if (nk > 0) { load_global(); store_lds(0); }
   __syncthreads();
 
   for (int kt = 0; kt < nk; ++kt) {
@@ -310,28 +365,17 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const GatherArgs a)
     const char* base = smem + (kt & 1) * STAGE;
     const char* wrow = base + (wco0 + r) * RS + h * 16;
     const char* prow = base + (BCO + wpix0 + r) * RS + h * 16;
-    if constexpr (sizeof(T) == 2) {
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 af[TCO], bf[TPIX];
+    for (int s = 0; s < 2; ++s) {
+      typedef std::conditional_t<sizeof(T) == 2, bf16x8, f32x4> Frag;      // 16 bytes of K either way
+      Frag af[TCO], bf[TPIX];
 #pragma unroll
-        for (int i = 0; i < TCO; ++i) af[i] = *(const bf16x8*)(wrow + i * 32 * RS + s * 32);
+      for (int i = 0; i < TCO; ++i) af[i] = *(const Frag*)(wrow + i * 32 * RS + s * 32);
 #pragma unroll
-        for (int j = 0; j < TPIX; ++j) bf[j] = *(const bf16x8*)(prow + j * 32 * RS + s * 32);
-#pragma unroll
-        for (int i = 0; i < TCO; ++i)
-#pragma unroll
-          for (int j = 0; j < TPIX; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        f32x4 af[TCO], bf[TPIX];
-#pragma unroll
-        for (int i = 0; i < TCO; ++i) af[i] = *(const f32x4*)(wrow + i * 32 * RS + s * 32);
-#pragma unroll
-        for (int j = 0; j < TPIX; ++j) bf[j] = *(const f32x4*)(prow + j * 32 * RS + s * 32);
+      for (int j = 0; j < TPIX; ++j) bf[j] = *(const Frag*)(prow + j * 32 * RS + s * 32);
+      if constexpr (sizeof(T) == 2) {
+        mfma_tile(acc, af, bf);
+      } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -345,152 +389,6 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const GatherArgs a)
     __syncthreads();
   }
 
-  conv_epilogue<T, BCO, BPIX, TCO, TPIX>(a, acc, smem, rowoff, g, co_base, wco0, wpix0, r, h, tid);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Fast path (bf16, Cin % 64 == 0, zero padding, tensors < 2 GiB): the bulk of the FLOPs.
-//   * BK = 64: one K step = one tap x 64 channels, so the tap is block-uniform (scalar) and steps are twice as long
-//     (16 MFMAs per wave between barriers);
-//   * global loads are buffer loads with a hardware range check: an invalid gather (padding, row >= M, co >= Cout)
-//     is expressed as an out-of-range offset that returns zeros -- no exec-mask branches, no per-load predicates;
-//   * validity of (pixel row, tap) is a 64-bit mask computed once per row; per step it costs a shift and a select;
-//   * all offsets are 32-bit byte offsets (host checks the tensors are < 2 GiB).
-template <int BCO, int BPIX, int WCO, int WPIX>
-__global__ __launch_bounds__(256, 2) void conv_fast_kernel(const GatherArgs a) {
-  typedef __bf16 T;
-  constexpr int CE = 8, BK = 64, RS = 144;           // 128 B of K per row + 16 B pad (conflict-free ds_read_b128)
-  constexpr int TCO = BCO / WCO / 32, TPIX = BPIX / WPIX / 32;
-  constexpr int NLW = BCO / 32, NLP = BPIX / 32;
-  constexpr int STAGE = (BCO + BPIX) * RS;
-  constexpr int ERS = BCO * 2 + 16;
-  constexpr int EPI = BPIX * ERS;
-  constexpr int MAIN = (2 * STAGE > EPI ? 2 * STAGE : EPI);
-  __shared__ __attribute__((aligned(16))) char smem[MAIN + BPIX * 4];
-  int* rowoff = (int*)(smem + MAIN);
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int g = blockIdx.y;
-  int nblk = a.npix_tiles * a.nco_tiles;
-  int bid = blockIdx.x;
-  {
-    int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, k = bid >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
-  const int co_tile = bid % a.nco_tiles, pix_tile = bid / a.nco_tiles;
-  const int co_base = co_tile * BCO, pix_base = pix_tile * BPIX;
-  const int QQ = a.Qh * a.Qw;
-  const double rcpQQ = s2p_rcp_f64(QQ), rcpQw = s2p_rcp_f64(a.Qw);
-  if (tid < BPIX) {
-    int m = pix_base + tid;
-    int off = -1;
-    if (m < a.M) {
-      int rr, qx;
-      const int n = divmod_rcp(m, QQ, rcpQQ, rr), qy = divmod_rcp(rr, a.Qw, rcpQw, qx);
-      off = ((n * a.Ho + qy * a.ostride + a.oy0) * a.Wo + qx * a.ostride + a.ox0);
-    }
-    rowoff[tid] = off;
-  }
-
-  const int jc = tid & 7, r0 = tid >> 3;            // 16-B chunk column (8 per row), row 0..31 (+32*i)
-  const unsigned OOB = 0x80000000u;
-  const T* xg = (const T*)a.x + (size_t)g * a.x_gstride;
-  const T* wg = (const T*)a.w + (size_t)g * a.w_gstride;
-  __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)xg, 0, a.x_bytes - (unsigned)g * (unsigned)a.x_gstride * 2u, 0x00020000);
-  __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)wg, 0, a.w_bytes, 0x00020000);
-
-  unsigned p_byte[NLP];
-  unsigned long long p_mask[NLP];
-#pragma unroll
-  for (int i = 0; i < NLP; ++i) {
-    int m = pix_base + r0 + 32 * i;
-    unsigned long long mask = 0ull;
-    unsigned byte = 0u;
-    if (m < a.M) {
-      int rr, qx;
-      const int n = divmod_rcp(m, QQ, rcpQQ, rr), qy = divmod_rcp(rr, a.Qw, rcpQw, qx);
-      int py = qy * a.istride, px = qx * a.istride;
-      byte = (unsigned)(((n * a.Hi + py) * a.Wi + px) * a.x_pitch * 2 + jc * 16);
-      for (int t = 0; t < a.T; ++t) {
-        int ti = a.tap[t];
-        int iy = py + (int)(signed char)(ti & 0xff), ix = px + (int)(signed char)((ti >> 8) & 0xff);
-        if (iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi) mask |= 1ull << t;
-      }
-    }
-    p_byte[i] = byte; p_mask[i] = mask;
-  }
-  unsigned w_byte[NLW];
-#pragma unroll
-  for (int i = 0; i < NLW; ++i) {
-    int co = co_base + r0 + 32 * i;
-    w_byte[i] = co < a.Cout ? (unsigned)(co * a.w_row * 2 + jc * 16) : OOB;
-  }
-
-  u32x4 regW[NLW], regP[NLP];
-  const int nk = a.Ktot / BK;
-  int tap = 0, c0 = 0;                                // block-uniform K position
-
-  auto load_global = [&]() {
-    const int ti = a.tap[tap];
-    const int dy = (int)(signed char)(ti & 0xff), dx = (int)(signed char)((ti >> 8) & 0xff), wt = ti >> 16;
-    const int toff = ((dy * a.Wi + dx) * a.x_pitch + c0) * 2;
-    const int woff = (wt * a.Cin + c0) * 2;
-#pragma unroll
-    for (int i = 0; i < NLW; ++i)
-      regW[i] = __builtin_amdgcn_raw_buffer_load_b128(wr, (int)(w_byte[i] == OOB ? OOB : w_byte[i] + (unsigned)woff), 0, 0);
-#pragma unroll
-    for (int i = 0; i < NLP; ++i) {
-      bool ok = (p_mask[i] >> tap) & 1ull;
-      regP[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, (int)(ok ? p_byte[i] + (unsigned)toff : OOB), 0, 0);
-    }
-    c0 += BK;
-    if (c0 >= a.Cin) { c0 = 0; ++tap; }
-  };
-  auto store_lds = [&](int buf) {
-    char* base = smem + buf * STAGE + r0 * RS + jc * 16;
-#pragma unroll
-    for (int i = 0; i < NLW; ++i) *(u32x4*)(base + 32 * i * RS) = regW[i];
-#pragma unroll
-    for (int i = 0; i < NLP; ++i) *(u32x4*)(base + (BCO + 32 * i) * RS) = regP[i];
-  };
-
-  f32x16 acc[TCO][TPIX];
-#pragma unroll
-  for (int i = 0; i < TCO; ++i)
-#pragma unroll
-    for (int j = 0; j < TPIX; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  const int wco0 = (wave / WPIX) * (TCO * 32);
-  const int wpix0 = (wave % WPIX) * (TPIX * 32);
-
-  if (nk > 0) { load_global(); store_lds(0); }
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const bool more = kt + 1 < nk;
-    if (more) load_global();
-    const char* base = smem + (kt & 1) * STAGE;
-    const char* wrow = base + (wco0 + r) * RS + h * 16;
-    const char* prow = base + (BCO + wpix0 + r) * RS + h * 16;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      bf16x8 af[TCO], bf[TPIX];
-#pragma unroll
-      for (int i = 0; i < TCO; ++i) af[i] = *(const bf16x8*)(wrow + i * 32 * RS + s * 32);
-#pragma unroll
-      for (int j = 0; j < TPIX; ++j) bf[j] = *(const bf16x8*)(prow + j * 32 * RS + s * 32);
-#pragma unroll
-      for (int i = 0; i < TCO; ++i)
-#pragma unroll
-        for (int j = 0; j < TPIX; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-    if (more) store_lds((kt + 1) & 1);
-    __syncthreads();
-  }
   conv_epilogue<T, BCO, BPIX, TCO, TPIX>(a, acc, smem, rowoff, g, co_base, wco0, wpix0, r, h, tid);
 }
 
@@ -522,11 +420,14 @@ static int launch_cfg(GatherArgs& a, int groups, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// LDS-DMA variant of the fast path: `buffer_load_dwordx4 ... lds` writes the staged tile straight into LDS, so the
-// register->LDS `ds_write_b128` pass (13 cycles per wave-instruction; with two co-resident workgroups it made the
-// kernel LDS-bound) disappears, and so do the 32 staging VGPRs.  An LDS-DMA wave-instruction writes 1 KiB linearly
-// (8 rows of 128 B), so rows cannot be padded; bank conflicts are avoided with an XOR swizzle of the 16-byte chunk
-// index, chunk' = chunk ^ ((row >> 1) & 7), applied on the per-lane global SOURCE address and again on the
+// LDS-DMA kernel (bf16, Cin % 64 == 0, zero padding, tensors < 2 GiB): the bulk of the FLOPs outside the plane-resident kernels.
+//   * BK = 64: one K step = one tap x 64 channels, so the tap is block-uniform (scalar), 16 MFMAs per wave between barriers;
+//   * `buffer_load_dwordx4 ... lds` writes the staged tile straight into LDS: no register->LDS `ds_write_b128` pass (13 cycles per
+//     wave-instruction; with two co-resident workgroups it made a register-staged kernel LDS-bound), no 32 staging VGPRs;
+//   * an invalid gather (padding, row >= M, co >= Cout) is an out-of-range offset that returns zeros through the descriptor's range
+//     check -- no exec-mask branches, no per-load predicates; all offsets are 32-bit byte offsets (host: tensors < 2 GiB).
+// An LDS-DMA wave-instruction writes 1 KiB linearly (8 rows of 128 B), so rows cannot be padded; bank conflicts are avoided with an XOR
+// swizzle of the 16-byte chunk index, chunk' = chunk ^ ((row >> 1) & 7), applied on the per-lane global SOURCE address and again on the
 // fragment read (conflict-free for the 16-lane groups of ds_read_b128 with 128-byte rows).
 template <int BCO, int BPIX, int WCO, int WPIX>
 __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const GatherArgs a) {
@@ -542,11 +443,9 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const GatherArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[MAIN + BPIX * 4];
   int* rowoff = (int*)(smem + MAIN);
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int g = blockIdx.y;
+  const int r = lane & 31, h = lane >> 5, g = blockIdx.y;
   // per-phase problem fields (block-uniform)
   int pQh = a.Qh, pQw = a.Qw, pM = a.M, poy0 = a.oy0, pox0 = a.ox0, pT = a.T, pKtot = a.Ktot, pnpt = a.npix_tiles;
   const int* ptap = a.tap;
@@ -562,37 +461,14 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const GatherArgs a) {
     pQh = P.Qh; pQw = P.Qw; pM = P.M; poy0 = P.oy0; pox0 = P.ox0; pT = P.T; pKtot = P.Ktot; pnpt = P.npix_tiles;
     ptap = P.tap;
   }
-  int nblk = pnpt * a.nco_tiles;
+  const int nblk = pnpt * a.nco_tiles;
   if (bid >= nblk) return;                            // phases differ in size; the grid is sized for the largest
-  {
-    int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, k = bid >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
-  const int co_tile = bid % a.nco_tiles, pix_tile = bid / a.nco_tiles;
-  const int co_base = co_tile * BCO, pix_base = pix_tile * BPIX;
-  const int QQ = pQh * pQw;
-  const double rcpQQ = s2p_rcp_f64(QQ), rcpQw = s2p_rcp_f64(pQw);
-  auto split_pixel = [&](int m, int& n, int& qy, int& qx) {
-    int rr;
-    n = divmod_rcp(m, QQ, rcpQQ, rr);
-    qy = divmod_rcp(rr, pQw, rcpQw, qx);
-  };
-  if (tid < BPIX) {
-    int m = pix_base + tid;
-    int off = -1;
-    if (m < pM) {
-      int n, qy, qx;
-      split_pixel(m, n, qy, qx);
-      off = ((n * a.Ho + qy * a.ostride + poy0) * a.Wo + qx * a.ostride + pox0);
-    }
-    rowoff[tid] = off;
-  }
+  int co_base, pix_base;
+  tile_of_block<BCO, BPIX>(bid, nblk, a.nco_tiles, co_base, pix_base);
+  const PixelSplit split(pQh, pQw);
+  fill_rowoff<BPIX>(rowoff, a, split, pix_base, pM, poy0, pox0);
 
-  const unsigned OOB = 0x80000000u;
-  const T* xg = (const T*)a.x + (size_t)g * a.x_gstride;
-  const T* wg = (const T*)a.w + (size_t)g * a.w_gstride;
-  __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)xg, 0, a.x_bytes - (unsigned)g * (unsigned)a.x_gstride * 2u, 0x00020000);
-  __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)wg, 0, a.w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xr = conv_x_rsrc(a, g), wr = conv_w_rsrc(a, g);
 
   // lane -> (row inside the 8-row piece, physical chunk); instruction i of wave w stages rows (4i + w)*8 .. +7
   const int lrow = lane >> 3, pc = lane & 7;
@@ -602,12 +478,7 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const GatherArgs a) {
   unsigned p_byte[NI - NIW];
   int p_y[NI - NIW], p_x[NI - NIW];
 #pragma unroll
-  for (int i = 0; i < NIW; ++i) {
-    int row = (4 * i + wave) * 8 + lrow;
-    int c = pc ^ ((row >> 1) & 7);
-    int co = co_base + row;
-    w_byte[i] = co < a.Cout ? (unsigned)(co * a.w_row * 2 + c * 16) : OOB;
-  }
+  for (int i = 0; i < NIW; ++i) w_byte[i] = w_row_dma_byte(a, co_base, (4 * i + wave) * 8 + lrow, pc);
 #pragma unroll
   for (int i = 0; i < NI - NIW; ++i) {
     int row = (4 * (i + NIW) + wave) * 8 + lrow;      // stage row (>= BCO)
@@ -617,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const GatherArgs a) {
     int py = -0x40000000, px = 0;                     // rows past the end of the problem: no tap is in bounds
     if (m < pM) {
       int n, qy, qx;
-      split_pixel(m, n, qy, qx);
+      split(m, n, qy, qx);
       py = qy * a.istride; px = qx * a.istride;
       byte = (unsigned)(((n * a.Hi + py) * a.Wi + px) * a.x_pitch * 2 + c * 16);
     }
@@ -633,7 +504,6 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const GatherArgs a) {
     tap = k0 / a.Cin; c0 = k0 - tap * a.Cin;
     nk = kt1 - kt0;
   }
-  typedef __attribute__((address_space(3))) void* lds_ptr;
 
   auto issue = [&](int buf) {
     const int ti = ptap[tap];
@@ -644,25 +514,19 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const GatherArgs a) {
 #pragma unroll
     for (int i = 0; i < NIW; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_ptr)(base + i * (32 * RS)), 16,
-                                               (int)(w_byte[i] == OOB ? OOB : w_byte[i] + (unsigned)woff), 0, 0, 0);
+                                               (int)(w_byte[i] == DMA_OOB ? DMA_OOB : w_byte[i] + (unsigned)woff), 0, 0, 0);
 #pragma unroll
     for (int i = 0; i < NI - NIW; ++i) {
       bool ok = (unsigned)(p_y[i] + dy) < (unsigned)a.Hi && (unsigned)(p_x[i] + dx) < (unsigned)a.Wi;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_ptr)(base + (i + NIW) * (32 * RS)), 16,
-                                               (int)(ok ? p_byte[i] + (unsigned)toff : OOB), 0, 0, 0);
+                                               (int)(ok ? p_byte[i] + (unsigned)toff : DMA_OOB), 0, 0, 0);
     }
     c0 += BK;
     if (c0 >= a.Cin) { c0 = 0; ++tap; }
   };
 
   f32x16 acc[TCO][TPIX];
-#pragma unroll
-  for (int i = 0; i < TCO; ++i)
-#pragma unroll
-    for (int j = 0; j < TPIX; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
+  clear_acc(acc);
   const int wco0 = (wave / WPIX) * (TCO * 32);
   const int wpix0 = (wave % WPIX) * (TPIX * 32);
   const int sw = (r >> 1) & 7;                        // read-side swizzle (tile bases are multiples of 16 rows)
@@ -676,18 +540,14 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(const GatherArgs a) {
     const char* prow = base + (BCO + wpix0 + r) * RS;
     if (S2P_DIAGV(a) != 2)
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < 4; ++s) {                     // (fragments read per sub-step: at 182 VGPRs the 128-row tile has no room for all 16)
       const int ch = ((2 * s + h) ^ sw) * 16;
       bf16x8 af[TCO], bf[TPIX];
 #pragma unroll
       for (int i = 0; i < TCO; ++i) af[i] = *(const bf16x8*)(wrow + i * 32 * RS + ch);
 #pragma unroll
       for (int j = 0; j < TPIX; ++j) bf[j] = *(const bf16x8*)(prow + j * 32 * RS + ch);
-#pragma unroll
-      for (int i = 0; i < TCO; ++i)
-#pragma unroll
-        for (int j = 0; j < TPIX; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+      mfma_tile(acc, af, bf);
     }
     __syncthreads();
   }
@@ -804,7 +664,7 @@ __global__ __launch_bounds__(64) void conv_part_reduce_kernel(const GatherArgs a
 // The environment ones are read once, at the first conv call; the numbered run-time switches (s2p_diag_set, listed in misc.hip) are
 // read at each use, because tools/ab_step.py flips them between two captures in one process.
 struct ConvSwitches {
-  int no_dma = s2p_env_set("S2P_NO_LDS_DMA");            // register-staged conv_fast_kernel instead of every LDS-DMA kernel
+  int no_dma = s2p_env_set("S2P_NO_LDS_DMA");            // no LDS-DMA kernel: the register-staged conv_gather_kernel<bf16> runs the conv
   int diag = s2p_env_int("S2P_DIAG", 0);                 // timing ablation passed to the kernels (GatherArgs::diag)
   int no_halo = s2p_env_set("S2P_NO_HALO");              // plain LDS-DMA kernel instead of the halo-resident one
   int no_split = s2p_env_set("S2P_NO_CONV_SPLITK");
@@ -841,445 +701,378 @@ static int conv_split_plan(int nwg, int nk) {
 // neighbouring rows and images) is staged ONCE and stays resident in LDS while all taps are swept; only the 16 KiB
 // weight stage is streamed per tap.  Per 3x3 slab: 22 + 9*16 KiB instead of 9*32 KiB (-42 % L2 traffic).
 // Tap validity (zero padding, image/row borders) is a per-pixel bit mask; an invalid (pixel, tap) reads a zero row.
-template <int NPOS_CAP, bool DBUF, int TS = 0, bool PIPE = false>   // TS: static tap count (9 = 3x3, taps unrolled) or 0 = run-time taps
-__global__ __launch_bounds__(256, 2) void conv_halo_kernel(const GatherArgs a) {
-  typedef __bf16 T;
-  constexpr int BCO = 128, BPIX = 128, WPIX = 2, TCO = 2, TPIX = 2;
-  constexpr int BK = 64, RS = 128;
-  constexpr int WSTAGE = BCO * RS;                     // 16 KiB weight stage
-  constexpr int HALO = (NPOS_CAP + 1) * RS;            // + one all-zero row per halo buffer (target of invalid taps, TS variant)
-  constexpr int ERS = BCO * 2 + 16;
-  constexpr int EPI = BPIX * ERS;
-  constexpr int NHB = DBUF ? 2 : 1;                    // halo buffers (double-buffered when two workgroups still fit a CU)
-  constexpr int MAIN0 = NHB * HALO + 2 * WSTAGE + 1024;      // + zero rows
-  constexpr int MAIN = MAIN0 > EPI ? MAIN0 : EPI;
-  __shared__ __attribute__((aligned(1024))) char smem[MAIN + BPIX * 4];
-  int* rowoff = (int*)(smem + MAIN);
-  char* hbase = smem;
-  char* wbase = smem + NHB * HALO;
-  char* zrow = smem + NHB * HALO + 2 * WSTAGE;
-  // diagnostics build, S2P_DIAG=9: the launch runs normally and stamps s_memrealtime (100 MHz) at entry / loop start / loop
-  // end / after the epilogue into `aux` (a debug buffer of its own: 4 x u64 per workgroup; epi must be STORE)
-  unsigned long long tl0 = 0, tl1 = 0, tl2 = 0;
-  if (S2P_DIAGV(a) == 9) tl0 = __builtin_amdgcn_s_memrealtime();
+//
+// conv_halo_kernel = HaloTile::setup (indices, descriptors, tap masks), then ONE of three K loops over (slab, tap) -- weights always
+// one step ahead; the next slab's halo prefetched into the other halo buffer during the current slab (DBUF) or loaded behind a
+// barrier at the slab boundary -- then the tail (conv_epilogue).  HaloTile is what the loops share.
+template <int NPOS_CAP, bool DBUF>
+struct HaloTile {
+  static constexpr int BCO = 128, BPIX = 128, WPIX = 2, TCO = 2, TPIX = 2;
+  static constexpr int BK = 64, RS = 128;
+  static constexpr int WSTAGE = BCO * RS;                     // 16 KiB weight stage
+  static constexpr int HALO = (NPOS_CAP + 1) * RS;            // + one all-zero row per halo buffer (target of invalid taps, static-tap forms)
+  static constexpr int ERS = BCO * 2 + 16, EPI = BPIX * ERS;
+  static constexpr int NHB = DBUF ? 2 : 1;                    // halo buffers (double-buffered when two workgroups still fit a CU)
+  static constexpr int MAIN0 = NHB * HALO + 2 * WSTAGE + 1024;      // + zero rows
+  static constexpr int MAIN = MAIN0 > EPI ? MAIN0 : EPI;
+  static constexpr int NHP = (NPOS_CAP / 8 + 3) / 4;          // halo pieces (8 positions) per wave
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int g = blockIdx.y;
-  int nblk = a.npix_tiles * a.nco_tiles;
-  int bid = blockIdx.x;
-  {
-    int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, k = bid >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
-  const int co_tile = bid % a.nco_tiles, pix_tile = bid / a.nco_tiles;
-  const int co_base = co_tile * BCO, pix_base = pix_tile * BPIX;
-  const int QQ = a.Qh * a.Qw;
-  if (tid < BPIX) {
-    int m = pix_base + tid;
-    rowoff[tid] = m < a.M ? m : -1;                   // same grid: output pixel index == GEMM pixel index
-  }
-  if (tid < 64) *(u32x4*)(zrow + tid * 16) = (u32x4){0u, 0u, 0u, 0u};
-  if (tid < 8 * NHB) *(u32x4*)(hbase + (tid >> 3) * HALO + NPOS_CAP * RS + (tid & 7) * 16) = (u32x4){0u, 0u, 0u, 0u};
+  char* hbase; char* wbase; char* zrow; int* rowoff;
+  int tid, lane, wave, r, h, g, lrow, pc;
+  int co_base, pix_base, wco0, wpix0, swr, npos, nslab;
+  unsigned w_byte[4], h_byte[NHP];
+  unsigned long long vmask[TPIX];      // tap-validity masks of the pixels this lane feeds to the MFMA (B operand columns)
+  __amdgpu_buffer_rsrc_t xr, wr;
 
-  const unsigned OOB = 0x80000000u;
-  const T* xg = (const T*)a.x + (size_t)g * a.x_gstride;
-  const T* wg = (const T*)a.w + (size_t)g * a.w_gstride;
-  __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)xg, 0, a.x_bytes - (unsigned)g * (unsigned)a.x_gstride * 2u, 0x00020000);
-  __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)wg, 0, a.w_bytes, 0x00020000);
+  __device__ __forceinline__ void setup(const GatherArgs& a, char* smem) {
+    rowoff = (int*)(smem + MAIN);
+    hbase = smem; wbase = smem + NHB * HALO; zrow = smem + NHB * HALO + 2 * WSTAGE;
+    tid = threadIdx.x; lane = tid & 63; r = lane & 31; h = lane >> 5; g = blockIdx.y;
+    wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    tile_of_block<BCO, BPIX>(blockIdx.x, a.npix_tiles * a.nco_tiles, a.nco_tiles, co_base, pix_base);
+    if (tid < BPIX) rowoff[tid] = pix_base + tid < a.M ? pix_base + tid : -1;      // same grid: output pixel index == GEMM pixel index
+    if (tid < 64) *(u32x4*)(zrow + tid * 16) = (u32x4){0u, 0u, 0u, 0u};
+    if (tid < 8 * NHB) *(u32x4*)(hbase + (tid >> 3) * HALO + NPOS_CAP * RS + (tid & 7) * 16) = (u32x4){0u, 0u, 0u, 0u};
+    xr = conv_x_rsrc(a, g); wr = conv_w_rsrc(a, g);
 
-  const int lrow = lane >> 3, pc = lane & 7;
-  // weight DMA: instruction i of wave w stages rows (4i + w)*8 .. +7 of the 128-row stage
-  unsigned w_byte[4];
+    lrow = lane >> 3; pc = lane & 7;
+    // weight DMA: instruction i of wave w stages rows (4i + w)*8 .. +7 of the 128-row stage
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int row = (4 * i + wave) * 8 + lrow;
-    int c = pc ^ ((row >> 1) & 7);
-    int co = co_base + row;
-    w_byte[i] = co < a.Cout ? (unsigned)(co * a.w_row * 2 + c * 16) : OOB;
-  }
-  // halo DMA: piece j (8 positions) for j = wave, wave + 4, ...; position p <-> pixel pix_base - halo_lo + p
-  const int npos = BPIX + a.halo_lo + a.halo_hi;
-  constexpr int NHP = (NPOS_CAP / 8 + 3) / 4;
-  unsigned h_byte[NHP];
+    for (int i = 0; i < 4; ++i) w_byte[i] = w_row_dma_byte(a, co_base, (4 * i + wave) * 8 + lrow, pc);
+    // halo DMA: piece j (8 positions) for j = wave, wave + 4, ...; position p <-> pixel pix_base - halo_lo + p
+    npos = BPIX + a.halo_lo + a.halo_hi;
 #pragma unroll
-  for (int i = 0; i < NHP; ++i) {
-    int pos = (4 * i + wave) * 8 + lrow;
-    int c = pc ^ ((pos >> 1) & 7);
-    long long gpix = (long long)pix_base - a.halo_lo + pos;
-    h_byte[i] = (pos < npos && gpix >= 0 && gpix < a.M) ? (unsigned)(gpix * a.x_pitch * 2 + c * 16) : OOB;
-  }
-  // tap-validity masks of the pixels this lane feeds to the MFMA (B operand columns)
-  const int wco0 = (wave / WPIX) * (TCO * 32);
-  const int wpix0 = (wave % WPIX) * (TPIX * 32);
-  unsigned long long vmask[TPIX];
-  const double hrcpQQ = s2p_rcp_f64(QQ), hrcpQw = s2p_rcp_f64(a.Qw);
+    for (int i = 0; i < NHP; ++i) h_byte[i] = halo_dma_byte(a, (4 * i + wave) * 8 + lrow);
+    wco0 = (wave / WPIX) * (TCO * 32);
+    wpix0 = (wave % WPIX) * (TPIX * 32);
+    const PixelSplit split(a.Qh, a.Qw);
 #pragma unroll
-  for (int j = 0; j < TPIX; ++j) {
-    int m = pix_base + wpix0 + 32 * j + r;
-    unsigned long long mask = 0ull;
-    if (m < a.M) {
-      int rr, qx;
-      const int n = divmod_rcp(m, QQ, hrcpQQ, rr), qy = divmod_rcp(rr, a.Qw, hrcpQw, qx);
-      (void)n;
-      for (int t0 = 0; t0 < a.T; t0 += 8) {            // 8 tap words per round: the scalar loads go out back to back
-        int tv[8];
+    for (int j = 0; j < TPIX; ++j) {
+      int m = pix_base + wpix0 + 32 * j + r;
+      unsigned long long mask = 0ull;
+      if (m < a.M) {
+        int n, qy, qx;
+        split(m, n, qy, qx);
+        for (int t0 = 0; t0 < a.T; t0 += 8) {            // 8 tap words per round: the scalar loads go out back to back
+          int tv[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) tv[u] = a.tap[(t0 + u) < MAX_TAPS ? t0 + u : MAX_TAPS - 1];
+          for (int u = 0; u < 8; ++u) tv[u] = a.tap[(t0 + u) < MAX_TAPS ? t0 + u : MAX_TAPS - 1];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          int iy = qy + (int)(signed char)(tv[u] & 0xff), ix = qx + (int)(signed char)((tv[u] >> 8) & 0xff);
-          if (t0 + u < a.T && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi) mask |= 1ull << (t0 + u);
+          for (int u = 0; u < 8; ++u) {
+            int iy = qy + (int)(signed char)(tv[u] & 0xff), ix = qx + (int)(signed char)((tv[u] >> 8) & 0xff);
+            if (t0 + u < a.T && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi) mask |= 1ull << (t0 + u);
+          }
         }
       }
+      vmask[j] = mask;
     }
-    vmask[j] = mask;
+    nslab = a.Cin / BK;
+    swr = (r >> 1) & 7;                                // weight rows: tile bases are multiples of 16 rows
   }
-
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  const int nslab = a.Cin / BK;
-  const int nk = nslab * a.T;
-
-  auto issue_w = [&](int buf, int tapword, int c0) {
-    const int wt = tapword >> 16;
+  // this lane's source byte offset of halo position `pos` (swizzled chunk), or DMA_OOB outside the window / the tensor
+  __device__ __forceinline__ unsigned halo_dma_byte(const GatherArgs& a, int pos) const {
+    const int c = pc ^ ((pos >> 1) & 7);
+    const long long gpix = (long long)pix_base - a.halo_lo + pos;
+    return (pos < npos && gpix >= 0 && gpix < a.M) ? (unsigned)(gpix * a.x_pitch * 2 + c * 16) : DMA_OOB;
+  }
+  __device__ __forceinline__ void issue_w(const GatherArgs& a, int buf, int wt, int c0) const {
     const int woff = (wt * a.Cin + c0) * 2;
     char* base = wbase + buf * WSTAGE + wave * (8 * RS);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_ptr)(base + i * (32 * RS)), 16,
-                                               (int)(w_byte[i] == OOB ? OOB : w_byte[i] + (unsigned)woff), 0, 0, 0);
-  };
-  auto issue_halo = [&](int hb, int c0) {
+                                               (int)(w_byte[i] == DMA_OOB ? DMA_OOB : w_byte[i] + (unsigned)woff), 0, 0, 0);
+  }
+  __device__ __forceinline__ void issue_halo(int hb, int c0) const {
     char* base = hbase + hb * HALO + wave * (8 * RS);
 #pragma unroll
     for (int i = 0; i < NHP; ++i)
       if ((4 * i + wave) * 8 < npos)                   // wave-uniform
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_ptr)(base + i * (32 * RS)), 16,
-                                                 (int)(h_byte[i] == OOB ? OOB : h_byte[i] + (unsigned)(c0 * 2)), 0, 0, 0);
-  };
-
-  f32x16 acc[TCO][TPIX];
-#pragma unroll
-  for (int i = 0; i < TCO; ++i)
-#pragma unroll
-    for (int j = 0; j < TPIX; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  const int swr = (r >> 1) & 7;                        // weight rows: tile bases are multiples of 16 rows
-
-  // one linear pipeline over (slab, tap): weights are always one step ahead; the next slab's halo is prefetched
-  // into the other halo buffer during the current slab (DBUF) or loaded behind a barrier at the slab boundary.
-  if (S2P_DIAGV(a) == 5) return;                              // timing ablation: index set-up only
-  if constexpr (TS > 0 && PIPE && DBUF) {
-    // Software-pipelined static-tap form.  The weight stage is split into BK=32 HALF-stages (4 x 8 KiB in the same
-    // 32 KiB as two full stages): the DMA of half-step h+3 is issued (inline asm, so the waits can be counted) while
-    // half-step h computes, the fragments of half-step h+1 are read from LDS into a second register set under the MFMAs
-    // of half-step h, and the only wait before the raw s_barrier is vmcnt(N) for the half-stage needed two steps later.
-    constexpr int WHALF = BCO * 64;                     // 8 KiB: 128 rows x 64 B, chunk' = chunk ^ ((row >> 2) & 3)
-    int pk[TS][TPIX];
-    int wtv[TS];
-#pragma unroll
-    for (int t = 0; t < TS; ++t) {
-      const int ti = a.tap[t];
-      wtv[t] = ti >> 16;
-      const int toff = (int)(signed char)(ti & 0xff) * a.Wi + (int)(signed char)((ti >> 8) & 0xff);
-#pragma unroll
-      for (int j = 0; j < TPIX; ++j) {
-        const int hp = wpix0 + 32 * j + r + a.halo_lo + toff;
-        const bool ok = (vmask[j] >> t) & 1ull;
-        pk[t][j] = ok ? hp * RS + ((hp >> 1) & 7) * 16 : NPOS_CAP * RS;
-      }
-    }
-    const int ch16[4] = {(0 + h) * 16, (2 + h) * 16, (4 + h) * 16, (6 + h) * 16};
-    const i32x4 wrs = s2p_make_rsrc(wg, a.w_bytes);
-    const i32x4 xrs = s2p_make_rsrc(xg, a.x_bytes - (unsigned)g * (unsigned)a.x_gstride * 2u);
-    const unsigned wb_lds = __builtin_amdgcn_readfirstlane(s2p_lds_addr(wbase));
-    const unsigned hb_lds = __builtin_amdgcn_readfirstlane(s2p_lds_addr(hbase));
-    // weight half-stage DMA: piece p = 16 rows x 64 B; wave w issues pieces w and w + 4
-    unsigned wv[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int row = 16 * (wave + 4 * q) + (lane >> 2);
-      const int c = (lane & 3) ^ ((row >> 2) & 3);
-      const int co = co_base + row;
-      wv[q] = co < a.Cout ? (unsigned)(co * a.w_row * 2 + c * 16) : OOB;
-    }
-    auto issue_wh = [&](int hs, int wt, int kofs) {
-      const unsigned dst = wb_lds + (unsigned)((hs & 3) * WHALF + wave * 1024);
-      const unsigned woff = (unsigned)((wt * a.Cin + kofs) * 2);
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        s2p_dma16(wrs, dst + q * 4096, (int)(wv[q] == OOB ? OOB : wv[q] + woff));
-    };
-    // halo DMA: every wave issues exactly NHP pieces (the last ones repeat its last real piece), so vmcnt counts are fixed
-    constexpr int NHPc = (NPOS_CAP / 8 + 3) / 4;
-    const int last_piece = (npos + 7) / 8 - 1;
-    unsigned hv[NHPc]; int hpc[NHPc];
-#pragma unroll
-    for (int i = 0; i < NHPc; ++i) {
-      int pc8 = 4 * i + wave; if (pc8 > last_piece) pc8 = last_piece - ((last_piece - wave) & 3);   // this wave's last real piece
-      if (pc8 < 0) pc8 = wave <= last_piece ? wave : 0;
-      hpc[i] = pc8;
-      const int pos = pc8 * 8 + lrow;
-      const int c = pc ^ ((pos >> 1) & 7);
-      const long long gpix = (long long)pix_base - a.halo_lo + pos;
-      hv[i] = (pos < npos && gpix >= 0 && gpix < a.M) ? (unsigned)(gpix * a.x_pitch * 2 + c * 16) : OOB;
-    }
-    auto issue_halo_p = [&](int hbuf, int c0) {
-      const unsigned dst = hb_lds + (unsigned)(hbuf * HALO);
-#pragma unroll
-      for (int i = 0; i < NHPc; ++i)
-        s2p_dma16(xrs, dst + (unsigned)(hpc[i] * 1024), (int)(hv[i] == OOB ? OOB : hv[i] + (unsigned)(c0 * 2)));
-    };
-    const int arow[TCO] = {(wco0 + r) * 64, (wco0 + 32 + r) * 64};
-    const int asw = (r >> 2) & 3;
-    bf16x8 FA[2][2][TCO], FB[2][2][TPIX];
-    auto read_frags = [&](auto bufc, int hs, auto tc, auto halfc, const char* hbp) {
-      constexpr int buf = decltype(bufc)::value, t = decltype(tc)::value, half = decltype(halfc)::value;
-      const char* wbp = wbase + (hs & 3) * WHALF;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-#pragma unroll
-        for (int i = 0; i < TCO; ++i) FA[buf][s2][i] = *(const bf16x8*)(wbp + arow[i] + (((2 * s2 + h) ^ asw) * 16));
-#pragma unroll
-        for (int j = 0; j < TPIX; ++j) FB[buf][s2][j] = *(const bf16x8*)(hbp + (pk[t][j] ^ ch16[2 * half + s2]));
-      }
-    };
-    const int nhs = nslab * TS * 2;
-    issue_halo_p(0, 0);
-    issue_wh(0, wtv[0], 0);
-    issue_wh(1, wtv[0], 32);
-    if (nhs > 2) { issue_wh(2, wtv[1], 0); S2P_WAIT_VMCNT(2); } else { S2P_WAIT_VMCNT(0); }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (S2P_DIAGV(a) == 3) return;
-    unsigned long long st_c0 = 0, st_r0 = 0;
-    if (S2P_DIAGV(a) == 8) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
-    if (S2P_DIAGV(a) == 9) tl1 = __builtin_amdgcn_s_memrealtime();
-    read_frags(std::integral_constant<int, 0>{}, 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, hbase);
-    int hs = 0;
-    for (int slab = 0; slab < nslab; ++slab) {
-      const char* hb = hbase + (slab & 1) * HALO;
-      const char* hb_next = hbase + ((slab + 1) & 1) * HALO;
-      const bool more_slabs = slab + 1 < nslab;
-      s2p_static_for<0, 2 * TS>([&](auto uc) {           // u = 2 * tap + half (compile time: register sets and taps are static)
-        constexpr int u = decltype(uc)::value;
-        // (1) DMA of half-step hs + 3
-        constexpr int u3 = u + 3;
-        bool issued = false, halo_issued = false;
-        if constexpr (u3 < 2 * TS) {
-          issue_wh(hs + 3, wtv[u3 >> 1], slab * BK + (u3 & 1) * 32); issued = true;
-        } else {
-          if (more_slabs) { issue_wh(hs + 3, wtv[(u3 - 2 * TS) >> 1], (slab + 1) * BK + ((u3 - 2 * TS) & 1) * 32); issued = true; }
-        }
-        if constexpr (u == 0) {
-          if (more_slabs) { issue_halo_p((slab + 1) & 1, (slab + 1) * BK); halo_issued = true; }
-        }
-        // (2) fragments of half-step hs + 1 into the other register set
-        if constexpr (u + 1 < 2 * TS) {
-          read_frags(std::integral_constant<int, (u + 1) & 1>{}, hs + 1, std::integral_constant<int, (u + 1) / 2>{},
-                     std::integral_constant<int, (u + 1) & 1>{}, hb);
-        } else {
-          if (more_slabs)
-            read_frags(std::integral_constant<int, 0>{}, hs + 1, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, hb_next);
-        }
-        // (3) the MFMAs of half-step hs from the current register set
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-          for (int i = 0; i < TCO; ++i)
-#pragma unroll
-            for (int j = 0; j < TPIX; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FA[u & 1][s2][i], FB[u & 1][s2][j], acc[i][j], 0, 0, 0);
-        // (4) half-stage hs + 2 must have landed for every wave before the next step reads it
-        if (issued) { if (halo_issued) S2P_WAIT_VMCNT(2 + NHPc); else S2P_WAIT_VMCNT(2); }
-        else S2P_WAIT_VMCNT(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        ++hs;
-      });
-    }
-    if (S2P_DIAGV(a) == 8) {
-      const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-      if (tid == 0 && g == 0) {
-        unsigned long long* o = (unsigned long long*)a.y + (size_t)blockIdx.x * 2;
-        o[0] = c1 - st_c0; o[1] = r1 - st_r0;
-      }
-      if (acc[0][0][0] == 12345.678f) ((float*)a.y)[7] = acc[1][1][3] + acc[0][1][2] + acc[1][0][1];
-      return;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (S2P_DIAGV(a) == 4) { if (acc[0][0][0] == 12345.678f) ((float*)a.y)[0] = acc[1][1][3] + acc[0][1][2] + acc[1][0][1]; return; }
-    if (S2P_DIAGV(a) == 9) {
-      tl2 = __builtin_amdgcn_s_memrealtime();
-      GatherArgs b = a; b.aux = nullptr;
-      conv_epilogue<T, BCO, BPIX, TCO, TPIX>(b, acc, smem, rowoff, g, co_base, wco0, wpix0, r, h, tid);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0 && g == 0 && a.aux) {
-        unsigned long long* o = (unsigned long long*)a.aux + (size_t)blockIdx.x * 4;
-        o[0] = tl0; o[1] = tl1; o[2] = tl2; o[3] = __builtin_amdgcn_s_memrealtime();
-      }
-      return;
-    }
-    conv_epilogue<T, BCO, BPIX, TCO, TPIX>(a, acc, smem, rowoff, g, co_base, wco0, wpix0, r, h, tid);
-    return;
-  } else if constexpr (TS > 0) {
-    // Static-tap form (3x3): everything that depends only on (lane, tap) is computed ONCE -- the halo row a lane reads
-    // for tap t (or the zero row when the tap falls outside the image), with the row's XOR swizzle folded into the low
-    // bits, so a fragment address in the loop is  halo_base + (pk[t][j] ^ chunk_offset)  -- and the taps are unrolled:
-    // no tap decode, validity test, address select or kernarg load per K step (they cost ~470 of ~1500 cycles a step).
-    int pk[TS][TPIX];
-    int wtv[TS];
-#pragma unroll
-    for (int t = 0; t < TS; ++t) {
-      const int ti = a.tap[t];
-      wtv[t] = ti >> 16;
-      const int toff = (int)(signed char)(ti & 0xff) * a.Wi + (int)(signed char)((ti >> 8) & 0xff);
-#pragma unroll
-      for (int j = 0; j < TPIX; ++j) {
-        const int hp = wpix0 + 32 * j + r + a.halo_lo + toff;
-        const bool ok = (vmask[j] >> t) & 1ull;
-        pk[t][j] = ok ? hp * RS + ((hp >> 1) & 7) * 16 : NPOS_CAP * RS;
-      }
-    }
-    const int ch16[4] = {(0 + h) * 16, (2 + h) * 16, (4 + h) * 16, (6 + h) * 16};
-    issue_halo(0, 0);
-    issue_w(0, wtv[0] << 16, 0);
-    __syncthreads();
-    if (S2P_DIAGV(a) == 3) return;
-    unsigned long long st_c0 = 0, st_r0 = 0;
-    if (S2P_DIAGV(a) == 8) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
-    int kt = 0;
-    for (int slab = 0; slab < nslab; ++slab) {
-      const char* hb = hbase + (DBUF ? (slab & 1) * HALO : 0);
-      const bool more_slabs = slab + 1 < nslab;
-#pragma unroll
-      for (int t = 0; t < TS; ++t, ++kt) {
-        if (S2P_DIAGV(a) != 1) {
-          if (t + 1 < TS) issue_w((kt + 1) & 1, wtv[t + 1] << 16, slab * BK);
-          else if (more_slabs) issue_w((kt + 1) & 1, wtv[0] << 16, (slab + 1) * BK);
-          if (DBUF && t == 0 && more_slabs) issue_halo((slab + 1) & 1, (slab + 1) * BK);
-        }
-        const char* wrow = wbase + (kt & 1) * WSTAGE + (wco0 + r) * RS;
-        if (S2P_DIAGV(a) != 2) {
-          bf16x8 af[4][TCO], bf[4][TPIX];
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) {
-#pragma unroll
-            for (int i = 0; i < TCO; ++i) af[s4][i] = *(const bf16x8*)(wrow + i * 32 * RS + (((2 * s4 + h) ^ swr) * 16));
-#pragma unroll
-            for (int j = 0; j < TPIX; ++j) bf[s4][j] = *(const bf16x8*)(hb + (pk[t][j] ^ ch16[s4]));
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-            for (int i = 0; i < TCO; ++i)
-#pragma unroll
-              for (int j = 0; j < TPIX; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s4][i], bf[s4][j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-      }
-      if (!DBUF && more_slabs) {                        // single halo buffer: reload it now that nobody reads it
-        issue_halo(0, (slab + 1) * BK);
-        __syncthreads();
-      }
-    }
-    if (S2P_DIAGV(a) == 8) {
-      const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-      if (tid == 0 && g == 0) {
-        unsigned long long* o = (unsigned long long*)a.y + (size_t)blockIdx.x * 2;
-        o[0] = c1 - st_c0; o[1] = r1 - st_r0;
-      }
-      if (acc[0][0][0] == 12345.678f) ((float*)a.y)[7] = acc[1][1][3] + acc[0][1][2] + acc[1][0][1];
-      return;
-    }
-    if (S2P_DIAGV(a) == 4) { if (acc[0][0][0] == 12345.678f) ((float*)a.y)[0] = acc[1][1][3] + acc[0][1][2] + acc[1][0][1]; return; }
-    conv_epilogue<T, BCO, BPIX, TCO, TPIX>(a, acc, smem, rowoff, g, co_base, wco0, wpix0, r, h, tid);
-    return;
+                                                 (int)(h_byte[i] == DMA_OOB ? DMA_OOB : h_byte[i] + (unsigned)(c0 * 2)), 0, 0, 0);
   }
+};
+
+// Static taps (3x3): everything that depends only on (lane, tap) is computed ONCE -- the halo row a lane reads for tap t (or the
+// zero row when the tap falls outside the image), with the row's XOR swizzle folded into the low bits, so a fragment address in the
+// loop is  halo_base + (pk[t][j] ^ ch16[sub-step])  -- and the taps are unrolled: no tap decode, validity test, address select or
+// kernarg load per K step (they cost ~470 of ~1500 cycles a step).
+template <int TS>
+struct HaloStaticTaps {
+  int pk[TS][2], wtv[TS], ch16[4];
+  template <int NPOS_CAP, bool DBUF>
+  __device__ __forceinline__ HaloStaticTaps(const GatherArgs& a, const HaloTile<NPOS_CAP, DBUF>& t) {
+    constexpr int RS = 128;
+#pragma unroll
+    for (int k = 0; k < TS; ++k) {
+      const int ti = a.tap[k];
+      wtv[k] = ti >> 16;
+      const int toff = (int)(signed char)(ti & 0xff) * a.Wi + (int)(signed char)((ti >> 8) & 0xff);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int hp = t.wpix0 + 32 * j + t.r + a.halo_lo + toff;
+        const bool ok = (t.vmask[j] >> k) & 1ull;
+        pk[k][j] = ok ? hp * RS + ((hp >> 1) & 7) * 16 : NPOS_CAP * RS;
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) ch16[s] = (2 * s + t.h) * 16;
+  }
+};
+
+// The loops return false when `loop_start` (called once the first stages are in LDS, before the first K step) asks to stop.
+// Software-pipelined static-tap form.  The weight stage is split into BK=32 HALF-stages (4 x 8 KiB in the same
+// 32 KiB as two full stages): the DMA of half-step h+3 is issued (inline asm, so the waits can be counted) while
+// half-step h computes, the fragments of half-step h+1 are read from LDS into a second register set under the MFMAs
+// of half-step h, and the only wait before the raw s_barrier is vmcnt(N) for the half-stage needed two steps later.
+template <int NPOS_CAP, int TS, typename LoopStart>
+__device__ __forceinline__ bool halo_loop_pipelined(const GatherArgs& a, const HaloTile<NPOS_CAP, true>& t, const HaloStaticTaps<TS>& tp, f32x16 (&acc)[2][2],
+                                                    LoopStart&& loop_start) {
+  typedef HaloTile<NPOS_CAP, true> HT;
+  constexpr int BCO = HT::BCO, BK = HT::BK, TCO = HT::TCO, TPIX = HT::TPIX, HALO = HT::HALO;
+  constexpr int WHALF = BCO * 64;                     // 8 KiB: 128 rows x 64 B, chunk' = chunk ^ ((row >> 2) & 3)
+  const int wave = t.wave, lane = t.lane, r = t.r, h = t.h, nslab = t.nslab;
+  const i32x4 wrs = s2p_make_rsrc((const __bf16*)a.w + (size_t)t.g * a.w_gstride, a.w_bytes);
+  const i32x4 xrs = s2p_make_rsrc((const __bf16*)a.x + (size_t)t.g * a.x_gstride, a.x_bytes - (unsigned)t.g * (unsigned)a.x_gstride * 2u);
+  const unsigned wb_lds = __builtin_amdgcn_readfirstlane(s2p_lds_addr(t.wbase));
+  const unsigned hb_lds = __builtin_amdgcn_readfirstlane(s2p_lds_addr(t.hbase));
+  // weight half-stage DMA: piece p = 16 rows x 64 B; wave w issues pieces w and w + 4
+  unsigned wv[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int row = 16 * (wave + 4 * q) + (lane >> 2), c = (lane & 3) ^ ((row >> 2) & 3), co = t.co_base + row;
+    wv[q] = co < a.Cout ? (unsigned)(co * a.w_row * 2 + c * 16) : DMA_OOB;
+  }
+  auto issue_wh = [&](int hs, int wt, int kofs) {
+    const unsigned dst = wb_lds + (unsigned)((hs & 3) * WHALF + wave * 1024);
+    const unsigned woff = (unsigned)((wt * a.Cin + kofs) * 2);
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+      s2p_dma16(wrs, dst + q * 4096, (int)(wv[q] == DMA_OOB ? DMA_OOB : wv[q] + woff));
+  };
+  // halo DMA: every wave issues exactly NHP pieces (the last ones repeat its last real piece), so vmcnt counts are fixed
+  constexpr int NHPc = HT::NHP;
+  const int last_piece = (t.npos + 7) / 8 - 1;
+  unsigned hv[NHPc]; int hpc[NHPc];
+#pragma unroll
+  for (int i = 0; i < NHPc; ++i) {
+    int pc8 = 4 * i + wave; if (pc8 > last_piece) pc8 = last_piece - ((last_piece - wave) & 3);   // this wave's last real piece
+    if (pc8 < 0) pc8 = wave <= last_piece ? wave : 0;
+    hpc[i] = pc8;
+    hv[i] = t.halo_dma_byte(a, pc8 * 8 + t.lrow);
+  }
+  auto issue_halo_p = [&](int hbuf, int c0) {
+    const unsigned dst = hb_lds + (unsigned)(hbuf * HALO);
+#pragma unroll
+    for (int i = 0; i < NHPc; ++i)
+      s2p_dma16(xrs, dst + (unsigned)(hpc[i] * 1024), (int)(hv[i] == DMA_OOB ? DMA_OOB : hv[i] + (unsigned)(c0 * 2)));
+  };
+  const int arow[TCO] = {(t.wco0 + r) * 64, (t.wco0 + 32 + r) * 64};
+  const int asw = (r >> 2) & 3;
+  bf16x8 FA[2][2][TCO], FB[2][2][TPIX];
+  auto read_frags = [&](auto bufc, int hs, auto tc, auto halfc, const char* hbp) {
+    constexpr int buf = decltype(bufc)::value, k = decltype(tc)::value, half = decltype(halfc)::value;
+    const char* wbp = t.wbase + (hs & 3) * WHALF;
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+#pragma unroll
+      for (int i = 0; i < TCO; ++i) FA[buf][s2][i] = *(const bf16x8*)(wbp + arow[i] + (((2 * s2 + h) ^ asw) * 16));
+#pragma unroll
+      for (int j = 0; j < TPIX; ++j) FB[buf][s2][j] = *(const bf16x8*)(hbp + (tp.pk[k][j] ^ tp.ch16[2 * half + s2]));
+    }
+  };
+  const int nhs = nslab * TS * 2;
+  issue_halo_p(0, 0);
+  issue_wh(0, tp.wtv[0], 0);
+  issue_wh(1, tp.wtv[0], 32);
+  if (nhs > 2) { issue_wh(2, tp.wtv[1], 0); S2P_WAIT_VMCNT(2); } else { S2P_WAIT_VMCNT(0); }
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  if (!loop_start()) return false;
+  read_frags(std::integral_constant<int, 0>{}, 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, t.hbase);
+  int hs = 0;
+  for (int slab = 0; slab < nslab; ++slab) {
+    const char* hb = t.hbase + (slab & 1) * HALO;
+    const char* hb_next = t.hbase + ((slab + 1) & 1) * HALO;
+    const bool more_slabs = slab + 1 < nslab;
+    s2p_static_for<0, 2 * TS>([&](auto uc) {           // u = 2 * tap + half (compile time: register sets and taps are static)
+      constexpr int u = decltype(uc)::value;
+      // (1) DMA of half-step hs + 3
+      constexpr int u3 = u + 3;
+      bool issued = false, halo_issued = false;
+      if constexpr (u3 < 2 * TS) {
+        issue_wh(hs + 3, tp.wtv[u3 >> 1], slab * BK + (u3 & 1) * 32); issued = true;
+      } else {
+        if (more_slabs) { issue_wh(hs + 3, tp.wtv[(u3 - 2 * TS) >> 1], (slab + 1) * BK + ((u3 - 2 * TS) & 1) * 32); issued = true; }
+      }
+      if constexpr (u == 0) {
+        if (more_slabs) { issue_halo_p((slab + 1) & 1, (slab + 1) * BK); halo_issued = true; }
+      }
+      // (2) fragments of half-step hs + 1 into the other register set
+      if constexpr (u + 1 < 2 * TS) {
+        read_frags(std::integral_constant<int, (u + 1) & 1>{}, hs + 1, std::integral_constant<int, (u + 1) / 2>{},
+                   std::integral_constant<int, (u + 1) & 1>{}, hb);
+      } else {
+        if (more_slabs)
+          read_frags(std::integral_constant<int, 0>{}, hs + 1, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, hb_next);
+      }
+      // (3) the MFMAs of half-step hs from the current register set
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) mfma_tile(acc, FA[u & 1][s2], FB[u & 1][s2]);
+      // (4) half-stage hs + 2 must have landed for every wave before the next step reads it
+      if (issued) { if (halo_issued) S2P_WAIT_VMCNT(2 + NHPc); else S2P_WAIT_VMCNT(2); }
+      else S2P_WAIT_VMCNT(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      ++hs;
+    });
+  }
+  return true;
+}
+
+// Static-tap form: one BK = 64 step per tap, two full weight stages
+template <int NPOS_CAP, bool DBUF, int TS, typename LoopStart>
+__device__ __forceinline__ bool halo_loop_static(const GatherArgs& a, const HaloTile<NPOS_CAP, DBUF>& t, const HaloStaticTaps<TS>& tp, f32x16 (&acc)[2][2],
+                                                 LoopStart&& loop_start) {
+  typedef HaloTile<NPOS_CAP, DBUF> HT;
+  constexpr int BK = HT::BK;
+  t.issue_halo(0, 0);
+  t.issue_w(a, 0, tp.wtv[0], 0);
+  __syncthreads();
+  if (!loop_start()) return false;
+  int kt = 0;
+  for (int slab = 0; slab < t.nslab; ++slab) {
+    const char* hb = t.hbase + (DBUF ? (slab & 1) * HT::HALO : 0);
+    const bool more_slabs = slab + 1 < t.nslab;
+#pragma unroll
+    for (int k = 0; k < TS; ++k, ++kt) {
+      if (S2P_DIAGV(a) != 1) {
+        if (k + 1 < TS) t.issue_w(a, (kt + 1) & 1, tp.wtv[k + 1], slab * BK);
+        else if (more_slabs) t.issue_w(a, (kt + 1) & 1, tp.wtv[0], (slab + 1) * BK);
+        if (DBUF && k == 0 && more_slabs) t.issue_halo((slab + 1) & 1, (slab + 1) * BK);
+      }
+      const char* wrow = t.wbase + (kt & 1) * HT::WSTAGE + (t.wco0 + t.r) * HT::RS;
+      if (S2P_DIAGV(a) != 2)
+        mma_step_swizzled(acc, wrow, t.swr, t.h, [&](int s, int j) { return hb + (tp.pk[k][j] ^ tp.ch16[s]); });
+      __syncthreads();
+    }
+    if (!DBUF && more_slabs) {                        // single halo buffer: reload it now that nobody reads it
+      t.issue_halo(0, (slab + 1) * BK);
+      __syncthreads();
+    }
+  }
+  return true;
+}
+
+// Run-time taps (any tap count up to MAX_TAPS): tap decode, validity select and halo row address per K step
+template <int NPOS_CAP, bool DBUF, typename LoopStart>
+__device__ __forceinline__ bool halo_loop_runtime(const GatherArgs& a, const HaloTile<NPOS_CAP, DBUF>& t, f32x16 (&acc)[2][2], LoopStart&& loop_start) {
+  typedef HaloTile<NPOS_CAP, DBUF> HT;
+  constexpr int BK = HT::BK, TPIX = HT::TPIX;
+  const int nk = t.nslab * a.T;
   // tap words travel one step ahead of their use (a kernarg scalar load waited for on the spot stalls every step)
   int tw_cur = a.tap[0];
   int tw_next = a.tap[a.T > 1 ? 1 : 0];
-  issue_halo(0, 0);
-  issue_w(0, tw_cur, 0);
+  t.issue_halo(0, 0);
+  t.issue_w(a, 0, tw_cur >> 16, 0);
   __syncthreads();                                     // hipcc drains vmcnt before the barrier
-  if (S2P_DIAGV(a) == 3) return;                              // timing ablation: prologue only
+  if (!loop_start()) return false;
   int slab = 0, tap = 0;
-  // S2P_DIAG=8 (diagnostic build of the launch, output invalid): stamp shader clock and 100 MHz wall clock around the
-  // main loop; the host tool derives the in-kernel clock and cycles per K step (diagnostics build)
-  unsigned long long st_c0 = 0, st_r0 = 0;
-  if (S2P_DIAGV(a) == 8) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
   for (int kt = 0; kt < nk; ++kt) {
     const int c0 = slab * BK;
     int ntap = tap + 1, nslab_i = slab;
     if (ntap == a.T) { ntap = 0; ++nslab_i; }
-    int n2tap = ntap + 1;
-    if (n2tap == a.T) n2tap = 0;
+    const int n2tap = ntap + 1 == a.T ? 0 : ntap + 1;
     const int tw_next2 = a.tap[n2tap];
-    if (kt + 1 < nk && S2P_DIAGV(a) != 1) issue_w((kt + 1) & 1, tw_next, nslab_i * BK);
-    if (DBUF && tap == 0 && slab + 1 < nslab && S2P_DIAGV(a) != 1) issue_halo((slab + 1) & 1, c0 + BK);
-    const char* hb = hbase + (DBUF ? (slab & 1) * HALO : 0);
+    if (kt + 1 < nk && S2P_DIAGV(a) != 1) t.issue_w(a, (kt + 1) & 1, tw_next >> 16, nslab_i * BK);
+    if (DBUF && tap == 0 && slab + 1 < t.nslab && S2P_DIAGV(a) != 1) t.issue_halo((slab + 1) & 1, c0 + BK);
+    const char* hb = t.hbase + (DBUF ? (slab & 1) * HT::HALO : 0);
     const int ti = tw_cur;
     const int toff = (int)(signed char)(ti & 0xff) * a.Wi + (int)(signed char)((ti >> 8) & 0xff);
-    const char* wrow = wbase + (kt & 1) * WSTAGE + (wco0 + r) * RS;
+    const char* wrow = t.wbase + (kt & 1) * HT::WSTAGE + (t.wco0 + t.r) * HT::RS;
     const char* prow[TPIX];
     int psw[TPIX];
 #pragma unroll
     for (int j = 0; j < TPIX; ++j) {
-      const int hp = wpix0 + 32 * j + r + a.halo_lo + toff;
-      const bool ok = (vmask[j] >> tap) & 1ull;
-      prow[j] = ok ? hb + hp * RS : zrow;
+      const int hp = t.wpix0 + 32 * j + t.r + a.halo_lo + toff;
+      const bool ok = (t.vmask[j] >> tap) & 1ull;
+      prow[j] = ok ? hb + hp * HT::RS : t.zrow;
       psw[j] = ok ? (hp >> 1) & 7 : 0;
     }
-    if (S2P_DIAGV(a) != 2) {
-      // all 16 fragment reads of the step are issued before its first MFMA (the waits become counted lgkmcnt(N)):
-      // reading per sub-step exposes the LDS latency four times per step
-      bf16x8 af[4][TCO], bf[4][TPIX];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-#pragma unroll
-        for (int i = 0; i < TCO; ++i) af[s][i] = *(const bf16x8*)(wrow + i * 32 * RS + (((2 * s + h) ^ swr) * 16));
-#pragma unroll
-        for (int j = 0; j < TPIX; ++j) bf[s][j] = *(const bf16x8*)(prow[j] + (((2 * s + h) ^ psw[j]) * 16));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int i = 0; i < TCO; ++i)
-#pragma unroll
-          for (int j = 0; j < TPIX; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][i], bf[s][j], acc[i][j], 0, 0, 0);
-    }
+    if (S2P_DIAGV(a) != 2)
+      mma_step_swizzled(acc, wrow, t.swr, t.h, [&](int s, int j) { return prow[j] + (((2 * s + t.h) ^ psw[j]) * 16); });
     __syncthreads();
     tap = ntap;
     tw_cur = tw_next; tw_next = tw_next2;
     if (nslab_i != slab) {
       slab = nslab_i;
-      if (!DBUF && slab < nslab) {                     // single halo buffer: reload it now that nobody reads it
-        issue_halo(0, slab * BK);
+      if (!DBUF && slab < t.nslab) {                   // single halo buffer: reload it now that nobody reads it
+        t.issue_halo(0, slab * BK);
         __syncthreads();
       }
     }
   }
-  (void)nk;
+  return true;
+}
+
+// Diagnostics build (S2P_DIAG, output invalid unless noted): 5 = index set-up only; 3 = up to the first stages in LDS; 4 = no epilogue;
+// 8 = stamp shader clock and 100 MHz wall clock around the K loop into y (the host tool derives the in-kernel clock and cycles per K
+// step); 9 (pipelined form; the launch runs normally, epi must be STORE) = stamp s_memrealtime at entry / loop start / loop end /
+// after the epilogue into `aux`, a debug buffer of its own: 4 x u64 per workgroup.  1 / 2 (in the loops) = skip in-loop loads / MFMAs.
+template <int NPOS_CAP, bool DBUF, int TS = 0, bool PIPE = false>   // TS: static tap count (9 = 3x3, taps unrolled) or 0 = run-time taps
+__global__ __launch_bounds__(256, 2) void conv_halo_kernel(const GatherArgs a) {
+  typedef HaloTile<NPOS_CAP, DBUF> HT;
+  constexpr bool PIPELINED = TS > 0 && PIPE && DBUF;
+  __shared__ __attribute__((aligned(1024))) char smem[HT::MAIN + HT::BPIX * 4];
+  unsigned long long tl0 = 0, tl1 = 0, tl2 = 0, st_c0 = 0, st_r0 = 0;
+  if (S2P_DIAGV(a) == 9) tl0 = __builtin_amdgcn_s_memrealtime();
+  HT t;
+  t.setup(a, smem);
+  f32x16 acc[HT::TCO][HT::TPIX];
+  clear_acc(acc);
+  if (S2P_DIAGV(a) == 5) return;
+  auto loop_start = [&]() {
+    if (S2P_DIAGV(a) == 3) return false;
+    if (S2P_DIAGV(a) == 8) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
+    if (PIPELINED && S2P_DIAGV(a) == 9) tl1 = __builtin_amdgcn_s_memrealtime();
+    return true;
+  };
+  bool done;
+  if constexpr (TS > 0) {
+    const HaloStaticTaps<TS> tp(a, t);
+    if constexpr (PIPELINED) done = halo_loop_pipelined(a, t, tp, acc, loop_start);
+    else done = halo_loop_static(a, t, tp, acc, loop_start);
+  } else {
+    done = halo_loop_runtime(a, t, acc, loop_start);
+  }
+  if (!done) return;
   if (S2P_DIAGV(a) == 8) {
     const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0 && g == 0) {
+    if (t.tid == 0 && t.g == 0) {
       unsigned long long* o = (unsigned long long*)a.y + (size_t)blockIdx.x * 2;
       o[0] = c1 - st_c0; o[1] = r1 - st_r0;
     }
     if (acc[0][0][0] == 12345.678f) ((float*)a.y)[7] = acc[1][1][3] + acc[0][1][2] + acc[1][0][1];
     return;
   }
+  if constexpr (PIPELINED) {                           // the raw s_barrier of the last half-step does not cover the fragment reads
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
   if (S2P_DIAGV(a) == 4) { if (acc[0][0][0] == 12345.678f) ((float*)a.y)[0] = acc[1][1][3] + acc[0][1][2] + acc[1][0][1]; return; }
-  conv_epilogue<T, BCO, BPIX, TCO, TPIX>(a, acc, smem, rowoff, g, co_base, wco0, wpix0, r, h, tid);
+  if (PIPELINED && S2P_DIAGV(a) == 9) {
+    tl2 = __builtin_amdgcn_s_memrealtime();
+    GatherArgs b = a; b.aux = nullptr;
+    conv_epilogue<__bf16, HT::BCO, HT::BPIX, HT::TCO, HT::TPIX>(b, acc, smem, t.rowoff, t.g, t.co_base, t.wco0, t.wpix0, t.r, t.h, t.tid);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t.tid == 0 && t.g == 0 && a.aux) {
+      unsigned long long* o = (unsigned long long*)a.aux + (size_t)blockIdx.x * 4;
+      o[0] = tl0; o[1] = tl1; o[2] = tl2; o[3] = __builtin_amdgcn_s_memrealtime();
+    }
+    return;
+  }
+  conv_epilogue<__bf16, HT::BCO, HT::BPIX, HT::TCO, HT::TPIX>(a, acc, smem, t.rowoff, t.g, t.co_base, t.wco0, t.wpix0, t.r, t.h, t.tid);
 }
 
 // ================================================================================================
@@ -1287,7 +1080,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const GatherArgs a) {
 // the caller wants and the scratch it offers, and write a ConvPlan: the path of every launch, whether the norm rides in the
 // epilogue, the scratch bytes used.  Planning dereferences no tensor pointer and launches nothing.  The real call launches that plan;
 // the workspace queries return its ws_bytes; s2p_conv2d_mat_is_fused returns its `fused`.  DESIGN.md section 3.1 lists the order.
-enum class ConvPath { Thin, Thin4, ThinCin, ThinRows, Plane, PlaneG, Halo, SplitK, Dma, Fast, Phases, Generic };
+enum class ConvPath { Thin, Thin4, ThinCin, ThinRows, Plane, PlaneG, Halo, SplitK, Dma, Phases, Generic };      // ids: S2P_CONV_PATH_* (s2p_conv2d_path)
+static_assert((int)ConvPath::Halo == S2P_CONV_PATH_HALO && (int)ConvPath::Generic == S2P_CONV_PATH_GENERIC, "ids of s2p_conv2d_path");
 enum class HaloKind { S9_176_PIPE, S9_176, S9_320, R_176, R_320 };      // static 3x3 taps / run-time taps, positions held, pipelined
 
 struct ConvOperands {       // tensors and epilogue of one call (all NULL / zero in the queries)
@@ -1351,10 +1145,10 @@ static void plan_fast(GatherArgs& a, GatherChoice& c, int groups, const NormWant
   // kernel runs it, so the K loop is spread over the idle CUs instead -- this takes precedence over the halo-resident kernel
   // (but not over the plane-resident ones).
   int S = 1;
-  if (!sw.no_dma && !sw.no_split && groups == 1 && whole && sc.any) S = conv_split_plan(nwg, a.Ktot / 64);
+  if (!sw.no_split && groups == 1 && whole && sc.any) S = conv_split_plan(nwg, a.Ktot / 64);
   // small planes (21x21 ResBlk / VGG conv3 / gamma-beta layers and their dgrads): one workgroup per (image, 64-channel slab),
   // the whole padded plane resident in LDS (conv_plane.hip)
-  if (!sw.no_plane && !sw.no_dma && a.T == 9 && a.istride == 1 && planes && a.Qh == a.Hi && a.Qw == a.Wi) {
+  if (!sw.no_plane && a.T == 9 && a.istride == 1 && planes && a.Qh == a.Hi && a.Qw == a.Wi) {
     PlaneArgs& p = c.plane;
     bool ok = true;
     for (int t = 0; t < 9; ++t) p.wt[t] = -1;
@@ -1373,7 +1167,7 @@ static void plan_fast(GatherArgs& a, GatherChoice& c, int groups, const NormWant
   }
   // other small planes -- the PatchGAN 4x4 layers and their stride-1 dgrads (with the InstanceNorm that follows (forward) / precedes
   // (backward) the conv in the epilogue), VGG conv4_x on 10x10 maps: the generalised plane-resident kernel (conv_planeg.hip)
-  if (!sw.no_plane && !sw.no_planeg() && !(a.T == 9 && sw.no_planeg_3x3()) && !sw.no_dma && groups == 1 && planes && !a.reflect) {
+  if (!sw.no_plane && !sw.no_planeg() && !(a.T == 9 && sw.no_planeg_3x3()) && groups == 1 && planes && !a.reflect) {
     PlaneGProblem pr{a.M / (a.Qh * a.Qw), a.Hi, a.Wi, a.Ho, a.Wo, a.Cin, a.Cout, a.Cst, a.x_pitch, a.y_pitch, a.istride, a.T, a.tap, want.any};
     PlaneGArgs& p = c.planeg;
     if (s2p_conv_planeg_setup(pr, p)) {
@@ -1385,7 +1179,7 @@ static void plan_fast(GatherArgs& a, GatherChoice& c, int groups, const NormWant
     }
   }
   // stride-1 "same" convs with the 128-row weight tile that are not K-split: the pixel tile and its halo resident in LDS
-  if (c.bco == 128 && S <= 1 && !sw.no_dma && !sw.no_halo && a.istride == 1 && a.ostride == 1 && a.Qh == a.Hi && a.Qw == a.Wi &&
+  if (c.bco == 128 && S <= 1 && !sw.no_halo && a.istride == 1 && a.ostride == 1 && a.Qh == a.Hi && a.Qw == a.Wi &&
       a.Ho == a.Qh && a.Wo == a.Qw && a.T >= 4) {
     int lo = 0, hi = 0;
     for (int t = 0; t < a.T; ++t) {
@@ -1411,7 +1205,7 @@ static void plan_fast(GatherArgs& a, GatherChoice& c, int groups, const NormWant
     if (a.psplit > 1 && need <= sc.bytes) { c.path = ConvPath::SplitK; c.ws_bytes = need; return; }
     a.psplit = 1;                                        // the caller's buffer is too small: unsplit
   }
-  c.path = sw.no_dma ? ConvPath::Fast : ConvPath::Dma;
+  c.path = ConvPath::Dma;
 }
 
 // one gather-form problem: `a` holds operands, geometry and taps
@@ -1419,7 +1213,7 @@ static GatherItem plan_gather(const GatherArgs& a_in, bool bf16, int groups, lon
   GatherItem it{a_in, {}};
   GatherArgs& a = it.a;
   const long long xb = x_elems * 2, wb = (long long)a.Cout * a.w_row * 2;
-  if (bf16 && a.Cin % 64 == 0 && !a.reflect && a.T > 0 && xb < (1ll << 31) && wb < (1ll << 31) && a.Cst > 32) {
+  if (bf16 && a.Cin % 64 == 0 && !a.reflect && a.T > 0 && xb < (1ll << 31) && wb < (1ll << 31) && a.Cst > 32 && !conv_switches().no_dma) {
     a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
     it.c.bco = a.Cst > 64 ? 128 : 64;
     plan_fast(a, it.c, groups, want, sc);
@@ -1628,10 +1422,6 @@ static int launch_bf16(GatherArgs& a, const GatherChoice& c, int groups, void* w
       S2P_CHECK_LAUNCH("conv_part_reduce_kernel");
       return 0;
     }
-    case ConvPath::Fast:
-      hipLaunchKernelGGL((conv_fast_kernel<BCO, 128, 2, 2>), grid, dim3(256), 0, st, a);
-      S2P_CHECK_LAUNCH("conv_fast_kernel");
-      return 0;
     default:
       hipLaunchKernelGGL((conv_dma_kernel<BCO, 128, 2, 2>), grid, dim3(256), 0, st, a);
       S2P_CHECK_LAUNCH("conv_dma_kernel");
@@ -1797,6 +1587,15 @@ extern "C" int s2p_conv2d_mat_is_fused(const s2p_conv_desc* d, int dgrad, int ha
   ConvPlan P;
   const int rc = dgrad ? conv_plan_dgrad(d, op, want, SCRATCH_UNLIMITED, P) : conv_plan_fwd(d, op, want, SCRATCH_UNLIMITED, P);
   return rc == 0 && P.fused ? 1 : 0;
+}
+extern "C" int s2p_conv2d_path(const s2p_conv_desc* d, int dgrad, int has_workspace) {
+  if (!d) return -1;
+  const ConvOperands op{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, S2P_ACT_NONE, 0.f, S2P_EPI_STORE, S2P_ACT_NONE, 0.f};
+  const ScratchAvail sc = has_workspace ? SCRATCH_UNLIMITED : ScratchAvail{false, 0};
+  ConvPlan P;
+  if (dgrad ? conv_plan_dgrad(d, op, NormWant{}, sc, P) : conv_plan_fwd(d, op, NormWant{}, sc, P)) return -1;
+  const int path = (int)P.path;
+  return P.path == ConvPath::Halo ? path | ((int)P.items[0].c.halo << 8) : path;
 }
 extern "C" size_t s2p_conv2d_dgrad_workspace(const s2p_conv_desc* d) {
   ConvPlan P;

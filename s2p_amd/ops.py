@@ -117,6 +117,15 @@ def conv_fwd(geom, x, w_fwd, bias, cin_pad, y_pitch=None, act=ACT_NONE, slope=0.
     return y
 
 
+def conv_path(geom, dtype, x_shape, cin_pad, dgrad=False, workspace=True):
+    """The dispatcher's path (_lib.PATH_*; _lib.halo_path(kind) for the halo-resident kernel) of conv_fwd / conv_dgrad on an input of
+    `x_shape` = (N, H, W, x_pitch): a dry run on the host, nothing is launched.  workspace=False: as called without a scratch."""
+    N, H, W, xp = x_shape
+    ce = chunk_elems(dtype)
+    d = geom.desc(dtype, N, H, W, cin_pad, xp, pad_to(geom.cout * geom.groups if geom.groups > 1 else geom.cout, ce))
+    return int(lib().s2p_conv2d_path(ctypes.byref(d), int(dgrad), int(workspace)))
+
+
 def conv_fwd_mat(geom, x, w_fwd, bias, cin_pad, gb, gb_off, gb_st, st_off, act=ACT_LRELU, slope=0.2, aux=None, epi=EPI_STORE,
                  want_y=True):
     """conv (+ bias, + residual aux) followed by InstanceNorm + MAT modulation + activation of its output, one launch where

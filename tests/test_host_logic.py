@@ -101,6 +101,44 @@ def test_fused_norm_dispatch_is_host_logic():
         assert fused(*a) == 0, a
 
 
+def test_conv_path_query_is_host_logic():
+    """`s2p_conv2d_path` is a dry run of the conv dispatcher as well: it names the kernel family of a problem's first launch (and the
+    variant of the halo-resident kernel) without a GPU, with and without the caller's scratch.  tests/test_kernels_gpu.py asserts
+    through it that its conv cases reach the kernels their comments name."""
+    import ctypes
+    from s2p_amd import ops
+    L = _lib.lib()
+    H = _lib.halo_path
+
+    def path(cin, cout, k, s, p, N, H_, W, dgrad=0, ws=1, dtype=torch.bfloat16, tr=False, refl=False):
+        g = ops.ConvGeom(cin, cout, k, s, p, transposed=tr, reflect=refl, output_padding=1 if tr else 0)
+        cp = ops.pad_to(cin, _lib.chunk_elems(dtype))
+        assert ops.conv_path(g, dtype, (N, H_, W, cp), cp, dgrad=bool(dgrad), workspace=bool(ws)) == \
+            L.s2p_conv2d_path(ctypes.byref(g.desc(dtype, N, H_, W, cp, cp, ops.pad_to(cout, _lib.chunk_elems(dtype)))), dgrad, ws)
+        return ops.conv_path(g, dtype, (N, H_, W, cp), cp, dgrad=bool(dgrad), workspace=bool(ws))
+
+    assert path(64, 72, 3, 1, 1, 3, 9, 11) == H(_lib.HALO_S9_176_PIPE)
+    assert path(192, 72, 3, 1, 1, 2, 6, 40) == H(_lib.HALO_S9_320)
+    assert path(64, 72, 5, 1, 2, 2, 8, 10) == H(_lib.HALO_R_176)
+    assert path(64, 160, 5, 1, 2, 2, 17, 23) == H(_lib.HALO_R_320)
+    assert path(72, 128, 3, 1, 1, 3, 9, 11) == _lib.PATH_GENERIC                     # Cin % 64 != 0
+    assert path(72, 128, 3, 1, 1, 3, 9, 11, dgrad=1) == H(_lib.HALO_S9_176_PIPE)      # the dgrad contracts Cout
+    assert path(64, 72, 3, 1, 1, 3, 9, 11, dtype=torch.float32) == _lib.PATH_GENERIC
+    assert path(256, 256, 3, 1, 1, 64, 21, 21) == _lib.PATH_PLANE                    # the train step's ResBlk conv
+    assert path(256, 512, 4, 1, 2, 64, 12, 12) == _lib.PATH_PLANEG
+    assert path(64, 128, 3, 2, 1, 2, 20, 20) == _lib.PATH_DMA
+    assert path(64, 128, 3, 2, 1, 2, 20, 20, dgrad=1) == _lib.PATH_PHASES
+    assert path(256, 128, 3, 2, 1, 2, 5, 5, tr=True) == _lib.PATH_PHASES
+    assert path(3, 64, 7, 1, 3, 2, 20, 20, refl=True) == _lib.PATH_THIN4
+    assert path(3, 64, 7, 1, 3, 2, 20, 20, refl=True, ws=0) != _lib.PATH_THIN4       # needs the caller's scratch
+    # 50 K steps on 3 workgroups: K-split where the caller offers scratch, the halo-resident kernel (two slabs of run-time taps) without
+    assert path(128, 72, 5, 1, 2, 2, 8, 10) == _lib.PATH_SPLITK
+    assert path(128, 72, 5, 1, 2, 2, 8, 10, ws=0) == H(_lib.HALO_R_176)
+    assert L.s2p_conv2d_path(None, 0, 1) == -1
+    bad = ops.ConvGeom(64, 72, 3, 1, 1).desc(torch.bfloat16, 2, 8, 8, 60, 60, 72)      # Cin not a multiple of the chunk
+    assert L.s2p_conv2d_path(ctypes.byref(bad), 0, 1) == -1
+
+
 def _step_conv_descs():
     """(name, ConvDesc) of every conv launch geometry of the bs-64 84x84 bf16 train step (generator, both discriminator scales, VGG19)
     and of the generator forward of the bs-16 256x256 rollout.  The layers come from the networks' own constructors (`lay`); only the

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from s2p_amd import ops  # noqa: E402
+from s2p_amd import _lib
 from s2p_amd._lib import lib, ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EPI_ADD, EPI_MUL_ACTGRAD, EPI_STORE, chunk_elems
 
 
@@ -59,8 +60,15 @@ CONV_CASES = [
     (512, 1, 4, 1, 2, False, False, 6, 5, 3),      # PatchGAN head at the real width (x-stationary Cout=1 wgrad, 64 chunks)
     (512, 1, 4, 1, 2, False, False, 13, 13, 4),    # ... at the real map size: the MFMA forward's 11 pixel tiles per image (the last one partial)
     (40, 72, 1, 1, 0, False, False, 1, 1, 64),     # linear layer as 1x1 conv (non power-of-two channels)
-    (128, 192, 3, 1, 1, False, False, 21, 21, 3),  # halo-resident fast path: 2 channel slabs, tiles spanning rows and images
-    (64, 160, 5, 1, 2, False, False, 17, 23, 2),   # halo-resident path, 5x5 taps, ragged Cout tile
+    (128, 192, 3, 1, 1, False, False, 21, 21, 3),  # plane-resident kernel (441-pixel plane, Cout % 64 == 0): 2 input slabs, 3 co slabs
+    (64, 160, 5, 1, 2, False, False, 17, 23, 2),   # halo-resident kernel, 25 run-time taps, 320 positions, ragged Cout tile
+    # the other forms of the halo-resident kernel (CONV_PATHS names them).  Cout % 64 != 0: neither plane kernel; < 32 K steps: no K split
+    (64, 72, 3, 1, 1, False, False, 9, 11, 3),     # pipelined 3x3: one slab; M = 297: 3 tiles, the last partial, tiles cross rows and images; 72 of 128 weight rows
+    (192, 72, 3, 1, 1, False, False, 9, 11, 3),    # ... three slabs: the next slab's halo prefetch, the `more_slabs` branches of the counted waits
+    (192, 72, 3, 1, 1, False, False, 6, 40, 2),    # static 3x3, window of 210 positions: the single halo buffer reloaded at each slab boundary
+    (72, 128, 3, 1, 1, False, False, 9, 11, 3),    # the DGRAD is the pipelined form: flipped taps of the transposed pack, two slabs (Cout padded to 128)
+    (64, 72, 5, 1, 2, False, False, 8, 10, 2),     # 25 run-time taps, window of 172 positions (two halo buffers)
+    (128, 64, 3, 2, 1, False, False, 13, 21, 3),   # LDS-DMA kernel on the 64-row weight tile (forward, 2 pixel tiles); dgrad: merged phases, 128 rows
     (64, 3, 7, 1, 3, False, True, 40, 36, 2),      # out conv at a size that takes the spatially tiled MFMA path (ragged tiles)
     (32, 2, 5, 1, 2, False, False, 33, 37, 1),     # tiled path, zero padding, Cout=2, K=5
     (64, 3, 7, 1, 3, False, True, 84, 84, 2),      # out conv, row-streaming path: 3 waves, several row bands
@@ -81,6 +89,24 @@ CONV_CASES = [
     (128, 128, 3, 1, 1, False, False, 30, 37, 8),  # bands on a ragged plane (11 rows per band), N * bands % 8 == 0: XCD-aware order
     (64, 128, 3, 1, 1, False, False, 19, 21, 131), # ... one pair per image, N % 8 != 0
 ]
+
+# case -> (forward, dgrad) path the bf16 call must plan (s2p_conv2d_path; None: not pinned), so that a case keeps reaching the kernel
+# its comment names.  fp32 always takes the generic kernel.
+_H = _lib.halo_path
+CONV_PATHS = {
+    (128, 192, 3, 1, 1, False, False, 21, 21, 3): (_lib.PATH_PLANE, _lib.PATH_PLANE),
+    (64, 160, 5, 1, 2, False, False, 17, 23, 2): (_H(_lib.HALO_R_320), None),
+    (64, 72, 3, 1, 1, False, False, 9, 11, 3): (_H(_lib.HALO_S9_176_PIPE), None),
+    (192, 72, 3, 1, 1, False, False, 9, 11, 3): (_H(_lib.HALO_S9_176_PIPE), None),
+    (192, 72, 3, 1, 1, False, False, 6, 40, 2): (_H(_lib.HALO_S9_320), None),
+    (72, 128, 3, 1, 1, False, False, 9, 11, 3): (_lib.PATH_GENERIC, _H(_lib.HALO_S9_176_PIPE)),
+    (64, 72, 5, 1, 2, False, False, 8, 10, 2): (_H(_lib.HALO_R_176), None),
+    (128, 64, 3, 2, 1, False, False, 13, 21, 3): (_lib.PATH_DMA, _lib.PATH_PHASES),       # Cst = 64: the 64-row tile
+    (64, 128, 3, 2, 1, False, False, 20, 20, 2): (_lib.PATH_DMA, _lib.PATH_PHASES),       # 128-row tile; phases on the 64-row tile (phase-fastest grid)
+    (256, 128, 3, 2, 1, True, False, 5, 5, 2): (_lib.PATH_PHASES, _lib.PATH_DMA),
+    (128, 256, 3, 1, 1, False, False, 9, 7, 3): (_H(_lib.HALO_S9_176_PIPE), _lib.PATH_SPLITK),
+}
+assert set(CONV_PATHS) <= set(CONV_CASES)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -114,6 +140,10 @@ def test_conv_fwd_dgrad_wgrad(hip_device, dtype, case):
     wf = pack_fwd(w_std, cin_pad, dtype, dev)
     wb = pack_bwd(w_std, cin_pad, cout_pad, dtype, dev)
     xd = nhwc(x, cin_pad, dtype, dev)
+    for dgrad, want in enumerate(CONV_PATHS.get(case, (None, None))):
+        want = _lib.PATH_GENERIC if dtype == torch.float32 and want is not None else want
+        if want is not None:
+            assert ops.conv_path(geom, dtype, tuple(xd.shape), cin_pad, dgrad=bool(dgrad)) == want, ("dgrad" if dgrad else "forward")
     y = ops.conv_fwd(geom, xd, wf, b.to(dev), cin_pad)
     torch.cuda.synchronize()
     assert rel_err(nchw(y, cout), y_ref.detach()) < TOL[dtype]
