@@ -355,6 +355,18 @@ int s2p_nhwc_to_nchw(int dtype, const void* x, int x_pitch, int c_off, int N, in
  * (u8 = clamp(round((v+1)*127.5))); the round trip is exact on all 256 values.          */
 int s2p_u8_to_nhwc(int dtype, const void* x, int64_t pixels, int C, void* y, int y_pitch, void* stream);
 int s2p_nhwc_to_u8(int dtype, const void* x, int x_pitch, int64_t pixels, int C, void* y, void* stream);
+/* SLAC sequence replay buffer (SPEC.md N3c): gather the frames of B sampled windows out of a uint8 frame pool.
+ *   pool   uint8 [n_slots][frame_pixels * C]   NHWC frames, each stored once
+ *   table  int32 [n_windows][T]                frame slots of every window
+ *   win    int64 [B]                           window ids (the caller checks them against n_windows)
+ *   x      dtype [B*T][frame_pixels][x_pitch]  from_f32((float)u8 / 255.0f) (true division); channels C..x_pitch are zero.  Nullable.
+ *   u8_out uint8 [B*T][frame_pixels * C]       the gathered frames unchanged.  Nullable (not both).
+ * Every source byte is read once for both outputs; all byte offsets are 64-bit.  A slot < 0 or >= n_slots reads as an all-zero
+ * frame and is never dereferenced.  Any frame_pixels >= 1, 1 <= C <= x_pitch and any alignment of the pool are accepted; C == 3 with
+ * frame_pixels % 4 == 0 (4-byte aligned pool / u8_out, x_pitch a whole number of 16-byte chunks) moves 4 pixels per thread step
+ * with dword loads and 16-byte stores.  x must be 16-byte aligned.  B * T == 0 is a successful no-op.                  */
+int s2p_window_gather_u8(int dtype, const void* pool, int64_t n_slots, int64_t frame_pixels, int C, const int32_t* table, int T,
+                         const int64_t* win, int B, void* x, int x_pitch, void* u8_out, void* stream);
 /* generic cast copy between dtypes (n elements)                                         */
 int s2p_cast(int src_dtype, const void* src, int dst_dtype, void* dst, int64_t n, void* stream);
 

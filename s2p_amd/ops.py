@@ -569,6 +569,24 @@ def nhwc_to_u8(x, C, out=None):
     return y
 
 
+def window_gather_u8(pool, table, win, dtype, pitch=None, want_x=True, want_u8=True):
+    """Frames of the windows `win` (int64 [B], ids into `table` int32 [n_windows,T]) out of the uint8 frame pool
+    [n_slots,H,W,C] (csrc/replay.hip): returns (x, u8) with x [B*T,H,W,pitch] = u8 / 255 in `dtype` (pad channels zero) and
+    u8 [B,T,H,W,C]; a form not wanted is None.  The caller has range-checked `win`."""
+    n_slots, H, W, C = pool.shape
+    T, B = table.shape[1], win.numel()
+    if pool.dtype != torch.uint8 or table.dtype != torch.int32 or win.dtype != torch.int64:
+        raise TypeError("pool is uint8, table int32 and win int64")
+    if not (pool.is_contiguous() and table.is_contiguous() and win.is_contiguous()):
+        raise ValueError("pool, table and win must be contiguous")
+    pitch = chunk_elems(dtype) if pitch is None else pitch
+    x = torch.empty((B * T, H, W, pitch), dtype=dtype, device=pool.device) if want_x else None
+    u8 = torch.empty((B, T, H, W, C), dtype=torch.uint8, device=pool.device) if want_u8 else None
+    check(lib().s2p_window_gather_u8(dtype_id(dtype), ptr(pool), n_slots, H * W, C, ptr(table), T, ptr(win), B, ptr(x), pitch,
+                                     ptr(u8), stream()), "s2p_window_gather_u8")
+    return x, u8
+
+
 # ---- SLAC latent model (csrc/gauss.hip).  Arguments are 2-D fp32 VIEWS (unit stride in the last dimension): the row pitch is the
 # view's stride, so a slice of a [B,S+1,288] sequence buffer is read or written in place -- no cat / chunk / stack copy.
 def _view2(t):

@@ -17,6 +17,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import ACT_LRELU, ACT_NONE, EPI_MUL_ACTGRAD, chunk_elems
 from .ops import ConvGeom, pad_to
+from .slac_buffer import FrameBatch
 
 ENCODER_100 = [("conv", 3, 32, 5, 2, 2, 0), ("conv", 32, 64, 3, 2, 1, 0), ("conv", 64, 128, 3, 2, 1, 0),
                ("conv", 128, 256, 3, 2, 1, 0), ("conv", 256, 256, 3, 2, 1, 0), ("conv", 256, 256, 4, 1, 0, 0)]
@@ -157,9 +158,15 @@ class Encoder(_Stack):
         super().__init__(ENCODER_100, dtype, device)
 
     def forward(self, x):
-        """x: fp32 [B,S,3,100,100] in [0,1] (or uint8 NHWC frames [B,S,100,100,3]) -> fp32 [B,S,256].
+        """x: fp32 [B,S,3,100,100] in [0,1] (or uint8 NHWC frames [B,S,100,100,3], or a FrameBatch) -> fp32 [B,S,256].
         Frames are data: no gradient is produced for x."""
         dev = self.device
+        if isinstance(x, FrameBatch):
+            B, S = x.shape[:2]
+            h = x.nhwc
+            if h.dtype == self.dtype and h.shape[3] == chunk_elems(self.dtype) and h.device == dev:
+                return self.run(h).reshape(B, S, -1).float()           # the replay buffer's gather wrote the encoder's input
+            x = x.u8
         with torch.no_grad():
             if x.dtype == torch.uint8:
                 B, S = x.shape[:2]
@@ -590,6 +597,8 @@ class LatentModel(nn.Module):
         reward_ = reward_.to(dev, torch.float32).reshape(B * S).contiguous()
         done_ = done_.to(dev, torch.float32).reshape(B * S).contiguous()
         feature_ = self.encoder(state_)
+        if isinstance(state_, FrameBatch):
+            state_ = state_.u8                                         # the image loss reads uint8 NHWC targets
         z1_mean_post_, z1_std_post_, z_ = self._posterior(feature_, action_, noise)
         z1_mean_pri_, z1_std_pri_ = self._prior(action_, z_[..., Z1:])
         loss_kld = _KlFn.apply(z1_mean_post_, z1_std_post_, z1_mean_pri_, z1_std_pri_, B, T)
