@@ -445,6 +445,56 @@ int s2p_ensemble_nll(const float* raw, int raw_pitch, const float* xin, int64_t 
                      float scale, float bound_reg, float* sums, float* loss, float* draw, int draw_pitch, float* dmin_logstd,
                      float* dmax_logstd, float* mean, float* std, void* stream);
 
+/* ---- IQL on SLAC latents (SPEC.md N3d; reference rlkit/torch/sac/iql_trainer.py:209-435; csrc/iql.hip).
+ * All fp32, the wide layers on v_mfma_f32_32x32x2_f32, no atomics, a fixed summation order (two identical calls give bitwise
+ * identical results).  Argument checking as stated above s2p_gauss_head_fwd: negative sizes, a required NULL tensor, a short
+ * pitch and a misaligned operand are refused before any launch; a size of 0 is a successful no-op that looks at no pointer.  */
+/* Grouped linear layer, group = network.  `groups` is a HOST array of G <= 8 views (copied into the kernel arguments): the
+ * groups share N and the activation but each has its own row count, input width K (padded to a multiple of 4 floats) and
+ * buffers, so networks of unequal input width, and vf on z and next_z (2 B rows) beside the Q networks on B rows, are ONE launch,
+ * grid z = group.  A group with rows == 0 is skipped.  Weights [N][K] with K contiguous: torch's nn.Linear orientation.
+ *   pre[m][n] = sum_k x[m][k] w[n][k] + bias[n];  act = relu(pre) (S2P_ACT_RELU) or pre (S2P_ACT_NONE);  pre and/or act.
+ * N > 16: the 32 x 64 MFMA wave tiles of the ensemble entry points.  N <= 16 (the N = 1 and N = 2 A last layers, where such a
+ * tile is mostly padding): a dot-product kernel, one wave per row.  Both: K, x_pitch multiples of 4, x and w 16-byte aligned. */
+typedef struct {
+  const float* x; const float* w; const float* bias; float* pre; float* act;
+  int32_t x_pitch, y_pitch, rows, K;
+} s2p_mlp_fwd_group;
+int s2p_mlp_linear_fwd(const s2p_mlp_fwd_group* groups, int G, int N, int act, void* stream);
+/* Its backward from dpre [rows][dpre_pitch]: dw[n][k] = sum_m dpre[m][n] x[m][k] and db[n] = sum_m dpre[m][n] (OVERWRITTEN, rows
+ * summed in row order), and with dprev != NULL  dprev[m][k] = (sum_n dpre[m][n] w[n][k]) * [pre_prev[m][k] > 0]  for act_prev =
+ * S2P_ACT_RELU (pre_prev: the producer's pre-activation or its ReLU output -- only the sign is used), unmasked for S2P_ACT_NONE
+ * (pre_prev may then be NULL).  pre_prev and dprev share prev_pitch.  N > 16: N, dpre_pitch multiples of 4 and dpre 16-byte
+ * aligned (MFMA tiles); N <= 16: no such demand (plain kernel, four row lanes added in lane order).  rows * K < 2^31.        */
+typedef struct {
+  const float* x; const float* dpre; const float* w; float* dw; float* db; const float* pre_prev; float* dprev;
+  int32_t x_pitch, dpre_pitch, prev_pitch, rows, K;
+} s2p_mlp_bwd_group;
+int s2p_mlp_linear_bwd(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream);
+/* Fused IQL critic head (iql_trainer.py:232-257, 309-314), every tensor fp32 [B] contiguous, one launch:
+ *   q_target = reward_scale * reward + (1 - terminal) * discount * v_next
+ *   losses[0..2] = mean (q1 - q_target)^2, mean (q2 - q_target)^2, mean w vf_err^2   with vf_err = v - min(tq1, tq2),
+ *                  w = 1 - quantile where vf_err > 0, else quantile
+ *   dq1, dq2, dv = d (losses[0] + losses[1] + losses[2]) / d (q1, q2, v)   (the 1 / B of the means included)
+ *   adv = min(tq1, tq2) - v,  weights = min(exp(adv / beta), clip_score)   (pass +inf for no clip)
+ * The eight inputs are required; every output is optional (at least one).  beta > 0.                                          */
+int s2p_iql_critic_head(const float* q1, const float* q2, const float* tq1, const float* tq2, const float* v,
+                        const float* v_next, const float* reward, const float* terminal, int B, float reward_scale,
+                        float discount, float quantile, float beta, float clip_score, float* losses, float* dq1, float* dq2,
+                        float* dv, float* weights, float* adv, float* q_target, void* stream);
+/* Fused policy head: log-probability of TanhNormal at a GIVEN action and the advantage-weighted loss (iql_trainer.py:307-315,
+ * rlkit/torch/distributions.py:339-354, gaussian_policy.py:119-123).  raw [B][raw_pitch >= 2 A] = (mu | raw log sigma):
+ *   v = clamp(action, +-0.999999),  u = log(1 + v) / 2 - log(1 - v) / 2,  ls = clamp(raw log sigma, -20, 2)
+ *   logp[b] = sum_d [-0.5 ((u - mu) / exp(ls))^2 - ls - 0.5 log 2 pi] - 2 sum_d [log 2 - u - softplus(-2 u)]
+ *   loss[0] = mean_b (-logp[b] weights[b]);   draw [B][draw_pitch] = d loss / d raw  (zero for a raw log sigma outside [-20, 2])
+ * softplus(x) = max(x, 0) + log1p(exp(-|x|)).  loss, draw, logp: each optional, at least one.                                */
+int s2p_tanh_gauss_policy_head(const float* raw, int raw_pitch, const float* action, int action_pitch, const float* weights,
+                               int B, int A, float* loss, float* draw, int draw_pitch, float* logp, void* stream);
+/* Polyak update of flat fp32 buffers: target[i] = target[i] * (1 - tau) + source[i] * tau, each product and the sum rounded on
+ * its own (torch's three element-wise operations: no fused multiply-add), 1 - tau formed in double and rounded once.  16-byte
+ * groups with a one-by-one tail like s2p_adam_step: target and source 16-byte aligned, any n.                               */
+int s2p_soft_update(float* target, const float* source, int64_t n, float tau, void* stream);
+
 /* ---- optimizer + weight packing ---------------------------------------------------- */
 /* torch.optim.Adam step on flat fp32 buffers; g is multiplied by grad_scale first.  All three forms move 16-byte groups:
  * p, g, m, v must be 16-byte aligned (a sub-range of a flat buffer starts at a multiple of 4 elements), else the call is

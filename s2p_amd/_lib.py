@@ -50,6 +50,17 @@ class SnJob(ctypes.Structure):
                 ("R", ctypes.c_int32), ("K", ctypes.c_int32)]
 
 
+class MlpFwdGroup(ctypes.Structure):
+    _fields_ = [("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("pre", c_void_p), ("act", c_void_p),
+                ("x_pitch", ctypes.c_int32), ("y_pitch", ctypes.c_int32), ("rows", ctypes.c_int32), ("K", ctypes.c_int32)]
+
+
+class MlpBwdGroup(ctypes.Structure):
+    _fields_ = [("x", c_void_p), ("dpre", c_void_p), ("w", c_void_p), ("dw", c_void_p), ("db", c_void_p), ("pre_prev", c_void_p),
+                ("dprev", c_void_p), ("x_pitch", ctypes.c_int32), ("dpre_pitch", ctypes.c_int32), ("prev_pitch", ctypes.c_int32),
+                ("rows", ctypes.c_int32), ("K", ctypes.c_int32)]
+
+
 # name -> argtypes; every entry returns int unless listed in _RESTYPE
 _P = c_void_p
 _DESC = ctypes.POINTER(ConvDesc)
@@ -130,6 +141,12 @@ SIGNATURES = {
                                 _P, _P, _P, _P, c_int, _P],
     "s2p_ensemble_nll": [_P, c_int, _P, c_int64, c_int, _P, c_int64, c_int, c_int, c_int, c_int, _P, _P, c_float, c_float,
                          _P, _P, _P, c_int, _P, _P, _P, _P, _P],
+    "s2p_mlp_linear_fwd": [ctypes.POINTER(MlpFwdGroup), c_int, c_int, c_int, _P],
+    "s2p_mlp_linear_bwd": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, _P],
+    "s2p_iql_critic_head": [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _P, _P,
+                            _P, _P, _P],
+    "s2p_tanh_gauss_policy_head": [_P, c_int, _P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P],
+    "s2p_soft_update": [_P, _P, c_int64, c_float, _P],
     "s2p_adam_step_dev": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, _P],
     "s2p_adam_step_dev_part": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, c_int, _P],
     "s2p_pack_weights": [_P, c_int, c_int, _P],

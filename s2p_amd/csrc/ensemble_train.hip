@@ -9,172 +9,54 @@
 // Layouts.  Activations of a layer: [B][G * N], group g at columns g * N (the layout the grouped conv path and s2p_ensemble_head
 // use).  Weights and their gradients: PACKED [E][N][K], K = the (padded) input width, contiguous -- the transpose of the
 // reference's [E, in, out].  `member[g]` maps group g to its slot e in the [E] arrays (set_select); activations are compact in g.
-#include "s2p_common.h"
+#include "ens_tile.h"
 
 #define ENS_MAX_G 8
 struct EnsSel { int m[ENS_MAX_G]; };
 
-__device__ __forceinline__ float ens_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-// d/dp [p sigmoid(p)]: needs the PRE-activation (not a function of swish's output)
-__device__ __forceinline__ float ens_swish_grad(float p) { const float s = ens_sigmoid(p); return s * (1.f + p * (1.f - s)); }
-__device__ __forceinline__ int ens_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
 // ---- forward: pre[m][g N + n] = sum_k x[g][m][k] W[e][n][k] + b[e][n];  act = swish(pre) ---------------------------------------
-// A wave owns 32 rows x 64 columns (two accumulators share the x operand), a workgroup four such row tiles.  A k-chunk of 8 is one
-// float4 per lane and operand (lane half h takes k = 8 t + 4 h .. + 3) consumed by four MFMAs (MFMA c uses component c of both
-// operands: the same k permutation on both sides, so the sum is the plain dot product).
+// The wave tile is ens_fwd_tile (ens_tile.h): 32 rows x 64 columns per wave, a workgroup four such row tiles; grid z = group.
 struct EnsFwdArgs {
   const float* x; long long xg; int xp; const float* w; const float* bias; float* pre; float* act; int yp, B, K, N; EnsSel sel;
 };
 __global__ __launch_bounds__(256) void ens_fwd_kernel(const EnsFwdArgs a) {
-  constexpr int U = 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
-  const int g = blockIdx.z, e = a.sel.m[g];
+  const int wave = threadIdx.x >> 6, g = blockIdx.z, e = a.sel.m[g];
   const int nb = blockIdx.x * 64, mb = blockIdx.y * 128 + wave * 32;
   if (mb >= a.B) return;                                     // (wave-uniform)
-  const bool two = nb + 32 < a.N;                            // (wave-uniform)
-  const int m = mb + i, n0 = nb + i, n1 = nb + 32 + i;
-  const bool mok = m < a.B, n0ok = n0 < a.N, n1ok = two && n1 < a.N;
-  const float* xr = a.x + (size_t)g * a.xg + (size_t)(mok ? m : 0) * a.xp;
-  const float* w0 = a.w + ((size_t)e * a.N + (n0ok ? n0 : 0)) * a.K;
-  const float* w1 = a.w + ((size_t)e * a.N + (n1ok ? n1 : 0)) * a.K;
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  f32x16 acc0 = {}, acc1 = {};
-  for (int kc = 0; kc < a.K; kc += 8 * U) {
-    f32x4 xv[U], wv0[U], wv1[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = kc + 8 * u + 4 * h;                      // K and the pitches are multiples of 4: a float4 is in or out
-      const bool in = k < a.K;
-      xv[u] = (mok && in) ? *(const f32x4*)(xr + k) : z4;
-      wv0[u] = (n0ok && in) ? *(const f32x4*)(w0 + k) : z4;
-      wv1[u] = (n1ok && in) ? *(const f32x4*)(w1 + k) : z4;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[u][c], wv0[u][c], acc0, 0, 0, 0);
-        if (two) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[u][c], wv1[u][c], acc1, 0, 0, 0);
-      }
-  }
-  auto store = [&](const f32x16& acc, int n, bool nok) {
-    if (!nok) return;
-    const float b = a.bias[(size_t)e * a.N + n];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int mo = mb + ens_row(r, h);
-      if (mo >= a.B) continue;
-      const float v = acc[r] + b;
-      const size_t o = (size_t)mo * a.yp + (size_t)g * a.N + n;
-      if (a.pre) a.pre[o] = v;
-      if (a.act) a.act[o] = v / (1.f + expf(-v));
-    }
-  };
-  store(acc0, n0, n0ok);
-  store(acc1, n1, n1ok);
+  const size_t yo = (size_t)g * a.N;
+  const EnsFwdTile t{a.x + (size_t)g * a.xg, a.w + (size_t)e * a.N * a.K, a.bias + (size_t)e * a.N, a.pre ? a.pre + yo : nullptr,
+                     a.act ? a.act + yo : nullptr, a.xp, a.yp, a.B, a.K, a.N};
+  ens_fwd_tile<ENS_ACT_SWISH>(t, mb, nb);
 }
 
-// ---- backward: one launch, two kinds of wave tiles ------------------------------------------------------------------------------
-//   weight tiles: dW[e][n][k] = sum_m dpre[m][g N + n] x[g][m][k]   (32 n x 64 k per wave, the whole batch in row order: no row
-//                 split, so no partial sums and no second pass at any B);  db[e][n] = sum_m dpre  from the same operand values
-//                 (per lane in row order, then the two lane halves);
-//   input tiles : dprev[m][g K + k] = (sum_n dpre[m][g N + n] W[e][n][k]) * swish'(pre_prev[m][g K + k])   (32 m x 64 k per wave).
+// ---- backward: one launch, the two kinds of wave tiles of ens_tile.h (weight tiles first, then the input tiles) -------------------
 struct EnsBwdArgs {
   const float* x; long long xg; int xp; const float* dpre; int dp; const float* w; float* dw; float* db;
   const float* pre_prev; float* dprev; int pp, B, K, N, G, w_tiles, w_blocks; EnsSel sel;
 };
+__device__ __forceinline__ EnsBwdTile ens_bwd_view(const EnsBwdArgs& a, int g) {
+  const int e = a.sel.m[g];
+  const size_t wo = (size_t)e * a.N * a.K, po = (size_t)g * a.K;
+  return EnsBwdTile{a.x + (size_t)g * a.xg, a.dpre + (size_t)g * a.N, a.w ? a.w + wo : nullptr, a.dw + wo, a.db + (size_t)e * a.N,
+                    a.pre_prev ? a.pre_prev + po : nullptr, a.dprev ? a.dprev + po : nullptr, a.xp, a.dp, a.pp, a.B, a.K, a.N};
+}
 __global__ __launch_bounds__(256) void ens_bwd_kernel(const EnsBwdArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
+  const int wave = threadIdx.x >> 6;
   const int tk = (a.K + 63) / 64;
   if ((int)blockIdx.x < a.w_blocks) {
-    constexpr int U = 8;
     const int tn = (a.N + 31) / 32;
     int id = blockIdx.x * 4 + wave;
     if (id >= a.w_tiles) return;                             // (wave-uniform)
     const int g = id / (tn * tk); id -= g * tn * tk;
-    const int nb = (id / tk) * 32, kb = (id % tk) * 64, e = a.sel.m[g];
-    const bool two = kb + 32 < a.K;                          // (wave-uniform)
-    const int n = nb + i, k0 = kb + i, k1 = kb + 32 + i;
-    const bool nok = n < a.N, k0ok = k0 < a.K, k1ok = two && k1 < a.K;
-    const float* dcol = a.dpre + (size_t)g * a.N + (nok ? n : 0);
-    const float* xcol = a.x + (size_t)g * a.xg;
-    f32x16 acc0 = {}, acc1 = {};
-    float bsum = 0.f;
-    for (int m0 = 0; m0 < a.B; m0 += 2 * U) {
-      float dv[U], x0[U], x1[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int m = m0 + 2 * u + h;
-        const bool mok = m < a.B;
-        dv[u] = (mok && nok) ? dcol[(size_t)m * a.dp] : 0.f;
-        x0[u] = (mok && k0ok) ? xcol[(size_t)m * a.xp + k0] : 0.f;
-        x1[u] = (mok && k1ok) ? xcol[(size_t)m * a.xp + k1] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[u], x0[u], acc0, 0, 0, 0);
-        if (two) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[u], x1[u], acc1, 0, 0, 0);
-        bsum += dv[u];
-      }
-    }
-    if (kb == 0) {
-      const float s = bsum + __shfl_xor(bsum, 32, 64);       // (half 0 + half 1 in both halves: one fixed order)
-      if (h == 0 && nok) a.db[(size_t)e * a.N + n] = s;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int no = nb + ens_row(r, h);
-      if (no >= a.N) continue;
-      float* row = a.dw + ((size_t)e * a.N + no) * a.K;
-      if (k0ok) row[k0] = acc0[r];
-      if (k1ok) row[k1] = acc1[r];
-    }
+    ens_wgrad_tile(ens_bwd_view(a, g), (id / tk) * 32, (id % tk) * 64);
     return;
   }
-  constexpr int U = 2;
   const int tm = (a.B + 127) / 128;
   int id = blockIdx.x - a.w_blocks;
   const int g = id / (tm * tk); id -= g * tm * tk;
-  const int mb = (id / tk) * 128 + wave * 32, kb = (id % tk) * 64, e = a.sel.m[g];
+  const int mb = (id / tk) * 128 + wave * 32, kb = (id % tk) * 64;
   if (mb >= a.B) return;                                     // (wave-uniform)
-  const bool two = kb + 32 < a.K;
-  const int m = mb + i, k0 = kb + i, k1 = kb + 32 + i;
-  const bool mok = m < a.B, k0ok = k0 < a.K, k1ok = two && k1 < a.K;
-  const float* dr = a.dpre + (size_t)(mok ? m : 0) * a.dp + (size_t)g * a.N;
-  const float* wc0 = a.w + (size_t)e * a.N * a.K + (k0ok ? k0 : 0);
-  const float* wc1 = a.w + (size_t)e * a.N * a.K + (k1ok ? k1 : 0);
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  f32x16 acc0 = {}, acc1 = {};
-  for (int nc = 0; nc < a.N; nc += 8 * U) {
-    f32x4 dv[U], w0[U], w1[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int n = nc + 8 * u + 4 * h;                      // N and dp are multiples of 4: a float4 of dpre is in or out
-      const bool in = n < a.N;
-      dv[u] = (mok && in) ? *(const f32x4*)(dr + n) : z4;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        w0[u][c] = (in && k0ok) ? wc0[(size_t)(n + c) * a.K] : 0.f;
-        w1[u][c] = (in && k1ok) ? wc1[(size_t)(n + c) * a.K] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[u][c], w0[u][c], acc0, 0, 0, 0);
-        if (two) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[u][c], w1[u][c], acc1, 0, 0, 0);
-      }
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int mo = mb + ens_row(r, h);
-    if (mo >= a.B) continue;
-    const size_t o = (size_t)mo * a.pp + (size_t)g * a.K;
-    if (k0ok) a.dprev[o + k0] = acc0[r] * ens_swish_grad(a.pre_prev[o + k0]);
-    if (k1ok) a.dprev[o + k1] = acc1[r] * ens_swish_grad(a.pre_prev[o + k1]);
-  }
+  ens_dgrad_tile<ENS_ACT_SWISH>(ens_bwd_view(a, g), mb, kb);
 }
 
 // ---- fused NLL head ---------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,93 @@
+"""Train IQL on SLAC latents from the device-resident replay buffer (SPEC.md N3d): the last stage of the S2P pipeline.
+
+  python train_iql.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --latent_dir DIR --steps N
+                      --out DIR [--freeze_slac] [--slac_policy_input_type feature_action|latent_z] [--bf16] [--seed S]
+
+Loads `latent.pth` from --latent_dir (written by train_latent.py), fills the buffer as the reference's `load_data_in_buffer` does,
+runs `IQLTrainer.train_from_torch` N times in the shipped configuration (`examples/iql/mujoco_finetune.py:91-119`) and writes
+`critic.pth` / `policy.pth` with the reference's keys, plus `encoder.pth` / `latent.pth`."""
+import argparse
+import os
+
+import torch
+
+from s2p_amd.slac_algo import UNCERTAINTY_TYPES
+
+IQL_KWARGS = dict(discount=0.99, policy_lr=1e-4, qf_lr=3e-4, reward_scale=1, soft_target_tau=0.005, beta=1.0 / 10, quantile=0.7,
+                  clip_score=100, target_update_period=2, slac_update_period=1)
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--real", required=True, help="dataset of real transitions (.npz, or .hdf5 with h5py)")
+    ap.add_argument("--gen", help="generated dataset (all_state_1step_random_action) made from the real one")
+    ap.add_argument("--uncertainty_type", choices=[t for t in UNCERTAINTY_TYPES if t], default=None)
+    ap.add_argument("--uncertainty_penalty_lambda", type=float, default=0.0)
+    ap.add_argument("--latent_dir", required=True, help="directory holding latent.pth")
+    ap.add_argument("--steps", type=int, required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--freeze_slac", action="store_true", help="do not train the latent model along")
+    ap.add_argument("--slac_policy_input_type", choices=["feature_action", "latent_z"], default="feature_action")
+    ap.add_argument("--bf16", action="store_true", help="bf16 conv stacks of the latent model (the IQL networks stay fp32)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--batch_size", type=int, default=256)
+    ap.add_argument("--batch_size_latent", type=int, default=32)
+    ap.add_argument("--num_sequences", type=int, default=8)
+    ap.add_argument("--hidden", type=int, default=1024, help="width of the two hidden layers of every IQL network")
+    ap.add_argument("--log_every", type=int, default=100)
+    a = ap.parse_args(argv)
+    if a.steps < 0 or a.batch_size < 1:
+        ap.error("--steps >= 0 and --batch_size >= 1")
+    if a.uncertainty_type and not a.gen:
+        ap.error("--uncertainty_type applies to a --gen dataset")
+    return a
+
+
+def policy_input_dim(a, action_dim, feature_dim=256, z_dim=288):
+    """finetune_rl.py:204: S features and S - 1 actions, or the latent."""
+    return a.num_sequences * feature_dim + (a.num_sequences - 1) * action_dim if a.slac_policy_input_type == "feature_action" else z_dim
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("train_iql.py needs a HIP device (no CPU fallback)")
+    from s2p_amd.data import load_arrays
+    from s2p_amd.iql import CriticSLAC, IQLTrainer, Qfunction, TanhGaussianPolicy, Vfunction
+    from s2p_amd.slac_algo import SlacAlgorithm
+    real = load_arrays(a.real)
+    gen = load_arrays(a.gen) if a.gen else None
+    rows = len(real["actions"]) + (len(gen["actions"]) if gen else 0)
+    C, A = real["image_observations"].shape[3], real["actions"].shape[1]
+    algo = SlacAlgorithm((C,) + real["image_observations"].shape[1:3], (A,), 1, "cuda:0", a.seed, batch_size_sac=a.batch_size,
+                         batch_size_latent=a.batch_size_latent, buffer_size=max(rows, 1), num_sequences=a.num_sequences,
+                         dtype=torch.bfloat16 if a.bf16 else torch.float32, frame_capacity=2 * rows + a.num_sequences + 1)
+    algo.latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
+    algo.load_data_in_buffer(real)
+    if gen is not None:
+        algo.load_data_in_buffer(gen, data_num=len(gen["actions"]), uncertainty_type=a.uncertainty_type,
+                                 uncertainty_penalty_lambda=a.uncertainty_penalty_lambda, generated_for_slac=True,
+                                 data_mix_type="all_state_1step_random_action")
+    print("buffer: %d windows (%d real)" % (len(algo.buffer), algo.buffer._real_n))
+    if len(algo.buffer) == 0:
+        raise SystemExit("no window of %d steps in the data" % a.num_sequences)
+    Z, hid = 288, [a.hidden, a.hidden]
+    q = [Qfunction(hidden_sizes=hid, output_size=1, input_size=Z + A) for _ in range(4)]
+    critic = CriticSLAC(q[0], q[1], q[2], q[3], vf=Vfunction(hidden_sizes=hid, output_size=1, input_size=Z))
+    policy = TanhGaussianPolicy(hidden_sizes=hid, obs_dim=policy_input_dim(a, A), action_dim=A)
+    trainer = IQLTrainer(None, policy, critic=critic, slac_algo=algo, freeze_slac=a.freeze_slac,
+                         slac_policy_input_type=a.slac_policy_input_type, **IQL_KWARGS)
+    for step in range(1, a.steps + 1):
+        trainer.train_from_torch(algo.buffer.random_batch(a.batch_size))
+        if step % a.log_every == 0 or step == a.steps:
+            trainer.end_epoch(step)
+            print("step %d  %s" % (step, "  ".join("%s %.4f" % kv for kv in trainer.eval_statistics.items())))
+    os.makedirs(a.out, exist_ok=True)
+    torch.save(critic.state_dict(), os.path.join(a.out, "critic.pth"))
+    torch.save(policy.state_dict(), os.path.join(a.out, "policy.pth"))
+    algo.save_model(a.out)
+    print("wrote %s/critic.pth, policy.pth, encoder.pth and latent.pth" % a.out)
+
+
+if __name__ == "__main__":
+    main()
