@@ -495,6 +495,85 @@ int s2p_tanh_gauss_policy_head(const float* raw, int raw_pitch, const float* act
  * groups with a one-by-one tail like s2p_adam_step: target and source 16-byte aligned, any n.                               */
 int s2p_soft_update(float* target, const float* source, int64_t n, float tau, void* stream);
 
+/* ---- CQL on SLAC latents (SPEC.md N3e; reference rlkit/torch/sac/cql_trainer.py:234-418, 576-585; csrc/cql.hip).
+ * All fp32, no atomics, a fixed summation order (two identical calls give bitwise identical results).  Argument checking as
+ * stated above s2p_gauss_head_fwd: negative sizes, a required NULL tensor, a short pitch and a misaligned operand are refused
+ * before any launch; a size of 0 is a successful no-op that looks at no pointer.  Tensors with a pitch take the pointer already
+ * offset to their first column.                                                                                            */
+/* The input-gradient half of s2p_mlp_linear_bwd alone, for both of its forms:  dprev[m][k] = (sum_n dpre[m][n] w[n][k]) *
+ * [pre_prev[m][k] > 0]  (act_prev = S2P_ACT_RELU; unmasked and pre_prev unused for S2P_ACT_NONE, the first layer), tile for tile
+ * what s2p_mlp_linear_bwd writes (bitwise).  dpre, w and dprev are required; x, dw and db are IGNORED and may be NULL: nothing
+ * but dprev is written, so a loss can be differentiated through a network down to its input (the SAC policy loss through qf1
+ * and qf2 to the action columns) while the network's gradient buffers keep what they hold.                                */
+int s2p_mlp_linear_dgrad(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream);
+/* s2p_mlp_linear_bwd (its MFMA-tile form: N > 16) with the rows of each weight tile divided into S contiguous chunks of
+ * ceil(ceil(rows / S) / 16) * 16 rows (the last one shorter; a chunk past the last row holds zeros): S waves per weight tile
+ * where s2p_mlp_linear_bwd has one, each summing its rows in row order into partial s of the caller-owned workspace
+ * ([S][dw [N][K] | db [N]] per group, groups in order); a second launch adds the partials in the order s = 0 .. S - 1 into dw /
+ * db.  For layers run on many rows, where the weight tiles alone do not fill the chip and one wave per tile means a summation
+ * chain as long as the batch.  S = 1 gives bitwise the result of s2p_mlp_linear_bwd; the input-gradient tiles are unchanged.
+ * 1 <= S <= 64.  The library never allocates: the workspace holds at least s2p_mlp_linear_bwd_split_workspace bytes, else
+ * the call is refused.  The query looks at sizes only -- rows, K, N, S -- and answers 0 for a NULL table and for G, N or S
+ * outside what the call takes; pitches, pointers and alignment are the call's to check.                                  */
+size_t s2p_mlp_linear_bwd_split_workspace(const s2p_mlp_bwd_group* groups, int G, int N, int S);
+int s2p_mlp_linear_bwd_split(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, int S, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* Reparameterised TanhNormal sample and its log-probability from the pre-tanh value (rlkit/torch/distributions.py:339-386).
+ * raw [M][raw_pitch >= 2 A] = (mu | raw log sigma), eps [M * rep][eps_pitch >= A], rep >= 1.  For the row m * rep + r:
+ *   ls = clamp(raw log sigma[m], -20, 2),  u = mu[m] + exp(ls) * eps,  action = tanh(u),
+ *   logp = sum_d [-0.5 eps^2 - ls - 0.5 log 2 pi] - 2 sum_d [log 2 - u - softplus(-2 u)]
+ * (log 2 the fp32 constant, softplus(x) = max(x, 0) + log1p(exp(-|x|)) as in s2p_tanh_gauss_policy_head).
+ *   action: row m * action_group + r of a buffer of pitch action_pitch, A columns written and no other -- with the pointer offset
+ *           to the action columns of a Q-input buffer, the samples land where the critics read them; action_group >= rep is the
+ *           number of buffer rows per m (rep: compact; 3 rep: one of three column blocks of a [M][3 rep] row group)
+ *   logp  : element m * logp_group + r (logp_group >= rep);   u [M * rep][u_pitch].   Each optional, at least one.
+ * rep lets the policy trunk run on M rows where the reference runs it on M * rep repeated rows.                            */
+int s2p_tanh_gauss_rsample(const float* raw, int raw_pitch, const float* eps, int eps_pitch, int M, int A, int rep,
+                           float* action, int action_pitch, int action_group, float* logp, int logp_group, float* u,
+                           int u_pitch, void* stream);
+/* Its backward at rep = 1, from dlogp [M] and the optional daction, daction2 [M][daction_pitch] (added: the action's gradient
+ * arrives once from each critic; daction2 needs daction) to draw [M][draw_pitch >= 2 A]:
+ *   du = (daction + daction2) (1 - tanh^2 u) + dlogp 2 tanh u,   d mu = du,
+ *   d raw log sigma = (du exp(ls) eps - dlogp) * [-20 <= raw log sigma <= 2]    (torch.clamp passes the gradient on [min, max])
+ * accumulate == 0: draw is overwritten; != 0: added to (the behaviour-cloning branch adds to what
+ * s2p_tanh_gauss_policy_head wrote with unit weights).                                                                    */
+int s2p_tanh_gauss_rsample_bwd(const float* raw, int raw_pitch, const float* eps, int eps_pitch, const float* dlogp,
+                               const float* daction, const float* daction2, int daction_pitch, int M, int A, float* draw,
+                               int draw_pitch, int accumulate, void* stream);
+/* Fused SAC policy head with the entropy-temperature step (cql_trainer.py:263-292), one launch of one workgroup, no host
+ * synchronisation.  logp [B]; q1, q2 [B] optional (together); log_alpha_state [3] = (log_alpha, Adam m, Adam v) and step_dev
+ * [1] in device memory.  In this order:
+ *   1. tune != 0: alpha_loss = -mean(log_alpha (logp + target_entropy)); ONE Adam step on log_alpha from that gradient (taken
+ *      at the old log_alpha; the arithmetic of s2p_adam_step_dev, the counter incremented first)
+ *   2. alpha[0] = exp(log_alpha) AFTER the step (tune == 0: alpha[0] = 1, alpha_loss = 0, the state is not looked at)
+ *   3. losses[0..3] = alpha_loss, mean(alpha logp - min(q1, q2)), mean(alpha logp), mean(logp - min(q1, q2)) -- the SAC policy
+ *      loss, its entropy part alone (the behaviour-cloning loss adds s2p_tanh_gauss_policy_head's to it) and the reference's
+ *      'Policy Loss' statistic, which leaves alpha out (cql_trainer.py:600).  With q1 == NULL the min term is 0.
+ *   4. dlogp [B] = alpha / B
+ *   5. dq1, dq2 [B] = -1 / B to the smaller of q1, q2 and 0 to the other; on a tie -1 / (2 B) to each, as the backward of
+ *      torch.min(a, b) splits it.
+ * losses, dlogp, dq1, dq2: each optional.                                                                                 */
+int s2p_sac_policy_head(const float* logp, const float* q1, const float* q2, int B, int tune, float target_entropy, float lr,
+                        float beta1, float beta2, float eps, float* log_alpha_state, int* step_dev, float* alpha,
+                        float* losses, float* dlogp, float* dq1, float* dq2, void* stream);
+/* Fused CQL critic head (cql_trainer.py:303-398, min_q_version 3), one launch of one workgroup, any B.  Network i of a
+ * two-network tensor lies i * its stride (in elements) behind network 0:
+ *   q_pred [2][B];  q_samp [2][B][3 R], column blocks random | next | current;  logp_samp [B][2 R] = next | current;
+ *   tq [2][B] contiguous (the target networks at the next latent and action);  new_log_pi, reward, terminal [B];  alpha [1].
+ *   q_target = reward_scale reward + (1 - terminal) discount (min(tq1, tq2) - alpha new_log_pi)   (deterministic_backup != 0:
+ *              without the alpha term; new_log_pi and alpha may then be NULL)
+ *   cat_i = [random - log 0.5^A | next - logp_next | current - logp_current] / temp,   lse max-shifted
+ *   min_qf_i = mean_b lse(cat_i) min_q_weight temp - mean(q_pred_i) min_q_weight;   qf_i = mean (q_pred_i - q_target)^2 + min_qf_i
+ * Outputs, each optional, at least one:  losses [4] = qf1, qf2, min_qf1, min_qf2;  dq_pred [2][B] = d (qf1 + qf2) / d q_pred;
+ * dq_samp [2][B][3 R] = softmax(cat_i) min_q_weight / B;  q_target [B];  std_mean [2] = mean_b of the unbiased standard
+ * deviation of (random, q_pred, next, current) per row (the 'Std QF values' statistics).  temp > 0, R >= 1.               */
+int s2p_cql_critic_head(const float* q_pred, int64_t q_pred_stride, const float* q_samp, int64_t q_samp_stride,
+                        const float* logp_samp, const float* tq, const float* new_log_pi, const float* alpha,
+                        const float* reward, const float* terminal, int B, int R, int A, float reward_scale, float discount,
+                        float temp, float min_q_weight, int deterministic_backup, float* losses, float* dq_pred,
+                        int64_t dq_pred_stride, float* dq_samp, int64_t dq_samp_stride, float* q_target, float* std_mean,
+                        void* stream);
+
 /* ---- optimizer + weight packing ---------------------------------------------------- */
 /* torch.optim.Adam step on flat fp32 buffers; g is multiplied by grad_scale first.  All three forms move 16-byte groups:
  * p, g, m, v must be 16-byte aligned (a sub-range of a flat buffer starts at a multiple of 4 elements), else the call is

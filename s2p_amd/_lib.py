@@ -147,6 +147,14 @@ SIGNATURES = {
                             _P, _P, _P],
     "s2p_tanh_gauss_policy_head": [_P, c_int, _P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P],
     "s2p_soft_update": [_P, _P, c_int64, c_float, _P],
+    "s2p_mlp_linear_dgrad": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, _P],
+    "s2p_mlp_linear_bwd_split_workspace": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int],
+    "s2p_mlp_linear_bwd_split": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, c_int, _P, ctypes.c_size_t, _P],
+    "s2p_tanh_gauss_rsample": [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, c_int, _P],
+    "s2p_tanh_gauss_rsample_bwd": [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int, _P],
+    "s2p_sac_policy_head": [_P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P],
+    "s2p_cql_critic_head": [_P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                            c_int, _P, _P, c_int64, _P, c_int64, _P, _P, _P],
     "s2p_adam_step_dev": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, _P],
     "s2p_adam_step_dev_part": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, c_int, _P],
     "s2p_pack_weights": [_P, c_int, c_int, _P],
@@ -160,7 +168,7 @@ SIGNATURES = {
     "s2p_copy_channels": [c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int64, c_int, _P],
     "s2p_image_metrics": [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P],
 }
-_RESTYPE = {"s2p_last_error": ctypes.c_char_p, "s2p_conv2d_wgrad_det_workspace": ctypes.c_size_t, "s2p_channel_sum_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_batched_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_workspace": ctypes.c_size_t, "s2p_conv2d_fwd_workspace": ctypes.c_size_t, "s2p_conv2d_dgrad_workspace": ctypes.c_size_t, "s2p_linear_bwd_workspace": ctypes.c_size_t, "s2p_in_stats_floats": c_int64, "s2p_in_bwd_sums_floats": c_int64,
+_RESTYPE = {"s2p_last_error": ctypes.c_char_p, "s2p_mlp_linear_bwd_split_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_det_workspace": ctypes.c_size_t, "s2p_channel_sum_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_batched_workspace": ctypes.c_size_t, "s2p_conv2d_wgrad_workspace": ctypes.c_size_t, "s2p_conv2d_fwd_workspace": ctypes.c_size_t, "s2p_conv2d_dgrad_workspace": ctypes.c_size_t, "s2p_linear_bwd_workspace": ctypes.c_size_t, "s2p_in_stats_floats": c_int64, "s2p_in_bwd_sums_floats": c_int64,
             "s2p_sn_workspace_floats": c_int64}
 
 _lib = None

@@ -82,15 +82,16 @@ template <int ACT> __device__ __forceinline__ void ens_fwd_tile(const EnsFwdTile
 }
 
 // ---- backward: two kinds of wave tiles ----------------------------------------------------------------------------------------------
-//   weight tile: dw[n][k] = sum_m dpre[m][n] x[m][k]   (32 n x 64 k per wave, the whole batch in row order: no row split, so no
-//                partial sums and no second pass at any B);  db[n] = sum_m dpre  from the same operand values (per lane in row
-//                order, then the two lane halves), written by the tiles at k = 0;
+//   weight tile: dw[n][k] = sum_m dpre[m][n] x[m][k]   (32 n x 64 k per wave, the rows [m_begin, min(m_end, B)) in row order -- the
+//                whole batch for the ensemble and IQL entry points: no row split, so no partial sums and no second pass at any B;
+//                a row range for s2p_mlp_linear_bwd_split, whose caller points dw / db at a partial);  db[n] = sum_m dpre  from
+//                the same operand values (per lane in row order, then the two lane halves), written by the tiles at k = 0;
 //   input tile : dprev[m][k] = (sum_n dpre[m][n] w[n][k]) * ACT'(pre_prev[m][k])   (32 m x 64 k per wave; N, dp multiples of 4).
 struct EnsBwdTile {
   const float* x; const float* dpre; const float* w; float* dw; float* db; const float* pre_prev; float* dprev;
   int xp, dp, pp, B, K, N;                                   // x [B][xp], dpre [B][dp], w / dw [N][K], db [N], pre_prev / dprev [B][pp]
 };
-__device__ __forceinline__ void ens_wgrad_tile(const EnsBwdTile& a, int nb, int kb) {
+__device__ __forceinline__ void ens_wgrad_tile(const EnsBwdTile& a, int nb, int kb, int m_begin = 0, int m_end = 0x7fffffff) {
   constexpr int U = 8;
   const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
   const bool two = kb + 32 < a.K;                            // (wave-uniform)
@@ -100,12 +101,13 @@ __device__ __forceinline__ void ens_wgrad_tile(const EnsBwdTile& a, int nb, int 
   const float* xcol = a.x;
   f32x16 acc0 = {}, acc1 = {};
   float bsum = 0.f;
-  for (int m0 = 0; m0 < a.B; m0 += 2 * U) {
+  const int me = m_end < a.B ? m_end : a.B;
+  for (int m0 = m_begin; m0 < me; m0 += 2 * U) {
     float dv[U], x0[U], x1[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int m = m0 + 2 * u + h;
-      const bool mok = m < a.B;
+      const bool mok = m < me;
       dv[u] = (mok && nok) ? dcol[(size_t)m * a.dp] : 0.f;
       x0[u] = (mok && k0ok) ? xcol[(size_t)m * a.xp + k0] : 0.f;
       x1[u] = (mok && k1ok) ? xcol[(size_t)m * a.xp + k1] : 0.f;
@@ -170,4 +172,16 @@ template <int ACT> __device__ __forceinline__ void ens_dgrad_tile(const EnsBwdTi
     if (k0ok) a.dprev[o + k0] = ens_act_bwd<ACT>(acc0[r], a.pre_prev + o + k0);
     if (k1ok) a.dprev[o + k1] = ens_act_bwd<ACT>(acc1[r], a.pre_prev + o + k1);
   }
+}
+
+// ---- the input gradient of a narrow layer (N <= 16: plain dot products, no tile): element idx = m K + k of dprev, n in order.
+//      Shared by the full backward of iql.hip and the input-gradient-only entry point of cql.hip, which must agree bit for bit.
+template <int ACT> __device__ __forceinline__ void ens_dot_dgrad_elem(const EnsBwdTile& t, long long idx) {
+  if (idx >= (long long)t.B * t.K) return;
+  const int m = (int)(idx / t.K), k = (int)(idx - (long long)m * t.K);
+  const float* dr = t.dpre + (size_t)m * t.dp;
+  float s = 0.f;
+  for (int n = 0; n < t.N; ++n) s += dr[n] * t.w[(size_t)n * t.K + k];
+  const size_t o = (size_t)m * t.pp + k;
+  t.dprev[o] = ens_act_bwd<ACT>(s, t.pre_prev + o);
 }

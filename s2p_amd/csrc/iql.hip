@@ -98,14 +98,7 @@ template <int ACT> __global__ __launch_bounds__(256) void mlp_dot_bwd_kernel(con
     return;
   }
   if (!t.dprev) return;
-  const long long idx = (long long)(blockIdx.x - wb) * 256 + threadIdx.x;
-  if (idx >= (long long)t.B * t.K) return;
-  const int m = (int)(idx / t.K), k = (int)(idx - (long long)m * t.K);
-  const float* dr = t.dpre + (size_t)m * t.dp;
-  float s = 0.f;
-  for (int n = 0; n < t.N; ++n) s += dr[n] * t.w[(size_t)n * t.K + k];
-  const size_t o = (size_t)m * t.pp + k;
-  t.dprev[o] = ens_act_bwd<ACT>(s, t.pre_prev + o);
+  ens_dot_dgrad_elem<ACT>(t, (long long)(blockIdx.x - wb) * 256 + threadIdx.x);
 }
 
 // ---- loss heads: one workgroup of 1024 threads, thread t owns the rows t, t + 1024, ...; the per-thread sums are added through LDS

@@ -17,7 +17,8 @@ IQL_KWARGS = dict(discount=0.99, policy_lr=1e-4, qf_lr=3e-4, reward_scale=1, sof
                   clip_score=100, target_update_period=2, slac_update_period=1)
 
 
-def parse_args(argv=None):
+def parse_args(argv=None, extend=None):
+    """`extend(parser)` adds a caller's own options before parsing (train_cql.py shares these options)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--real", required=True, help="dataset of real transitions (.npz, or .hdf5 with h5py)")
     ap.add_argument("--gen", help="generated dataset (all_state_1step_random_action) made from the real one")
@@ -35,6 +36,8 @@ def parse_args(argv=None):
     ap.add_argument("--num_sequences", type=int, default=8)
     ap.add_argument("--hidden", type=int, default=1024, help="width of the two hidden layers of every IQL network")
     ap.add_argument("--log_every", type=int, default=100)
+    if extend is not None:
+        extend(ap)
     a = ap.parse_args(argv)
     if a.steps < 0 or a.batch_size < 1:
         ap.error("--steps >= 0 and --batch_size >= 1")
