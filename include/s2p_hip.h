@@ -445,7 +445,8 @@ int s2p_ensemble_nll(const float* raw, int raw_pitch, const float* xin, int64_t 
                      float scale, float bound_reg, float* sums, float* loss, float* draw, int draw_pitch, float* dmin_logstd,
                      float* dmax_logstd, float* mean, float* std, void* stream);
 
-/* ---- IQL on SLAC latents (SPEC.md N3d; reference rlkit/torch/sac/iql_trainer.py:209-435; csrc/iql.hip).
+/* ---- IQL on SLAC latents (SPEC.md N3d; reference rlkit/torch/sac/iql_trainer.py:209-435; the grouped layers s2p_mlp_linear_* in
+ * csrc/mlp.hip, the heads and the Polyak update in csrc/iql.hip).
  * All fp32, the wide layers on v_mfma_f32_32x32x2_f32, no atomics, a fixed summation order (two identical calls give bitwise
  * identical results).  Argument checking as stated above s2p_gauss_head_fwd: negative sizes, a required NULL tensor, a short
  * pitch and a misaligned operand are refused before any launch; a size of 0 is a successful no-op that looks at no pointer.  */
@@ -495,7 +496,8 @@ int s2p_tanh_gauss_policy_head(const float* raw, int raw_pitch, const float* act
  * groups with a one-by-one tail like s2p_adam_step: target and source 16-byte aligned, any n.                               */
 int s2p_soft_update(float* target, const float* source, int64_t n, float tau, void* stream);
 
-/* ---- CQL on SLAC latents (SPEC.md N3e; reference rlkit/torch/sac/cql_trainer.py:234-418, 576-585; csrc/cql.hip).
+/* ---- CQL on SLAC latents (SPEC.md N3e; reference rlkit/torch/sac/cql_trainer.py:234-418, 576-585; the two further
+ * s2p_mlp_linear_* entry points in csrc/mlp.hip, the sampling and the heads in csrc/cql.hip).
  * All fp32, no atomics, a fixed summation order (two identical calls give bitwise identical results).  Argument checking as
  * stated above s2p_gauss_head_fwd: negative sizes, a required NULL tensor, a short pitch and a misaligned operand are refused
  * before any launch; a size of 0 is a successful no-op that looks at no pointer.  Tensors with a pitch take the pointer already

@@ -1,81 +1,42 @@
 """CQL on SLAC latents (SPEC.md N3e; reference `rlkit/torch/sac/cql_trainer.py:234-418, 576-585` in its SLAC configuration): the
-second consumer of the replay buffer and the latent model, on the networks, flat buffers and optimizer of `s2p_amd/iql.py`.  A step
-has two phases.  The policy phase runs the policy on B rows, draws the reparameterised action into the action columns of a Q-input
-buffer, runs qf1 | qf2 on it, and differentiates the SAC loss THROUGH the critics to the action (s2p_mlp_linear_dgrad: the critics'
-gradient buffer is not touched).  The critic phase runs the UPDATED policy once on [policy_input; policy_next_input], fills the
-B (1 + 3 num_random) rows of the Q-input buffer with three s2p_tanh_gauss_rsample calls (the policy trunk runs on B rows, not on
-B num_random repeated ones), runs qf1 | qf2 on them and the targets on B rows as ONE grouped launch per layer, and the fused CQL
-head.  DESIGN.md section 6b.5 counts the launches.  No CPU fallback, no host synchronisation inside a step."""
-import ctypes
+second consumer of the replay buffer and the latent model, on the networks, flat buffers, optimizer and trainer base of
+`s2p_amd/offline_rl.py` and the grouped layers of `s2p_amd/mlp.py`.  A step has two phases.  The policy phase runs the policy on B
+rows, draws the reparameterised action into the action columns of a Q-input buffer, runs qf1 | qf2 on it, and differentiates the SAC
+loss THROUGH the critics to the action (s2p_mlp_linear_dgrad: the critics' gradient buffer is not touched).  The critic phase runs
+the UPDATED policy once on [policy_input; policy_next_input], fills the B (1 + 3 num_random) rows of the Q-input buffer with three
+s2p_tanh_gauss_rsample calls (the policy trunk runs on B rows, not on B num_random repeated ones), runs qf1 | qf2 on them and the
+targets on B rows as ONE grouped launch per layer, and the fused CQL head.  DESIGN.md section 6b.5 counts the launches.  No CPU
+fallback, no host synchronisation inside a step."""
 from collections import OrderedDict
 
 import torch
 
-from ._lib import ACT_NONE, ACT_RELU, MlpBwdGroup, MlpFwdGroup, check, lib, ptr, stream
-from .iql import CriticSLAC, Qfunction, TanhGaussianPolicy, Vfunction, _Adam, _export, _load  # noqa: F401  (the networks are IQL's)
+from ._lib import check, lib, ptr, stream
+from .mlp import Net, bwd_plan, bwd_tables, fwd_plan, fwd_tables, run, split_chunks
+from .offline_rl import CriticSLAC, LatentTrainer, Qfunction, TanhGaussianPolicy, Vfunction  # noqa: F401  (re-exported)
 from .ops import pad_to
 
 NOISE = ("eps0", "eps1", "uniform", "eps2", "eps3")
 
 
-class _Net:
-    """One network's view for the grouped launches: its packed layers, the buffers holding parameters and gradients, its input, the
-    ReLU outputs it keeps (all the backward needs), their gradients, its output and the output's gradient."""
-
-    def __init__(self, pk, flat, grad, x, rows, hid, out, dout=None, dx=None):
-        dev, f = x.device, torch.float32
-        self.pk, self.flat, self.grad, self.x, self.rows, self.out, self.dout, self.dx = pk, flat, grad, x, rows, out, dout, dx
-        self.act = [torch.empty(rows, h, dtype=f, device=dev) for h in hid]
-        self.dact = [torch.empty(rows, h, dtype=f, device=dev) for h in hid] if dout is not None else None
-
-
-def _pitch(t):
-    return t.shape[1] if t.dim() == 2 else 1
-
-
-def _fwd_table(nets):
-    """One grouped launch per layer for networks of one hidden width: [(groups, G, N, act)]."""
-    L, out = len(nets[0].act), []
-    for li in range(L + 1):
-        gs = []
-        for n in nets:
-            x, last = (n.x if li == 0 else n.act[li - 1]), li == L
-            y = n.out if last else n.act[li]
-            gs.append(MlpFwdGroup(ptr(x), ptr(n.pk.w(n.flat, li)), ptr(n.pk.b(n.flat, li)), ptr(y) if last else None,
-                                  None if last else ptr(y), x.shape[1], _pitch(y), n.rows, n.pk.off[li][2]))
-        widths = {n.pk.dims[li][1] for n in nets}
-        assert len(widths) == 1
-        out.append(((MlpFwdGroup * len(gs))(*gs), len(gs), widths.pop(), ACT_NONE if li == L else ACT_RELU))
-    return out
+def step_plan(critic, policy, B, R):
+    """The networks' views of a step at batch size B with R sampled actions per row, and its launches, from shapes alone:
+    (nets, plans).  The policy on B rows (trained) and on 2 B rows (forward only), qf1 | qf2 under the policy's action on B rows
+    (differentiated to the action, no weight gradient), qf1 | qf2 on the B (1 + 3 R) rows of the critic loss, the targets on B."""
+    M, q_names = B * (1 + 3 * R), ("qf1", "qf2")
+    nets = dict(pol=[Net("policy", policy.packed, B, B)], pol2=[Net("policy", policy.packed, 2 * B)],
+                qpol=[Net(n, critic.packed[n], B, B) for n in q_names], qcrit=[Net(n, critic.packed[n], M, M) for n in q_names],
+                qtgt=[Net("target_" + n, critic.packed[n], B) for n in q_names])
+    plans = dict(policy_fwd=fwd_plan(nets["pol"], True), policy_bwd=bwd_plan(nets["pol"], True), policy2_fwd=fwd_plan(nets["pol2"], True),
+                 qpol_fwd=fwd_plan(nets["qpol"], True), qpol_dgrad=bwd_plan(nets["qpol"], True),
+                 critic_fwd=fwd_plan(nets["qcrit"] + nets["qtgt"], True), critic_bwd=bwd_plan(nets["qcrit"], True))
+    return nets, plans
 
 
-def _bwd_table(nets, with_weights):
-    """The backward of _fwd_table, last layer first: [(groups, G, N, act_prev)]; without weights the table feeds
-    s2p_mlp_linear_dgrad (dw / db NULL) and the first layer's input gradient goes to `dx`."""
-    L, out = len(nets[0].act), []
-    for li in range(L, -1, -1):
-        gs = []
-        for n in nets:
-            x = n.x if li == 0 else n.act[li - 1]
-            d = n.dout if li == L else n.dact[li]
-            prev = n.dact[li - 1] if li else n.dx
-            gs.append(MlpBwdGroup(ptr(x), ptr(d), ptr(n.pk.w(n.flat, li)), ptr(n.pk.w(n.grad, li)) if with_weights else None,
-                                  ptr(n.pk.b(n.grad, li)) if with_weights else None, ptr(x) if li else None, ptr(prev), x.shape[1],
-                                  _pitch(d), prev.shape[1] if prev is not None else 0, n.rows, n.pk.off[li][2]))
-        out.append(((MlpBwdGroup * len(gs))(*gs), len(gs), nets[0].pk.dims[li][1], ACT_RELU if li else ACT_NONE))
-    return out
-
-
-def split_chunks(tiles, rows, max_rows=1024, waves=1024, cap=8):
-    """S of s2p_mlp_linear_bwd_split for a launch of `tiles` weight tiles over `rows` rows: enough chunks that the weight waves reach
-    the chip's 1 024 SIMDs and that no wave sums more than `max_rows` rows in one chain (the accuracy floor), at most `cap`.  Measured at
-    7 936 rows: K 296 is fastest at S = 8, K 1024 at S = 4 with S = 8 within 4 % (the table of DESIGN.md section 6b.5)."""
-    return max(1, min(cap, max(-(-waves // max(tiles, 1)), -(-rows // max_rows))))
-
-
-class CQLTrainer:
+class CQLTrainer(LatentTrainer):
     """`CQLTrainer` of the reference in its SLAC configuration (`image_rl`, `slac_representation`, two Q networks,
     `min_q_version = 3`), the arguments it uses under their reference names.  Not built: see SPEC.md N3e."""
+    TRAINED = ("qf1", "qf2")                    # (vf takes part in no loss: no gradient, no optimizer state, as in the reference)
 
     def __init__(self, env, policy, qf1=None, qf2=None, target_qf1=None, target_qf2=None, discount=0.99, reward_scale=1.0,
                  policy_lr=1e-3, qf_lr=1e-3, soft_target_tau=1e-2, use_automatic_entropy_tuning=True, target_entropy=None,
@@ -89,16 +50,10 @@ class CQLTrainer:
                            (policy_weight_decay or q_weight_decay, "weight decay")):
             if flag:
                 raise NotImplementedError(what)
-        if slac_policy_input_type not in ("feature_action", "latent_z"):
-            raise ValueError("slac_policy_input_type %r" % (slac_policy_input_type,))
         if int(num_random) < 1 or not temp > 0:
             raise ValueError("num_random >= 1 and temp > 0")
-        self.env, self.policy = env, policy
-        self.critic = critic if critic is not None else CriticSLAC(qf1, qf2, target_qf1, target_qf2, vf, device=policy.device)
-        if self.critic.device != policy.device or policy.device is None:
-            raise ValueError("the policy and the critic share a HIP device")
-        self.qf1, self.qf2, self.target_qf1, self.target_qf2, self.vf = (self.critic.nets[n] for n in CriticSLAC.NETS)
-        self.device = policy.device
+        super().__init__(env, policy, critic, qf1, qf2, target_qf1, target_qf2, vf, qf_lr, policy_lr, slac_algo, freeze_slac,
+                         slac_update_period, slac_policy_input_type)
         self.obs_dim, self.action_dim = self.qf1.input_size - policy.action_dim, policy.action_dim
         if self.qf1.output_size != 1 or self.obs_dim <= 0:
             raise ValueError("qf: (Z + A) -> 1")
@@ -110,19 +65,12 @@ class CQLTrainer:
         self.target_entropy = float(target_entropy)
         self.policy_eval_start, self.num_random = int(policy_eval_start), int(num_random)
         self.temp, self.min_q_weight, self.deterministic_backup = float(temp), float(min_q_weight), bool(deterministic_backup)
-        self.slac_algo, self.freeze_slac, self.slac_update_period = slac_algo, bool(freeze_slac), int(slac_update_period)
-        self.slac_policy_input_type, self.generator = slac_policy_input_type, generator
-        self.policy_lr = float(policy_lr)
-        self.critic_optimizer = _Adam(self.critic.flat, self.critic.grad, qf_lr, betas=(0.9, 0.999))
-        self.policy_optimizer = _Adam(policy.flat, policy.grad, policy_lr)
+        self.generator, self.policy_lr = generator, float(policy_lr)
         # log_alpha with its Adam moments, and its step counter: read and written by s2p_sac_policy_head alone
         self.log_alpha_state = torch.zeros(3, dtype=torch.float32, device=self.device)
         self.log_alpha_step = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.alpha = torch.ones(1, dtype=torch.float32, device=self.device)
-        self.eval_statistics = OrderedDict()
-        self._n_train_steps_total = self._current_epoch = self._num_q_update_steps = self._num_policy_update_steps = 0
-        self._need_to_update_eval_statistics = True
-        self._buf = {}
+        self._current_epoch = self._num_q_update_steps = self._num_policy_update_steps = 0
         self.launches = OrderedDict()           # the last step's library calls and torch copies, by name
 
     @property
@@ -135,7 +83,7 @@ class CQLTrainer:
             return self._buf[B]
         cr, po, dev, f = self.critic, self.policy, self.device, torch.float32
         Z, A, R = self.obs_dim, self.action_dim, self.num_random
-        M, Kq, hid = B * (1 + 3 * R), pad_to(Z + A, 4), self.qf1.hidden_sizes
+        M, Kq = B * (1 + 3 * R), pad_to(Z + A, 4)
 
         def z(*shape):
             return torch.zeros(*shape, dtype=f, device=dev)
@@ -144,17 +92,18 @@ class CQLTrainer:
                  q_all=z(2, M), dq_all=z(2, M), tq=z(2, B), qn=z(2, B), dqn=z(2, B), dxpq=z(2, B, Kq), logp0=z(B), dlogp=z(B),
                  new_log_pi=z(B), logp_samp=z(B, 2 * R), sac=z(4), losses=z(4), std=z(2), bc=z(1), q_target=z(B), ones=torch.ones(B, dtype=f, device=dev),
                  action=z(B, A), reward=z(B), terminal=z(B), eps0=z(B, A), eps1=z(B, A), uniform=z(B * R, A), eps2=z(B * R, A), eps3=z(B * R, A))
-        q_names = ("qf1", "qf2")
-        pol = _Net(po.packed, po.flat, po.grad, t["xp"], B, po.hidden_sizes, t["raw"], t["draw"])
-        pol2 = _Net(po.packed, po.flat, po.grad, t["xp"], 2 * B, po.hidden_sizes, t["raw"])
-        qpol = [_Net(cr.packed[n], cr.flat, cr.grad, t["xpq"], B, hid, t["qn"][i], t["dqn"][i], t["dxpq"][i]) for i, n in enumerate(q_names)]
-        qcrit = [_Net(cr.packed[n], cr.flat, cr.grad, t["xq"], M, hid, t["q_all"][i], t["dq_all"][i]) for i, n in enumerate(q_names)]
-        qtgt = [_Net(cr.packed[n], cr.target_flat, None, t["xt"], B, hid, t["tq"][i]) for i, n in enumerate(q_names)]
-        t["nets"] = (pol, pol2, qpol, qcrit, qtgt)
-        t["policy_fwd"], t["policy_bwd"] = _fwd_table([pol]), _bwd_table([pol], True)
-        t["policy2_fwd"] = _fwd_table([pol2])
-        t["qpol_fwd"], t["qpol_dgrad"] = _fwd_table(qpol), _bwd_table(qpol, False)
-        t["critic_fwd"], t["critic_bwd"] = _fwd_table(qcrit + qtgt), _bwd_table(qcrit, True)
+        nets, plans = step_plan(cr, po, B, R)
+        nets["pol"][0].bind(po.flat, po.grad, t["xp"], t["raw"], t["draw"])
+        nets["pol2"][0].bind(po.flat, po.grad, t["xp"], t["raw"])
+        for i, n in enumerate(nets["qpol"]):
+            n.bind(cr.flat, cr.grad, t["xpq"], t["qn"][i], t["dqn"][i], t["dxpq"][i])
+        for i, n in enumerate(nets["qcrit"]):
+            n.bind(cr.flat, cr.grad, t["xq"], t["q_all"][i], t["dq_all"][i])
+        for i, n in enumerate(nets["qtgt"]):
+            n.bind(cr.target_flat, None, t["xt"], t["tq"][i])
+        t["nets"] = nets
+        for k, plan in plans.items():
+            t[k] = fwd_tables(plan) if k.endswith("fwd") else bwd_tables(plan, with_weights=k != "qpol_dgrad")
         # the critics' wide layers run on B (1 + 3 R) rows: their weight gradient is split by rows (the N = 1 last layer is not)
         t["critic_split"], need = [], 0
         for gs, G, N, a in t["critic_bwd"]:
@@ -197,9 +146,7 @@ class CQLTrainer:
             self._copy(t[k], noise[k].to(dev, torch.float32))
 
     def _run(self, table, entry="s2p_mlp_linear_fwd"):
-        st = stream()
-        for gs, G, N, a in table:
-            self._call(entry, gs, G, N, a, st)
+        run(table, entry, self._call)
 
     def _rsample(self, raw, eps, M, rep, action, action_pitch, group, logp, logp_group):
         A = self.action_dim
@@ -271,9 +218,7 @@ class CQLTrainer:
                 self._call("s2p_mlp_linear_bwd", gs, G, N, a, st)
         self._adam(self.critic_optimizer)
         self._num_q_update_steps += 1
-        if _latent and not self.freeze_slac and self._n_train_steps_total % self.slac_update_period == 0:
-            with torch.enable_grad():
-                self._latent_losses = self.slac_algo.update_latent(writer=None)
+        self._update_latent(_latent)
         self._call("s2p_soft_update", ptr(self.critic.target_flat), ptr(self.critic.flat), self.critic.n_target, self.soft_target_tau, st)
         self._bc = bc
         if self._need_to_update_eval_statistics:
@@ -281,9 +226,7 @@ class CQLTrainer:
             self.eval_statistics.update(self.last_statistics())
             self.eval_statistics["Num Q Updates"] = self._num_q_update_steps
             self.eval_statistics["Num Policy Updates"] = self._num_policy_update_steps
-            if _latent and not self.freeze_slac and hasattr(self, "_latent_losses"):
-                for k, val in zip(("SLAC Loss kld", "SLAC Loss image", "SLAC Loss reward"), self._latent_losses):
-                    self.eval_statistics[k] = float(val)
+            self._latent_statistics(_latent)
         self._n_train_steps_total += 1
         return t["losses"]
 
@@ -304,48 +247,19 @@ class CQLTrainer:
     def train_from_torch(self, batch):
         """One step on a `random_batch` dict of `slac_buffer.ReplayBuffer` (cql_trainer.py:234-418, the SLAC branch)."""
         z, next_z, action, feature_action, next_feature_action = self.slac_algo.prepare_batch(batch["observations"], batch["actions"])
-        if self.slac_policy_input_type == "feature_action":
-            policy_input, policy_next_input = feature_action, next_feature_action
-        else:
-            policy_input, policy_next_input = z, next_z
+        policy_input, policy_next_input = self._policy_inputs(z, next_z, feature_action, next_feature_action)
         return self.train_from_latents(z, next_z, action, policy_input, policy_next_input, batch["rewards"], batch["terminals"], _latent=True)
 
-    def end_epoch(self, epoch):
-        self._need_to_update_eval_statistics = True
-
-    def get_diagnostics(self):
-        return OrderedDict(self.eval_statistics)
-
-    # ---- snapshots --------------------------------------------------------------------------------------------------------------
-    def _critic_tensors(self, flat):
-        out = OrderedDict()
-        for n in ("qf1", "qf2"):                # (vf takes part in no loss: no gradient, no optimizer state, as in the reference)
-            out.update(_export(self.critic.nets[n], self.critic.packed[n], flat, n + "."))
-        return out
-
-    def _critic_put(self, flat, named):
-        for n in ("qf1", "qf2"):
-            sub = {k: v for k, v in named.items() if k.startswith(n + ".")}
-            if sub:
-                _load(self.critic.nets[n], self.critic.packed[n], flat, sub, n + ".")
-
+    # ---- snapshots: the base's, and log_alpha with its optimizer and the epoch counter on top -------------------------------------
     def state_dict(self):
-        po, la, step = self.policy, self.log_alpha_state.cpu(), int(self.log_alpha_step.item())
+        la, step = self.log_alpha_state.cpu(), int(self.log_alpha_step.item())
         group = dict(lr=self.policy_lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, params=[0])
         state = {0: {"step": torch.tensor(float(step)), "exp_avg": la[1:2].clone(), "exp_avg_sq": la[2:3].clone()}} if step else {}
-        return dict(critic=self.critic.state_dict(), policy=po.state_dict(),
-                    critic_optimizer=self.critic_optimizer.state_dict(self._critic_tensors, self.critic.keys()),
-                    policy_optimizer=self.policy_optimizer.state_dict(lambda fl: _export(po, po.packed, fl), po.keys()),
-                    log_alpha=la[:1].clone(), alpha_optimizer={"state": state, "param_groups": [group]},
-                    n_train_steps_total=self._n_train_steps_total, current_epoch=self._current_epoch)
+        return dict(super().state_dict(), log_alpha=la[:1].clone(), alpha_optimizer={"state": state, "param_groups": [group]},
+                    current_epoch=self._current_epoch)
 
     def load_state_dict(self, sd):
-        po = self.policy
-        self.critic.load_state_dict(sd["critic"])
-        po.load_state_dict(sd["policy"])
-        self.critic_optimizer.load_state_dict(sd["critic_optimizer"], self._critic_put, self.critic.keys())
-        self.policy_optimizer.load_state_dict(sd["policy_optimizer"], lambda fl, named: named and _load(po, po.packed, fl, named),
-                                              po.keys())
+        super().load_state_dict(sd)
         s = sd["alpha_optimizer"]["state"].get(0)
         la = torch.zeros(3)
         la[0] = torch.as_tensor(sd["log_alpha"]).reshape(-1)[0]
@@ -354,14 +268,5 @@ class CQLTrainer:
         self.log_alpha_state.copy_(la)
         self.log_alpha_step.fill_(int(s["step"]) if s is not None else 0)
         self.alpha.copy_(torch.exp(la[:1]) if self.use_automatic_entropy_tuning else torch.ones(1))
-        self._n_train_steps_total = int(sd.get("n_train_steps_total", 0))
         self._current_epoch = int(sd.get("current_epoch", self._n_train_steps_total))
         return self
-
-    def get_snapshot(self):
-        """cql_trainer.py:722-740, as state_dicts (the reference pickles the modules)."""
-        snap = self.state_dict()
-        if self.slac_algo is not None:
-            snap["slac_algo_latent"] = self.slac_algo.latent.state_dict()
-            snap["slac_algo_latent_optimizer"] = self.slac_algo.optim_latent.state_dict()
-        return snap

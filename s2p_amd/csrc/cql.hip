@@ -1,74 +1,12 @@
 // CQL on SLAC latents (SPEC.md N3e; reference rlkit/torch/sac/cql_trainer.py:234-418, 576-585): what the CQL step needs beyond the
-// grouped layers and heads of iql.hip.  The input-gradient half of the grouped backward alone (the policy loss is differentiated
-// THROUGH the critics to the action, and the critics' gradient buffers must stay as they are); the reparameterised TanhNormal sample
-// with its log-probability from the pre-tanh value, and its backward; the fused SAC policy head with the entropy-temperature step;
-// the fused CQL critic head (backup, MSE, importance-weighted log-sum-exp, their gradients).  All fp32, no atomics, a fixed
-// summation order: two identical calls give bitwise identical results.
-#include "ens_tile.h"
-
-#define CQL_MAX_G 8
-#define CQL_DOT_MAX_N 16
-struct CqlBwdArgs { EnsBwdTile g[CQL_MAX_G]; };
-
-// ---- input gradient alone: the input tiles of mlp_bwd_kernel / the input blocks of mlp_dot_bwd_kernel (iql.hip) through the same
-//      device functions of ens_tile.h, so dprev is bitwise what s2p_mlp_linear_bwd writes -----------------------------------------------
-template <int ACT> __global__ __launch_bounds__(256) void mlp_dgrad_kernel(const CqlBwdArgs a) {
-  const EnsBwdTile t = a.g[blockIdx.z];
-  if (t.B == 0) return;
-  const int wave = threadIdx.x >> 6, tk = (t.K + 63) / 64, tm = (t.B + 127) / 128, id = blockIdx.x;
-  if (id >= tm * tk) return;
-  const int mb = (id / tk) * 128 + wave * 32;
-  if (mb >= t.B) return;                                     // (wave-uniform)
-  ens_dgrad_tile<ACT>(t, mb, (id % tk) * 64);
-}
-template <int ACT> __global__ __launch_bounds__(256) void mlp_dot_dgrad_kernel(const CqlBwdArgs a) {
-  const EnsBwdTile t = a.g[blockIdx.z];
-  if (t.B == 0) return;
-  ens_dot_dgrad_elem<ACT>(t, (long long)blockIdx.x * 256 + threadIdx.x);
-}
-
-// ---- the grouped backward with the rows of each weight tile divided into S contiguous chunks: chunk s of a tile is one wave that
-//      sums its rows in row order into partial s of a caller-owned workspace ([S][dw [N][K] | db [N]] per group); a second kernel
-//      adds the partials in the order s = 0 .. S - 1.  More waves for a launch whose weight tiles alone do not fill the chip, and
-//      S shorter summation chains.  The input tiles are those of mlp_bwd_kernel (iql.hip) --------------------------------------------
-struct CqlSplitArgs { EnsBwdTile g[CQL_MAX_G]; float* ws[CQL_MAX_G]; int chunk[CQL_MAX_G]; int S; };
-template <int ACT> __global__ __launch_bounds__(256) void mlp_bwd_split_kernel(const CqlSplitArgs a) {
-  EnsBwdTile t = a.g[blockIdx.z];
-  const int wave = threadIdx.x >> 6;
-  if (t.B == 0) return;
-  const int tk = (t.K + 63) / 64, w_tiles = ((t.N + 31) / 32) * tk, w_blocks = (w_tiles + 3) / 4;
-  if ((int)blockIdx.x < w_blocks * a.S) {
-    const int s = blockIdx.x / w_blocks, id = (blockIdx.x % w_blocks) * 4 + wave;
-    if (id >= w_tiles) return;                               // (wave-uniform)
-    const size_t nk = (size_t)t.N * t.K;
-    t.dw = a.ws[blockIdx.z] + (size_t)s * (nk + t.N);
-    t.db = t.dw + nk;
-    const int mb = s * a.chunk[blockIdx.z];                  // (a chunk past the last row sums nothing and writes zeros)
-    ens_wgrad_tile(t, (id / tk) * 32, (id % tk) * 64, mb, mb + a.chunk[blockIdx.z]);
-    return;
-  }
-  if (!t.dprev) return;
-  const int id = blockIdx.x - w_blocks * a.S, tm = (t.B + 127) / 128;
-  if (id >= tm * tk) return;
-  const int mb = (id / tk) * 128 + wave * 32;
-  if (mb >= t.B) return;                                     // (wave-uniform)
-  ens_dgrad_tile<ACT>(t, mb, (id % tk) * 64);
-}
-__global__ __launch_bounds__(256) void mlp_split_sum_kernel(const CqlSplitArgs a) {
-  const EnsBwdTile t = a.g[blockIdx.z];
-  if (t.B == 0) return;
-  const size_t nk = (size_t)t.N * t.K, per = nk + t.N, idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= per) return;
-  const float* p = a.ws[blockIdx.z] + idx;
-  float s = p[0];                                            // (S = 1 hands the one partial on bit for bit)
-  for (int c = 1; c < a.S; ++c) s += p[(size_t)c * per];
-  if (idx < nk) t.dw[idx] = s;
-  else t.db[idx - nk] = s;
-}
+// grouped layers of mlp.hip and the heads of iql.hip.  The reparameterised TanhNormal sample with its log-probability from the
+// pre-tanh value, and its backward; the fused SAC policy head with the entropy-temperature step; the fused CQL critic head (backup,
+// MSE, importance-weighted log-sum-exp, their gradients).  All fp32, no atomics, a fixed summation order: two identical calls give
+// bitwise identical results.
+#include "rl_head.h"
 
 // ---- reparameterised TanhNormal sample (rlkit/torch/distributions.py:339-386, gaussian_policy.py:113-146): one thread per
 //      output row m * rep + r, the A components in order ------------------------------------------------------------------------------
-__device__ __forceinline__ float cql_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 struct CqlSampleArgs {
   const float* raw; int rp; const float* eps; int ep; int M, A, rep;
   float* action; int ap, agroup; float* logp; int lgroup; float* u; int up;
@@ -87,7 +25,7 @@ __global__ __launch_bounds__(256) void cql_rsample_kernel(const CqlSampleArgs a)
     const float u = rw[d] + expf(ls) * ev;
     lp += -0.5f * ev * ev - ls - 0.91893853320467274f;       // 0.5 log 2 pi;  (u - mu) / sigma IS eps
     const float x = -2.f * u;
-    corr += 0.69314718055994531f - u - cql_softplus(x);
+    corr += 0.69314718055994531f - u - head_softplus(x);
     if (ac) ac[d] = tanhf(u);
     if (uo) uo[d] = u;
   }
@@ -119,16 +57,7 @@ __global__ __launch_bounds__(256) void cql_rsample_bwd_kernel(const CqlSampleBwd
 }
 
 // ---- loss heads: one workgroup of 1024 threads, thread t owns the rows t, t + 1024, ...; the per-thread sums are added through LDS
-//      by a halving tree (a fixed order), as the IQL heads add theirs -------------------------------------------------------------------
-template <int S> __device__ __forceinline__ void cql_tree_sum(float (&red)[S][1024], int t) {
-  for (int w = 512; w > 0; w >>= 1) {
-    __syncthreads();
-    if (t < w)
-#pragma unroll
-      for (int s = 0; s < S; ++s) red[s][t] += red[s][t + w];
-  }
-  __syncthreads();
-}
+//      by the halving tree of rl_head.h --------------------------------------------------------------------------------------------------
 struct CqlSacArgs {
   const float *logp, *q1, *q2; int B, tune; float target_entropy, lr, beta1, beta2, eps;
   float* la; int* step; float* alpha; float* losses; float* dlogp; float* dq1; float* dq2;
@@ -141,7 +70,7 @@ __global__ __launch_bounds__(1024) void cql_sac_head_kernel(const CqlSacArgs a) 
   float sl = 0.f;
   for (int b = t; b < a.B; b += 1024) sl += a.logp[b];
   red[0][t] = sl; red[1][t] = 0.f;
-  cql_tree_sum<2>(red, t);
+  head_tree_sum<2>(red, t);
   const float mean_lp = red[0][0] * inv_b;
   if (t == 0) {
     float alpha = 1.f, alpha_loss = 0.f;
@@ -184,7 +113,7 @@ __global__ __launch_bounds__(1024) void cql_sac_head_kernel(const CqlSacArgs a) 
   if (!a.losses) return;                                     // (launch-uniform)
   __syncthreads();
   red[0][t] = sp; red[1][t] = ss;
-  cql_tree_sum<2>(red, t);
+  head_tree_sum<2>(red, t);
   if (t == 0) { a.losses[1] = red[0][0] * inv_b; a.losses[3] = red[1][0] * inv_b; }
 }
 
@@ -234,7 +163,7 @@ __global__ __launch_bounds__(1024) void cql_critic_head_kernel(const CqlCriticAr
   if (!a.losses && !a.std_mean) return;                      // (launch-uniform)
 #pragma unroll
   for (int s = 0; s < 8; ++s) red[s][t] = sum[s];
-  cql_tree_sum<8>(red, t);
+  head_tree_sum<8>(red, t);
   if (t < 2) {
     const float min_qf = red[2 + t][0] * inv_b * a.min_q_weight * a.temp - red[4 + t][0] * inv_b * a.min_q_weight;
     if (a.losses) { a.losses[t] = red[t][0] * inv_b + min_qf; a.losses[2 + t] = min_qf; }
@@ -243,103 +172,6 @@ __global__ __launch_bounds__(1024) void cql_critic_head_kernel(const CqlCriticAr
 }
 
 // ---- entry points -------------------------------------------------------------------------------------------------------------------
-static inline bool cql_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-extern "C" int s2p_mlp_linear_dgrad(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
-  const char* who = "s2p_mlp_linear_dgrad";
-  if (G < 0 || N < 0) S2P_FAIL(-1, "%s: negative size", who);
-  if (G == 0 || N == 0) return 0;
-  if (!groups) S2P_FAIL(-1, "%s: null group table", who);
-  if (G > CQL_MAX_G) S2P_FAIL(-1, "%s: at most %d groups (G %d)", who, CQL_MAX_G, G);
-  if (act_prev != S2P_ACT_NONE && act_prev != S2P_ACT_RELU) S2P_FAIL(-1, "%s: activation %d (none and relu only)", who, act_prev);
-  const bool dot = N <= CQL_DOT_MAX_N;
-  if (!dot && N % 4) S2P_FAIL(-1, "%s: N above %d must be a multiple of 4 (N %d)", who, CQL_DOT_MAX_N, N);
-  CqlBwdArgs a{};
-  int blocks = 0;
-  for (int g = 0; g < G; ++g) {
-    const s2p_mlp_bwd_group& s = groups[g];
-    if (s.rows < 0 || s.K < 0) S2P_FAIL(-1, "%s: group %d: negative size", who, g);
-    if (s.rows == 0 || s.K == 0) continue;
-    if (!s.dpre || !s.w || !s.dprev || (act_prev != S2P_ACT_NONE && !s.pre_prev))
-      S2P_FAIL(-1, "%s: group %d: null tensor (dpre, w, dprev are required, and pre_prev with relu)", who, g);
-    if (!dot && (s.dpre_pitch % 4 || !cql_al16(s.dpre)))
-      S2P_FAIL(-1, "%s: group %d: dpre_pitch must be a multiple of 4 floats, dpre 16-byte aligned", who, g);
-    if (s.dpre_pitch < N || s.prev_pitch < s.K) S2P_FAIL(-1, "%s: group %d: pitch shorter than the row", who, g);
-    if ((int64_t)s.rows * s.K >= ((int64_t)1 << 31)) S2P_FAIL(-1, "%s: group %d: rows * K must stay below 2^31", who, g);
-    a.g[g] = EnsBwdTile{nullptr, s.dpre, s.w, nullptr, nullptr, s.pre_prev, s.dprev, 0, s.dpre_pitch, s.prev_pitch, s.rows, s.K, N};
-    const int b = dot ? cdiv((int64_t)s.rows * s.K, 256) : cdiv(s.rows, 128) * cdiv(s.K, 64);
-    blocks = b > blocks ? b : blocks;
-  }
-  if (blocks == 0) return 0;
-  const hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(blocks, 1, G);
-  if (dot) {
-    if (act_prev == S2P_ACT_RELU) hipLaunchKernelGGL(mlp_dot_dgrad_kernel<ENS_ACT_RELU>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(mlp_dot_dgrad_kernel<ENS_ACT_NONE>, grid, dim3(256), 0, st, a);
-    S2P_CHECK_LAUNCH("mlp_dot_dgrad_kernel");
-    return 0;
-  }
-  if (act_prev == S2P_ACT_RELU) hipLaunchKernelGGL(mlp_dgrad_kernel<ENS_ACT_RELU>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(mlp_dgrad_kernel<ENS_ACT_NONE>, grid, dim3(256), 0, st, a);
-  S2P_CHECK_LAUNCH("mlp_dgrad_kernel");
-  return 0;
-}
-
-static inline size_t cql_split_floats(const s2p_mlp_bwd_group& s, int N, int S) {
-  return (s.rows <= 0 || s.K <= 0) ? 0 : (size_t)S * ((size_t)N * s.K + N);
-}
-extern "C" size_t s2p_mlp_linear_bwd_split_workspace(const s2p_mlp_bwd_group* groups, int G, int N, int S) {
-  if (!groups || G <= 0 || G > CQL_MAX_G || N <= CQL_DOT_MAX_N || N % 4 || S < 1 || S > 64) return 0;
-  size_t n = 0;
-  for (int g = 0; g < G; ++g) n += cql_split_floats(groups[g], N, S);
-  return n * sizeof(float);
-}
-extern "C" int s2p_mlp_linear_bwd_split(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, int S, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  const char* who = "s2p_mlp_linear_bwd_split";
-  if (G < 0 || N < 0) S2P_FAIL(-1, "%s: negative size", who);
-  if (G == 0 || N == 0) return 0;
-  if (!groups) S2P_FAIL(-1, "%s: null group table", who);
-  if (G > CQL_MAX_G) S2P_FAIL(-1, "%s: at most %d groups (G %d)", who, CQL_MAX_G, G);
-  if (act_prev != S2P_ACT_NONE && act_prev != S2P_ACT_RELU) S2P_FAIL(-1, "%s: activation %d (none and relu only)", who, act_prev);
-  if (S < 1 || S > 64) S2P_FAIL(-1, "%s: S must be in [1, 64] (S %d)", who, S);
-  if (N <= CQL_DOT_MAX_N || N % 4) S2P_FAIL(-1, "%s: the MFMA-tile form only: N above %d and a multiple of 4 (N %d)", who, CQL_DOT_MAX_N, N);
-  CqlSplitArgs a{};
-  a.S = S;
-  int blocks = 0, sum_blocks = 0;
-  size_t off = 0;
-  for (int g = 0; g < G; ++g) {
-    const s2p_mlp_bwd_group& s = groups[g];
-    if (s.rows < 0 || s.K < 0) S2P_FAIL(-1, "%s: group %d: negative size", who, g);
-    if (s.rows == 0 || s.K == 0) continue;
-    if (!s.x || !s.dpre || !s.dw || !s.db) S2P_FAIL(-1, "%s: group %d: null tensor (x, dpre, dw, db are required)", who, g);
-    if (s.dprev && (!s.w || (act_prev != S2P_ACT_NONE && !s.pre_prev))) S2P_FAIL(-1, "%s: group %d: dprev needs w (and pre_prev with relu)", who, g);
-    if (s.dpre_pitch % 4 || !cql_al16(s.dpre)) S2P_FAIL(-1, "%s: group %d: dpre_pitch must be a multiple of 4 floats, dpre 16-byte aligned", who, g);
-    if (s.x_pitch < s.K || s.dpre_pitch < N || (s.dprev && s.prev_pitch < s.K)) S2P_FAIL(-1, "%s: group %d: pitch shorter than the row", who, g);
-    if ((int64_t)s.rows * s.K >= ((int64_t)1 << 31)) S2P_FAIL(-1, "%s: group %d: rows * K must stay below 2^31", who, g);
-    if (!workspace) S2P_FAIL(-1, "%s: null workspace", who);
-    a.g[g] = EnsBwdTile{s.x, s.dpre, s.w, s.dw, s.db, s.pre_prev, s.dprev, s.x_pitch, s.dpre_pitch, s.prev_pitch, s.rows, s.K, N};
-    a.ws[g] = (float*)workspace + off;
-    a.chunk[g] = cdiv(cdiv(s.rows, S), 16) * 16;             // a multiple of the tile's row step; the last chunk is the shorter one
-    off += cql_split_floats(s, N, S);
-    const int tk = cdiv(s.K, 64);
-    const int b = cdiv((int64_t)cdiv(N, 32) * tk, 4) * S + (s.dprev ? cdiv(s.rows, 128) * tk : 0);
-    blocks = b > blocks ? b : blocks;
-    const int sb = cdiv((int64_t)N * s.K + N, 256);
-    sum_blocks = sb > sum_blocks ? sb : sum_blocks;
-  }
-  if (blocks == 0) return 0;
-  if (workspace_bytes < off * sizeof(float))
-    S2P_FAIL(-1, "%s: workspace of %zu bytes, %zu needed (s2p_mlp_linear_bwd_split_workspace)", who, workspace_bytes, off * sizeof(float));
-  const hipStream_t st = (hipStream_t)stream;
-  if (act_prev == S2P_ACT_RELU) hipLaunchKernelGGL(mlp_bwd_split_kernel<ENS_ACT_RELU>, dim3(blocks, 1, G), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(mlp_bwd_split_kernel<ENS_ACT_NONE>, dim3(blocks, 1, G), dim3(256), 0, st, a);
-  S2P_CHECK_LAUNCH("mlp_bwd_split_kernel");
-  hipLaunchKernelGGL(mlp_split_sum_kernel, dim3(sum_blocks, 1, G), dim3(256), 0, st, a);
-  S2P_CHECK_LAUNCH("mlp_split_sum_kernel");
-  return 0;
-}
-
 extern "C" int s2p_tanh_gauss_rsample(const float* raw, int raw_pitch, const float* eps, int eps_pitch, int M, int A, int rep,
                                       float* action, int action_pitch, int action_group, float* logp, int logp_group, float* u,
                                       int u_pitch, void* stream) {

@@ -1,5 +1,5 @@
 // The wave tiles of the grouped fp32 linear layers, shared by the ensemble entry points (ensemble_train.hip: group = ensemble member,
-// Swish) and the IQL entry points (iql.hip: group = network, ReLU or identity, a row count and an input width per group).  A tile
+// Swish) and the grouped MLP entry points (mlp.hip: group = network, ReLU or identity, a row count and an input width per group).  A tile
 // function is handed ONE group's view -- base pointers already offset to the group's slot and column -- and the tile's origin;
 // the caller's kernel only maps its grid onto groups and tiles.  All fp32 on v_mfma_f32_32x32x2_f32 (lane l holds
 // A[row l & 31][k = l >> 5] and B[k = l >> 5][col l & 31]; result register r of lane l is
@@ -175,7 +175,7 @@ template <int ACT> __device__ __forceinline__ void ens_dgrad_tile(const EnsBwdTi
 }
 
 // ---- the input gradient of a narrow layer (N <= 16: plain dot products, no tile): element idx = m K + k of dprev, n in order.
-//      Shared by the full backward of iql.hip and the input-gradient-only entry point of cql.hip, which must agree bit for bit.
+//      Shared by the full backward and the input-gradient-only entry point of mlp.hip, which must agree bit for bit.
 template <int ACT> __device__ __forceinline__ void ens_dot_dgrad_elem(const EnsBwdTile& t, long long idx) {
   if (idx >= (long long)t.B * t.K) return;
   const int m = (int)(idx / t.K), k = (int)(idx - (long long)m * t.K);

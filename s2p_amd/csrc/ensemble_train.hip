@@ -126,7 +126,6 @@ __global__ __launch_bounds__(1024) void ens_nll_kernel(const EnsNllArgs a) {
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------------------
-static inline bool ens_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static int ens_sel(const char* who, const int32_t* member, int G, int E, EnsSel* s) {
   if (E < 1 || E > ENS_MAX_G || G > E) S2P_FAIL(-1, "%s: 1 <= G <= E <= %d needed (G %d, E %d)", who, ENS_MAX_G, G, E);
   for (int g = 0; g < ENS_MAX_G; ++g) s->m[g] = 0;
@@ -145,7 +144,7 @@ extern "C" int s2p_ensemble_linear_fwd(const float* x, int64_t x_gstride, int x_
   if (G == 0 || B == 0 || N == 0) return 0;
   EnsSel sel; if (int rc = ens_sel(who, member, G, E, &sel)) return rc;
   if (!x || !w || !bias || (!pre && !act)) S2P_FAIL(-1, "%s: null tensor (x, w, bias and one of pre / act are required)", who);
-  if (K == 0 || K % 4 || x_pitch % 4 || x_gstride % 4 || !ens_al16(x) || !ens_al16(w))
+  if (K == 0 || K % 4 || x_pitch % 4 || x_gstride % 4 || !s2p_al16(x) || !s2p_al16(w))
     S2P_FAIL(-1, "%s: K, x_pitch, x_gstride must be multiples of 4 floats (K > 0), x and w 16-byte aligned", who);
   if (x_pitch < K || (int64_t)y_pitch < (int64_t)G * N) S2P_FAIL(-1, "%s: pitch shorter than the row", who);
   EnsFwdArgs a{x, (long long)x_gstride, x_pitch, w, bias, pre, act, y_pitch, B, K, N, sel};
@@ -163,7 +162,7 @@ extern "C" int s2p_ensemble_linear_bwd(const float* x, int64_t x_gstride, int x_
   EnsSel sel; if (int rc = ens_sel(who, member, G, E, &sel)) return rc;
   if (!x || !dpre || !dw || !db) S2P_FAIL(-1, "%s: null tensor (x, dpre, dw, db are required)", who);
   if (dprev && (!w || !pre_prev)) S2P_FAIL(-1, "%s: dprev needs w and pre_prev", who);
-  if (K % 4 || N % 4 || dpre_pitch % 4 || !ens_al16(dpre))
+  if (K % 4 || N % 4 || dpre_pitch % 4 || !s2p_al16(dpre))
     S2P_FAIL(-1, "%s: K, N, dpre_pitch must be multiples of 4 floats, dpre 16-byte aligned", who);
   if (x_pitch < K || (int64_t)dpre_pitch < (int64_t)G * N || (dprev && (int64_t)prev_pitch < (int64_t)G * K))
     S2P_FAIL(-1, "%s: pitch shorter than the row", who);

@@ -179,6 +179,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline bool s2p_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // compute units of the current device (256 where there is none to ask: the workspace queries answer without a GPU)
 inline int s2p_num_cus() {

@@ -1,4 +1,4 @@
-"""N3e -- the CQL step on HIP (s2p_amd/cql.py, csrc/cql.hip).  PINNED parity: tests/golden/cql_golden_v1.npz holds fp64 results of
+"""N3e -- the CQL step on HIP (s2p_amd/cql.py, csrc/mlp.hip, csrc/cql.hip).  PINNED parity: tests/golden/cql_golden_v1.npz holds fp64 results of
 the REAL reference trainer, the noise it drew, and `ref32_err`, the deviation of the trainer's own fp32 run from them; a larger shape,
 which the fixture does not hold, is checked against tests/cql_ref.py run in fp64 and fp32 on the CPU inside the test
 (tests/test_cql.py pins that restatement to the fixture at 1e-9).

@@ -1,4 +1,4 @@
-"""Kernel-level parity of csrc/cql.hip through the C ABI against float64 torch on the CPU: the input-gradient half of the grouped
+"""Kernel-level parity of csrc/cql.hip and the CQL half of csrc/mlp.hip through the C ABI against float64 torch on the CPU: the input-gradient half of the grouped
 backward (bitwise against s2p_mlp_linear_bwd), the row-split backward (S = 1 bitwise, S > 1 against fp64), the reparameterised TanhNormal sample and its backward, the fused SAC policy head
 with the entropy-temperature step, the fused CQL critic head, the refused arguments, and bitwise repeatability of every entry point.
 

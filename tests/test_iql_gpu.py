@@ -1,4 +1,4 @@
-"""N3d -- the IQL step on HIP (s2p_amd/iql.py, csrc/iql.hip).  PINNED parity: tests/golden/iql_golden_v1.npz holds fp64 results of
+"""N3d -- the IQL step on HIP (s2p_amd/iql.py, csrc/mlp.hip, csrc/iql.hip).  PINNED parity: tests/golden/iql_golden_v1.npz holds fp64 results of
 the REAL reference trainer and `ref32_err`, the deviation of the trainer's own fp32 run from them; the production widths, which the
 fixture does not hold, are checked against tests/iql_ref.py run in fp64 and fp32 on the CPU inside the test (tests/test_iql.py pins
 that restatement to the fixture at 1e-9).
@@ -211,6 +211,51 @@ def test_train_from_torch_on_a_tiny_real_buffer(hip_device, freeze):
     assert all(same) if freeze else not any(same)
     c1 = tr.critic.state_dict()
     assert all(not torch.equal(c0[k], c1[k]) for k in c0 if k.endswith("weight"))
+
+
+def test_the_step_and_act_run_the_policy_through_one_table_builder(hip_device):
+    """The trainer's grouped forward (the policy as group 5 of 6, then alone on the narrow last layer) and `TanhGaussianPolicy.act`
+    (one group a launch, two ping-pong buffers) build their groups in s2p_amd/mlp.py and call the same kernels on the same operands:
+    the step's pre-update policy output is `act`'s, bit for bit.  Hidden widths off the 32 / 64 tile, a partial row tile."""
+    from s2p_amd.iql import CriticSLAC, IQLTrainer, Qfunction, TanhGaussianPolicy, Vfunction
+    z, a, p, b, hid = 10, 3, 13, 37, [20, 24]
+    torch.manual_seed(11)
+    q = [Qfunction(hidden_sizes=hid, output_size=1, input_size=z + a) for _ in range(4)]
+    critic = CriticSLAC(q[0], q[1], q[2], q[3], vf=Vfunction(hidden_sizes=hid, output_size=1, input_size=z), device=hip_device)
+    policy = TanhGaussianPolicy(hidden_sizes=hid, obs_dim=p, action_dim=a, device=hip_device)
+    before = policy.state_dict()
+    tr = IQLTrainer(None, policy, critic=critic, **R.CFG)
+    batch = R.make_batch(b, z, a, p, 5, terminals=True)
+    _step(tr, batch)
+    raw = tr._buf[b]["raw"]
+    assert not torch.equal(policy.state_dict()["fc0.weight"], before["fc0.weight"])            # the step did move the policy
+    other = TanhGaussianPolicy(hidden_sizes=hid, obs_dim=p, action_dim=a, device=hip_device).load_state_dict(before)
+    got = other.act(batch["policy_input"])
+    assert got.shape == (b, a) and float(got.abs().max()) > 0
+    assert torch.equal(torch.tanh(raw[:, :a]), got)
+
+
+def test_act_keeps_its_scratch_buffers_between_calls(hip_device):
+    """`act` caches a table of bare addresses per batch size, so the cached entry must own every buffer the table names: tensors
+    allocated between two calls (of the scratch buffers' very size, which a caching allocator would hand freed memory to first)
+    keep their values, an earlier result the caller still holds keeps its own, and the second call returns the first's result."""
+    from s2p_amd.iql import TanhGaussianPolicy
+    p, a, b, hid = 13, 3, 37, [20, 24]
+    torch.manual_seed(12)
+    policy = TanhGaussianPolicy(hidden_sizes=hid, obs_dim=p, action_dim=a, device=hip_device)
+    x = torch.randn(b, p, generator=torch.Generator().manual_seed(6))
+    first = policy.act(x)
+    kept = first.clone()
+    net, table = policy._eval[b]
+    owned = {t.data_ptr() for t in [net.x, net.out] + net.act}
+    named = {g.x for gs, G, N, act in table for g in gs[:G]} | {g.pre or g.act for gs, G, N, act in table for g in gs[:G]}
+    assert named <= owned and len(named) == 4                                                  # xp, two scratch buffers, raw
+    sentinels = [torch.full((b, max(hid)), 7.0, device=hip_device) for _ in range(4)] + [torch.full((b, 2 * a), 7.0, device=hip_device)]
+    assert not {t.data_ptr() for t in sentinels} & owned
+    second = policy.act(x)
+    torch.cuda.synchronize()
+    assert all(bool((t == 7.0).all()) for t in sentinels)
+    assert torch.equal(first, kept) and torch.equal(second, kept)
 
 
 def test_zz_report_worst_ratios(hip_device):

@@ -1,4 +1,4 @@
-"""Kernel-level parity of csrc/iql.hip through the C ABI against float64 torch on the CPU: the grouped ReLU linear layer forward and
+"""Kernel-level parity of csrc/mlp.hip and csrc/iql.hip through the C ABI against float64 torch on the CPU: the grouped ReLU linear layer forward and
 backward (MFMA tiles for N > 16, dot-product kernels for the N = 1 / N = 2 A last layers), the two fused loss heads, the Polyak
 update, the refused arguments, and bitwise repeatability of every entry point.
 

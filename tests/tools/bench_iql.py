@@ -21,8 +21,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import iql_ref as R  # noqa: E402
-from s2p_amd._lib import ACT_NONE, ACT_RELU, check, lib, stream  # noqa: E402
+from s2p_amd._lib import check, lib, stream  # noqa: E402
 from s2p_amd.iql import CriticSLAC, IQLTrainer, Qfunction, TanhGaussianPolicy, Vfunction  # noqa: E402
+from s2p_amd.mlp import run  # noqa: E402
 
 Z, A, H, P, B = 288, 6, 1024, 2090, 256
 CFG = dict(discount=0.99, policy_lr=1e-4, qf_lr=3e-4, reward_scale=1, soft_target_tau=0.005, beta=0.1, quantile=0.7, clip_score=100,
@@ -96,17 +97,14 @@ def main():
     calls = len(t["fwd"]) + 2 + len(t["bwd"]) + 2 + 0.5
     stages = {
         "staging_copies": timed(lambda: _stage(tr, t, args), a.iters, a.warmup, 3),
-        "forward_%d_launches" % len(t["fwd"]): timed(lambda: [check(L.s2p_mlp_linear_fwd(g, G, N, act, st), "fwd")
-                                                              for (g, G, N), act in zip(t["fwd"], t["fwd_act"])], a.iters, a.warmup, 3),
-        "backward_%d_launches" % len(t["bwd"]): timed(lambda: [check(L.s2p_mlp_linear_bwd(g, G, N, ACT_RELU if i < len(t["bwd"]) - 1 else ACT_NONE, st), "bwd")
-                                                               for i, (g, G, N) in enumerate(t["bwd"])], a.iters, a.warmup, 3),
+        "forward_%d_launches" % len(t["fwd"]): timed(lambda: run(t["fwd"]), a.iters, a.warmup, 3),
+        "backward_%d_launches" % len(t["bwd"]): timed(lambda: run(t["bwd"], "s2p_mlp_linear_bwd"), a.iters, a.warmup, 3),
         "two_adam_steps": timed(lambda: (tr.critic_optimizer.step(), tr.policy_optimizer.step()), a.iters, a.warmup, 3),
     }
-    for i, (g, G, N) in enumerate(t["fwd"]):
-        stages["forward_launch_%d_G%d_N%d" % (i, G, N)] = timed(lambda: check(L.s2p_mlp_linear_fwd(g, G, N, t["fwd_act"][i], st), "fwd"), a.iters, a.warmup, 3)
-    for i, (g, G, N) in enumerate(t["bwd"]):
-        stages["backward_launch_%d_G%d_N%d" % (i, G, N)] = timed(
-            lambda: check(L.s2p_mlp_linear_bwd(g, G, N, ACT_RELU if i < len(t["bwd"]) - 1 else ACT_NONE, st), "bwd"), a.iters, a.warmup, 3)
+    for i, (g, G, N, act) in enumerate(t["fwd"]):
+        stages["forward_launch_%d_G%d_N%d" % (i, G, N)] = timed(lambda: check(L.s2p_mlp_linear_fwd(g, G, N, act, st), "fwd"), a.iters, a.warmup, 3)
+    for i, (g, G, N, act) in enumerate(t["bwd"]):
+        stages["backward_launch_%d_G%d_N%d" % (i, G, N)] = timed(lambda: check(L.s2p_mlp_linear_bwd(g, G, N, act, st), "bwd"), a.iters, a.warmup, 3)
     print(json.dumps({"bench": "iql_train_from_latents", "Z": Z, "A": A, "H": H, "P": P, "B": B, "hip_ms": hip[0], "hip_ms_min_max": hip[1:],
                       "torch_eager_ms": ref[0], "torch_eager_ms_min_max": ref[1:], "speedup": round(ref[0] / hip[0], 2),
                       "library_calls_per_step": calls, "kernel_launches_per_step": calls + 2, "staging_copies_per_step": 8,
