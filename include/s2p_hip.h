@@ -445,6 +445,19 @@ int s2p_ensemble_nll(const float* raw, int raw_pitch, const float* xin, int64_t 
                      float scale, float bound_reg, float* sums, float* loss, float* draw, int draw_pitch, float* dmin_logstd,
                      float* dmax_logstd, float* mean, float* std, void* stream);
 
+/* ---- state-transition rollout input (SPEC.md N2c; reference state_transition_rollout.py:149, 180; csrc/transition.hip).
+ * Raw observations [rows][obs_pitch] and actions [rows][act_pitch] of a whole dataset -> the ensemble's first-layer input
+ *   x[r][j] = (obs[r][j] - obs_mean[j]) / obs_std[j]   j < obs_dim
+ *           = action[r][j - obs_dim]                   the next act_dim columns
+ *           = 0                                        every remaining column up to x_pitch
+ * in ONE launch, row offsets 64-bit.  The subtraction and the division are separately rounded IEEE fp32 operations (a true
+ * division), so x equals numpy's fp32 `(obs - mean) / std` bit for bit.  x_pitch % 4 == 0 with a 16-byte aligned x takes
+ * 16-byte stores; any other pitch or alignment a per-element kernel.  Negative sizes, a required NULL pointer and a pitch
+ * shorter than its row (x_pitch < obs_dim + act_dim, obs_pitch < obs_dim, act_pitch < act_dim) are refused before any launch;
+ * rows == 0 is a successful no-op that looks at no pointer.                                                                  */
+int s2p_transition_pack(const float* obs, int obs_pitch, const float* action, int act_pitch, const float* obs_mean,
+                        const float* obs_std, int64_t rows, int obs_dim, int act_dim, float* x, int x_pitch, void* stream);
+
 /* ---- IQL on SLAC latents (SPEC.md N3d; reference rlkit/torch/sac/iql_trainer.py:209-435; the grouped layers s2p_mlp_linear_* in
  * csrc/mlp.hip, the heads and the Polyak update in csrc/iql.hip).
  * All fp32, the wide layers on v_mfma_f32_32x32x2_f32, no atomics, a fixed summation order (two identical calls give bitwise

@@ -141,6 +141,7 @@ SIGNATURES = {
                                 _P, _P, _P, _P, c_int, _P],
     "s2p_ensemble_nll": [_P, c_int, _P, c_int64, c_int, _P, c_int64, c_int, c_int, c_int, c_int, _P, _P, c_float, c_float,
                          _P, _P, _P, c_int, _P, _P, _P, _P, _P],
+    "s2p_transition_pack": [_P, c_int, _P, c_int, _P, _P, c_int64, c_int, c_int, _P, c_int, _P],
     "s2p_mlp_linear_fwd": [ctypes.POINTER(MlpFwdGroup), c_int, c_int, c_int, _P],
     "s2p_mlp_linear_bwd": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, _P],
     "s2p_iql_critic_head": [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _P, _P,

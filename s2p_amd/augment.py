@@ -2,7 +2,7 @@
 ("Then, you should run generation code...", README.md:54).
 
 Input  : the file written by the reference's `state_transition_rollout.py:222-243`
-         (`all_state_1step_random_action_dataset_augment.hdf5`, or an .npz with the same keys):
+         (`all_state_1step_random_action_dataset_augment.hdf5`, or an .npz with the same keys: what rollout_dynamics.py writes):
          `image_observations` uint8 [N,H,W,3] (I_t, NHWC) and `next_observations` fp32 [N,S] (predicted s_{t+1}).
 Output : the same keys plus `image_observations_tp1` uint8 [N,H,W,3] = G(I_t, s_{t+1}), the key and layout the
          reference's RL consumer reads (`rlkit/torch/slac/algo.py:189-190`, used at :336).

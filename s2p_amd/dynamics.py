@@ -7,6 +7,8 @@ per-batch post-processing of state_transition_rollout.py:180-204, running on HIP
     the same input for every group via x_gstride = 0), Swish fused in the epilogue;
   * one fused head kernel does soft-clamp + exp, the 'local'-mode residual, member pick + de-normalisation and the
     disagreement / aleatoric reductions (s2p_ensemble_head).
+The rollout of a whole dataset (SPEC.md N2c) is `rollout_sweep`: one s2p_transition_pack launch for the input of every row, then the
+grouped fp32 layers and the head per chunk of rows, writing into dataset-long outputs.
 Training (SPEC.md N2b): the parameters live in ONE flat fp32 buffer in the packed layout the forward consumes, beside flat
 gradient / Adam-moment buffers of the same layout, so an optimizer step is one s2p_adam_step_dev launch.  A train step is
 4 grouped linear forwards that keep the pre-activations, 1 fused NLL head, 4 grouped linear backwards, 1 Adam
@@ -274,6 +276,62 @@ class EnsembleTransition:
         check(lib().s2p_ensemble_head(ptr(raw), raw.shape[3], ptr(x), x.shape[3], B, self.E, self.D, ptr(self.min_logstd),
                                       ptr(self.max_logstd), None, None, ptr(idx), ptr(om), ptr(os_), float(reward_mean),
                                       float(reward_std), ptr(nobs), ptr(rew), ptr(dis), ptr(ale), stream()), "s2p_ensemble_head")
+        return nobs, rew, dis, ale
+
+    @torch.no_grad()
+    def rollout_sweep(self, observations, actions, ensemble_idx, obs_mean, obs_std, next_obs_mean, next_obs_std, reward_mean,
+                      reward_std, chunk=16384):
+        """The whole `all_state_1step_random_action` rollout of a dataset (state_transition_rollout.py:149-204, SPEC.md N2c) on
+        the device: RAW fp32 observations [N, obs_dim], actions [N, A] and member indices [N], each uploaded once -> (next_obs
+        [N, obs_dim], reward [N], disagreement [N, 1], aleatoric [N, 1]) fp32 on the device.  One s2p_transition_pack launch
+        normalises and packs every row; then per `chunk` rows the grouped fp32 layer chain over ALL E members (the reference
+        picks among all of them, not among the elites: `select` is neither read nor changed) and one s2p_ensemble_head that
+        writes straight into the dataset-long outputs.  No host synchronisation.  The sweep owns its activations: two ping-pong
+        [chunk][E * width] buffers and the raw head input.  A row's result does not depend on `chunk`, bit for bit."""
+        dev, E, D, f32, L = self.device, self.E, self.D, torch.float32, lib()
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be positive")
+        obs = torch.as_tensor(observations, dtype=f32).to(dev).contiguous()
+        act = torch.as_tensor(actions, dtype=f32).to(dev).contiguous()
+        N = obs.shape[0]
+        if obs.shape != (N, self.obs_dim) or act.shape != (N, self.action_dim):
+            raise ValueError("observations [N, %d] and actions [N, %d] are needed, got %s and %s" % (
+                self.obs_dim, self.action_dim, tuple(obs.shape), tuple(act.shape)))
+        idx = torch.as_tensor(ensemble_idx).reshape(-1)
+        if idx.numel() != N or (N and not idx.is_cuda and (int(idx.min()) < 0 or int(idx.max()) >= E)):   # (host indices only: no device sync)
+            raise ValueError("ensemble_idx: %d member indices in [0, %d) are needed" % (N, E))
+        idx = idx.to(dev, torch.int32).contiguous()
+
+        def vec(v):
+            v = torch.as_tensor(v, dtype=f32).reshape(-1).to(dev).contiguous()
+            if v.numel() != self.obs_dim:
+                raise ValueError("a normalisation vector has %d entries, obs_dim is %d" % (v.numel(), self.obs_dim))
+            return v
+        om, os_, nom, nos = vec(obs_mean), vec(obs_std), vec(next_obs_mean), vec(next_obs_std)
+        kp = self._off[0][2]
+        x = ops.transition_pack(obs, act, om, os_, torch.empty((N, kp), dtype=f32, device=dev))
+        nobs = torch.empty((N, self.obs_dim), dtype=f32, device=dev)
+        rew = torch.empty((N,), dtype=f32, device=dev)
+        dis = torch.empty((N, 1), dtype=f32, device=dev)
+        ale = torch.empty((N, 1), dtype=f32, device=dev)
+        rows = min(chunk, N)
+        widths = [cout for _, cout in self._dims]
+        ping = [torch.empty(rows * E * max(widths[:-1]), dtype=f32, device=dev) for _ in range(min(2, len(widths) - 1))]
+        raw = torch.empty((rows, E * 2 * D), dtype=f32, device=dev)
+        for lo in range(0, N, chunk):
+            B = min(chunk, N - lo)
+            xc = x[lo:lo + B]
+            h, hg, hp = xc, 0, kp
+            for li, ((cin, cout), (geom, w, b, k)) in enumerate(zip(self._dims, self.layers)):
+                last = li == len(self.layers) - 1
+                y = raw if last else ping[li % 2]
+                check(L.s2p_ensemble_linear_fwd(ptr(h), hg, hp, ptr(w), ptr(b), None, E, E, B, k, cout, ptr(y) if last else None,
+                                                None if last else ptr(y), E * cout, stream()), "s2p_ensemble_linear_fwd")
+                h, hg, hp = y, cout, E * cout
+            check(L.s2p_ensemble_head(ptr(raw), E * 2 * D, ptr(xc), kp, B, E, D, ptr(self.min_logstd), ptr(self.max_logstd), None,
+                                      None, ptr(idx[lo:]), ptr(nom), ptr(nos), float(reward_mean), float(reward_std),
+                                      ptr(nobs[lo:]), ptr(rew[lo:]), ptr(dis[lo:]), ptr(ale[lo:]), stream()), "s2p_ensemble_head")
         return nobs, rew, dis, ale
 
 

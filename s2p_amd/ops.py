@@ -587,6 +587,24 @@ def window_gather_u8(pool, table, win, dtype, pitch=None, want_x=True, want_u8=T
     return x, u8
 
 
+def transition_pack(obs, action, obs_mean, obs_std, out):
+    """out[r] = [(obs[r] - obs_mean) / obs_std | action[r] | 0 ...] for every row of a dataset in one launch (csrc/transition.hip):
+    the two operations separately rounded in fp32, i.e. numpy's `(obs - mean) / std` bit for bit.  obs [N,obs_dim], action [N,A] and
+    are 2-D fp32 views with unit stride in their last dimension (the row pitch is the view's stride); out [N,pitch >= obs_dim + A]
+    is dense (every column of it is written) at any alignment; obs_mean / obs_std are contiguous fp32 [obs_dim]."""
+    (po, so), (pa, sa), (px, sx) = _view2(obs), _view2(action), _view2(out)
+    N, obs_dim, A = obs.shape[0], obs.shape[1], action.shape[1]
+    if sx != out.shape[1]:
+        raise ValueError("out must be dense: its row pitch is its width")
+    if action.shape[0] != N or out.shape[0] != N or obs_mean.shape != (obs_dim,) or obs_std.shape != (obs_dim,):
+        raise ValueError("obs [N,obs_dim], action [N,A], out [N,pitch], obs_mean / obs_std [obs_dim] are needed")
+    if obs_mean.dtype != torch.float32 or obs_std.dtype != torch.float32 or not (obs_mean.is_contiguous() and obs_std.is_contiguous()):
+        raise ValueError("obs_mean and obs_std must be contiguous fp32")
+    check(lib().s2p_transition_pack(po, so, pa, sa, ptr(obs_mean), ptr(obs_std), N, obs_dim, A, px, out.shape[1], stream()),
+          "s2p_transition_pack")
+    return out
+
+
 # ---- SLAC latent model (csrc/gauss.hip).  Arguments are 2-D fp32 VIEWS (unit stride in the last dimension): the row pitch is the
 # view's stride, so a slice of a [B,S+1,288] sequence buffer is read or written in place -- no cat / chunk / stack copy.
 def _view2(t):
