@@ -249,13 +249,16 @@ int s2p_in_norm_bwd_res(int dtype, const void* da, int da_pitch, const void* x, 
 /* Small fp32 linear layers of the state path (replaces F.linear + LeakyReLU and their autograd backward for the
  * StateMapping MLP and the per-norm state affine; batch M of a few dozen rows: latency-bound, csrc/linear_small.hip).
  * y[M][y_pitch] = act(x[M][K] . w[N][w_row]^T + bias[N]); columns [N, n_store) of y are written as zeros.
- * K, pitches and w_row must be multiples of 4 floats.                                    */
+ * K, pitches and w_row must be multiples of 4 floats.  act: any of S2P_ACT_NONE .. S2P_ACT_SWISH (tanh as tanhf, swish as
+ * v / (1 + exp(-v))); any other id is refused before the launch.  M == 0 (an empty batch) is a successful no-op that looks at
+ * no pointer, here and in s2p_linear_bwd; M < 0, K <= 0 and N <= 0 are refused.            */
 int s2p_linear_fwd(const float* x, int M, int K, int x_pitch, const float* w, int w_row, const float* bias, int N,
                    int act, float slope, float* y, int y_pitch, int n_store, void* stream);
 /* Backward given dy = dL/dy and the layer OUTPUT y (needed when act != NONE; dpre = dy * act'(y)):
  *   dw[N][dw_row] += dpre^T . x (columns < k_real), db[N] += sum_m dpre (db may be NULL),
  *   dx[M][dx_pitch] = dpre . w  (dx may be NULL; needs w_bwd [K][wb_row], the transpose of w).
- * No atomics: fixed summation order.  workspace: s2p_linear_bwd_workspace(M,K,N) bytes (0 for N < 2048).
+ * No atomics: fixed summation order.  workspace: s2p_linear_bwd_workspace(M,K,N) bytes (0 for N < 2048; needed only with dx);
+ * a missing or short workspace is refused before anything is launched, dw and db included.
  * act: none / relu / lrelu; anything else is refused (the forward also takes tanh and swish).              */
 size_t s2p_linear_bwd_workspace(int M, int K, int N);
 int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int dy_pitch, const float* y, int y_pitch, int M,
@@ -401,7 +404,11 @@ int s2p_hinge_loss_strided(int dtype, const void* x, int64_t pixels, int pitch, 
  *         exp(soft_clamp(logstd, min_logstd, max_logstd))
  * pick  : int32 [B] member index per sample; next_obs [B][D-1] = mean[pick]*obs_std+obs_mean,
  *         reward [B] = mean[pick][D-1]*rew_std+rew_mean
- * disagreement[B] = max_e || mean_e[:D-1] - avg_e mean[:D-1] ||_2 ; aleatoric[B] = max_e || std_e ||_2 */
+ * disagreement[B] = max_e || mean_e[:D-1] - avg_e mean[:D-1] ||_2 ; aleatoric[B] = max_e || std_e ||_2
+ * Argument checking as for the training entry points below: B < 0, a required NULL tensor, raw_pitch < E*2*D and
+ * x_pitch < D-1 are refused before any launch (non-zero, s2p_last_error); B == 0 is a successful no-op that looks at no
+ * pointer.  2 <= D <= 33, E >= 1.  pick[b] outside [0, E): nothing is read out of range, that row of next_obs and its reward
+ * are written as NaN (a poisoned row stays visible downstream); the other rows and the other outputs are unaffected.  */
 int s2p_ensemble_head(const float* raw, int raw_pitch, const float* xin, int x_pitch, int B, int E, int D,
                       const float* min_logstd, const float* max_logstd, float* mean, float* std,
                       const int32_t* pick, const float* obs_mean, const float* obs_std, float rew_mean,
@@ -438,7 +445,7 @@ int s2p_ensemble_linear_bwd(const float* x, int64_t x_gstride, int x_pitch, cons
  *   sums [2G]: sum nll per group, then sum (mu - target)^2 per group;   loss[0] = scale * sum nll + bound_reg * sum_d (max - min)
  *   draw [B][draw_pitch] = scale * d sum nll / d raw (both soft-clamp factors included)
  *   dmin_logstd / dmax_logstd [D] (together) = scale * d sum nll / d bound -/+ bound_reg
- *   mean / std [G][B][D] (the forward alone: target may then be NULL).
+ *   mean / std [G][B][D] (the forward alone: target may then be NULL).  A call with no output at all is refused.
  * The caller owns the scaling: scale = 1 / (G B D), bound_reg = 0.01 / D give the loss of SPEC.md N2b.  2 <= D <= 33.     */
 int s2p_ensemble_nll(const float* raw, int raw_pitch, const float* xin, int64_t x_gstride, int x_pitch, const float* target,
                      int64_t t_gstride, int t_pitch, int B, int G, int D, const float* min_logstd, const float* max_logstd,

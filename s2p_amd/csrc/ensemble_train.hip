@@ -186,7 +186,7 @@ extern "C" int s2p_ensemble_nll(const float* raw, int raw_pitch, const float* xi
   if (G > ENS_MAX_G || D < 2 || D > 33) S2P_FAIL(-1, "%s: G <= %d and 2 <= D <= 33 needed (G %d, D %d)", who, ENS_MAX_G, G, D);
   if (!raw || !xin || !min_logstd || !max_logstd) S2P_FAIL(-1, "%s: null tensor (raw, xin and the two bounds are required)", who);
   if (!target && (sums || loss || draw || dmin_logstd || dmax_logstd)) S2P_FAIL(-1, "%s: the loss outputs need a target", who);
-  if (!target && !mean && !std) S2P_FAIL(-1, "%s: no output", who);
+  if (!sums && !loss && !draw && !dmin_logstd && !dmax_logstd && !mean && !std) S2P_FAIL(-1, "%s: no output", who);
   if (!dmin_logstd != !dmax_logstd) S2P_FAIL(-1, "%s: dmin_logstd and dmax_logstd come together", who);
   if ((int64_t)raw_pitch < (int64_t)G * 2 * D || x_pitch < D - 1 || (target && t_pitch < D) ||
       (draw && (int64_t)draw_pitch < (int64_t)G * 2 * D))

@@ -78,6 +78,7 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
     if (a.ksplit > 1) { a.part[((size_t)z * a.M + mo) * a.n_store + n] = acc[r]; continue; }   // partial tile -> workspace [z][M][n_store]
     float v = nok ? acc[r] + b : 0.f;
     v = a.act == S2P_ACT_LRELU ? (v > 0.f ? v : v * a.slope) : (a.act == S2P_ACT_RELU ? (v > 0.f ? v : 0.f) : v);
+    if (a.act >= S2P_ACT_TANH) v = a.act == S2P_ACT_TANH ? tanhf(v) : v / (1.f + expf(-v));   // (launch-uniform; as act_fwd)
     a.y[(size_t)mo * a.y_pitch + n] = v;
   }
 }
@@ -222,6 +223,7 @@ __global__ __launch_bounds__(256) void lin_fwd_lds_kernel(const LinArgs a) {
     if (m < a.M) {
       float v = n < a.N ? acc[i] + b : 0.f;
       v = a.act == S2P_ACT_LRELU ? (v > 0.f ? v : v * a.slope) : (a.act == S2P_ACT_RELU ? (v > 0.f ? v : 0.f) : v);
+      if (a.act >= S2P_ACT_TANH) v = a.act == S2P_ACT_TANH ? tanhf(v) : v / (1.f + expf(-v));
       a.y[(size_t)m * a.y_pitch + n] = v;
     }
   }
@@ -299,7 +301,7 @@ static inline bool lin_use_lds() { static const int v = s2p_env_set("S2P_LIN_LDS
 #endif
 
 static int lin_check(const char* who, int M, int K, int N, int xp) {
-  if (M <= 0 || K <= 0 || N <= 0) S2P_FAIL(-1, "%s: empty problem", who);
+  if (M < 0 || K <= 0 || N <= 0) S2P_FAIL(-1, "%s: empty problem", who);
   if (K % 4 || xp % 4) S2P_FAIL(-1, "%s: K and pitches must be multiples of 4 floats", who);
   return 0;
 }
@@ -307,8 +309,10 @@ static int lin_check(const char* who, int M, int K, int N, int xp) {
 // y[M][y_pitch] = act(x[M][K] . w[N][w_row]^T + bias); columns [N, n_store) are written as zeros (channel padding)
 extern "C" int s2p_linear_fwd(const float* x, int M, int K, int x_pitch, const float* w, int w_row, const float* bias, int N,
                               int act, float slope, float* y, int y_pitch, int n_store, void* stream) {
+  if (M == 0) return 0;                                    // an empty batch: a no-op that looks at no pointer
   int rc = lin_check("s2p_linear_fwd", M, K, N, x_pitch); if (rc) return rc;
   if (!x || !w || !y || w_row % 4 || n_store < N || n_store > y_pitch) S2P_FAIL(-1, "s2p_linear_fwd: bad arguments");
+  if (act < S2P_ACT_NONE || act > S2P_ACT_SWISH) S2P_FAIL(-1, "s2p_linear_fwd: unknown activation %d", act);
   LinArgs a{}; a.x = x; a.w = w; a.bias = bias; a.y = y; a.M = M; a.Kr = K; a.N = N; a.x_pitch = x_pitch; a.w_row = w_row;
   a.y_pitch = y_pitch; a.n_store = n_store; a.act = act; a.slope = slope; a.ksplit = 1; a.k_per_split = K;
   LIN_LAUNCH_FWD(dim3(cdiv(n_store, 16), cdiv(M, 64), 1), (hipStream_t)stream, a);
@@ -328,12 +332,18 @@ extern "C" int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int 
                               int K, int k_real, int N, const float* w_bwd, int wb_row, int act, float slope, float* dw,
                               int dw_row, float* db, float* dx, int dx_pitch, void* workspace, size_t workspace_bytes,
                               void* stream) {
+  if (M == 0) return 0;                                    // an empty batch: nothing to add to dw / db, no row of dx
   int rc = lin_check("s2p_linear_bwd", M, K, N, x_pitch); if (rc) return rc;
   if (!x || !dy || !dw || dy_pitch % 4 || N % 4) S2P_FAIL(-1, "s2p_linear_bwd: bad arguments (N and pitches must be multiples of 4)");
   if (act != S2P_ACT_NONE && act != S2P_ACT_RELU && act != S2P_ACT_LRELU)      // (lin_actgrad has these three cases only)
     S2P_FAIL(-1, "s2p_linear_bwd: activation %d has no backward here (none / relu / lrelu only)", act);
   if (act != S2P_ACT_NONE && (!y || y_pitch % 4)) S2P_FAIL(-1, "s2p_linear_bwd: the activation output is needed");
   if (dx && (!w_bwd || wb_row % 4)) S2P_FAIL(-1, "s2p_linear_bwd: dx needs w_bwd");
+  // the split-K input gradient's geometry and its workspace, settled before anything is launched
+  const int ks = N >= 2048 ? cdiv(N, 512) : 1;
+  const int kcols = (K + 3) / 4 * 4, dx_cols = kcols <= dx_pitch ? kcols : K;
+  const size_t need = (size_t)ks * M * dx_cols * sizeof(float);
+  if (dx && ks > 1 && (!workspace || workspace_bytes < need)) S2P_FAIL(-1, "s2p_linear_bwd: workspace of %zu bytes needed", need);
   hipStream_t st = (hipStream_t)stream;
   LinArgs a{};
   a.M = M; a.act = act; a.slope = slope;
@@ -345,12 +355,10 @@ extern "C" int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int 
   S2P_CHECK_LAUNCH("lin_wgrad_kernel");
   if (!dx) return 0;
   // dgrad: "x" = dy (with the activation derivative folded in), reduction over N, output columns = the K inputs
-  const int ks = N >= 2048 ? cdiv(N, 512) : 1;
   LinArgs g = a;
   g.x = dy; g.x_pitch = dy_pitch; g.xact = a.yact; g.xact_pitch = y_pitch; g.in_act = act; g.w = w_bwd; g.w_row = wb_row;
   g.bias = nullptr; g.y = dx; g.y_pitch = dx_pitch; g.Kr = N; g.act = S2P_ACT_NONE;
-  const int kcols = (K + 3) / 4 * 4;
-  g.n_store = kcols <= dx_pitch ? kcols : K;
+  g.n_store = dx_cols;
   g.N = K;
   if (ks == 1) {
     g.ksplit = 1; g.k_per_split = g.Kr;
@@ -358,8 +366,6 @@ extern "C" int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int 
     S2P_CHECK_LAUNCH("lin_fwd_kernel(dgrad)");
     return 0;
   }
-  const size_t need = (size_t)ks * M * g.n_store * sizeof(float);
-  if (!workspace || workspace_bytes < need) S2P_FAIL(-1, "s2p_linear_bwd: workspace of %zu bytes needed", need);
   g.part = (float*)workspace; g.ksplit = ks; g.k_per_split = cdiv(g.Kr, ks); g.k_per_split = (g.k_per_split + 63) / 64 * 64;
   g.ksplit = cdiv(g.Kr, g.k_per_split);
   LIN_LAUNCH_FWD(dim3(cdiv(g.n_store, 16), cdiv(M, 64), g.ksplit), st, g);

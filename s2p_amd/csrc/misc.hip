@@ -1028,6 +1028,11 @@ __global__ void ensemble_head_kernel(const float* raw, int rp, const float* xin,
   for (int d = 0; d < Do; ++d) avg[d] = 0.f;
   float amax = 0.f;
   const int pk = pick ? pick[b] : 0;
+  if (pick && (pk < 0 || pk >= E)) {                                         // no such member: a poisoned row, not stale memory
+    const float qnan = __int_as_float(0x7fc00000);
+    for (int d = 0; d < Do; ++d) nobs[(size_t)b * Do + d] = qnan;
+    rew[b] = qnan;
+  }
   for (int e = 0; e < E; ++e) {
     const float* r = raw + (size_t)b * rp + e * 2 * D;
     float s2 = 0.f;
@@ -1038,7 +1043,11 @@ __global__ void ensemble_head_kernel(const float* raw, int rp, const float* xin,
       ls = mn[d] + softplus_f(ls - mn[d]);
       float s = expf(ls);
       s2 += s * s;
-      if (d < Do) avg[d] += mu;
+      // avg lives in registers behind a dynamic index.  The index itself must stay inside the array even where the update is
+      // skipped: hipcc turns `if (d < Do) avg[d] += mu` into an unconditional indexed register write plus a select, and at
+      // D = 33 the write with d = 32 landed on the register that holds b (an illegal address in every later access).
+      const int da = d < Do ? d : 0;
+      avg[da] = d < Do ? avg[da] + mu : avg[da];
       if (mean) mean[((size_t)e * B + b) * D + d] = mu;
       if (sd) sd[((size_t)e * B + b) * D + d] = s;
       if (pick && e == pk) { if (d < Do) nobs[(size_t)b * Do + d] = mu * os[d] + om[d]; else rew[b] = mu * rs + rm; }
@@ -1062,7 +1071,10 @@ extern "C" int s2p_ensemble_head(const float* raw, int raw_pitch, const float* x
                                  const int32_t* pick, const float* obs_mean, const float* obs_std, float rew_mean,
                                  float rew_std, float* next_obs, float* reward, float* disagreement, float* aleatoric,
                                  void* stream) {
+  if (B < 0) S2P_FAIL(-1, "s2p_ensemble_head: negative size");
+  if (B == 0) return 0;
   if (!raw || !xin || !min_logstd || !max_logstd || D < 2 || D > 33 || E < 1) S2P_FAIL(-1, "s2p_ensemble_head: bad argument");
+  if ((int64_t)raw_pitch < (int64_t)E * 2 * D || x_pitch < D - 1) S2P_FAIL(-1, "s2p_ensemble_head: pitch shorter than the row");
   if (pick && (!obs_mean || !obs_std || !next_obs || !reward)) S2P_FAIL(-1, "s2p_ensemble_head: pick needs outputs");
   hipLaunchKernelGGL(ensemble_head_kernel, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)stream, raw, raw_pitch, xin, x_pitch,
                      B, E, D, min_logstd, max_logstd, mean, std, (const int*)pick, obs_mean, obs_std, rew_mean, rew_std,

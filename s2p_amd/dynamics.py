@@ -263,7 +263,12 @@ class EnsembleTransition:
     @torch.no_grad()
     def rollout_step(self, obs_action, ensemble_idx, next_obs_mean, next_obs_std, reward_mean, reward_std):
         """One trajectory batch of state_transition_rollout.py:180-204: returns (next_obs [B,obs_dim], reward [B],
-        disagreement [B,1], aleatoric [B,1]) -- de-normalised prediction of the picked member + uncertainties."""
+        disagreement [B,1], aleatoric [B,1]) -- de-normalised prediction of the picked member + uncertainties.  An empty batch
+        gives empty outputs without a launch."""
+        if obs_action.shape[0] == 0:
+            f32, dev = torch.float32, self.device
+            return (torch.empty((0, self.obs_dim), dtype=f32, device=dev), torch.empty((0,), dtype=f32, device=dev),
+                    torch.empty((0, 1), dtype=f32, device=dev), torch.empty((0, 1), dtype=f32, device=dev))
         x, raw = self._raw(obs_action)
         B, dev = x.shape[0], self.device
         idx = torch.as_tensor(ensemble_idx).to(dev, torch.int32).contiguous()

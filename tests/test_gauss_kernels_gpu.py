@@ -8,33 +8,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from guard_region import SENT, Region
+
 pytestmark = pytest.mark.gpu
 
-BAND = 256
-SENT = 1.3e36
 MS = (1, 3, 32, 33, 288)
 DS = (1, 32, 256)
-
-
-class Region:
-    """A [M, width] fp32 view with row pitch `pitch` and column offset `off` inside a sentinel-filled device buffer."""
-
-    def __init__(self, M, width, pitch=None, off=0, fill=None):
-        self.M, self.width, self.off = M, width, off
-        self.pitch = pitch if pitch is not None else width + off + 4
-        assert self.pitch >= off + width
-        self.buf = torch.full((2 * BAND + M * self.pitch,), SENT, dtype=torch.float32, device="cuda")
-        self.v = self.buf[BAND:BAND + M * self.pitch].view(M, self.pitch)[:, off:off + width]
-        if fill is not None:
-            self.v.copy_(fill.float())
-
-    def get(self, what=""):
-        """The view's content (CPU, fp64) after checking that nothing outside it was written."""
-        torch.cuda.synchronize()
-        rest = self.buf.clone()
-        rest[BAND:BAND + self.M * self.pitch].view(self.M, self.pitch)[:, self.off:self.off + self.width] = SENT
-        assert bool((rest == SENT).all()), "guard band overwritten: " + what
-        return self.v.cpu().double()
 
 
 def inp(M, width, gen, pitch=None, off=0, scale=1.0):
