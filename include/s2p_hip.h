@@ -596,6 +596,35 @@ int s2p_cql_critic_head(const float* q_pred, int64_t q_pred_stride, const float*
                         int64_t dq_pred_stride, float* dq_samp, int64_t dq_samp_stride, float* q_target, float* std_mean,
                         void* stream);
 
+/* ---- the acting step of a SLAC policy (SPEC.md N3f; reference rlkit/torch/slac/trainer.py:12-47, slac/algo.py:75-81,
+ * rlkit/samplers/rollout_functions.py:127-205; csrc/actor.hip).  All fp32 (the frame conversion writes bf16 too), no atomics, a
+ * fixed summation order.  Argument checking as stated above s2p_gauss_head_fwd: negative sizes, a required NULL pointer, a short
+ * pitch and a misaligned operand are refused before any launch; a size of 0 is a successful no-op that looks at no pointer.    */
+/* uint8 frames [N][C][H][W], the layout an environment hands out, -> the encoder's NHWC input [N][H][W][y_pitch] in fp32 or bf16:
+ * channels < C hold float(x) / 255.0f, a true IEEE division (torch's `.float().div_(255.0)` bit for bit in fp32, that value
+ * rounded to nearest-even in bf16); channels C .. y_pitch - 1 are exactly 0.  H * W % 4 == 0 with a 4-byte aligned x reads
+ * dwords, anything else bytes.  N <= 65535.                                                                                */
+int s2p_u8_chw_to_nhwc01(int dtype, const void* x, int N, int C, int H, int W, void* y, int y_pitch, void* stream);
+/* The policy-input rows as the observation state of N environments.  Row n of src / dst [N][pitch] is
+ * [f_0 .. f_{S-1} | a_0 .. a_{S-2} | 0 pad]: S F + (S - 1) A values, pitch a multiple of 4 floats (`SlacAlgorithm.preprocess`'s
+ * layout).  dst is written from src, feat [N][feat_pitch >= F], action [N][action_pitch >= A] and the row's reset code:
+ *   reset[n] == 0 (or reset == NULL): features shifted left by F with feat[n] last, actions shifted left by A with action[n] last
+ *                                     (`SlacObservation.append`)
+ *   reset[n] == 1: S - 1 copies of fill [F], then feat[n]; all actions 0   (`reset_episode`; fill = the feature of a zero frame)
+ *   reset[n] == 2: S copies of feat[n]; all actions 0                      (`reset_w_same_obs=True`)
+ * Pad columns are written as 0.  src is not modified and may not overlap dst (the caller ping-pongs two buffers); both 16-byte
+ * aligned.  action is not looked at for rows with a reset code.  N <= 65535.                                                */
+int s2p_feature_action_push(const float* src, float* dst, int pitch, int N, int S, int F, int A, const float* feat,
+                            int feat_pitch, const float* action, int action_pitch, const int32_t* reset, const float* fill,
+                            void* stream);
+/* s2p_mlp_linear_fwd -- the same group table, activations and contract -- for rows <= 16 in every group (a larger group is
+ * refused before any launch), any N: one wave per output column reads its weight row once (lane l the k = 4 l .. 4 l + 3 of
+ * every 256, in k order), keeps one fused-multiply-add accumulator per row and reduces each in the same 64-lane butterfly.  N
+ * waves whatever the row count, each weight byte read once, no LDS.  ROW INVARIANCE: the value of a row does not depend on how
+ * many other rows the launch has (bitwise), so a batch of environments computes what each environment alone computes.  Not
+ * bitwise s2p_mlp_linear_fwd's result (another summation order).                                                            */
+int s2p_mlp_linear_fwd_skinny(const s2p_mlp_fwd_group* groups, int G, int N, int act, void* stream);
+
 /* ---- optimizer + weight packing ---------------------------------------------------- */
 /* torch.optim.Adam step on flat fp32 buffers; g is multiplied by grad_scale first.  All three forms move 16-byte groups:
  * p, g, m, v must be 16-byte aligned (a sub-range of a flat buffer starts at a multiple of 4 elements), else the call is

@@ -156,6 +156,9 @@ SIGNATURES = {
     "s2p_sac_policy_head": [_P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P],
     "s2p_cql_critic_head": [_P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
                             c_int, _P, _P, c_int64, _P, c_int64, _P, _P, _P],
+    "s2p_u8_chw_to_nhwc01": [c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P],
+    "s2p_feature_action_push": [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P],
+    "s2p_mlp_linear_fwd_skinny": [ctypes.POINTER(MlpFwdGroup), c_int, c_int, c_int, _P],
     "s2p_adam_step_dev": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, _P],
     "s2p_adam_step_dev_part": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_float, c_int, _P],
     "s2p_pack_weights": [_P, c_int, c_int, _P],
