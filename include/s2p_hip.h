@@ -370,6 +370,25 @@ int s2p_nhwc_to_u8(int dtype, const void* x, int x_pitch, int64_t pixels, int C,
  * with dword loads and 16-byte stores.  x must be 16-byte aligned.  B * T == 0 is a successful no-op.                  */
 int s2p_window_gather_u8(int dtype, const void* pool, int64_t n_slots, int64_t frame_pixels, int C, const int32_t* table, int T,
                          const int64_t* win, int B, void* x, int x_pitch, void* u8_out, void* stream);
+/* Cached encoder features of the replay buffer (SPEC.md N3g): with a frozen encoder a frame's feature row is a constant, kept in a
+ * table beside the frame pool; one launch turns B sampled window ids into everything an RL step on a frozen latent model reads.
+ *   feat        fp32  [n_slots][feat_pitch]    feature row of every pool slot, F floats used
+ *   table / win                                as above; T = S + 1 >= 2; for row b: w = win[b], slot_t = table[w][t]
+ *   action_     fp32  [n_windows][T-1][A]      reward_, done_  fp32 [n_windows][T-1]
+ *   feature_    fp32  [B][T][F]                row (b, t) = feat[slot_t][0..F)
+ *   fa          fp32  [B][fa_pitch]            [f_0 .. f_{T-2} | a_0 .. a_{T-3} | 0 pad]
+ *   next_fa     fp32  [B][fa_pitch]            [f_1 .. f_{T-1} | a_1 .. a_{T-2} | 0 pad]   (create_feature_actions, features first)
+ *   action_seq  fp32  [B][T-1][A]              action_[w]
+ *   action_last fp32  [B][action_last_pitch]   action_[w][T-2], pad columns 0
+ *   reward, terminal fp32 [B]                  reward_[w][T-2], done_[w][T-2]
+ * Every output is nullable (all null is refused); an input is needed only by the outputs that read it.  Each feature row is read
+ * once for its up to three destinations; all byte offsets are 64-bit.  A slot < 0 or >= n_slots reads as a zero row and is never
+ * dereferenced; window ids are the caller's to check.  F % 4 == 0, feat_pitch % 4 == 0, feat_pitch >= F, fa_pitch % 4 == 0 and
+ * >= (T-1) F + (T-2) A, A <= action_last_pitch; feat, feature_, fa, next_fa 16-byte aligned.  B * T == 0 is a successful no-op.  */
+int s2p_feature_window_gather(const float* feat, int64_t n_slots, int feat_pitch, int F, const int32_t* table, int T,
+                              const int64_t* win, int B, const float* action_, const float* reward_, const float* done_, int A,
+                              float* feature_, float* fa, float* next_fa, int fa_pitch, float* action_seq, float* action_last,
+                              int action_last_pitch, float* reward, float* terminal, void* stream);
 /* generic cast copy between dtypes (n elements)                                         */
 int s2p_cast(int src_dtype, const void* src, int dst_dtype, void* dst, int64_t n, void* stream);
 

@@ -106,3 +106,92 @@ extern "C" int s2p_window_gather_u8(int dtype, const void* pool, int64_t n_slots
   S2P_CHECK_LAUNCH("window_gather_kernel");
   return 0;
 }
+
+// Cached encoder features (SPEC.md N3g): sampled window ids -> everything a frozen-encoder RL step reads, out of a feature table
+// that holds one row of F floats per pool slot.  Row (b, t) is block-uniform as above (blockIdx.y = t, blockIdx.z strides over b):
+// the table lookup and the slot check are scalar work, a lane owns one 16-byte chunk of the row, reads it once and stores it to up
+// to three places: feature_[b][t], fa[b] at feature t (t <= T-2) and next_fa[b] at feature t-1 (t >= 1).  The first block of t == 0
+// also copies the window's actions (action_seq, the action columns of fa / next_fa, action_last), zeroes the pad columns and picks
+// the last reward / terminal.  No division in the per-thread path; a slot outside [0, n_slots) reads as a zero row.
+__global__ __launch_bounds__(64) void feature_window_gather_kernel(const float* feat, long long n_slots, int feat_pitch, int F4,
+                                                                   const int* table, int Tn, const long long* win, int B,
+                                                                   const float* action_, const float* reward_, const float* done_,
+                                                                   int A, float* feature_, float* fa, float* next_fa, int fa_pitch,
+                                                                   float* action_seq, float* action_last, int action_last_pitch,
+                                                                   float* reward, float* terminal) {
+  const int t = blockIdx.y;
+  const int F = 4 * F4;
+  for (int b = blockIdx.z; b < B; b += gridDim.z) {
+    const long long w = win[b];
+    const long long slot = table[w * Tn + t];
+    const bool ok = slot >= 0 && slot < n_slots;
+    const u32x4* src = (const u32x4*)(feat + (size_t)(ok ? slot : 0) * (size_t)feat_pitch);
+    u32x4* d0 = feature_ ? (u32x4*)(feature_ + ((size_t)b * Tn + t) * (size_t)F) : nullptr;
+    u32x4* d1 = fa && t < Tn - 1 ? (u32x4*)(fa + (size_t)b * fa_pitch + (size_t)t * F) : nullptr;
+    u32x4* d2 = next_fa && t > 0 ? (u32x4*)(next_fa + (size_t)b * fa_pitch + (size_t)(t - 1) * F) : nullptr;
+    for (int q = blockIdx.x * 64 + threadIdx.x; q < F4; q += gridDim.x * 64) {
+      const u32x4 v = ok ? src[q] : (u32x4){0u, 0u, 0u, 0u};
+      if (d0) d0[q] = v;
+      if (d1) d1[q] = v;
+      if (d2) d2[q] = v;
+    }
+    if (t == 0 && blockIdx.x == 0) {
+      const int S = Tn - 1;                                   // actions per window; the policy input holds S - 1 of them
+      const int na = S * A, nfa = na - A;
+      const float* a = action_ + (size_t)w * na;              // (never formed into a load when action_ is null: the launcher checks)
+      const size_t cols = (size_t)S * F;                      // feature columns of fa / next_fa
+      if (action_)
+        for (int j = threadIdx.x; j < na; j += 64) {
+          const float v = a[j];
+          if (action_seq) action_seq[(size_t)b * na + j] = v;
+          if (fa && j < nfa) fa[(size_t)b * fa_pitch + cols + j] = v;
+          if (next_fa && j >= A) next_fa[(size_t)b * fa_pitch + cols + (j - A)] = v;
+        }
+      if (fa || next_fa)
+        for (size_t j = cols + nfa + threadIdx.x; j < (size_t)fa_pitch; j += 64) {
+          if (fa) fa[(size_t)b * fa_pitch + j] = 0.f;
+          if (next_fa) next_fa[(size_t)b * fa_pitch + j] = 0.f;
+        }
+      if (action_last)
+        for (int j = threadIdx.x; j < action_last_pitch; j += 64) action_last[(size_t)b * action_last_pitch + j] = j < A ? a[nfa + j] : 0.f;
+      if (threadIdx.x == 0) {
+        if (reward) reward[b] = reward_[(size_t)w * S + (S - 1)];
+        if (terminal) terminal[b] = done_[(size_t)w * S + (S - 1)];
+      }
+    }
+  }
+}
+
+extern "C" int s2p_feature_window_gather(const float* feat, int64_t n_slots, int feat_pitch, int F, const int32_t* table, int T,
+                                         const int64_t* win, int B, const float* action_, const float* reward_, const float* done_,
+                                         int A, float* feature_, float* fa, float* next_fa, int fa_pitch, float* action_seq,
+                                         float* action_last, int action_last_pitch, float* reward, float* terminal, void* stream) {
+  S2P_REQUIRE(n_slots >= 0 && feat_pitch >= 0 && F >= 0 && T >= 0 && B >= 0 && A >= 0 && fa_pitch >= 0 && action_last_pitch >= 0,
+              "s2p_feature_window_gather: negative size");
+  S2P_REQUIRE(T <= 65535, "s2p_feature_window_gather: at most 65535 frames per window");
+  if ((long long)B * T == 0) return 0;                                 // nothing to gather: no pointer is looked at
+  S2P_REQUIRE(feature_ || fa || next_fa || action_seq || action_last || reward || terminal, "s2p_feature_window_gather: every output is null");
+  S2P_REQUIRE(T >= 2, "s2p_feature_window_gather: a window holds at least 2 frames (T = S + 1)");
+  S2P_REQUIRE(F % 4 == 0 && feat_pitch % 4 == 0 && feat_pitch >= F, "s2p_feature_window_gather: F and feat_pitch are multiples of 4, feat_pitch >= F");
+  S2P_REQUIRE(table && win, "s2p_feature_window_gather: null pointer");
+  const bool rows = feature_ || fa || next_fa;
+  S2P_REQUIRE(!rows || F == 0 || feat, "s2p_feature_window_gather: null feature table");
+  S2P_REQUIRE((((uintptr_t)feat | (uintptr_t)feature_ | (uintptr_t)fa | (uintptr_t)next_fa) & 15) == 0,
+              "s2p_feature_window_gather: feat, feature_, fa and next_fa must be 16-byte aligned");
+  if (fa || next_fa)
+    S2P_REQUIRE(fa_pitch % 4 == 0 && (long long)(T - 1) * F + (long long)(T - 2) * A <= fa_pitch,
+                "s2p_feature_window_gather: fa_pitch is a multiple of 4 and at least (T-1) F + (T-2) A");
+  S2P_REQUIRE(!action_last || A <= action_last_pitch, "s2p_feature_window_gather: A exceeds action_last_pitch");
+  S2P_REQUIRE((long long)(T - 1) * A <= 0x7fffffffLL, "s2p_feature_window_gather: (T-1) A exceeds 2^31");
+  const bool acts = A > 0 && (action_seq || action_last || ((fa || next_fa) && T > 2));
+  S2P_REQUIRE(!acts || action_, "s2p_feature_window_gather: null action_");
+  S2P_REQUIRE((!reward || reward_) && (!terminal || done_), "s2p_feature_window_gather: null reward_ / done_");
+  const int F4 = F / 4;
+  int gx = (F4 + 63) / 64; if (gx > 64) gx = 64; if (gx < 1) gx = 1;
+  const dim3 grid((unsigned)gx, (unsigned)T, (unsigned)(B < 65535 ? B : 65535));
+  hipLaunchKernelGGL(feature_window_gather_kernel, grid, dim3(64), 0, (hipStream_t)stream, feat, (long long)n_slots, feat_pitch, F4, table, T,
+                     (const long long*)win, B, action_, reward_, done_, A, feature_, fa, next_fa, fa_pitch, action_seq, action_last,
+                     action_last_pitch, reward, terminal);
+  S2P_CHECK_LAUNCH("feature_window_gather_kernel");
+  return 0;
+}

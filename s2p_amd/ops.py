@@ -587,6 +587,35 @@ def window_gather_u8(pool, table, win, dtype, pitch=None, want_x=True, want_u8=T
     return x, u8
 
 
+def feature_window_gather(feat, table, win, action_, reward_, done_):
+    """Cached encoder features of the windows `win` (int64 [B], ids into `table` int32 [n_windows,T]) out of the feature table `feat`
+    fp32 [n_slots,F] (row pitch = its stride), with the windows' actions [n_windows,T-1,A], rewards and terminals [n_windows,T-1,1], in
+    one launch (csrc/replay.hip): returns (feature_ [B,T,F], fa, next_fa [B,P] = `create_feature_actions`, action_seq [B,T-1,A],
+    action_last [B,A], reward [B,1], terminal [B,1]).  fa / next_fa are `[:, :P]` views of buffers whose row pitch is P rounded up to 4 floats
+    (pad columns zero).  The caller has range-checked `win`."""
+    if feat.dtype != torch.float32 or table.dtype != torch.int32 or win.dtype != torch.int64 or feat.dim() != 2 or feat.stride(1) != 1:
+        raise TypeError("feat is fp32 [n_slots,F] with unit column stride, table int32 and win int64")
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in (action_, reward_, done_)) or not (table.is_contiguous() and win.is_contiguous()):
+        raise ValueError("action_, reward_, done_ are contiguous fp32; table and win are contiguous")
+    (n_slots, F), T, B = feat.shape, table.shape[1], win.numel()
+    A = 1
+    for d in action_.shape[2:]:
+        A *= d
+    if action_.dim() < 2 or action_.shape[:2] != (table.shape[0], T - 1) or reward_.numel() != table.shape[0] * (T - 1) or done_.numel() != reward_.numel():
+        raise ValueError("action_ [n_windows,T-1,A], reward_ and done_ [n_windows,T-1,1] are needed")
+    P = (T - 1) * F + (T - 2) * A
+    fa_pitch = pad_to(P, 4)
+    dev, f = feat.device, torch.float32
+    feature_ = torch.empty((B, T, F), dtype=f, device=dev)
+    fa, next_fa = torch.empty((B, fa_pitch), dtype=f, device=dev), torch.empty((B, fa_pitch), dtype=f, device=dev)
+    action_seq, action_last = torch.empty((B, T - 1) + tuple(action_.shape[2:]), dtype=f, device=dev), torch.empty((B,) + tuple(action_.shape[2:]), dtype=f, device=dev)
+    reward, terminal = torch.empty((B, 1), dtype=f, device=dev), torch.empty((B, 1), dtype=f, device=dev)
+    check(lib().s2p_feature_window_gather(ptr(feat), n_slots, feat.stride(0), F, ptr(table), T, ptr(win), B, ptr(action_), ptr(reward_),
+                                          ptr(done_), A, ptr(feature_), ptr(fa), ptr(next_fa), fa_pitch, ptr(action_seq), ptr(action_last),
+                                          A, ptr(reward), ptr(terminal), stream()), "s2p_feature_window_gather")
+    return feature_, fa[:, :P], next_fa[:, :P], action_seq, action_last, reward, terminal
+
+
 def transition_pack(obs, action, obs_mean, obs_std, out):
     """out[r] = [(obs[r] - obs_mean) / obs_std | action[r] | 0 ...] for every row of a dataset in one launch (csrc/transition.hip):
     the two operations separately rounded in fp32, i.e. numpy's `(obs - mean) / std` bit for bit.  obs [N,obs_dim], action [N,A] and

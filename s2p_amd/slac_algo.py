@@ -8,7 +8,7 @@ from torch.optim import Adam
 
 from .data import load_arrays
 from .slac import LatentModel, create_feature_actions
-from .slac_buffer import ReplayBuffer
+from .slac_buffer import FeatureBatch, ReplayBuffer
 
 INTEGER_INF = int(1e9)                             # `slac_observation_indices` of rows without a full window (rollout.py:111)
 SEQUENTIAL_MIX_TYPES = ("random_state_5step_random_action", "random_state_1step_random_action", "random_state_5step_offRL_action")
@@ -126,11 +126,23 @@ class SlacAlgorithm:
         self.optim_latent.step()
         return loss_kld, loss_image, loss_reward
 
-    def prepare_batch(self, state_, action_):
+    def cache_features(self, chunk=1024):
+        """Build the buffers' feature tables from the encoder as it is now (for `freeze_slac` runs; SPEC.md N3g): afterwards
+        `buffer.random_batch(..., frames="features")` yields a `FeatureBatch`, on which `prepare_batch` skips the encoder."""
+        self.buffer.attach_features(self.latent.encoder, chunk)
+        if self.use_seperate_buffer:
+            self.buffer_gen.attach_features(self.latent.encoder, chunk)
+
+    def prepare_batch(self, state_, action_, noise=None):
+        """`state_`: frames (a FrameBatch or a frame tensor) or a `FeatureBatch`, whose cached features, policy-input rows and last
+        action the sampling launch already wrote: only the posterior chain runs.  `noise` is `sample_posterior`'s."""
+        cached = isinstance(state_, FeatureBatch)
         with torch.no_grad():
-            feature_ = self.latent.encoder(state_)                                               # f(1:t+1)
-            z_ = torch.cat(self.latent.sample_posterior(feature_, action_)[2:4], dim=-1)         # z(1:t+1)
+            feature_ = state_.feature_ if cached else self.latent.encoder(state_)                # f(1:t+1)
+            z_ = torch.cat(self.latent.sample_posterior(feature_, action_, noise)[2:4], dim=-1)  # z(1:t+1)
         z, next_z = z_[:, -2], z_[:, -1]
+        if cached:
+            return z, next_z, state_.action, state_.feature_action, state_.next_feature_action
         action = action_[:, -1]
         feature_action, next_feature_action = self.create_feature_actions(feature_, action_)
         return z, next_z, action, feature_action, next_feature_action

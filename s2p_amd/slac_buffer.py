@@ -7,7 +7,11 @@ latent model reads: the encoder's NHWC input in the compute dtype and the uint8 
 
 Call surface, return tuples / dict keys, `_n` / `_p` / `_real_n` and the host-side `np.random.randint` draw are the reference's, so
 the same `np.random.seed` selects the same windows.  The bookkeeping is host Python and works with device="cpu"; only the `sample_*`
-methods in "packed" / "u8" / "float" form need a HIP device (`window_frames` is the plain-torch accessor for any device)."""
+methods in "packed" / "u8" / "float" form need a HIP device (`window_frames` is the plain-torch accessor for any device).
+
+With a frozen encoder a frame's feature is a constant of the run (SPEC.md N3g): `attach_features(encoder)` keeps one 256-float row
+per pool slot beside the pool, and `random_batch` / `sample_sac` with frames="features" return a `FeatureBatch` -- features, both
+policy-input rows, actions, reward and terminal out of one launch (`ops.feature_window_gather`), no frame touched."""
 from collections import deque
 
 import numpy as np
@@ -34,6 +38,28 @@ class FrameBatch:
 
     def __len__(self):
         return self.shape[0]
+
+
+class FeatureBatch:
+    """B sampled windows as cached encoder features (`ReplayBuffer.attach_features`), with everything a step on a frozen latent model
+    reads, written by one launch: `feature_` [B,S+1,256], `feature_action` / `next_feature_action` [B,S*256+(S-1)*A] (the two results
+    of `create_feature_actions`), `action_` [B,S,A] and `action` [B,A] = action_[:, -1].  `shape` is the reference's (B,S+1,C,H,W),
+    as `FrameBatch`; there are no frames in it."""
+
+    def __init__(self, feature_, feature_action, next_feature_action, action_, action, state_shape):
+        self.feature_, self.feature_action, self.next_feature_action = feature_, feature_action, next_feature_action
+        self.action_, self.action = action_, action
+        self.shape = tuple(feature_.shape[:2]) + tuple(state_shape)
+
+    @property
+    def device(self):
+        return self.feature_.device
+
+    def __len__(self):
+        return self.shape[0]
+
+
+FEATURE_DIM = 256                                 # the encoder's output width: one row of the feature table
 
 
 def _take(parts, idx):
@@ -80,6 +106,69 @@ class ReplayBuffer:
         self._tail = 0
         self._wmin = np.full(self.buffer_size, _NONE, dtype=np.int64)
         self._reset_pending()
+        # the feature table (attach_features): features[slot] = encoder(pool[slot]); _fhead counts the frames encoded so far, so the
+        # frames stored since are [_fhead, _head)
+        self.features = None
+        self._fhead = 0
+        self._feat_encoder, self._feat_chunk, self._feat_version = None, 1024, None
+
+    # ---- cached encoder features (SPEC.md N3g) ---------------------------------------------------------------------------
+    @staticmethod
+    def _encoder_version(encoder):
+        return sum(p._version for p in encoder.parameters())
+
+    def _encode_slots(self, slots):
+        """features[slots] = encoder(pool[slots]) for an int64 array of pool slots: one gather over a one-column slot table (the
+        encoder's NHWC input, as a sampled FrameBatch holds it) and one run of the conv stack."""
+        enc = self._feat_encoder
+        where = torch.from_numpy(slots).to(self.device)
+        x, _ = ops.window_gather_u8(self.pool, where.to(torch.int32).view(-1, 1), torch.arange(len(slots), device=self.device), enc.dtype,
+                                    ops.pad_to(self.state_shape[0], chunk_elems(enc.dtype)), want_u8=False)
+        with torch.no_grad():
+            y = enc.run(x)
+        self.features.index_copy_(0, where, y.reshape(len(slots), -1).float())
+
+    def _encode_frames(self, lo, hi):
+        """Encode the frames with running numbers [lo, hi), `_feat_chunk` at a time; frames the ring has overwritten are left out."""
+        lo = max(lo, hi - self.frame_capacity)
+        for c in range(lo, hi, self._feat_chunk):
+            self._encode_slots(np.arange(c, min(c + self._feat_chunk, hi), dtype=np.int64) % self.frame_capacity)
+        self._fhead = hi
+
+    def attach_features(self, encoder, chunk=1024):
+        """Build the feature table, fp32 [frame_capacity, 256], from every live frame, `chunk` frames a launch.  The table is valid
+        while the encoder's parameters stay as they are (`freeze_slac`); frames stored later are encoded before the next sample."""
+        if chunk < 1:
+            raise ValueError("chunk >= 1")
+        self._feat_encoder, self._feat_chunk = encoder, int(chunk)
+        self.features = torch.zeros((self.frame_capacity, FEATURE_DIM), dtype=torch.float32, device=self.device)
+        self.refresh_features()
+
+    def refresh_features(self):
+        """Re-encode every live frame with the encoder as it is now."""
+        if self.features is None:
+            raise RuntimeError("no feature table: call attach_features(encoder) first")
+        self._feat_version = self._encoder_version(self._feat_encoder)
+        self._encode_frames(self._tail, self._head)
+
+    def detach_features(self):
+        self.features, self._feat_encoder, self._feat_version = None, None, None
+
+    def _features(self, idxes):
+        """-> (FeatureBatch, action_ [B,S,A], reward [B,1], terminal [B,1]) of the windows `idxes`: one id upload, one launch."""
+        if self.features is None:
+            raise RuntimeError("frames='features' needs a feature table: call attach_features(encoder) first")
+        if self._encoder_version(self._feat_encoder) != self._feat_version:
+            raise RuntimeError("the encoder's parameters changed since the feature table was built (the cache is for a frozen latent "
+                               "model): call refresh_features(), or sample frames")
+        if self._fhead < self._head:
+            self._encode_frames(self._fhead, self._head)
+        if self.device.type != "cuda":
+            raise RuntimeError("sampling features runs on a HIP device only (no CPU fallback)")
+        win = torch.from_numpy(np.ascontiguousarray(idxes, dtype=np.int64)).to(self.device)
+        feature_, fa, next_fa, action_, action, reward, terminal = ops.feature_window_gather(
+            self.features, self.table, win, self.action_, self.reward_, self.done_)
+        return FeatureBatch(feature_, fa, next_fa, action_, action, self.state_shape), action_, reward, terminal
 
     # ---- frame ring ------------------------------------------------------------------------------------------------------
     def _reset_pending(self):
@@ -224,17 +313,25 @@ class ReplayBuffer:
         raise ValueError("frames is 'packed', 'u8' or 'float'")
 
     def sample_latent(self, batch_size, idxes=None, frames=None):
+        if frames == "features":
+            raise ValueError("sample_latent trains the latent model, whose image loss needs the frames: frames='features' is for "
+                             "sample_sac / random_batch")
         idxes = self._idxes(batch_size, idxes)
         state_ = self._state(idxes, frames)
         return state_, self.action_[idxes], self.reward_[idxes], self.done_[idxes]
 
     def sample_sac(self, batch_size, idxes=None, frames=None):
         idxes = self._idxes(batch_size, idxes)
+        if frames == "features":
+            return self._features(idxes)
         state_ = self._state(idxes, frames)
         return state_, self.action_[idxes], self.reward_[idxes, -1], self.done_[idxes, -1]
 
     def random_batch(self, batch_size, idxes=None, frames=None):
         idxes = self._idxes(batch_size, idxes)
+        if frames == "features":                  # the cached features of a frozen encoder: observations is a FeatureBatch
+            state_, actions, rewards, terminals = self._features(idxes)
+            return dict(observations=state_, actions=actions, rewards=rewards, terminals=terminals)
         state_ = self._state(idxes, frames)
         return dict(observations=state_, actions=self.action_[idxes], rewards=self.reward_[idxes, -1],
                     terminals=self.done_[idxes, -1])

@@ -2,7 +2,8 @@
 counterpart of the reference's `run_cql_image.sh`.
 
   python train_cql.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --latent_dir DIR --steps N
-                      --out DIR [--freeze_slac] [--slac_policy_input_type feature_action|latent_z] [--bf16] [--seed S]
+                      --out DIR [--freeze_slac [--cache_features]] [--slac_policy_input_type feature_action|latent_z] [--bf16]
+                      [--seed S]
                       [--num_random R] [--min_q_weight W] [--temp T] [--policy_eval_start E] [--deterministic_backup]
 
 Loads `latent.pth` from --latent_dir (written by train_latent.py), fills the buffer as the reference's `load_data_in_buffer` does,
@@ -12,7 +13,7 @@ import os
 
 import torch
 
-from train_iql import parse_args as iql_args, policy_input_dim
+from train_iql import parse_args as iql_args, policy_input_dim, sample_form
 
 CQL_KWARGS = dict(discount=0.99, soft_target_tau=5e-3, policy_lr=1e-4, qf_lr=3e-4, reward_scale=1, use_automatic_entropy_tuning=True,
                   num_qs=2, min_q_version=3, with_lagrange=False, lagrange_thresh=-1.0, max_q_backup=False, slac_update_period=1)
@@ -68,8 +69,9 @@ def main(argv=None):
     trainer = CQLTrainer(None, policy, critic=critic, slac_algo=algo, freeze_slac=a.freeze_slac, slac_policy_input_type=a.slac_policy_input_type,
                          num_random=a.num_random, min_q_weight=a.min_q_weight, temp=a.temp, policy_eval_start=a.policy_eval_start,
                          deterministic_backup=a.deterministic_backup, generator=gen_noise, **CQL_KWARGS)
+    frames = sample_form(a, algo)
     for step in range(1, a.steps + 1):
-        trainer.train_from_torch(algo.buffer.random_batch(a.batch_size))
+        trainer.train_from_torch(algo.buffer.random_batch(a.batch_size, frames=frames))
         if step % a.log_every == 0 or step == a.steps:
             trainer.end_epoch(step)
             print("step %d  %s" % (step, "  ".join("%s %.4f" % kv for kv in trainer.eval_statistics.items())))

@@ -1,11 +1,13 @@
 """Train IQL on SLAC latents from the device-resident replay buffer (SPEC.md N3d): the last stage of the S2P pipeline.
 
   python train_iql.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --latent_dir DIR --steps N
-                      --out DIR [--freeze_slac] [--slac_policy_input_type feature_action|latent_z] [--bf16] [--seed S]
+                      --out DIR [--freeze_slac [--cache_features]] [--slac_policy_input_type feature_action|latent_z] [--bf16]
+                      [--seed S]
 
 Loads `latent.pth` from --latent_dir (written by train_latent.py), fills the buffer as the reference's `load_data_in_buffer` does,
 runs `IQLTrainer.train_from_torch` N times in the shipped configuration (`examples/iql/mujoco_finetune.py:91-119`) and writes
-`critic.pth` / `policy.pth` with the reference's keys, plus `encoder.pth` / `latent.pth`."""
+`critic.pth` / `policy.pth` with the reference's keys, plus `encoder.pth` / `latent.pth`.  With --freeze_slac the encoder never
+changes: --cache_features encodes every stored frame once and samples cached features (SPEC.md N3g)."""
 import argparse
 import os
 
@@ -28,6 +30,8 @@ def parse_args(argv=None, extend=None):
     ap.add_argument("--steps", type=int, required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--freeze_slac", action="store_true", help="do not train the latent model along")
+    ap.add_argument("--cache_features", action="store_true",
+                    help="with --freeze_slac: encode every stored frame once and sample cached features, not frames")
     ap.add_argument("--slac_policy_input_type", choices=["feature_action", "latent_z"], default="feature_action")
     ap.add_argument("--bf16", action="store_true", help="bf16 conv stacks of the latent model (the IQL networks stay fp32)")
     ap.add_argument("--seed", type=int, default=0)
@@ -43,12 +47,29 @@ def parse_args(argv=None, extend=None):
         ap.error("--steps >= 0 and --batch_size >= 1")
     if a.uncertainty_type and not a.gen:
         ap.error("--uncertainty_type applies to a --gen dataset")
+    if a.cache_features and not a.freeze_slac:
+        ap.error("--cache_features needs --freeze_slac: a feature is a constant of the run only while the encoder is not trained")
     return a
 
 
 def policy_input_dim(a, action_dim, feature_dim=256, z_dim=288):
     """finetune_rl.py:204: S features and S - 1 actions, or the latent."""
     return a.num_sequences * feature_dim + (a.num_sequences - 1) * action_dim if a.slac_policy_input_type == "feature_action" else z_dim
+
+
+def sample_form(a, algo):
+    """The `frames` argument of `random_batch`: with --cache_features, build the feature table first and report its size and time."""
+    if not a.cache_features:
+        return None
+    import time
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    algo.cache_features()
+    torch.cuda.synchronize()
+    t = algo.buffer.features
+    print("feature table: %d rows x %d fp32 = %.1f MB, built in %.2f s" % (t.shape[0], t.shape[1], t.numel() * 4 / 1e6,
+                                                                         time.perf_counter() - t0))
+    return "features"
 
 
 def main(argv=None):
@@ -80,8 +101,9 @@ def main(argv=None):
     policy = TanhGaussianPolicy(hidden_sizes=hid, obs_dim=policy_input_dim(a, A), action_dim=A)
     trainer = IQLTrainer(None, policy, critic=critic, slac_algo=algo, freeze_slac=a.freeze_slac,
                          slac_policy_input_type=a.slac_policy_input_type, **IQL_KWARGS)
+    frames = sample_form(a, algo)
     for step in range(1, a.steps + 1):
-        trainer.train_from_torch(algo.buffer.random_batch(a.batch_size))
+        trainer.train_from_torch(algo.buffer.random_batch(a.batch_size, frames=frames))
         if step % a.log_every == 0 or step == a.steps:
             trainer.end_epoch(step)
             print("step %d  %s" % (step, "  ".join("%s %.4f" % kv for kv in trainer.eval_statistics.items())))
