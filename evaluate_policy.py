@@ -30,6 +30,8 @@ def parse_args(argv=None):
     ap.add_argument("--max_path_length", type=int, default=1000)
     ap.add_argument("--num_envs", type=int, default=4)
     ap.add_argument("--slac_policy_input_type", choices=["feature_action", "latent_z"], default="feature_action")
+    ap.add_argument("--fused_chain", action="store_true",
+                    help="latent_z: run the posterior chain of every acting step as one launch (bitwise the same result)")
     ap.add_argument("--reset_w_same_obs", action="store_true", help="pad a new episode's window with its first frame, not with zero frames")
     ap.add_argument("--bf16", action="store_true", help="bf16 conv stack of the encoder (the policy stays fp32)")
     ap.add_argument("--num_sequences", type=int, default=8)
@@ -93,6 +95,7 @@ def main(argv=None):
     state_shape = (3, 100, 100)
     latent = LatentModel(state_shape, (A,), dtype=torch.bfloat16 if a.bf16 else torch.float32, device="cuda:0")
     latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
+    latent.fused_chain = a.fused_chain
     algo = types.SimpleNamespace(latent=latent, state_shape=state_shape, action_shape=(A,), num_sequences=a.num_sequences)
     actor = SlacActor(policy, algo, a.num_envs, a.slac_policy_input_type, a.reset_w_same_obs)
     out = run_episodes(make_envs(a), actor, a.episodes, a.max_path_length)

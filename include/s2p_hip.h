@@ -303,6 +303,31 @@ int s2p_linear_add_bwd(const float* x, int x_pitch, const float* dy, int dy_pitc
                        int K, int k_real, int N, const float* w_bwd, int wb_row, int act, float slope, float* dw,
                        int dw_row, float* db, float* dx, int dx_pitch, int dx_accumulate, float* dadd, int dadd_pitch,
                        void* stream);
+/* The whole forward of the reparameterised posterior chain (latent.py:250-281) for B rows and T time steps in ONE launch
+ * (SPEC.md N3h; csrc/gauss_chain.hip): what the no-grad path otherwise runs as 8 T launches of s2p_linear_fwd /
+ * s2p_linear_add_fwd / s2p_gauss_head_fwd, and BITWISE what those return (the same MFMA sequence per output element, K never
+ * split, the same epilogues; a row's values do not depend on B).  No backward: nothing is kept.  feature 256, z1 32, z2 256,
+ * hidden 256 are compile-time constants.
+ *   feat   feat(0) of batch row b at feat + b * feat_pitch (feat_pitch = T * 256 inside a [B][T][256] tensor); 16-byte
+ *          aligned, feat_pitch a multiple of 4 floats
+ *   ra, rb [(T-1) * B][256], time-major (row (t-1) * B + b): the hoisted terms of the two chain MLPs' first layers, i.e.
+ *          [feat(t) | a(t-1)] . w^T of z1_posterior and a(t-1) . w^T of z2_prior, without bias (one s2p_linear_fwd each over
+ *          all time steps).  May be NULL when T == 1.
+ *   eps    [B][T][eps_pitch >= 288], the noise of z1 | z2; row (b, t) at (b * T + t) * eps_pitch -- as mean, std, z below
+ *   mlps   HOST array of 4 (copied into the kernel arguments): z1_posterior_init, z2_prior_init, z1_posterior, z2_prior
+ *          (the last two are not looked at when T == 1).  w1 [256][w1_row >= k1] holds the CHAIN columns of the first layer only:
+ *          k1 = 256 (feat), 32 (z1), 256 (z2(t-1)), 288 (z1(t) | z2(t-1)); w2 [256][256]; w3 [2 D][256] = [mean | raw_std] rows,
+ *          D = 32, 256, 32, 256; the weights 16-byte aligned, w1_row a multiple of 4 floats.
+ *   mean, std [B][T][pitch >= 32]  of z1;   z [B][T][z_pitch >= 288] = z1 | z2.  Nothing else is written to device memory.
+ * A negative size is refused; B == 0 (or T == 0) is a successful no-op that looks at no pointer; T == 1 runs the two init MLPs
+ * only; a NULL required tensor, a short pitch, another k1 and a misaligned operand are refused before the launch.           */
+typedef struct {
+  const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3;
+  int32_t k1, w1_row;
+} s2p_chain_mlp;
+int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
+                            int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch,
+                            float* z, int z_pitch, int B, int T, void* stream);
 /* KL(p || q) of diagonal Gaussians, value and all four gradients in one pass (slac/utils.py:66-69):
  *   loss[0] += scale * sum 0.5 ((sp/sq)^2 + ((mp-mq)/sq)^2 - 1 - log (sp/sq)^2),  d* = scale * dKL/d*  (overwritten; any NULL).
  * p: [B][T][p_pitch >= D].  const_first == 0: q is [B][T][q_pitch]; const_first != 0: q is [B][T-1][q_pitch] and holds the

@@ -55,6 +55,12 @@ class MlpFwdGroup(ctypes.Structure):
                 ("x_pitch", ctypes.c_int32), ("y_pitch", ctypes.c_int32), ("rows", ctypes.c_int32), ("K", ctypes.c_int32)]
 
 
+class ChainMlp(ctypes.Structure):
+    """s2p_chain_mlp: the packed operands of one Gaussian MLP of the fused posterior chain (k1: the chain columns of its first layer)."""
+    _fields_ = [("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("w3", c_void_p), ("b3", c_void_p),
+                ("k1", ctypes.c_int32), ("w1_row", ctypes.c_int32)]
+
+
 class MlpBwdGroup(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("dpre", c_void_p), ("w", c_void_p), ("dw", c_void_p), ("db", c_void_p), ("pre_prev", c_void_p),
                 ("dprev", c_void_p), ("x_pitch", ctypes.c_int32), ("dpre_pitch", ctypes.c_int32), ("prev_pitch", ctypes.c_int32),
@@ -111,6 +117,8 @@ SIGNATURES = {
     "s2p_gauss_head_fwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P],
     "s2p_gauss_head_bwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P],
     "s2p_linear_add_fwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_float, _P, c_int, c_int, _P],
+    "s2p_posterior_chain_fwd": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int, c_int, c_int,
+                                _P],
     "s2p_linear_add_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int, _P, _P,
                            c_int, c_int, _P, c_int, _P],
     "s2p_gauss_kl": [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int, _P, _P, c_int, _P],

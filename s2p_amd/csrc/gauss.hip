@@ -1,7 +1,9 @@
 // The SLAC latent model's Gaussian heads and likelihood terms (SPEC.md N3b; rlkit/torch/slac/network/latent.py:174-311), all fp32.
 // The posterior chain is 9 strictly sequential time steps of two 3-layer MLPs at M = batch rows: latency-bound like the state path
-// (linear_small.hip), so a layer stays one short launch.  What this file adds so that NO torch.cat / chunk / stack / element-wise
-// kernel runs between those launches:
+// (linear_small.hip).  With grad enabled a layer stays one short launch (the backward needs every activation in memory); a call
+// that keeps no backward state can run the whole chain as ONE launch instead (gauss_chain.hip, LatentModel.fused_chain), built from
+// the same device functions (gauss_dev.h) and bitwise equal.  What this file adds so that NO torch.cat / chunk / stack /
+// element-wise kernel runs between the per-layer launches:
 //   gauss_head_{fwd,bwd}_kernel : [mean | raw] -> mean, std = softplus(raw) + 1e-5, z = mean + eps * std, every output with its own
 //                                 pitch and column offset (the sample to two places: the sequence buffer and the next MLP's input
 //                                 row); backward [dmean + dz | (dstd + dz eps) sigmoid(raw)].
@@ -16,16 +18,10 @@
 // Reductions: the KL and the masked (reward) likelihood are ONE workgroup each, summed in a fixed order, no atomics.  The image
 // likelihood (8.6 M elements at B = 32) ends in ONE fp32 atomicAdd per workgroup on the loss word, as s2p_l1_loss does: its VALUE
 // can differ in the last bits between calls, its gradient cannot (element-wise).
-#include "s2p_common.h"
+#include "gauss_dev.h"
 
 #define GAUSS_REQUIRE(cond, ...) do { if (!(cond)) S2P_FAIL(-1, __VA_ARGS__); } while (0)
 static inline bool gauss_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ float gauss_softplus(float r) { return fmaxf(r, 0.f) + log1pf(expf(-fabsf(r))); }
-__device__ __forceinline__ float gauss_sigmoid(float r) {
-  const float e = expf(-fabsf(r));
-  return r >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
 
 // ---- Gaussian head ---------------------------------------------------------------------------------------------------------------
 struct HeadArgs {
@@ -40,11 +36,11 @@ __global__ __launch_bounds__(256) void gauss_head_fwd_kernel(const HeadArgs a) {
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
     const int m = (int)(idx / a.D), d = (int)(idx - (long long)m * a.D);
     const float* r = a.raw + (size_t)m * a.raw_pitch;
-    const float mu = r[d], sd = gauss_softplus(r[a.D + d]) + 1e-5f;
+    const float mu = r[d], sd = gauss_head_std(r[a.D + d]);
     if (a.mean) a.mean[(size_t)m * a.mean_pitch + d] = mu;
     if (a.std) a.std[(size_t)m * a.std_pitch + d] = sd;
     if (a.eps) {
-      const float zv = __builtin_fmaf(a.eps[(size_t)m * a.eps_pitch + d], sd, mu);
+      const float zv = gauss_head_sample(a.eps[(size_t)m * a.eps_pitch + d], sd, mu);
       if (a.z) a.z[(size_t)m * a.z_pitch + d] = zv;
       if (a.z2) a.z2[(size_t)m * a.z2_pitch + d] = zv;
     }
@@ -139,9 +135,7 @@ __global__ __launch_bounds__(256) void gauss_lin_add_kernel(const LinAddArgs a) 
       }
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[u][e], wv[u][e], acc, 0, 0, 0);
+    for (int u = 0; u < U; ++u) acc = lin_mfma_chunk(xv[u], wv[u], acc);
   }
   if (n >= a.n_store) return;
   const float b = (a.bias && nok) ? a.bias[n] : 0.f;

@@ -1,0 +1,272 @@
+// The no-grad SLAC posterior chain as ONE launch (SPEC.md N3h; rlkit/torch/slac/network/latent.py:250-281): all T time steps of the
+// two 3-layer Gaussian MLPs, fp32.  linear_small.hip's argument for "a layer is a launch" is about COLUMNS (a layer needs every
+// output column of the previous one); the batch ROWS of the chain never meet.  So a workgroup owns 16 rows -- one MFMA 16x16x4 row
+// tile -- and every output column of every layer, and runs the whole chain with workgroup barriers only: no grid barrier, no
+// cooperative launch, no traffic between workgroups.  grid = ceil(B / 16); at B = 256 that is 16 workgroups on 256 CUs, which is
+// accepted: the unfused chain is 72 launches whose time is launch latency, not arithmetic.
+//
+// Bitwise the per-layer path (lin_fwd_kernel / gauss_lin_add_kernel / gauss_head_fwd_kernel): an output element is the accumulator
+// after lin_mfma_chunk over the k-chunks in ascending order from 0 (gauss_dev.h, the same function those kernels call), K is never
+// split, then (acc + add) + bias or acc + bias, LeakyReLU 0.2, and the head of gauss_dev.h.  A row of an MFMA tile depends on that
+// row's operands alone, so which rows share a tile does not matter; rows >= B are zero operands and are never stored.
+//
+// 512 threads = 8 waves, two per SIMD.  The waves split the 16-column tiles of a layer: 2 tiles each in a 256-wide layer, and in a
+// head layer (64 or 512 wide, [mean | raw_std]) a wave takes PAIRS of tiles (mean tile p, raw_std tile p + D/16), so the lane that
+// holds mean[row][d] also holds raw_std[row][d] and the head is evaluated in registers: `raw` is never stored anywhere.  A wave
+// reads its A operand (the activations) from LDS once per k-chunk and uses it for all of its tiles; the B operand (weights, 1.9 MB
+// per time step, L2-resident) goes from global memory straight into the MFMA registers: a layer's first block of weights is asked
+// for before the barrier that ends the previous layer, then the next block loads while the current one is multiplied.  One CU's
+// fp32 MFMA rate bounds a 16-row step (13.4 MFLOP, ~52 k cycles), so more waves would only divide the same pipe; fewer (4) leave a
+// SIMD idle whenever its one wave waits for weights.  Measured: 425 us per chain at 512 threads, 451-459
+// at 256, 504 at 1 024 -- where 128 VGPRs per lane no longer hold the double-buffered operands.
+//
+// LDS (51 968 bytes of the CU's 160 KiB, static, nothing aliased):
+//   xz [16][292]  z1(t) | z2(t-1), the input row of both first layers (at t = 0 columns 32.. hold feat(0))
+//   h1 [16][260]  first-layer output        h2 [16][260]  second-layer output
+// Row pitches are K + 4 floats: lane 16 j + i reads row i at k = 16 c + 4 j as one 16-byte read; with a 1 024- or 1 152-byte pitch
+// all 16 rows start on one bank, with +4 floats row i starts on bank 4 i (mod 64).  (The 16-lane groups a ds_read_b128 is served in
+// are not the j groups, so one lane pair per group still collides; +8 removes that and measures the same: the LDS is not the limit.)
+#include "gauss_dev.h"
+
+#define CHAIN_REQUIRE(cond, ...) do { if (!(cond)) S2P_FAIL(-1, __VA_ARGS__); } while (0)
+
+namespace {
+constexpr int CH_Z1 = 32, CH_Z2 = 256, CH_Z = CH_Z1 + CH_Z2, CH_HID = 256, CH_FEAT = 256;
+#ifndef S2P_CHAIN_THREADS
+#define S2P_CHAIN_THREADS 512
+#endif
+#ifndef S2P_CHAIN_INFLIGHT
+#define S2P_CHAIN_INFLIGHT 8                               // weight loads (16 bytes per lane) a wave asks for per block of k-chunks
+#endif
+constexpr int CH_THREADS = S2P_CHAIN_THREADS, CH_WAVES = CH_THREADS / 64, CH_ROWS = 16;
+constexpr int ch_u(int nt) { return S2P_CHAIN_INFLIGHT / nt > 0 ? S2P_CHAIN_INFLIGHT / nt : 1; }
+#ifndef S2P_CHAIN_PAD
+#define S2P_CHAIN_PAD 4                                    // floats added to the LDS row pitch of the activation tiles
+#endif
+constexpr int CH_XZ_P = CH_Z + S2P_CHAIN_PAD, CH_H_P = CH_HID + S2P_CHAIN_PAD;
+constexpr float CH_SLOPE = 0.2f;
+
+struct ChainArgs {
+  const float* feat; const float* ra; const float* rb; const float* eps; float* mean; float* std; float* z;
+  int feat_pitch, eps_pitch, mean_pitch, std_pitch, z_pitch, B, T;
+  s2p_chain_mlp m[4];                                      // z1_posterior_init, z2_prior_init, z1_posterior, z2_prior
+};
+
+// The weights of NT column tiles for one block of k-chunks; wr: this lane's weight rows, already at k = 4 j.
+template <int K, int NT, int U>
+__device__ __forceinline__ void chain_load_w(const float* const (&wr)[NT], int blk, f32x4 (&wv)[NT][U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if ((blk * U + u) * 16 < K) {
+#pragma unroll
+      for (int q = 0; q < NT; ++q) wv[q][u] = *(const f32x4*)(wr[q] + 16 * (blk * U + u));
+    }
+}
+
+// acc[q] += x[16 rows][K] . w[tile q]^T: the chunk sequence of lin_fwd_kernel.  xr: this lane's activation row in LDS at k = 4 j.
+// w0: the first block of weights, asked for before the barrier this layer waited at.  While a block is multiplied the next one
+// loads; the scheduling barriers keep hipcc from sinking those loads to their first use (it does, leaving one load in flight).
+template <int K, int NT, int U>
+__device__ __forceinline__ void chain_gemm(const float* xr, const float* const (&wr)[NT], f32x4 (&w0)[NT][U], f32x4 (&acc)[NT]) {
+  static_assert(K % 16 == 0, "whole k-chunks");
+  constexpr int NC = K / 16, NB = (NC + U - 1) / U;
+  f32x4 xv[2][U], w1[NT][U];
+  auto load_x = [&](int buf, int blk) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (blk * U + u < NC) xv[buf][u] = *(const f32x4*)(xr + 16 * (blk * U + u));
+  };
+  load_x(0, 0);
+#pragma unroll
+  for (int blk = 0; blk < NB; ++blk) {
+    f32x4 (&cur)[NT][U] = (blk & 1) ? w1 : w0;
+    f32x4 (&nxt)[NT][U] = (blk & 1) ? w0 : w1;
+    if (blk + 1 < NB) { chain_load_w<K, NT, U>(wr, blk + 1, nxt); load_x((blk + 1) & 1, blk + 1); }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (blk * U + u < NC) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) acc[q] = lin_mfma_chunk(xv[blk & 1][u], cur[q][u], acc[q]);
+      }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// A hidden layer: ys[16][CH_H_P] = lrelu(xs[16][K] . w[256][w_row]^T (+ add) + bias); wave v owns the column tiles v and v + 8.
+// ask(): everything that does not depend on the previous layer -- the first weights, the bias, the additive term -- is asked for
+// BEFORE the barrier that ends the previous layer; run() after it.
+template <int K, bool ADD>
+struct ChainHidden {
+  static constexpr int NT = CH_HID / 16 / CH_WAVES, U = ch_u(NT);
+  const float* wr[NT];
+  f32x4 w0[NT][U];
+  float av[NT][4], bv[NT];
+
+  __device__ __forceinline__ void ask(const float* w, int w_row, const float* bias, const float* add, int row0, int B) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int n = 16 * (wave + q * CH_WAVES) + i;
+      wr[q] = w + (size_t)n * w_row + 4 * j;
+      bv[q] = bias[n];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gm = row0 + 4 * j + r;
+        av[q][r] = (ADD && gm < B) ? add[(size_t)gm * CH_HID + n] : 0.f;
+      }
+    }
+    chain_load_w<K, NT, U>(wr, 0, w0);
+  }
+
+  __device__ __forceinline__ void run(const float* xs, int xp, int row0, int B, float* ys) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    f32x4 acc[NT];
+#pragma unroll
+    for (int q = 0; q < NT; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    chain_gemm<K, NT, U>(xs + i * xp + 4 * j, wr, w0, acc);
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int n = 16 * (wave + q * CH_WAVES) + i;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 4 * j + r;
+        float v = acc[q][r];
+        if (ADD) v += av[q][r];
+        v = act_fwd(v + bv[q], S2P_ACT_LRELU, CH_SLOPE);
+        ys[row * CH_H_P + n] = row0 + row < B ? v : 0.f;
+      }
+    }
+  }
+};
+
+// The last layer [mean | raw_std] (2 D wide) and the head, in registers.  A wave owns PAIRS (mean tile p, raw_std tile p + D / 16).
+// Writes z(t)[:, off : off + D] to global memory and to xz; with D == 32 also mean and std.
+template <int D>
+struct ChainHead {
+  static constexpr int PAIRS = D / 16, NP = (PAIRS + CH_WAVES - 1) / CH_WAVES, NT = 2 * NP, U = ch_u(NT);
+  const float* wr[NT];
+  f32x4 w0[NT][U];
+  float ev[NP][4], bm[NP], bs[NP];
+
+  static __device__ __forceinline__ bool idle() { return (int)(threadIdx.x >> 6) >= PAIRS; }   // (wave-uniform; the 64-wide head has two pairs)
+
+  __device__ __forceinline__ void ask(const ChainArgs& a, const float* w, const float* bias, int t, int off, int row0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    if (idle()) return;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int d = 16 * (wave + p * CH_WAVES) + i;
+      wr[2 * p] = w + (size_t)d * CH_HID + 4 * j;
+      wr[2 * p + 1] = w + (size_t)(D + d) * CH_HID + 4 * j;
+      bm[p] = bias[d]; bs[p] = bias[D + d];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gm = row0 + 4 * j + r;
+        ev[p][r] = gm < a.B ? a.eps[((size_t)gm * a.T + t) * a.eps_pitch + off + d] : 0.f;
+      }
+    }
+    chain_load_w<CH_HID, NT, U>(wr, 0, w0);
+  }
+
+  __device__ __forceinline__ void run(const ChainArgs& a, const float* hs, int t, int off, int row0, float* xz) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    if (idle()) return;
+    f32x4 acc[NT];
+#pragma unroll
+    for (int q = 0; q < NT; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    chain_gemm<CH_HID, NT, U>(hs + i * CH_H_P + 4 * j, wr, w0, acc);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int d = 16 * (wave + p * CH_WAVES) + i;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 4 * j + r, gm = row0 + row;
+        const bool ok = gm < a.B;
+        const float mu = acc[2 * p][r] + bm[p], sd = gauss_head_std(acc[2 * p + 1][r] + bs[p]);
+        const float zv = gauss_head_sample(ev[p][r], sd, mu);
+        xz[row * CH_XZ_P + off + d] = ok ? zv : 0.f;
+        if (!ok) continue;
+        const size_t bt = (size_t)gm * a.T + t;
+        if (D == CH_Z1) { a.mean[bt * a.mean_pitch + d] = mu; a.std[bt * a.std_pitch + d] = sd; }
+        a.z[bt * a.z_pitch + off + d] = zv;
+      }
+    }
+  }
+};
+
+// Layers 2 and 3 of a Gaussian MLP whose first layer `l1` has been asked for: input xs, output z(t)[:, off : off + D].  Before its
+// last barrier it asks for the first layer of the NEXT MLP through `next()`.
+template <int D, typename L1, typename Next>
+__device__ __forceinline__ void chain_mlp(const ChainArgs& a, const s2p_chain_mlp& m, L1& l1, const float* xs, int t, int off, int row0,
+                                          float* xz, float* h1, float* h2, Next next) {
+  ChainHidden<CH_HID, false> l2;
+  ChainHead<D> l3;
+  __syncthreads();
+  l1.run(xs, CH_XZ_P, row0, a.B, h1);
+  l2.ask(m.w2, CH_HID, m.b2, nullptr, row0, a.B);
+  __syncthreads();
+  l2.run(h1, CH_H_P, row0, a.B, h2);
+  l3.ask(a, m.w3, m.b3, t, off, row0);
+  __syncthreads();
+  l3.run(a, h2, t, off, row0, xz);
+  next();
+}
+
+__global__ __launch_bounds__(CH_THREADS) void posterior_chain_kernel(const ChainArgs a) {
+  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
+  const int row0 = blockIdx.x * CH_ROWS;
+  ChainHidden<CH_FEAT, false> i1;
+  ChainHidden<CH_Z1, false> j1;
+  ChainHidden<CH_Z2, true> a1;
+  ChainHidden<CH_Z, true> b1;
+  i1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, nullptr, row0, a.B);
+  // feat(0) -> xz[:, 32:]; rows >= B are zeros, and so is every activation row derived from them
+  for (int idx = threadIdx.x; idx < CH_ROWS * (CH_FEAT / 4); idx += CH_THREADS) {
+    const int row = idx / (CH_FEAT / 4), c4 = idx % (CH_FEAT / 4), gm = row0 + row;
+    const f32x4 v = gm < a.B ? *(const f32x4*)(a.feat + (size_t)gm * a.feat_pitch + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    *(f32x4*)(xz + row * CH_XZ_P + CH_Z1 + 4 * c4) = v;
+  }
+  auto ask_a1 = [&](int t) {
+    if (t < a.T) a1.ask(a.m[2].w1, a.m[2].w1_row, a.m[2].b1, a.ra + (size_t)(t - 1) * a.B * CH_HID, row0, a.B);
+  };
+  // t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
+  chain_mlp<CH_Z1>(a, a.m[0], i1, xz + CH_Z1, 0, 0, row0, xz, h1, h2, [&] { j1.ask(a.m[1].w1, a.m[1].w1_row, a.m[1].b1, nullptr, row0, a.B); });
+  chain_mlp<CH_Z2>(a, a.m[1], j1, xz, 0, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(1); });
+  for (int t = 1; t < a.T; ++t) {
+    // q(z1(t) | feat(t), z2(t-1), a(t-1)), q(z2(t) | z1(t), z2(t-1), a(t-1)): the feat / action columns arrive as ra / rb
+    chain_mlp<CH_Z1>(a, a.m[2], a1, xz + CH_Z1, t, 0, row0, xz, h1, h2,
+                     [&] { b1.ask(a.m[3].w1, a.m[3].w1_row, a.m[3].b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, row0, a.B); });
+    chain_mlp<CH_Z2>(a, a.m[3], b1, xz, t, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(t + 1); });
+  }
+}
+}  // namespace
+
+extern "C" int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
+                                       int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std,
+                                       int std_pitch, float* z, int z_pitch, int B, int T, void* stream) {
+  const char* who = "s2p_posterior_chain_fwd";
+  static const int k1[4] = {CH_FEAT, CH_Z1, CH_Z2, CH_Z};
+  static const char* const name[4] = {"z1_posterior_init", "z2_prior_init", "z1_posterior", "z2_prior"};
+  CHAIN_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
+  if (B == 0 || T == 0) return 0;
+  CHAIN_REQUIRE(feat && eps && mlps && mean && std && z, "%s: null pointer (feat, eps, mlps, mean, std and z are required)", who);
+  CHAIN_REQUIRE(T == 1 || (ra && rb), "%s: ra and rb are required when T > 1", who);
+  CHAIN_REQUIRE(feat_pitch >= CH_FEAT && eps_pitch >= CH_Z && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
+                "%s: a pitch is below its row (feat 256, eps 288, mean 32, std 32, z 288)", who);
+  CHAIN_REQUIRE(s2p_al16(feat) && feat_pitch % 4 == 0, "%s: feat must be 16-byte aligned, its pitch a multiple of 4 floats", who);
+  ChainArgs a{};
+  for (int g = 0; g < (T > 1 ? 4 : 2); ++g) {
+    const s2p_chain_mlp& m = mlps[g];
+    CHAIN_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name[g]);
+    CHAIN_REQUIRE(m.k1 == k1[g], "%s: %s: the first layer's K is %d, %d is built", who, name[g], (int)m.k1, k1[g]);
+    CHAIN_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name[g]);
+    CHAIN_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name[g]);
+    a.m[g] = m;
+  }
+  a.feat = feat; a.feat_pitch = feat_pitch; a.ra = ra; a.rb = rb; a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean;
+  a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z; a.z_pitch = z_pitch; a.B = B; a.T = T;
+  hipLaunchKernelGGL(posterior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
+  S2P_CHECK_LAUNCH("posterior_chain_kernel");
+  return 0;
+}

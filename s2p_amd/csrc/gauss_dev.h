@@ -1,0 +1,22 @@
+// Device functions shared by the kernels of the SLAC Gaussian heads (linear_small.hip, gauss.hip, gauss_chain.hip).  The fused
+// posterior chain returns bitwise what the per-layer launches return BECAUSE both are made of these: the same MFMA sequence per
+// k-chunk, the same softplus, the same sample.
+#pragma once
+#include "s2p_common.h"
+
+// One k-chunk of 16 of the fp32 16x16x4 MFMA tile: lane 16 j + i holds x[row i][16 c + 4 j .. + 3] and w[col i][16 c + 4 j .. + 3];
+// MFMA e consumes component e of both.  An output element is acc after "for chunk c ascending: lin_mfma_chunk" from 0.
+__device__ __forceinline__ f32x4 lin_mfma_chunk(const f32x4 xv, const f32x4 wv, f32x4 acc) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[e], wv[e], acc, 0, 0, 0);
+  return acc;
+}
+
+__device__ __forceinline__ float gauss_softplus(float r) { return fmaxf(r, 0.f) + log1pf(expf(-fabsf(r))); }
+__device__ __forceinline__ float gauss_sigmoid(float r) {
+  const float e = expf(-fabsf(r));
+  return r >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+}
+// std of a Gaussian head from its raw output, and the reparameterised sample
+__device__ __forceinline__ float gauss_head_std(float raw) { return gauss_softplus(raw) + 1e-5f; }
+__device__ __forceinline__ float gauss_head_sample(float eps, float sd, float mu) { return __builtin_fmaf(eps, sd, mu); }

@@ -12,9 +12,11 @@
 //   wgrad (+ bias)  : dW[N][K] += sum_m dpre[m][n] x[m][k]                       a wave owns 16 n x 16 k, loop over the batch;
 // where f / dpre fold the LeakyReLU derivative of the layer's saved OUTPUT into the operand staging, so the backward of a
 // layer is two short launches (wgrad + bias grad; dgrad) -- no act_bwd pass, no atomics, fixed summation order.
-// (One launch per layer, not one per chain: a layer needs every output of the previous one, and on this chip a kernel
-// boundary (~1.5 us, hipGraph) is cheaper than an in-kernel grid barrier (~4-7 us).)
-#include "s2p_common.h"
+// (One launch per layer, not one per chain: a layer needs every output COLUMN of the previous one, and on this chip a kernel
+// boundary (~1.5 us, hipGraph) is cheaper than an in-kernel grid barrier (~4-7 us).  That holds wherever the rows of a layer are
+// spread over workgroups: the state path, and the SLAC posterior chain with grad enabled.  The no-grad posterior chain can give a
+// workgroup 16 rows and ALL columns and then needs workgroup barriers only: gauss_chain.hip runs it as one launch.)
+#include "gauss_dev.h"
 
 struct LinArgs {
   const float* x; const float* xact; const float* w; const float* bias; float* y; float* part;
@@ -65,9 +67,7 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
       }
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[u][e], wv[u][e], acc, 0, 0, 0);
+    for (int u = 0; u < U; ++u) acc = lin_mfma_chunk(xv[u], wv[u], acc);
   }
   if (n >= a.n_store) return;
   const float b = (a.bias && nok && a.ksplit <= 1) ? a.bias[n] : 0.f;

@@ -679,6 +679,29 @@ def gauss_head_fwd(raw, D, eps=None, mean=None, std=None, z=None, z2=None):
     check(lib().s2p_gauss_head_fwd(rp, rs, raw.shape[0], D, ep, es, mp, ms, sp, ss, zp, zs, z2p, z2s, stream()), "s2p_gauss_head_fwd")
 
 
+def chain_mlp(pk, group=0):
+    """The s2p_chain_mlp of a Gaussian.packed() dict; `group`: which first-layer column group is the chain's."""
+    w1, _, k1 = pk["g1"][group]
+    return _lib.ChainMlp(ptr(w1), ptr(pk["b1"]), ptr(pk["w2"]), ptr(pk["b2"]), ptr(pk["w3"]), ptr(pk["b3"]), k1, w1.shape[1])
+
+
+def posterior_chain_fwd(feat0, ra, rb, eps, mlps, mean, std, z):
+    """The whole no-grad posterior chain in one launch (s2p_posterior_chain_fwd).  feat0: the [B, 256] view feat[:, 0]; ra, rb
+    [(T-1)*B, 256] contiguous (None when T == 1); eps, mean, std, z: [B, T, C] views with unit stride in C and stride(0) =
+    T * stride(1) (a slice of a wider [B, T, W] buffer is written in place); mlps: four chain_mlp() structs."""
+    B, T = eps.shape[:2]
+    for t in (eps, mean, std, z):
+        if t.dtype != torch.float32 or t.shape[:2] != (B, T) or t.stride(2) != 1 or (B > 1 and T > 0 and t.stride(0) != T * t.stride(1)):
+            raise ValueError("[B, T, C] fp32 views whose rows (b, t) are evenly pitched are needed")
+    fp, fs = _view2(feat0)
+    for r in (ra, rb):
+        if r is not None and (not r.is_contiguous() or r.dtype != torch.float32 or r.shape != ((T - 1) * B, 256)):
+            raise ValueError("ra / rb are contiguous fp32 [(T-1)*B, 256]")
+    arr = (_lib.ChainMlp * 4)(*mlps)
+    check(lib().s2p_posterior_chain_fwd(fp, fs, ptr(ra), ptr(rb), ptr(eps), eps.stride(1), arr, ptr(mean), mean.stride(1), ptr(std),
+                                        std.stride(1), ptr(z), z.stride(1), B, T, stream()), "s2p_posterior_chain_fwd")
+
+
 def gauss_head_bwd(raw, D, draw, eps=None, dmean=None, dstd=None, dz=None, dz2=None):
     """draw[:, :2D] = [dmean + dz + dz2 | (dstd + (dz + dz2) * eps) * sigmoid(raw_std)]."""
     views = [_view2(t) for t in (raw, eps, dmean, dstd, dz, dz2, draw)]

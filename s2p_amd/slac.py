@@ -349,7 +349,8 @@ class _PosteriorFn(torch.autograd.Function):
     feat [B,T,256], action [B,T-1,A], noise [B,T,288] (keep: the caller's grad mode; activations are saved only then) -> z1_mean [B,T,32], z1_std [B,T,32], z [B,T,288] (z1 | z2).
     Per time step the chain is 8 launches forward (2 x (3 layers + head)) and 8 backward (2 x (head + 3 dgrads)): the
     feature / action columns of the two first layers are one batched GEMM before the chain, every weight gradient and the
-    feature / action gradients are batched launches after it."""
+    feature / action gradients are batched launches after it.  With `model.fused_chain` a call that keeps no backward state
+    (keep False) runs the hoisted GEMMs and then the whole chain as one launch (_fused; SPEC.md N3h), bitwise the same."""
 
     @staticmethod
     def forward(ctx, feat, action, noise, model, keep, *params):
@@ -362,6 +363,8 @@ class _PosteriorFn(torch.autograd.Function):
         slot = (lambda t: t - 1) if keep else (lambda t: 0)
         z = _f32((B, T, Z1 + Z2), dev)
         mean, std = _f32((B, T, Z1), dev), _f32((B, T, Z1), dev)
+        if model.fused_chain and not keep:
+            return _PosteriorFn._fused(ctx, model, feat, action, noise, (pi1, pi2, p1, p2), mean, std, z)
         # t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
         xz = _f32((Tn, B, Z1 + Z2), dev)                               # [slot(t)] = z1(t) | z2(t-1): the chain's input rows
         a0 = _mlp_fwd(gi1, pi1, feat[:, 0], B, dev)
@@ -370,15 +373,7 @@ class _PosteriorFn(torch.autograd.Function):
         ops.gauss_head_fwd(b0[2], Z2, eps=noise[:, 0, Z1:], z=z[:, 0, Z1:], z2=xz[0][:, Z1:] if S > 0 else None)
         sv = None
         if S > 0:
-            # what does not depend on the chain: feat(t) | a(t-1) -> the row term of z1_posterior's first layer, a(t-1) -> z2_posterior's
-            ka, kb = p1["g1"][1][0].shape[1], p2["g1"][1][0].shape[1]
-            xa, xb = _f32((S, B, ka), dev, True), _f32((S, B, kb), dev, True)
-            xa[:, :, :FEAT] = feat[:, 1:].transpose(0, 1)
-            xa[:, :, FEAT:FEAT + A] = action.transpose(0, 1)
-            xb[:, :, :A] = action.transpose(0, 1)
-            ra, rb = _f32((S * B, HID), dev), _f32((S * B, HID), dev)
-            ops.linear_fwd_into(xa.view(S * B, ka), p1["g1"][1][0], None, HID, ra)
-            ops.linear_fwd_into(xb.view(S * B, kb), p2["g1"][1][0], None, HID, rb)
+            xa, xb, ra, rb = _PosteriorFn._hoisted(feat, action, p1, p2)
             h1a, h2a, rawa = _f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g1.Npad), dev)
             h1b, h2b, rawb = _f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g2.Npad), dev)
             for t in range(1, T):
@@ -395,6 +390,36 @@ class _PosteriorFn(torch.autograd.Function):
         ctx.model, ctx.packs, ctx.A = model, (pi1, pi2, p1, p2), A
         ctx.saved = (feat, noise, z, xz, a0, b0, sv) if keep else None
         model.chain_state_bytes = sum(t.numel() * 4 for t in (xz,) + a0 + b0 + (sv or ())) if keep else 0
+        return mean, std, z
+
+    @staticmethod
+    def _hoisted(feat, action, p1, p2):
+        """What does not depend on the chain: feat(t) | a(t-1) -> the row term of z1_posterior's first layer, a(t-1) -> z2_posterior's.
+        Returns the two inputs [S,B,Kpad] and the two terms [S*B, 256] (time-major)."""
+        dev = feat.device
+        B, T, _ = feat.shape
+        S, A = T - 1, action.shape[2]
+        ka, kb = p1["g1"][1][0].shape[1], p2["g1"][1][0].shape[1]
+        xa, xb = _f32((S, B, ka), dev, True), _f32((S, B, kb), dev, True)
+        xa[:, :, :FEAT] = feat[:, 1:].transpose(0, 1)
+        xa[:, :, FEAT:FEAT + A] = action.transpose(0, 1)
+        xb[:, :, :A] = action.transpose(0, 1)
+        ra, rb = _f32((S * B, HID), dev), _f32((S * B, HID), dev)
+        ops.linear_fwd_into(xa.view(S * B, ka), p1["g1"][1][0], None, HID, ra)
+        ops.linear_fwd_into(xb.view(S * B, kb), p2["g1"][1][0], None, HID, rb)
+        return xa, xb, ra, rb
+
+    @staticmethod
+    def _fused(ctx, model, feat, action, noise, packs, mean, std, z):
+        """No backward state is wanted: the hoisted terms as in forward(), then the whole chain as ONE launch
+        (s2p_posterior_chain_fwd; bitwise the per-layer path)."""
+        pi1, pi2, p1, p2 = packs
+        ra = rb = None
+        if feat.shape[1] > 1:
+            _, _, ra, rb = _PosteriorFn._hoisted(feat, action, p1, p2)
+        ops.posterior_chain_fwd(feat[:, 0], ra, rb, noise, [ops.chain_mlp(p) for p in packs], mean, std, z)
+        ctx.model, ctx.packs, ctx.A, ctx.saved = model, packs, action.shape[2], None
+        model.chain_state_bytes = 0
         return mean, std, z
 
     @staticmethod
@@ -549,6 +574,7 @@ class LatentModel(nn.Module):
                     nn.init.xavier_uniform_(p, gain=1.0)
         self.to(dev)
         self.chain_state_bytes = 0              # bytes the last sample_posterior kept for its backward (0 under no_grad)
+        self.fused_chain = False                # True: a no-grad sample_posterior runs its chain as ONE launch (SPEC.md N3h)
 
     @property
     def device(self):
