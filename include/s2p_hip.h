@@ -288,7 +288,8 @@ int s2p_gauss_head_bwd(const float* raw, int raw_pitch, int M, int D, const floa
 /* s2p_linear_fwd with an additive input:  y = act(x[M][K] . w[N][w_row]^T + add[M][add_pitch] + bias)  (add, bias may be
  * NULL; y may be the add buffer itself).  For a first layer whose input is a concatenation of which only some columns
  * change per time step: the other columns' product is one batched s2p_linear_fwd over all time steps, passed here as add.
- * K, x_pitch, w_row multiples of 4 floats, x and w 16-byte aligned; columns [N, n_store) of y are written as zeros.       */
+ * K, x_pitch, w_row multiples of 4 floats, x and w 16-byte aligned; columns [N, n_store) of y are written as zeros.
+ * The kernel is s2p_linear_fwd's (csrc/linear_small.hip): with add == NULL the two return the same bits.                  */
 int s2p_linear_add_fwd(const float* x, int M, int K, int x_pitch, const float* w, int w_row, const float* bias, int N,
                        const float* add, int add_pitch, int act, float slope, float* y, int y_pitch, int n_store,
                        void* stream);

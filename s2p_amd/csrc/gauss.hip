@@ -2,26 +2,17 @@
 // The posterior chain is 9 strictly sequential time steps of two 3-layer MLPs at M = batch rows: latency-bound like the state path
 // (linear_small.hip).  With grad enabled a layer stays one short launch (the backward needs every activation in memory); a call
 // that keeps no backward state can run the whole chain as ONE launch instead (gauss_chain.hip, LatentModel.fused_chain), built from
-// the same device functions (gauss_dev.h) and bitwise equal.  What this file adds so that NO torch.cat / chunk / stack /
-// element-wise kernel runs between the per-layer launches:
+// the same device functions (gauss_dev.h) and bitwise equal.  The chain's linear layers, with the additive term that takes the
+// part of a first layer's input the chain does not produce, are in linear_small.hip.  This file holds the heads and the three
+// losses, so that NO torch.cat / chunk / stack / element-wise kernel runs between the per-layer launches:
 //   gauss_head_{fwd,bwd}_kernel : [mean | raw] -> mean, std = softplus(raw) + 1e-5, z = mean + eps * std, every output with its own
 //                                 pitch and column offset (the sample to two places: the sequence buffer and the next MLP's input
 //                                 row); backward [dmean + dz | (dstd + dz eps) sigmoid(raw)].
-//   gauss_lin_add_kernel        : y = act(f(x) . W^T + add + bias), the forward GEMM tile of lin_fwd_kernel (fp32 MFMA 16x16x4,
-//                                 operands from global memory, no LDS) with an additive [M][N] term: the part of a first layer's
-//                                 pre-activation that does not depend on the chain (features, actions) is ONE batched GEMM before
-//                                 the chain.  f folds the activation derivative of a saved output into x, so the same kernel is the
-//                                 dgrad (add = the gradient already accumulated at the destination).
-//   gauss_actgrad_kernel        : dpre = dy * act'(y), the gradient of the additive term (and the operand of the batched weight
-//                                 gradient that runs once after the chain).
 //   gauss_kl_kernel, gauss_ll_kernel, gauss_ll_image_kernel : loss value and every gradient in one pass.
 // Reductions: the KL and the masked (reward) likelihood are ONE workgroup each, summed in a fixed order, no atomics.  The image
 // likelihood (8.6 M elements at B = 32) ends in ONE fp32 atomicAdd per workgroup on the loss word, as s2p_l1_loss does: its VALUE
 // can differ in the last bits between calls, its gradient cannot (element-wise).
 #include "gauss_dev.h"
-
-#define GAUSS_REQUIRE(cond, ...) do { if (!(cond)) S2P_FAIL(-1, __VA_ARGS__); } while (0)
-static inline bool gauss_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---- Gaussian head ---------------------------------------------------------------------------------------------------------------
 struct HeadArgs {
@@ -71,13 +62,13 @@ static inline int gauss_grid(long long total, int cap = 1024) {
 extern "C" int s2p_gauss_head_fwd(const float* raw, int raw_pitch, int M, int D, const float* eps, int eps_pitch, float* mean,
                                   int mean_pitch, float* std, int std_pitch, float* z, int z_pitch, float* z2, int z2_pitch,
                                   void* stream) {
-  GAUSS_REQUIRE(M >= 0 && D >= 0, "s2p_gauss_head_fwd: negative size");
+  S2P_REQUIRE(M >= 0 && D >= 0, "s2p_gauss_head_fwd: negative size");
   if (M == 0 || D == 0) return 0;
-  GAUSS_REQUIRE(raw && raw_pitch >= 2 * D, "s2p_gauss_head_fwd: raw is NULL or its pitch is below 2 D");
-  GAUSS_REQUIRE(mean || std || z || z2, "s2p_gauss_head_fwd: no output");
-  GAUSS_REQUIRE((!z && !z2) || eps, "s2p_gauss_head_fwd: a sample needs eps");
-  GAUSS_REQUIRE((!eps || eps_pitch >= D) && (!mean || mean_pitch >= D) && (!std || std_pitch >= D) && (!z || z_pitch >= D) &&
-                (!z2 || z2_pitch >= D), "s2p_gauss_head_fwd: a pitch is below D");
+  S2P_REQUIRE(raw && raw_pitch >= 2 * D, "s2p_gauss_head_fwd: raw is NULL or its pitch is below 2 D");
+  S2P_REQUIRE(mean || std || z || z2, "s2p_gauss_head_fwd: no output");
+  S2P_REQUIRE((!z && !z2) || eps, "s2p_gauss_head_fwd: a sample needs eps");
+  S2P_REQUIRE((!eps || eps_pitch >= D) && (!mean || mean_pitch >= D) && (!std || std_pitch >= D) && (!z || z_pitch >= D) &&
+              (!z2 || z2_pitch >= D), "s2p_gauss_head_fwd: a pitch is below D");
   HeadArgs a{}; a.raw = raw; a.raw_pitch = raw_pitch; a.M = M; a.D = D; a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean;
   a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z; a.z_pitch = z_pitch; a.z2 = z2; a.z2_pitch = z2_pitch;
   hipLaunchKernelGGL(gauss_head_fwd_kernel, dim3(gauss_grid((long long)M * D)), dim3(256), 0, (hipStream_t)stream, a);
@@ -88,145 +79,17 @@ extern "C" int s2p_gauss_head_fwd(const float* raw, int raw_pitch, int M, int D,
 extern "C" int s2p_gauss_head_bwd(const float* raw, int raw_pitch, int M, int D, const float* eps, int eps_pitch,
                                   const float* dmean, int dmean_pitch, const float* dstd, int dstd_pitch, const float* dz,
                                   int dz_pitch, const float* dz2, int dz2_pitch, float* draw, int draw_pitch, void* stream) {
-  GAUSS_REQUIRE(M >= 0 && D >= 0, "s2p_gauss_head_bwd: negative size");
+  S2P_REQUIRE(M >= 0 && D >= 0, "s2p_gauss_head_bwd: negative size");
   if (M == 0 || D == 0) return 0;
-  GAUSS_REQUIRE(raw && raw_pitch >= 2 * D && draw && draw_pitch >= 2 * D, "s2p_gauss_head_bwd: raw / draw is NULL or its pitch is below 2 D");
-  GAUSS_REQUIRE((!dz && !dz2) || eps, "s2p_gauss_head_bwd: the gradient of a sample needs eps");
-  GAUSS_REQUIRE((!eps || eps_pitch >= D) && (!dmean || dmean_pitch >= D) && (!dstd || dstd_pitch >= D) && (!dz || dz_pitch >= D) &&
-                (!dz2 || dz2_pitch >= D), "s2p_gauss_head_bwd: a pitch is below D");
+  S2P_REQUIRE(raw && raw_pitch >= 2 * D && draw && draw_pitch >= 2 * D, "s2p_gauss_head_bwd: raw / draw is NULL or its pitch is below 2 D");
+  S2P_REQUIRE((!dz && !dz2) || eps, "s2p_gauss_head_bwd: the gradient of a sample needs eps");
+  S2P_REQUIRE((!eps || eps_pitch >= D) && (!dmean || dmean_pitch >= D) && (!dstd || dstd_pitch >= D) && (!dz || dz_pitch >= D) &&
+              (!dz2 || dz2_pitch >= D), "s2p_gauss_head_bwd: a pitch is below D");
   HeadArgs a{}; a.raw = raw; a.raw_pitch = raw_pitch; a.M = M; a.D = D; a.eps = eps; a.eps_pitch = eps_pitch; a.dmean = dmean;
   a.dmean_pitch = dmean_pitch; a.dstd = dstd; a.dstd_pitch = dstd_pitch; a.dz = dz; a.dz_pitch = dz_pitch; a.dz2 = dz2;
   a.dz2_pitch = dz2_pitch; a.draw = draw; a.draw_pitch = draw_pitch;
   hipLaunchKernelGGL(gauss_head_bwd_kernel, dim3(gauss_grid((long long)M * D)), dim3(256), 0, (hipStream_t)stream, a);
   S2P_CHECK_LAUNCH("gauss_head_bwd_kernel");
-  return 0;
-}
-
-// ---- linear layer with an additive term --------------------------------------------------------------------------------------------
-struct LinAddArgs {
-  const float* x; const float* xact; const float* w; const float* bias; const float* add; float* y;
-  int M, K, N, x_pitch, xact_pitch, w_row, add_pitch, y_pitch, n_store, act, in_act; float slope;
-};
-
-// The tile of lin_fwd_kernel (linear_small.hip: MFMA operand layout and the k permutation are explained there); the epilogue adds
-// add[m][n] before bias and activation.  y may be the same buffer as add: every element is read and written by one lane.
-__global__ __launch_bounds__(256) void gauss_lin_add_kernel(const LinAddArgs a) {
-  constexpr int U = 8;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
-  const int nb = blockIdx.x * 16, mb = blockIdx.y * 64 + wave * 16;
-  if (mb >= a.M) return;                                   // (wave-uniform)
-  const int m = mb + i, n = nb + i;
-  const bool mok = m < a.M, nok = n < a.N;
-  const float* xr = a.x + (size_t)(mok ? m : 0) * a.x_pitch;
-  const float* ar = a.xact ? a.xact + (size_t)(mok ? m : 0) * a.xact_pitch : nullptr;
-  const float* wr = a.w + (size_t)(nok ? n : 0) * a.w_row;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int kc = 0; kc < a.K; kc += 16 * U) {
-    f32x4 xv[U], wv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = kc + 16 * u + 4 * j;                   // K and the pitches are multiples of 4: a float4 is in or out
-      xv[u] = (mok && k < a.K) ? *(const f32x4*)(xr + k) : (f32x4){0.f, 0.f, 0.f, 0.f};
-      wv[u] = (nok && k < a.K) ? *(const f32x4*)(wr + k) : (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (ar && mok && k < a.K) {
-        const f32x4 yv = *(const f32x4*)(ar + k);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xv[u][e] *= act_grad_from_out(yv[e], a.in_act, a.slope);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) acc = lin_mfma_chunk(xv[u], wv[u], acc);
-  }
-  if (n >= a.n_store) return;
-  const float b = (a.bias && nok) ? a.bias[n] : 0.f;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int mo = mb + 4 * j + r;
-    if (mo >= a.M) continue;
-    float v = 0.f;
-    if (nok) {
-      v = acc[r];
-      if (a.add) v += a.add[(size_t)mo * a.add_pitch + n];
-      v = act_fwd(v + b, a.act, a.slope);
-    }
-    a.y[(size_t)mo * a.y_pitch + n] = v;
-  }
-}
-
-__global__ __launch_bounds__(256) void gauss_actgrad_kernel(const float* dy, int dy_pitch, const float* y, int y_pitch, int M, int N,
-                                                            int act, float slope, float* out, int out_pitch) {
-  const long long total = (long long)M * N;
-  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
-    const int m = (int)(idx / N), n = (int)(idx - (long long)m * N);
-    float v = dy[(size_t)m * dy_pitch + n];
-    if (y) v *= act_grad_from_out(y[(size_t)m * y_pitch + n], act, slope);
-    out[(size_t)m * out_pitch + n] = v;
-  }
-}
-
-static int lin_add_launch(const char* who, const float* x, const float* xact, int xact_pitch, int in_act, int M, int K, int x_pitch,
-                          const float* w, int w_row, const float* bias, int N, const float* add, int add_pitch, int act, float slope,
-                          float* y, int y_pitch, int n_store, hipStream_t st) {
-  GAUSS_REQUIRE(K % 4 == 0 && x_pitch % 4 == 0 && w_row % 4 == 0 && x_pitch >= K && w_row >= K,
-                "%s: K, x_pitch and w_row must be multiples of 4 floats, the pitches at least K", who);
-  GAUSS_REQUIRE(gauss_al16(x) && gauss_al16(w) && (!xact || (gauss_al16(xact) && xact_pitch % 4 == 0 && xact_pitch >= K)),
-                "%s: x, w (and the activation output) must be 16-byte aligned", who);
-  GAUSS_REQUIRE(n_store >= N && n_store <= y_pitch, "%s: N <= n_store <= y_pitch is required", who);
-  GAUSS_REQUIRE(!add || add_pitch >= N, "%s: add_pitch is below N", who);
-  LinAddArgs a{}; a.x = x; a.xact = xact; a.xact_pitch = xact_pitch; a.in_act = in_act; a.M = M; a.K = K; a.x_pitch = x_pitch; a.w = w;
-  a.w_row = w_row; a.bias = bias; a.N = N; a.add = add; a.add_pitch = add_pitch; a.act = act; a.slope = slope; a.y = y;
-  a.y_pitch = y_pitch; a.n_store = n_store;
-  hipLaunchKernelGGL(gauss_lin_add_kernel, dim3(cdiv(n_store, 16), cdiv(M, 64), 1), dim3(256), 0, st, a);
-  S2P_CHECK_LAUNCH("gauss_lin_add_kernel");
-  return 0;
-}
-
-extern "C" int s2p_linear_add_fwd(const float* x, int M, int K, int x_pitch, const float* w, int w_row, const float* bias, int N,
-                                  const float* add, int add_pitch, int act, float slope, float* y, int y_pitch, int n_store,
-                                  void* stream) {
-  GAUSS_REQUIRE(M >= 0 && K >= 0 && N >= 0, "s2p_linear_add_fwd: negative size");
-  if (M == 0 || N == 0) return 0;
-  GAUSS_REQUIRE(K > 0, "s2p_linear_add_fwd: empty reduction");
-  GAUSS_REQUIRE(x && w && y, "s2p_linear_add_fwd: null pointer");
-  GAUSS_REQUIRE(act >= S2P_ACT_NONE && act <= S2P_ACT_SWISH, "s2p_linear_add_fwd: unknown activation %d", act);
-  return lin_add_launch("s2p_linear_add_fwd", x, nullptr, 0, S2P_ACT_NONE, M, K, x_pitch, w, w_row, bias, N, add, add_pitch, act, slope,
-                        y, y_pitch, n_store, (hipStream_t)stream);
-}
-
-extern "C" int s2p_linear_add_bwd(const float* x, int x_pitch, const float* dy, int dy_pitch, const float* y, int y_pitch, int M,
-                                  int K, int k_real, int N, const float* w_bwd, int wb_row, int act, float slope, float* dw,
-                                  int dw_row, float* db, float* dx, int dx_pitch, int dx_accumulate, float* dadd, int dadd_pitch,
-                                  void* stream) {
-  GAUSS_REQUIRE(M >= 0 && K >= 0 && N >= 0, "s2p_linear_add_bwd: negative size");
-  if (M == 0 || N == 0 || K == 0) return 0;
-  GAUSS_REQUIRE(dy && dy_pitch >= N, "s2p_linear_add_bwd: dy is NULL or its pitch is below N");
-  GAUSS_REQUIRE(act == S2P_ACT_NONE || act == S2P_ACT_RELU || act == S2P_ACT_LRELU,
-                "s2p_linear_add_bwd: activation %d has no backward here (none / relu / lrelu only)", act);
-  GAUSS_REQUIRE(act == S2P_ACT_NONE || (y && y_pitch >= N), "s2p_linear_add_bwd: the activation output is needed");
-  GAUSS_REQUIRE(dw || dx || dadd, "s2p_linear_add_bwd: no output");
-  GAUSS_REQUIRE(!dadd || dadd_pitch >= N, "s2p_linear_add_bwd: dadd_pitch is below N");
-  GAUSS_REQUIRE(!dw || (x && dw_row >= k_real && k_real >= 0 && k_real <= K), "s2p_linear_add_bwd: dw needs x and k_real <= dw_row, K");
-  GAUSS_REQUIRE(!db || dw, "s2p_linear_add_bwd: db is produced by the weight-gradient pass (dw is NULL)");
-  GAUSS_REQUIRE(!dx || (w_bwd && dx_pitch >= K && N % 4 == 0 && dy_pitch % 4 == 0 && gauss_al16(dy)),
-                "s2p_linear_add_bwd: dx needs w_bwd, dx_pitch >= K, N and dy_pitch multiples of 4, dy 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const float* ya = act != S2P_ACT_NONE ? y : nullptr;
-  if (dadd) {
-    hipLaunchKernelGGL(gauss_actgrad_kernel, dim3(gauss_grid((long long)M * N)), dim3(256), 0, st, dy, dy_pitch, ya, y_pitch, M, N, act,
-                       slope, dadd, dadd_pitch);
-    S2P_CHECK_LAUNCH("gauss_actgrad_kernel");
-  }
-  if (dw) {
-    int rc = s2p_linear_bwd(x, x_pitch, dy, dy_pitch, y, y_pitch, M, K, k_real, N, nullptr, 0, act, slope, dw, dw_row, db, nullptr, 0,
-                            nullptr, 0, stream);
-    if (rc) return rc;
-  }
-  if (dx) {
-    // dgrad: "x" = dy with the activation derivative folded in, reduction over N, output columns = the K inputs
-    const int kcols = (K + 3) / 4 * 4 <= dx_pitch ? (K + 3) / 4 * 4 : K;
-    return lin_add_launch("s2p_linear_add_bwd", dy, ya, y_pitch, act, M, N, dy_pitch, w_bwd, wb_row, nullptr, K,
-                          dx_accumulate ? dx : nullptr, dx_pitch, S2P_ACT_NONE, slope, dx, dx_pitch, dx_accumulate ? K : kcols, st);
-  }
   return 0;
 }
 
@@ -274,13 +137,13 @@ __global__ __launch_bounds__(256) void gauss_kl_kernel(const KlArgs a) {
 extern "C" int s2p_gauss_kl(const float* mu_p, const float* std_p, int p_pitch, const float* mu_q, const float* std_q, int q_pitch,
                             int B, int T, int D, int const_first, float scale, float* loss, float* dmu_p, float* dstd_p,
                             int dp_pitch, float* dmu_q, float* dstd_q, int dq_pitch, void* stream) {
-  GAUSS_REQUIRE(B >= 0 && T >= 0 && D >= 0, "s2p_gauss_kl: negative size");
+  S2P_REQUIRE(B >= 0 && T >= 0 && D >= 0, "s2p_gauss_kl: negative size");
   if (B == 0 || T == 0 || D == 0) return 0;
   const bool need_q = !(const_first && T == 1);
-  GAUSS_REQUIRE(mu_p && std_p && loss && p_pitch >= D, "s2p_gauss_kl: null pointer or p_pitch below D");
-  GAUSS_REQUIRE(!need_q || (mu_q && std_q && q_pitch >= D), "s2p_gauss_kl: the prior is NULL or q_pitch below D");
-  GAUSS_REQUIRE((!dmu_p && !dstd_p) || dp_pitch >= D, "s2p_gauss_kl: dp_pitch below D");
-  GAUSS_REQUIRE((!dmu_q && !dstd_q) || dq_pitch >= D, "s2p_gauss_kl: dq_pitch below D");
+  S2P_REQUIRE(mu_p && std_p && loss && p_pitch >= D, "s2p_gauss_kl: null pointer or p_pitch below D");
+  S2P_REQUIRE(!need_q || (mu_q && std_q && q_pitch >= D), "s2p_gauss_kl: the prior is NULL or q_pitch below D");
+  S2P_REQUIRE((!dmu_p && !dstd_p) || dp_pitch >= D, "s2p_gauss_kl: dp_pitch below D");
+  S2P_REQUIRE((!dmu_q && !dstd_q) || dq_pitch >= D, "s2p_gauss_kl: dq_pitch below D");
   KlArgs a{}; a.mu_p = mu_p; a.std_p = std_p; a.p_pitch = p_pitch; a.mu_q = mu_q; a.std_q = std_q; a.q_pitch = q_pitch; a.B = B; a.T = T;
   a.D = D; a.const_first = const_first ? 1 : 0; a.scale = scale; a.loss = loss; a.dmu_p = dmu_p; a.dstd_p = dstd_p; a.dp_pitch = dp_pitch;
   a.dmu_q = dmu_q; a.dstd_q = dstd_q; a.dq_pitch = dq_pitch;
@@ -309,10 +172,10 @@ __global__ __launch_bounds__(256) void gauss_ll_kernel(const float* mu, int mu_p
 
 extern "C" int s2p_gauss_ll(const float* mu, int mu_pitch, const float* std, int std_pitch, const float* target, const float* done,
                             int64_t n, float scale, float* loss, float* dmu, float* dstd, void* stream) {
-  GAUSS_REQUIRE(n >= 0, "s2p_gauss_ll: negative size");
+  S2P_REQUIRE(n >= 0, "s2p_gauss_ll: negative size");
   if (n == 0) return 0;
-  GAUSS_REQUIRE(mu && std && target && loss, "s2p_gauss_ll: null pointer");
-  GAUSS_REQUIRE(mu_pitch >= 1 && std_pitch >= 1, "s2p_gauss_ll: a pitch is below 1");
+  S2P_REQUIRE(mu && std && target && loss, "s2p_gauss_ll: null pointer");
+  S2P_REQUIRE(mu_pitch >= 1 && std_pitch >= 1, "s2p_gauss_ll: a pitch is below 1");
   hipLaunchKernelGGL(gauss_ll_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, mu, mu_pitch, std, std_pitch, target, done,
                      (long long)n, scale, loss, dmu, dstd);
   S2P_CHECK_LAUNCH("gauss_ll_kernel");
@@ -357,15 +220,15 @@ __global__ __launch_bounds__(256) void gauss_ll_image_kernel(const T* mu, int pi
 
 extern "C" int s2p_gauss_ll_image(int dtype, const void* mu, int pitch, const void* target, int target_u8, int N, int C, int HW,
                                   float sigma, float scale, float* loss, void* dmu, void* stream) {
-  GAUSS_REQUIRE(dtype == S2P_F32 || dtype == S2P_BF16, "s2p_gauss_ll_image: bad dtype");
-  GAUSS_REQUIRE(N >= 0 && C >= 0 && HW >= 0, "s2p_gauss_ll_image: negative size");
+  S2P_REQUIRE(dtype == S2P_F32 || dtype == S2P_BF16, "s2p_gauss_ll_image: bad dtype");
+  S2P_REQUIRE(N >= 0 && C >= 0 && HW >= 0, "s2p_gauss_ll_image: negative size");
   if (N == 0 || C == 0 || HW == 0) return 0;
   const int ce = dtype == S2P_F32 ? 4 : 8;
-  GAUSS_REQUIRE(mu && target && loss, "s2p_gauss_ll_image: null pointer");
-  GAUSS_REQUIRE(pitch >= C && pitch % ce == 0, "s2p_gauss_ll_image: pitch must be a multiple of %d and at least C", ce);
-  GAUSS_REQUIRE(gauss_al16(mu) && gauss_al16(dmu), "s2p_gauss_ll_image: mu and dmu must be 16-byte aligned");
-  GAUSS_REQUIRE(target_u8 || ((uintptr_t)target & 3) == 0, "s2p_gauss_ll_image: an fp32 target must be 4-byte aligned");
-  GAUSS_REQUIRE(sigma > 0.f, "s2p_gauss_ll_image: sigma must be positive");
+  S2P_REQUIRE(mu && target && loss, "s2p_gauss_ll_image: null pointer");
+  S2P_REQUIRE(pitch >= C && pitch % ce == 0, "s2p_gauss_ll_image: pitch must be a multiple of %d and at least C", ce);
+  S2P_REQUIRE(s2p_al16(mu) && s2p_al16(dmu), "s2p_gauss_ll_image: mu and dmu must be 16-byte aligned");
+  S2P_REQUIRE(target_u8 || ((uintptr_t)target & 3) == 0, "s2p_gauss_ll_image: an fp32 target must be 4-byte aligned");
+  S2P_REQUIRE(sigma > 0.f, "s2p_gauss_ll_image: sigma must be positive");
   const long long pixels = (long long)N * HW;
   const dim3 g(gauss_grid(pixels, 512));                   // one atomicAdd per workgroup on the loss word (see s2p_l1_loss)
   hipStream_t st = (hipStream_t)stream;

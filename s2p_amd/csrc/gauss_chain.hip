@@ -5,10 +5,10 @@
 // cooperative launch, no traffic between workgroups.  grid = ceil(B / 16); at B = 256 that is 16 workgroups on 256 CUs, which is
 // accepted: the unfused chain is 72 launches whose time is launch latency, not arithmetic.
 //
-// Bitwise the per-layer path (lin_fwd_kernel / gauss_lin_add_kernel / gauss_head_fwd_kernel): an output element is the accumulator
-// after lin_mfma_chunk over the k-chunks in ascending order from 0 (gauss_dev.h, the same function those kernels call), K is never
-// split, then (acc + add) + bias or acc + bias, LeakyReLU 0.2, and the head of gauss_dev.h.  A row of an MFMA tile depends on that
-// row's operands alone, so which rows share a tile does not matter; rows >= B are zero operands and are never stored.
+// Bitwise the per-layer path (lin_fwd_kernel with and without its additive term, gauss_head_fwd_kernel): an output element is the
+// accumulator after lin_mfma_chunk over the k-chunks in ascending order from 0 (gauss_dev.h, the function lin_fwd_kernel calls), K is
+// never split, then (acc + add) + bias or acc + bias, LeakyReLU 0.2, and the head of gauss_dev.h.  A row of an MFMA tile depends on
+// that row's operands alone, so which rows share a tile does not matter; rows >= B are zero operands and are never stored.
 //
 // 512 threads = 8 waves, two per SIMD.  The waves split the 16-column tiles of a layer: 2 tiles each in a 256-wide layer, and in a
 // head layer (64 or 512 wide, [mean | raw_std]) a wave takes PAIRS of tiles (mean tile p, raw_std tile p + D/16), so the lane that
@@ -27,8 +27,6 @@
 // all 16 rows start on one bank, with +4 floats row i starts on bank 4 i (mod 64).  (The 16-lane groups a ds_read_b128 is served in
 // are not the j groups, so one lane pair per group still collides; +8 removes that and measures the same: the LDS is not the limit.)
 #include "gauss_dev.h"
-
-#define CHAIN_REQUIRE(cond, ...) do { if (!(cond)) S2P_FAIL(-1, __VA_ARGS__); } while (0)
 
 namespace {
 constexpr int CH_Z1 = 32, CH_Z2 = 256, CH_Z = CH_Z1 + CH_Z2, CH_HID = 256, CH_FEAT = 256;
@@ -248,20 +246,20 @@ extern "C" int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const 
   const char* who = "s2p_posterior_chain_fwd";
   static const int k1[4] = {CH_FEAT, CH_Z1, CH_Z2, CH_Z};
   static const char* const name[4] = {"z1_posterior_init", "z2_prior_init", "z1_posterior", "z2_prior"};
-  CHAIN_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
+  S2P_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
   if (B == 0 || T == 0) return 0;
-  CHAIN_REQUIRE(feat && eps && mlps && mean && std && z, "%s: null pointer (feat, eps, mlps, mean, std and z are required)", who);
-  CHAIN_REQUIRE(T == 1 || (ra && rb), "%s: ra and rb are required when T > 1", who);
-  CHAIN_REQUIRE(feat_pitch >= CH_FEAT && eps_pitch >= CH_Z && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
-                "%s: a pitch is below its row (feat 256, eps 288, mean 32, std 32, z 288)", who);
-  CHAIN_REQUIRE(s2p_al16(feat) && feat_pitch % 4 == 0, "%s: feat must be 16-byte aligned, its pitch a multiple of 4 floats", who);
+  S2P_REQUIRE(feat && eps && mlps && mean && std && z, "%s: null pointer (feat, eps, mlps, mean, std and z are required)", who);
+  S2P_REQUIRE(T == 1 || (ra && rb), "%s: ra and rb are required when T > 1", who);
+  S2P_REQUIRE(feat_pitch >= CH_FEAT && eps_pitch >= CH_Z && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
+              "%s: a pitch is below its row (feat 256, eps 288, mean 32, std 32, z 288)", who);
+  S2P_REQUIRE(s2p_al16(feat) && feat_pitch % 4 == 0, "%s: feat must be 16-byte aligned, its pitch a multiple of 4 floats", who);
   ChainArgs a{};
   for (int g = 0; g < (T > 1 ? 4 : 2); ++g) {
     const s2p_chain_mlp& m = mlps[g];
-    CHAIN_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name[g]);
-    CHAIN_REQUIRE(m.k1 == k1[g], "%s: %s: the first layer's K is %d, %d is built", who, name[g], (int)m.k1, k1[g]);
-    CHAIN_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name[g]);
-    CHAIN_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name[g]);
+    S2P_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name[g]);
+    S2P_REQUIRE(m.k1 == k1[g], "%s: %s: the first layer's K is %d, %d is built", who, name[g], (int)m.k1, k1[g]);
+    S2P_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name[g]);
+    S2P_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name[g]);
     a.m[g] = m;
   }
   a.feat = feat; a.feat_pitch = feat_pitch; a.ra = ra; a.rb = rb; a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean;

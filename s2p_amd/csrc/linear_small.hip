@@ -16,28 +16,34 @@
 // boundary (~1.5 us, hipGraph) is cheaper than an in-kernel grid barrier (~4-7 us).  That holds wherever the rows of a layer are
 // spread over workgroups: the state path, and the SLAC posterior chain with grad enabled.  The no-grad posterior chain can give a
 // workgroup 16 rows and ALL columns and then needs workgroup barriers only: gauss_chain.hip runs it as one launch.)
+//
+// The SLAC Gaussian MLPs' variant of a layer is here too (s2p_linear_add_fwd / s2p_linear_add_bwd): the same forward kernel with an
+// additive [M][N] term in its epilogue, y = act(f(x) . W^T + add + bias).  The part of a first layer's pre-activation that does not
+// depend on the posterior chain (features, actions) is ONE batched GEMM before the chain and comes in as `add`; in the dgrad `add` is
+// the gradient already accumulated at the destination.  lin_actgrad_kernel (dpre = dy * act'(y)) is the additive term's gradient,
+// and the operand of the batched weight gradient that runs once after the chain.  There is ONE forward tile: s2p_linear_fwd and
+// s2p_linear_add_fwd with add == NULL are the same launch, and the fused chain (gauss_chain.hip) promises the bits of both.
 #include "gauss_dev.h"
 
 struct LinArgs {
-  const float* x; const float* xact; const float* w; const float* bias; float* y; float* part;
+  const float* x; const float* xact; const float* w; const float* bias; const float* add; float* y; float* part;
   // backward extras
   const float* dy; const float* yact; const float* xin; float* dw; float* db;
-  int M, Kr, N, x_pitch, xact_pitch, w_row, y_pitch, n_store;
+  int M, Kr, N, x_pitch, xact_pitch, w_row, add_pitch, y_pitch, n_store;
   int act, in_act; float slope;
   int ksplit, k_per_split;
   // wgrad
   int K, xin_pitch, dy_pitch, yact_pitch, dw_row, k_real;
 };
 
-__device__ __forceinline__ float lin_actgrad(float yv, int act, float slope) {
-  return act == S2P_ACT_LRELU ? (yv > 0.f ? 1.f : slope) : (act == S2P_ACT_RELU ? (yv > 0.f ? 1.f : 0.f) : 1.f);
-}
-
-// y tile of  x'[M][Kr] . W[N][Kr]^T,  x' = x * act'(xact) when xact != nullptr.
+// y tile of  act(x'[M][Kr] . W[N][Kr]^T + add + bias),  x' = x * act'(xact) when xact != nullptr.
 // MFMA 16x16x4 f32 operand layout: lane l = 16 j + i holds A[row i][k j] and B[k j][col i]; the result register r of lane l is
 // D[row 4 j + r][col i].  A k-chunk of 16 is loaded as ONE float4 per lane and operand (lane group j takes k = 16 t + 4 j .. + 3)
 // and consumed by four MFMAs (MFMA e uses component e: the same k permutation on both operands, so the sum is the plain dot
 // product).  U chunks are loaded before the first MFMA: 2 U (3 U with xact) independent 16-byte loads in flight per lane.
+// Epilogue: (acc + add[m][n]) + bias, then the activation -- additions only, nothing a compiler could contract into a fused
+// multiply-add.  y may be the same buffer as add (the accumulating dgrad): every element is read and written by one lane.  With
+// ksplit > 1 the tile of split z goes to the workspace as it is (no add, bias or activation: the host never asks for those there).
 #ifndef S2P_LIN_U
 #define S2P_LIN_U 8
 #endif
@@ -46,6 +52,9 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
   const int nb = blockIdx.x * 16, mb = blockIdx.y * 64 + wave * 16, z = blockIdx.z;
   if (mb >= a.M) return;                                   // (wave-uniform)
+  // in_act is none / relu / lrelu, the backward entry points refuse every other id: spares act_grad_from_out's tanh arithmetic per
+  // operand element
+  __builtin_assume(a.in_act >= S2P_ACT_NONE && a.in_act <= S2P_ACT_LRELU);
   const int k0 = z * a.k_per_split, k1 = k0 + a.k_per_split < a.Kr ? k0 + a.k_per_split : a.Kr;
   const int m = mb + i, n = nb + i;
   const bool mok = m < a.M, nok = n < a.N;
@@ -63,7 +72,7 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
       if (ar && mok && k < k1) {
         const f32x4 yv = *(const f32x4*)(ar + k);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) xv[u][e] *= lin_actgrad(yv[e], a.in_act, a.slope);
+        for (int e = 0; e < 4; ++e) xv[u][e] *= act_grad_from_out(yv[e], a.in_act, a.slope);
       }
     }
 #pragma unroll
@@ -76,9 +85,12 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
     const int mo = mb + 4 * j + r;
     if (mo >= a.M) continue;
     if (a.ksplit > 1) { a.part[((size_t)z * a.M + mo) * a.n_store + n] = acc[r]; continue; }   // partial tile -> workspace [z][M][n_store]
-    float v = nok ? acc[r] + b : 0.f;
-    v = a.act == S2P_ACT_LRELU ? (v > 0.f ? v : v * a.slope) : (a.act == S2P_ACT_RELU ? (v > 0.f ? v : 0.f) : v);
-    if (a.act >= S2P_ACT_TANH) v = a.act == S2P_ACT_TANH ? tanhf(v) : v / (1.f + expf(-v));   // (launch-uniform; as act_fwd)
+    float v = 0.f;                                         // columns [N, n_store): zeros
+    if (nok) {
+      v = acc[r];
+      if (a.add) v += a.add[(size_t)mo * a.add_pitch + n];
+      v = act_fwd(v + b, a.act, a.slope);
+    }
     a.y[(size_t)mo * a.y_pitch + n] = v;
   }
 }
@@ -102,6 +114,7 @@ __global__ __launch_bounds__(256) void lin_wgrad_kernel(const LinArgs a) {
   const int kt_n = (a.K + 63) / 64;
   const int nb = (blockIdx.x / kt_n) * 16, kb = (blockIdx.x % kt_n) * 64 + wave * 16;
   if (kb >= a.K) return;                                   // (wave-uniform)
+  __builtin_assume(a.act >= S2P_ACT_NONE && a.act <= S2P_ACT_LRELU);         // (as in lin_fwd_kernel: every other id is refused)
   const int n = nb + i, k = kb + i;
   const bool nok = n < a.N, kok = k < a.K;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f}, accb = {0.f, 0.f, 0.f, 0.f};
@@ -113,7 +126,7 @@ __global__ __launch_bounds__(256) void lin_wgrad_kernel(const LinArgs a) {
       const int m = m0 + 4 * u + j;
       const bool mok = m < a.M;
       dv[u] = (mok && nok) ? a.dy[(size_t)m * a.dy_pitch + n] : 0.f;
-      if (a.yact && mok && nok) dv[u] *= lin_actgrad(a.yact[(size_t)m * a.yact_pitch + n], a.act, a.slope);
+      if (a.yact && mok && nok) dv[u] *= act_grad_from_out(a.yact[(size_t)m * a.yact_pitch + n], a.act, a.slope);
       xv[u] = (mok && kok) ? a.xin[(size_t)m * a.xin_pitch + k] : 0.f;
     }
 #pragma unroll
@@ -131,174 +144,40 @@ __global__ __launch_bounds__(256) void lin_wgrad_kernel(const LinArgs a) {
   }
 }
 
-#ifdef S2P_DIAG_BUILD
-// ---- diagnostics build only: the LDS-staged VALU kernels of rounds 2-3 (S2P_LIN_LDS=1 selects them; tools/bench_lin.py times them
-// against the MFMA kernels above).  They are where the co-residency wrong-result hazard was first seen (lanes 48..63, ~1 % of a
-// partial sum, beside an LDS-DMA conv kernel).  Rounds 2-3 read that as an LDS effect of the MERGED reads hipcc formed on the
-// odd-pitch tiles and bisected read forms (S2P_LIN_LDS_MODE 1..4: plain loads at pitch 65 / 68, element-wise lds_ld() on one tile
-// or the other).  Round 4 showed the cause to be PACKED fp32 instructions with an op_sel swizzle: the merged
-// reads only put the operands in adjacent registers, which let the SLP vectoriser pack the FMAs; lds_ld() blocked that.  With the
-// library built without packed fp32 every mode is safe; the modes stay as the record of that bisection.
-#ifndef S2P_LIN_LDS_MODE
-#define S2P_LIN_LDS_MODE 0
-#endif
-constexpr int LIN_LD = S2P_LIN_LDS_MODE == 2 ? 68 : 65;
-__device__ __forceinline__ float lin_ld_x(const float* p) { return (S2P_LIN_LDS_MODE == 0 || S2P_LIN_LDS_MODE == 4) ? lds_ld(p) : *p; }
-__device__ __forceinline__ float lin_ld_w(const float* p) { return (S2P_LIN_LDS_MODE == 0 || S2P_LIN_LDS_MODE == 3) ? lds_ld(p) : *p; }
-
-// y tile [64 rows][16 cols] of  x'[M][Kr] . W[N][Kr]^T,  x' = x * act'(xact) when xact != nullptr
-__device__ __forceinline__ void lin_gemm_tile(const LinArgs& a, int mb, int nb, int k0, int k1, float (&acc)[4], float* xs, float* ws) {
-  constexpr int KC = 64, LD = LIN_LD;
-  const int t = threadIdx.x, mq = t & 15, c = t >> 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i] = 0.f;
-  for (int kc = k0; kc < k1; kc += KC) {
-    __syncthreads();
-    // stage x' : 64 rows x 64 k  (4 float4 per thread), W : 16 rows x 64 k (1 float4 per thread)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = t + 256 * i, r = idx >> 4, q = idx & 15;
-      const int m = mb + r, k = kc + q * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (m < a.M && k < k1) {
-        v = *(const f32x4*)(a.x + (size_t)m * a.x_pitch + k);
-        if (a.xact) {
-          const f32x4 yv = *(const f32x4*)(a.xact + (size_t)m * a.xact_pitch + k);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] *= lin_actgrad(yv[e], a.in_act, a.slope);
-        }
-        if (k + 4 > k1) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) if (k + e >= k1) v[e] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) xs[r * LD + q * 4 + e] = v[e];
-    }
-    {
-      const int r = t >> 4, q = t & 15;
-      const int n = nb + r, k = kc + q * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (n < a.N && k < k1) {
-        v = *(const f32x4*)(a.w + (size_t)n * a.w_row + k);
-        if (k + 4 > k1) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) if (k + e >= k1) v[e] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ws[r * LD + q * 4 + e] = v[e];
-    }
-    __syncthreads();
-    // element-wise LDS reads: see lds_ld() above
-#pragma unroll 8
-    for (int k = 0; k < KC; ++k) {
-      const float wv = lin_ld_w(ws + c * LD + k);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(lin_ld_x(xs + (4 * mq + i) * LD + k), wv, acc[i]);
-    }
-  }
+// ---- host side: ONE place fills the forward arguments, ONE turns a backward call into them, ONE launches ---------------------------
+// y[M][y_pitch] = act(x[M][Kr] . w[N][w_row]^T + add + bias), columns [N, n_store) zero; add and bias may be nullptr
+static LinArgs lin_fwd_args(const float* x, int x_pitch, int M, int Kr, const float* w, int w_row, const float* bias, int N,
+                            const float* add, int add_pitch, int act, float slope, float* y, int y_pitch, int n_store) {
+  LinArgs a{}; a.x = x; a.x_pitch = x_pitch; a.M = M; a.Kr = Kr; a.w = w; a.w_row = w_row; a.bias = bias; a.N = N; a.add = add;
+  a.add_pitch = add_pitch; a.act = act; a.slope = slope; a.y = y; a.y_pitch = y_pitch; a.n_store = n_store;
+  a.ksplit = 1; a.k_per_split = Kr;
+  return a;
 }
 
-__global__ __launch_bounds__(256) void lin_fwd_lds_kernel(const LinArgs a) {
-  __shared__ __attribute__((aligned(16))) float xs[64 * LIN_LD], ws[16 * LIN_LD];
-  const int nb = blockIdx.x * 16, mb = blockIdx.y * 64, z = blockIdx.z;
-  const int k0 = z * a.k_per_split, k1 = k0 + a.k_per_split < a.Kr ? k0 + a.k_per_split : a.Kr;
-  float acc[4];
-  lin_gemm_tile(a, mb, nb, k0, k1, acc, xs, ws);
-  const int t = threadIdx.x, mq = t & 15, c = t >> 4, n = nb + c;
-  if (n >= a.n_store) return;
-  if (a.ksplit > 1) {                                     // partial tile -> workspace [z][M][n_store]
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = mb + 4 * mq + i;
-      if (m < a.M) a.part[((size_t)z * a.M + m) * a.n_store + n] = acc[i];
-    }
-    return;
-  }
-  const float b = (a.bias && n < a.N) ? a.bias[n] : 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = mb + 4 * mq + i;
-    if (m < a.M) {
-      float v = n < a.N ? acc[i] + b : 0.f;
-      v = a.act == S2P_ACT_LRELU ? (v > 0.f ? v : v * a.slope) : (a.act == S2P_ACT_RELU ? (v > 0.f ? v : 0.f) : v);
-      if (a.act >= S2P_ACT_TANH) v = a.act == S2P_ACT_TANH ? tanhf(v) : v / (1.f + expf(-v));
-      a.y[(size_t)m * a.y_pitch + n] = v;
-    }
-  }
+// dx columns a dgrad writes: K rounded up to 4 (the padding columns as zeros) where the row has room for them, else K
+static inline int lin_dx_cols(int K, int dx_pitch) { const int kcols = (K + 3) / 4 * 4; return kcols <= dx_pitch ? kcols : K; }
+
+// The input gradient as a forward: "x" = dy with the activation derivative of the saved output y folded in (ya = nullptr: none),
+// reduction over N, output columns = the K inputs, weights = the transpose.  accumulate: dx += (add = dx itself, exactly K columns).
+static LinArgs lin_dgrad_args(const float* dy, int dy_pitch, const float* ya, int y_pitch, int M, int N, const float* w_bwd, int wb_row,
+                              int K, int act, float slope, float* dx, int dx_pitch, bool accumulate) {
+  LinArgs g = lin_fwd_args(dy, dy_pitch, M, N, w_bwd, wb_row, nullptr, K, accumulate ? dx : nullptr, dx_pitch, S2P_ACT_NONE, slope, dx,
+                           dx_pitch, accumulate ? K : lin_dx_cols(K, dx_pitch));
+  g.xact = ya; g.xact_pitch = y_pitch; g.in_act = act;
+  return g;
 }
 
-// dW[N][K] += dpre^T x, db[N] += sum_m dpre   (dpre = dy * act'(y))
-__global__ __launch_bounds__(256) void lin_wgrad_lds_kernel(const LinArgs a) {
-  constexpr int LDX = LIN_LD, LDD = S2P_LIN_LDS_MODE == 2 ? 20 : 17;   // pitches of the x / dpre tiles (mode 2: 16-byte-aligned rows)
-  __shared__ __attribute__((aligned(16))) float xs[64 * LDX], ws[64 * LDD];
-  const int t = threadIdx.x;
-  // ---- wgrad tile: 16 outputs n x 64 inputs k; dpre staged [m][16], x staged [m][64]; thread = (4 k, 1 n) ----------
-  const int kt_n = (a.K + 63) / 64;
-  const int nb = (blockIdx.x / kt_n) * 16, kb = (blockIdx.x % kt_n) * 64;
-  const int kq = t & 15, c = t >> 4;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  float accb = 0.f;
-  float* ds = ws;                                          // [64 m][16 n] (+1 pad)
-  for (int mb = 0; mb < a.M; mb += 64) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {                          // x : 64 rows x 64 k
-      const int idx = t + 256 * i, r = idx >> 4, q = idx & 15;
-      const int m = mb + r, k = kb + q * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (m < a.M && k < a.K) v = *(const f32x4*)(a.xin + (size_t)m * a.xin_pitch + k);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) xs[r * LDX + q * 4 + e] = v[e];
-    }
-    {                                                      // dpre : 64 rows x 16 n
-      const int r = t >> 2, q = t & 3;
-      const int m = mb + r, n = nb + q * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (m < a.M && n < a.N) {
-        v = *(const f32x4*)(a.dy + (size_t)m * a.dy_pitch + n);
-        if (a.yact) {
-          const f32x4 yv = *(const f32x4*)(a.yact + (size_t)m * a.yact_pitch + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] *= lin_actgrad(yv[e], a.act, a.slope);
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ds[r * LDD + q * 4 + e] = v[e];
-    }
-    __syncthreads();
-    const int mlim = a.M - mb < 64 ? a.M - mb : 64;
-    for (int m = 0; m < mlim; ++m) {
-      const float d = lin_ld_w(ds + m * LDD + c);            // element-wise LDS reads: see lds_ld()
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(d, lin_ld_x(xs + m * LDX + 4 * kq + i), acc[i]);
-      accb += d;
-    }
+// ks > 1: the reduction in about ks parts (multiples of 64), partial tiles in `part` [ksplit][M][n_store], then the fixed-order reduce
+static int lin_fwd_launch(LinArgs a, float* part, int ks, hipStream_t st) {
+  if (ks > 1) { a.part = part; a.k_per_split = (cdiv(a.Kr, ks) + 63) / 64 * 64; a.ksplit = cdiv(a.Kr, a.k_per_split); }
+  hipLaunchKernelGGL(lin_fwd_kernel, dim3(cdiv(a.n_store, 16), cdiv(a.M, 64), a.ksplit), dim3(256), 0, st, a);
+  S2P_CHECK_LAUNCH("lin_fwd_kernel");
+  if (a.ksplit > 1) {
+    hipLaunchKernelGGL(lin_splitk_reduce_kernel, dim3(cdiv((long long)a.M * a.n_store, 256)), dim3(256), 0, st, a);
+    S2P_CHECK_LAUNCH("lin_splitk_reduce_kernel");
   }
-  const int n = nb + c;
-  if (n < a.N) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = kb + 4 * kq + i;
-      if (k < a.k_real) a.dw[(size_t)n * a.dw_row + k] += acc[i];
-    }
-    if (a.db && kb == 0 && kq == 0) a.db[n] += accb;
-  }
+  return 0;
 }
-
-#endif  // S2P_DIAG_BUILD
-
-#ifdef S2P_DIAG_BUILD
-static inline bool lin_use_lds() { static const int v = s2p_env_set("S2P_LIN_LDS"); return v != 0; }
-#define LIN_LAUNCH_FWD(grid, st, args) do { if (lin_use_lds()) hipLaunchKernelGGL(lin_fwd_lds_kernel, grid, dim3(256), 0, st, args); \
-                                            else hipLaunchKernelGGL(lin_fwd_kernel, grid, dim3(256), 0, st, args); } while (0)
-#define LIN_LAUNCH_WGRAD(grid, st, args) do { if (lin_use_lds()) hipLaunchKernelGGL(lin_wgrad_lds_kernel, grid, dim3(256), 0, st, args); \
-                                              else hipLaunchKernelGGL(lin_wgrad_kernel, grid, dim3(256), 0, st, args); } while (0)
-#else
-#define LIN_LAUNCH_FWD(grid, st, args) hipLaunchKernelGGL(lin_fwd_kernel, grid, dim3(256), 0, st, args)
-#define LIN_LAUNCH_WGRAD(grid, st, args) hipLaunchKernelGGL(lin_wgrad_kernel, grid, dim3(256), 0, st, args)
-#endif
 
 static int lin_check(const char* who, int M, int K, int N, int xp) {
   if (M < 0 || K <= 0 || N <= 0) S2P_FAIL(-1, "%s: empty problem", who);
@@ -313,11 +192,8 @@ extern "C" int s2p_linear_fwd(const float* x, int M, int K, int x_pitch, const f
   int rc = lin_check("s2p_linear_fwd", M, K, N, x_pitch); if (rc) return rc;
   if (!x || !w || !y || w_row % 4 || n_store < N || n_store > y_pitch) S2P_FAIL(-1, "s2p_linear_fwd: bad arguments");
   if (act < S2P_ACT_NONE || act > S2P_ACT_SWISH) S2P_FAIL(-1, "s2p_linear_fwd: unknown activation %d", act);
-  LinArgs a{}; a.x = x; a.w = w; a.bias = bias; a.y = y; a.M = M; a.Kr = K; a.N = N; a.x_pitch = x_pitch; a.w_row = w_row;
-  a.y_pitch = y_pitch; a.n_store = n_store; a.act = act; a.slope = slope; a.ksplit = 1; a.k_per_split = K;
-  LIN_LAUNCH_FWD(dim3(cdiv(n_store, 16), cdiv(M, 64), 1), (hipStream_t)stream, a);
-  S2P_CHECK_LAUNCH("lin_fwd_kernel");
-  return 0;
+  return lin_fwd_launch(lin_fwd_args(x, x_pitch, M, K, w, w_row, bias, N, nullptr, 0, act, slope, y, y_pitch, n_store), nullptr, 1,
+                        (hipStream_t)stream);
 }
 
 extern "C" size_t s2p_linear_bwd_workspace(int M, int K, int N) {
@@ -335,42 +211,96 @@ extern "C" int s2p_linear_bwd(const float* x, int x_pitch, const float* dy, int 
   if (M == 0) return 0;                                    // an empty batch: nothing to add to dw / db, no row of dx
   int rc = lin_check("s2p_linear_bwd", M, K, N, x_pitch); if (rc) return rc;
   if (!x || !dy || !dw || dy_pitch % 4 || N % 4) S2P_FAIL(-1, "s2p_linear_bwd: bad arguments (N and pitches must be multiples of 4)");
-  if (act != S2P_ACT_NONE && act != S2P_ACT_RELU && act != S2P_ACT_LRELU)      // (lin_actgrad has these three cases only)
+  if (act != S2P_ACT_NONE && act != S2P_ACT_RELU && act != S2P_ACT_LRELU)      // (as s2p_linear_add_bwd)
     S2P_FAIL(-1, "s2p_linear_bwd: activation %d has no backward here (none / relu / lrelu only)", act);
   if (act != S2P_ACT_NONE && (!y || y_pitch % 4)) S2P_FAIL(-1, "s2p_linear_bwd: the activation output is needed");
   if (dx && (!w_bwd || wb_row % 4)) S2P_FAIL(-1, "s2p_linear_bwd: dx needs w_bwd");
   // the split-K input gradient's geometry and its workspace, settled before anything is launched
   const int ks = N >= 2048 ? cdiv(N, 512) : 1;
-  const int kcols = (K + 3) / 4 * 4, dx_cols = kcols <= dx_pitch ? kcols : K;
-  const size_t need = (size_t)ks * M * dx_cols * sizeof(float);
+  const size_t need = (size_t)ks * M * lin_dx_cols(K, dx_pitch) * sizeof(float);
   if (dx && ks > 1 && (!workspace || workspace_bytes < need)) S2P_FAIL(-1, "s2p_linear_bwd: workspace of %zu bytes needed", need);
   hipStream_t st = (hipStream_t)stream;
-  LinArgs a{};
-  a.M = M; a.act = act; a.slope = slope;
-  // wgrad part
-  a.xin = x; a.xin_pitch = x_pitch; a.dy = dy; a.dy_pitch = dy_pitch; a.yact = act != S2P_ACT_NONE ? y : nullptr;
+  const float* ya = act != S2P_ACT_NONE ? y : nullptr;
+  LinArgs a{};                                             // the weight (+ bias) gradient
+  a.M = M; a.act = act; a.slope = slope; a.xin = x; a.xin_pitch = x_pitch; a.dy = dy; a.dy_pitch = dy_pitch; a.yact = ya;
   a.yact_pitch = y_pitch; a.dw = dw; a.dw_row = dw_row; a.db = db; a.K = K; a.k_real = k_real; a.N = N;
-  const int wg_blocks = cdiv(N, 16) * cdiv(K, 64);
-  LIN_LAUNCH_WGRAD(dim3(wg_blocks), st, a);
+  hipLaunchKernelGGL(lin_wgrad_kernel, dim3(cdiv(N, 16) * cdiv(K, 64)), dim3(256), 0, st, a);
   S2P_CHECK_LAUNCH("lin_wgrad_kernel");
   if (!dx) return 0;
-  // dgrad: "x" = dy (with the activation derivative folded in), reduction over N, output columns = the K inputs
-  LinArgs g = a;
-  g.x = dy; g.x_pitch = dy_pitch; g.xact = a.yact; g.xact_pitch = y_pitch; g.in_act = act; g.w = w_bwd; g.w_row = wb_row;
-  g.bias = nullptr; g.y = dx; g.y_pitch = dx_pitch; g.Kr = N; g.act = S2P_ACT_NONE;
-  g.n_store = dx_cols;
-  g.N = K;
-  if (ks == 1) {
-    g.ksplit = 1; g.k_per_split = g.Kr;
-    LIN_LAUNCH_FWD(dim3(cdiv(g.n_store, 16), cdiv(M, 64), 1), st, g);
-    S2P_CHECK_LAUNCH("lin_fwd_kernel(dgrad)");
-    return 0;
+  return lin_fwd_launch(lin_dgrad_args(dy, dy_pitch, ya, y_pitch, M, N, w_bwd, wb_row, K, act, slope, dx, dx_pitch, false),
+                        (float*)workspace, ks, st);
+}
+
+// ---- the same layer with an additive term (the SLAC Gaussian MLPs) ---------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lin_actgrad_kernel(const float* dy, int dy_pitch, const float* y, int y_pitch, int M, int N,
+                                                          int act, float slope, float* out, int out_pitch) {
+  const long long total = (long long)M * N;
+  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const int m = (int)(idx / N), n = (int)(idx - (long long)m * N);
+    float v = dy[(size_t)m * dy_pitch + n];
+    if (y) v *= act_grad_from_out(y[(size_t)m * y_pitch + n], act, slope);
+    out[(size_t)m * out_pitch + n] = v;
   }
-  g.part = (float*)workspace; g.ksplit = ks; g.k_per_split = cdiv(g.Kr, ks); g.k_per_split = (g.k_per_split + 63) / 64 * 64;
-  g.ksplit = cdiv(g.Kr, g.k_per_split);
-  LIN_LAUNCH_FWD(dim3(cdiv(g.n_store, 16), cdiv(M, 64), g.ksplit), st, g);
-  S2P_CHECK_LAUNCH("lin_fwd_kernel(dgrad, split)");
-  hipLaunchKernelGGL(lin_splitk_reduce_kernel, dim3(cdiv((long long)M * g.n_store, 256)), dim3(256), 0, st, g);
-  S2P_CHECK_LAUNCH("lin_splitk_reduce_kernel");
+}
+
+// What these two entry points refuse of a forward launch and s2p_linear_fwd / s2p_linear_bwd do not, in the launch's own terms
+// (for the dgrad "x" is dy, "K" the reduction over N and "N" the K inputs)
+static int lin_add_check(const char* who, const LinArgs& a) {
+  S2P_REQUIRE(a.Kr % 4 == 0 && a.x_pitch % 4 == 0 && a.w_row % 4 == 0 && a.x_pitch >= a.Kr && a.w_row >= a.Kr,
+              "%s: K, x_pitch and w_row must be multiples of 4 floats, the pitches at least K", who);
+  S2P_REQUIRE(s2p_al16(a.x) && s2p_al16(a.w) && (!a.xact || (s2p_al16(a.xact) && a.xact_pitch % 4 == 0 && a.xact_pitch >= a.Kr)),
+              "%s: x, w (and the activation output) must be 16-byte aligned", who);
+  S2P_REQUIRE(a.n_store >= a.N && a.n_store <= a.y_pitch, "%s: N <= n_store <= y_pitch is required", who);
+  S2P_REQUIRE(!a.add || a.add_pitch >= a.N, "%s: add_pitch is below N", who);
+  return 0;
+}
+
+extern "C" int s2p_linear_add_fwd(const float* x, int M, int K, int x_pitch, const float* w, int w_row, const float* bias, int N,
+                                  const float* add, int add_pitch, int act, float slope, float* y, int y_pitch, int n_store,
+                                  void* stream) {
+  S2P_REQUIRE(M >= 0 && K >= 0 && N >= 0, "s2p_linear_add_fwd: negative size");
+  if (M == 0 || N == 0) return 0;
+  S2P_REQUIRE(K > 0, "s2p_linear_add_fwd: empty reduction");
+  S2P_REQUIRE(x && w && y, "s2p_linear_add_fwd: null pointer");
+  S2P_REQUIRE(act >= S2P_ACT_NONE && act <= S2P_ACT_SWISH, "s2p_linear_add_fwd: unknown activation %d", act);
+  const LinArgs a = lin_fwd_args(x, x_pitch, M, K, w, w_row, bias, N, add, add_pitch, act, slope, y, y_pitch, n_store);
+  int rc = lin_add_check("s2p_linear_add_fwd", a); if (rc) return rc;
+  return lin_fwd_launch(a, nullptr, 1, (hipStream_t)stream);
+}
+
+extern "C" int s2p_linear_add_bwd(const float* x, int x_pitch, const float* dy, int dy_pitch, const float* y, int y_pitch, int M,
+                                  int K, int k_real, int N, const float* w_bwd, int wb_row, int act, float slope, float* dw,
+                                  int dw_row, float* db, float* dx, int dx_pitch, int dx_accumulate, float* dadd, int dadd_pitch,
+                                  void* stream) {
+  S2P_REQUIRE(M >= 0 && K >= 0 && N >= 0, "s2p_linear_add_bwd: negative size");
+  if (M == 0 || N == 0 || K == 0) return 0;
+  S2P_REQUIRE(dy && dy_pitch >= N, "s2p_linear_add_bwd: dy is NULL or its pitch is below N");
+  S2P_REQUIRE(act == S2P_ACT_NONE || act == S2P_ACT_RELU || act == S2P_ACT_LRELU,
+              "s2p_linear_add_bwd: activation %d has no backward here (none / relu / lrelu only)", act);
+  S2P_REQUIRE(act == S2P_ACT_NONE || (y && y_pitch >= N), "s2p_linear_add_bwd: the activation output is needed");
+  S2P_REQUIRE(dw || dx || dadd, "s2p_linear_add_bwd: no output");
+  S2P_REQUIRE(!dadd || dadd_pitch >= N, "s2p_linear_add_bwd: dadd_pitch is below N");
+  S2P_REQUIRE(!dw || (x && dw_row >= k_real && k_real >= 0 && k_real <= K), "s2p_linear_add_bwd: dw needs x and k_real <= dw_row, K");
+  S2P_REQUIRE(!db || dw, "s2p_linear_add_bwd: db is produced by the weight-gradient pass (dw is NULL)");
+  S2P_REQUIRE(!dx || (w_bwd && dx_pitch >= K && N % 4 == 0 && dy_pitch % 4 == 0 && s2p_al16(dy)),
+              "s2p_linear_add_bwd: dx needs w_bwd, dx_pitch >= K, N and dy_pitch multiples of 4, dy 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const float* ya = act != S2P_ACT_NONE ? y : nullptr;
+  if (dadd) {
+    const long long blocks = ((long long)M * N + 255) / 256;
+    hipLaunchKernelGGL(lin_actgrad_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, dy, dy_pitch, ya, y_pitch, M,
+                       N, act, slope, dadd, dadd_pitch);
+    S2P_CHECK_LAUNCH("lin_actgrad_kernel");
+  }
+  if (dw) {
+    int rc = s2p_linear_bwd(x, x_pitch, dy, dy_pitch, y, y_pitch, M, K, k_real, N, nullptr, 0, act, slope, dw, dw_row, db, nullptr, 0,
+                            nullptr, 0, stream);
+    if (rc) return rc;
+  }
+  if (dx) {
+    const LinArgs g = lin_dgrad_args(dy, dy_pitch, ya, y_pitch, M, N, w_bwd, wb_row, K, act, slope, dx, dx_pitch, dx_accumulate != 0);
+    int rc = lin_add_check("s2p_linear_add_bwd", g); if (rc) return rc;
+    return lin_fwd_launch(g, nullptr, 1, st);
+  }
   return 0;
 }

@@ -21,7 +21,6 @@ static inline int grid_for(long long total, int cap = 4096) {
 // A negative size or an unknown dtype is refused.  A call that covers no element is a successful no-op: nothing is launched and no
 // pointer is looked at (an empty tensor may well have a null data pointer).  Otherwise null pointers are refused, and so are pointers
 // that are not 16-byte aligned wherever the kernel moves whole 16-byte chunks unconditionally (include/s2p_hip.h says which).
-#define S2P_REQUIRE(cond, ...) do { if (!(cond)) S2P_FAIL(-1, __VA_ARGS__); } while (0)
 static inline bool is_dtype(int dtype) { return dtype == S2P_F32 || dtype == S2P_BF16; }
 static inline bool host_al16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;

@@ -3,8 +3,6 @@
 // in the compute dtype (u8 / 255, zero-padded pitch) and the uint8 frames the image loss takes as its target.
 #include "s2p_common.h"
 
-#define S2P_REQUIRE(cond, ...) do { if (!(cond)) S2P_FAIL(-1, __VA_ARGS__); } while (0)
-
 // Frame (b, t) of the output is block-uniform: blockIdx.y = t, blockIdx.z strides over b, so the window id, the table entry and the
 // slot check are scalar work once per workgroup and a thread's only index is its position inside the frame (no division anywhere).
 // A slot outside [0, n_slots) is never dereferenced: the frame reads as zeros.  All byte offsets are 64-bit (a production pool of

@@ -40,6 +40,7 @@ static inline int s2p_env_set(const char*) { return 0; }
 // ---- error plumbing ---------------------------------------------------------
 void s2p_set_error(const char* fmt, ...);
 #define S2P_FAIL(code, ...) do { s2p_set_error(__VA_ARGS__); return (code); } while (0)
+#define S2P_REQUIRE(cond, ...) do { if (!(cond)) S2P_FAIL(-1, __VA_ARGS__); } while (0)
 // leaky-relu slopes above 1 are rejected by the forward entry points: the kernels compute  max(v, v * slope)  (lrelu_ns below)
 #define S2P_CHECK_SLOPE(who, act, slope) do { if ((act) == S2P_ACT_LRELU && !((slope) <= 1.f)) \
     S2P_FAIL(-1, "%s: leaky-relu slope %g > 1 is not supported", who, (double)(slope)); } while (0)

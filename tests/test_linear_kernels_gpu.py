@@ -247,6 +247,74 @@ def test_backward_refusals_leave_every_output_alone(hip_device):
     assert dx_r.untouched() and torch.equal(dw_r.bits(), c.dw0) and torch.equal(db_r.bits()[0], c.db0)
 
 
+# ---- the additive-term entry points against the plain ones, bit for bit ------------------------------------------------------------------
+def add_fwd_call(x_r, w_r, b_r, M, K, N, add_r, act, y_r, n_store, slope=SLOPE):
+    return _L().lib().s2p_linear_add_fwd(x_r.ptr, M, K, x_r.pitch, w_r.ptr, w_r.pitch, _p(b_r), N, _p(add_r), add_r.pitch if add_r is not None else 0,
+                                         act, slope, y_r.ptr, y_r.pitch, n_store, _st())
+
+
+def _fwd_inputs(M, K, N, seed):
+    g = torch.Generator().manual_seed(seed)
+    x, w, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / K ** 0.5 * 1.5, torch.randn(N, generator=g)
+    return Region(M, K, pitch=K + 8, off=4, fill=x), Region(N, K, pitch=K + 8, off=4, fill=w), Region(1, N, off=1, fill=b[None])
+
+
+@pytest.mark.parametrize("M,K,N,n_store", [(1, 4, 1, 4), (17, 132, 20, 24), (65, 260, 72, 72)])
+def test_linear_add_fwd_without_add_equals_linear_fwd_bitwise(hip_device, M, K, N, n_store):
+    """slac.py picks s2p_linear_fwd or s2p_linear_add_fwd per layer (ops.linear_fwd_into) and the fused posterior chain promises the
+    bits of both: with add == NULL the two entry points return the same bits, zero padding columns included."""
+    L = _L()
+    x_r, w_r, b_r = _fwd_inputs(M, K, N, seed=7000 + 10 * M + K)
+    for act in (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU, L.ACT_TANH, L.ACT_SWISH):
+        for bias in (b_r, None):
+            y_r, ya_r = Region(M, n_store, pitch=n_store + 8, off=4), Region(M, n_store, pitch=n_store + 8, off=4)
+            L.check(fwd_call(x_r, w_r, bias, M, K, N, act, y_r, n_store), "s2p_linear_fwd")
+            L.check(add_fwd_call(x_r, w_r, bias, M, K, N, None, act, ya_r, n_store), "s2p_linear_add_fwd")
+            what = "act %d bias %d" % (act, bias is not None)
+            assert torch.equal(ya_r.bits("add_fwd " + what), y_r.bits("fwd " + what)), what
+    for r in (x_r, w_r, b_r):
+        r.get("an input was written")
+
+
+def test_linear_add_fwd_with_a_zero_add_equals_no_add_bitwise(hip_device):
+    """add = +0.0f everywhere: (acc + 0) + bias has the bits of acc + bias (x + 0 = x for every x but -0, and -0 + 0 = +0 differs
+    from -0 only until the bias is added: a random bias is never -0)."""
+    L = _L()
+    M, K, N, n_store = 17, 132, 20, 24
+    x_r, w_r, b_r = _fwd_inputs(M, K, N, seed=7777)
+    add_r = Region(M, N, pitch=N + 8, off=4, fill=torch.zeros(M, N))
+    for act in (L.ACT_NONE, L.ACT_LRELU):
+        y0_r, y1_r = Region(M, n_store, pitch=n_store + 8, off=4), Region(M, n_store, pitch=n_store + 8, off=4)
+        L.check(add_fwd_call(x_r, w_r, b_r, M, K, N, None, act, y0_r, n_store), "s2p_linear_add_fwd")
+        L.check(add_fwd_call(x_r, w_r, b_r, M, K, N, add_r, act, y1_r, n_store), "s2p_linear_add_fwd")
+        assert torch.equal(y1_r.bits("zero add, act %d" % act), y0_r.bits("no add, act %d" % act)), act
+    for r in (x_r, w_r, b_r, add_r):
+        r.get("an input was written")
+
+
+@pytest.mark.parametrize("wide_dx", [True, False])
+@pytest.mark.parametrize("M", [1, 65])
+@pytest.mark.parametrize("k_real,K,N", [(5, 8, 4), (130, 132, 20)])
+def test_linear_add_bwd_equals_linear_bwd_bitwise(hip_device, M, k_real, K, N, wide_dx):
+    """dx_accumulate = 0 and dadd = NULL: s2p_linear_add_bwd is s2p_linear_bwd in dw, db and dx, from the same starting dw / db.
+    Both dx geometries of BwdCase: a pitch above K with a column offset, and dx_pitch == K exactly (the rule for how many dx columns
+    are written compares K rounded up to 4 with dx_pitch)."""
+    L = _L()
+    lib = L.lib()
+    for i, act in enumerate((L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU)):
+        c = BwdCase(M, k_real, K, N, seed=9000 + 100 * M + K + i, wide_dx=wide_dx)
+        dw_r, db_r, dx_r = c.outputs()
+        L.check(c.call(act, dw_r, db_r, dx_r), "s2p_linear_bwd")
+        dwa_r, dba_r, dxa_r = c.outputs()
+        L.check(lib.s2p_linear_add_bwd(c.x_r.ptr, c.x_r.pitch, c.dy_r.ptr, c.dy_r.pitch, c.y_r.ptr, c.y_r.pitch, M, K, k_real, N, c.wb_r.ptr,
+                                       c.wb_r.pitch, act, SLOPE, dwa_r.ptr, dwa_r.pitch, dba_r.ptr, dxa_r.ptr, dxa_r.pitch, 0, None, 0, _st()),
+                "s2p_linear_add_bwd")
+        for name, a, b in (("dw", dwa_r, dw_r), ("db", dba_r, db_r), ("dx", dxa_r, dx_r)):
+            assert torch.equal(a.bits("add_bwd " + name), b.bits("bwd " + name)), (name, act)
+        for r in (c.x_r, c.dy_r, c.y_r, c.wb_r):
+            r.get("an input was written")
+
+
 def test_zz_report_worst_ratios(hip_device):
     print("\nworst deviation / max(ref32_err, 1e-6) per group:", {k: round(v, 3) for k, v in WORST.items()})
     assert WORST and max(WORST.values()) <= K_TOL
