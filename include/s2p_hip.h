@@ -329,6 +329,24 @@ typedef struct {
 int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
                             int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch,
                             float* z, int z_pitch, int B, int T, void* stream);
+/* Open-loop rollout of the generative model (SPEC.md N3i; latent.py:240-248 z1_prior, :270-277 z2_prior, fed their own samples) for B
+ * rows and H steps in ONE launch, the kernel design and the step body of s2p_posterior_chain_fwd.  For h = 1..H:
+ *   (mu1, sd1) = z1_prior([z2(h-1) | a(h-1)]),  z1(h) = mu1 + eps1(h) sd1;
+ *   (mu2, sd2) = z2_prior([z1(h) | z2(h-1) | a(h-1)]),  z2(h) = mu2 + eps2(h) sd2;   the slot of step h is h - 1.
+ * Both first layers are pre = (acc + add) + bias with acc the MFMA sum over the chain columns only (K = 256, 288) and add the action
+ * columns' product: BITWISE the per-layer path out of s2p_linear_add_fwd / s2p_linear_fwd / s2p_gauss_head_fwd.
+ *   z2_0   z2(0) of batch row b at z2_0 + b * z2_0_pitch (a column slice of a [B][288] z(0) is read in place); 16-byte aligned,
+ *          the pitch >= 256 and a multiple of 4 floats
+ *   rc, rb [H * B][256], time-major (row (h-1) * B + b): a(h-1) . w^T of z1_prior's and of z2_prior's action columns, no bias
+ *   eps    [B][H][eps_pitch >= 288], the noise of z1(h) | z2(h); row (b, h-1) at (b * H + h - 1) * eps_pitch -- as mean, std, z
+ *   mlps   HOST array of 2: z1_prior with k1 == 256 (w1 may be the packed [256][pad4(256 + A)] matrix, w1_row its pitch: the
+ *          chain columns are read in place), z2_prior with k1 == 288; other fields as for s2p_posterior_chain_fwd
+ *   mean, std [B][H][pitch >= 32]  of z1;   z [B][H][z_pitch >= 288] = z1 | z2.  Nothing else is written to device memory.
+ * A negative size is refused; B == 0 (or H == 0) is a successful no-op that looks at no pointer; a NULL tensor, a short pitch,
+ * another k1, a short or odd w1_row and a misaligned operand are refused before the launch.                                   */
+int s2p_prior_chain_fwd(const float* z2_0, int z2_0_pitch, const float* rc, const float* rb, const float* eps, int eps_pitch,
+                        const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z, int z_pitch,
+                        int B, int H, void* stream);
 /* KL(p || q) of diagonal Gaussians, value and all four gradients in one pass (slac/utils.py:66-69):
  *   loss[0] += scale * sum 0.5 ((sp/sq)^2 + ((mp-mq)/sq)^2 - 1 - log (sp/sq)^2),  d* = scale * dKL/d*  (overwritten; any NULL).
  * p: [B][T][p_pitch >= D].  const_first == 0: q is [B][T][q_pitch]; const_first != 0: q is [B][T-1][q_pitch] and holds the

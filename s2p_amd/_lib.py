@@ -119,6 +119,7 @@ SIGNATURES = {
     "s2p_linear_add_fwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_float, _P, c_int, c_int, _P],
     "s2p_posterior_chain_fwd": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int, c_int, c_int,
                                 _P],
+    "s2p_prior_chain_fwd": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
     "s2p_linear_add_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int, _P, _P,
                            c_int, c_int, _P, c_int, _P],
     "s2p_gauss_kl": [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int, _P, _P, c_int, _P],

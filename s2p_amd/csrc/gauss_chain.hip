@@ -26,6 +26,10 @@
 // Row pitches are K + 4 floats: lane 16 j + i reads row i at k = 16 c + 4 j as one 16-byte read; with a 1 024- or 1 152-byte pitch
 // all 16 rows start on one bank, with +4 floats row i starts on bank 4 i (mod 64).  (The 16-lane groups a ds_read_b128 is served in
 // are not the j groups, so one lane pair per group still collides; +8 removes that and measures the same: the LDS is not the limit.)
+//
+// The open-loop PRIOR chain (SPEC.md N3i; s2p_prior_chain_fwd) is the same kernel design around the same step: chain_step() below is
+// the posterior chain's t >= 1 body, and the prior chain runs it H times from z2(0) with z1_prior's weights in place of
+// z1_posterior's and the action term rc in place of ra.  It is bitwise its own per-layer path for the same reason.
 #include "gauss_dev.h"
 
 namespace {
@@ -48,7 +52,7 @@ struct ChainArgs {
   const float* feat; const float* ra; const float* rb; const float* eps; float* mean; float* std; float* z;
   int feat_pitch, eps_pitch, mean_pitch, std_pitch, z_pitch, B, T;
   s2p_chain_mlp m[4];                                      // z1_posterior_init, z2_prior_init, z1_posterior, z2_prior
-};
+};                                                         // (prior chain: feat = z2(0), ra = rc, T = H, m = z1_prior, z2_prior)
 
 // The weights of NT column tiles for one block of k-chunks; wr: this lane's weight rows, already at k = 4 j.
 template <int K, int NT, int U>
@@ -211,6 +215,26 @@ __device__ __forceinline__ void chain_mlp(const ChainArgs& a, const s2p_chain_ml
   next();
 }
 
+// One chain step, shared by the posterior chain (t >= 1) and the prior chain (every step): the z1 MLP `ma` on xz[:, 32:288] =
+// z2(t-1) with its first layer `a1` already asked for, then the z2 MLP `mb` on xz = z1(t) | z2(t-1) with the additive term `add_b`.
+// Results go to slot t of eps / mean / std / z.  `next()` asks for whatever follows the step, before the step's last barrier.
+template <typename Next>
+__device__ __forceinline__ void chain_step(const ChainArgs& a, const s2p_chain_mlp& ma, const s2p_chain_mlp& mb, ChainHidden<CH_Z2, true>& a1,
+                                           ChainHidden<CH_Z, true>& b1, const float* add_b, int t, int row0, float* xz, float* h1, float* h2,
+                                           Next next) {
+  chain_mlp<CH_Z1>(a, ma, a1, xz + CH_Z1, t, 0, row0, xz, h1, h2, [&] { b1.ask(mb.w1, mb.w1_row, mb.b1, add_b, row0, a.B); });
+  chain_mlp<CH_Z2>(a, mb, b1, xz, t, CH_Z1, row0, xz, h1, h2, next);
+}
+
+// src[16 rows][256] -> xz[:, 32:]; rows >= B are zeros, and so is every activation row derived from them
+__device__ __forceinline__ void chain_load_rows(const float* src, int pitch, int row0, int B, float* xz) {
+  for (int idx = threadIdx.x; idx < CH_ROWS * (CH_Z2 / 4); idx += CH_THREADS) {
+    const int row = idx / (CH_Z2 / 4), c4 = idx % (CH_Z2 / 4), gm = row0 + row;
+    const f32x4 v = gm < B ? *(const f32x4*)(src + (size_t)gm * pitch + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    *(f32x4*)(xz + row * CH_XZ_P + CH_Z1 + 4 * c4) = v;
+  }
+}
+
 __global__ __launch_bounds__(CH_THREADS) void posterior_chain_kernel(const ChainArgs a) {
   __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
   const int row0 = blockIdx.x * CH_ROWS;
@@ -219,24 +243,33 @@ __global__ __launch_bounds__(CH_THREADS) void posterior_chain_kernel(const Chain
   ChainHidden<CH_Z2, true> a1;
   ChainHidden<CH_Z, true> b1;
   i1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, nullptr, row0, a.B);
-  // feat(0) -> xz[:, 32:]; rows >= B are zeros, and so is every activation row derived from them
-  for (int idx = threadIdx.x; idx < CH_ROWS * (CH_FEAT / 4); idx += CH_THREADS) {
-    const int row = idx / (CH_FEAT / 4), c4 = idx % (CH_FEAT / 4), gm = row0 + row;
-    const f32x4 v = gm < a.B ? *(const f32x4*)(a.feat + (size_t)gm * a.feat_pitch + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    *(f32x4*)(xz + row * CH_XZ_P + CH_Z1 + 4 * c4) = v;
-  }
+  chain_load_rows(a.feat, a.feat_pitch, row0, a.B, xz);          // feat(0) -> xz[:, 32:]
   auto ask_a1 = [&](int t) {
     if (t < a.T) a1.ask(a.m[2].w1, a.m[2].w1_row, a.m[2].b1, a.ra + (size_t)(t - 1) * a.B * CH_HID, row0, a.B);
   };
   // t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
   chain_mlp<CH_Z1>(a, a.m[0], i1, xz + CH_Z1, 0, 0, row0, xz, h1, h2, [&] { j1.ask(a.m[1].w1, a.m[1].w1_row, a.m[1].b1, nullptr, row0, a.B); });
   chain_mlp<CH_Z2>(a, a.m[1], j1, xz, 0, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(1); });
-  for (int t = 1; t < a.T; ++t) {
-    // q(z1(t) | feat(t), z2(t-1), a(t-1)), q(z2(t) | z1(t), z2(t-1), a(t-1)): the feat / action columns arrive as ra / rb
-    chain_mlp<CH_Z1>(a, a.m[2], a1, xz + CH_Z1, t, 0, row0, xz, h1, h2,
-                     [&] { b1.ask(a.m[3].w1, a.m[3].w1_row, a.m[3].b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, row0, a.B); });
-    chain_mlp<CH_Z2>(a, a.m[3], b1, xz, t, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(t + 1); });
-  }
+  // q(z1(t) | feat(t), z2(t-1), a(t-1)), q(z2(t) | z1(t), z2(t-1), a(t-1)): the feat / action columns arrive as ra / rb
+  for (int t = 1; t < a.T; ++t)
+    chain_step(a, a.m[2], a.m[3], a1, b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, t, row0, xz, h1, h2, [&] { ask_a1(t + 1); });
+}
+
+// The open-loop prior chain (SPEC.md N3i): z2(0) -> xz[:, 32:], then H steps of p(z1(h) | z2(h-1), a(h-1)), p(z2(h) | z1(h), z2(h-1),
+// a(h-1)) on the model's own samples.  a.feat is z2(0), a.ra / a.rb the action terms of the two first layers, a.T the horizon H,
+// a.m[0] / a.m[1] z1_prior / z2_prior; step h writes slot h - 1.  xz[:, :32] is written by the first z1 head before b1 reads it.
+__global__ __launch_bounds__(CH_THREADS) void prior_chain_kernel(const ChainArgs a) {
+  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
+  const int row0 = blockIdx.x * CH_ROWS;
+  ChainHidden<CH_Z2, true> a1;
+  ChainHidden<CH_Z, true> b1;
+  auto ask_a1 = [&](int s) {
+    if (s < a.T) a1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, a.ra + (size_t)s * a.B * CH_HID, row0, a.B);
+  };
+  ask_a1(0);
+  chain_load_rows(a.feat, a.feat_pitch, row0, a.B, xz);
+  for (int s = 0; s < a.T; ++s)
+    chain_step(a, a.m[0], a.m[1], a1, b1, a.rb + (size_t)s * a.B * CH_HID, s, row0, xz, h1, h2, [&] { ask_a1(s + 1); });
 }
 }  // namespace
 
@@ -266,5 +299,34 @@ extern "C" int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const 
   a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z; a.z_pitch = z_pitch; a.B = B; a.T = T;
   hipLaunchKernelGGL(posterior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
   S2P_CHECK_LAUNCH("posterior_chain_kernel");
+  return 0;
+}
+
+extern "C" int s2p_prior_chain_fwd(const float* z2_0, int z2_0_pitch, const float* rc, const float* rb, const float* eps, int eps_pitch,
+                                   const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
+                                   int z_pitch, int B, int H, void* stream) {
+  const char* who = "s2p_prior_chain_fwd";
+  static const int k1[2] = {CH_Z2, CH_Z};
+  static const char* const name[2] = {"z1_prior", "z2_prior"};
+  S2P_REQUIRE(B >= 0 && H >= 0, "%s: negative size", who);
+  if (B == 0 || H == 0) return 0;
+  S2P_REQUIRE(z2_0 && rc && rb && eps && mlps && mean && std && z,
+              "%s: null pointer (z2_0, rc, rb, eps, mlps, mean, std and z are required)", who);
+  S2P_REQUIRE(z2_0_pitch >= CH_Z2 && eps_pitch >= CH_Z && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
+              "%s: a pitch is below its row (z2_0 256, eps 288, mean 32, std 32, z 288)", who);
+  S2P_REQUIRE(s2p_al16(z2_0) && z2_0_pitch % 4 == 0, "%s: z2_0 must be 16-byte aligned, its pitch a multiple of 4 floats", who);
+  ChainArgs a{};
+  for (int g = 0; g < 2; ++g) {
+    const s2p_chain_mlp& m = mlps[g];
+    S2P_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name[g]);
+    S2P_REQUIRE(m.k1 == k1[g], "%s: %s: the first layer's K is %d, %d is built", who, name[g], (int)m.k1, k1[g]);
+    S2P_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name[g]);
+    S2P_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name[g]);
+    a.m[g] = m;
+  }
+  a.feat = z2_0; a.feat_pitch = z2_0_pitch; a.ra = rc; a.rb = rb; a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean;
+  a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z; a.z_pitch = z_pitch; a.B = B; a.T = H;
+  hipLaunchKernelGGL(prior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
+  S2P_CHECK_LAUNCH("prior_chain_kernel");
   return 0;
 }

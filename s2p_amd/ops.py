@@ -679,10 +679,33 @@ def gauss_head_fwd(raw, D, eps=None, mean=None, std=None, z=None, z2=None):
     check(lib().s2p_gauss_head_fwd(rp, rs, raw.shape[0], D, ep, es, mp, ms, sp, ss, zp, zs, z2p, z2s, stream()), "s2p_gauss_head_fwd")
 
 
-def chain_mlp(pk, group=0):
-    """The s2p_chain_mlp of a Gaussian.packed() dict; `group`: which first-layer column group is the chain's."""
-    w1, _, k1 = pk["g1"][group]
-    return _lib.ChainMlp(ptr(w1), ptr(pk["b1"]), ptr(pk["w2"]), ptr(pk["b2"]), ptr(pk["w3"]), ptr(pk["b3"]), k1, w1.shape[1])
+def chain_mlp(pk, group=0, k1=None):
+    """The s2p_chain_mlp of a Gaussian.packed() dict; `group`: which first-layer column group is the chain's; `k1`: the chain reads
+    only the first k1 columns of that group, in place (z1_prior in the prior chain: its action columns are hoisted)."""
+    w1, _, k = pk["g1"][group]
+    return _lib.ChainMlp(ptr(w1), ptr(pk["b1"]), ptr(pk["w2"]), ptr(pk["b2"]), ptr(pk["w3"]), ptr(pk["b3"]), k if k1 is None else k1,
+                         w1.shape[1])
+
+
+def _chain_views(B, T, *ts):
+    for t in ts:
+        if t.dtype != torch.float32 or t.shape[:2] != (B, T) or t.stride(2) != 1 or (B > 1 and T > 0 and t.stride(0) != T * t.stride(1)):
+            raise ValueError("[B, T, C] fp32 views whose rows (b, t) are evenly pitched are needed")
+
+
+def prior_chain_fwd(z2_0, rc, rb, eps, mlps, mean, std, z):
+    """The whole open-loop prior rollout in one launch (s2p_prior_chain_fwd).  z2_0: a [B, 256] view (a column slice of z(0) is read
+    in place); rc, rb [H*B, 256] contiguous, time-major; eps, mean, std, z: [B, H, C] views as for posterior_chain_fwd; mlps: the
+    chain_mlp() structs of z1_prior (k1 = 256) and z2_prior."""
+    B, H = eps.shape[:2]
+    _chain_views(B, H, eps, mean, std, z)
+    zp, zs = _view2(z2_0)
+    for r in (rc, rb):
+        if not r.is_contiguous() or r.dtype != torch.float32 or r.shape != (H * B, 256):
+            raise ValueError("rc / rb are contiguous fp32 [H*B, 256]")
+    arr = (_lib.ChainMlp * 2)(*mlps)
+    check(lib().s2p_prior_chain_fwd(zp, zs, ptr(rc), ptr(rb), ptr(eps), eps.stride(1), arr, ptr(mean), mean.stride(1), ptr(std),
+                                    std.stride(1), ptr(z), z.stride(1), B, H, stream()), "s2p_prior_chain_fwd")
 
 
 def posterior_chain_fwd(feat0, ra, rb, eps, mlps, mean, std, z):
@@ -690,9 +713,7 @@ def posterior_chain_fwd(feat0, ra, rb, eps, mlps, mean, std, z):
     [(T-1)*B, 256] contiguous (None when T == 1); eps, mean, std, z: [B, T, C] views with unit stride in C and stride(0) =
     T * stride(1) (a slice of a wider [B, T, W] buffer is written in place); mlps: four chain_mlp() structs."""
     B, T = eps.shape[:2]
-    for t in (eps, mean, std, z):
-        if t.dtype != torch.float32 or t.shape[:2] != (B, T) or t.stride(2) != 1 or (B > 1 and T > 0 and t.stride(0) != T * t.stride(1)):
-            raise ValueError("[B, T, C] fp32 views whose rows (b, t) are evenly pitched are needed")
+    _chain_views(B, T, eps, mean, std, z)
     fp, fs = _view2(feat0)
     for r in (ra, rb):
         if r is not None and (not r.is_contiguous() or r.dtype != torch.float32 or r.shape != ((T - 1) * B, 256)):

@@ -233,6 +233,7 @@ class Gaussian(nn.Module):
         self.net.add_module("2", _Lin(HID, HID))
         self.net.add_module("4", _Lin(HID, self.N))
         self._pack_key, self._packed = None, None
+        self._cols_key, self._cols = None, {}
 
     def layer_params(self):
         out = []
@@ -265,6 +266,21 @@ class Gaussian(nn.Module):
                        w3t=w3p.t().contiguous(), b3=b3p)
         self._pack_key, self._packed = key, out
         return out
+
+    def packed_cols(self, lo, hi):
+        """net.0.weight[:, lo:hi] as a GEMM operand of its own, [256][(hi - lo) padded to 4] with a zero pad, beside packed() and
+        under its key rule (the prior chain hoists z1_prior's action columns; packed() keeps that head's one [z2 | a] group)."""
+        ps = self.layer_params()
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if key != self._cols_key:
+            self._cols_key, self._cols = key, {}
+        if (lo, hi) not in self._cols:
+            with torch.no_grad():
+                w1 = ps[0].detach().float()
+                wp = _f32((HID, pad_to(hi - lo, 4)), w1.device, zero=True)
+                wp[:, :hi - lo] = w1[:, lo:hi]
+            self._cols[(lo, hi)] = wp
+        return self._cols[(lo, hi)]
 
     def unpack_dw1(self, dws):
         """Gradients of the packed first-layer groups -> the gradient of net.0.weight (reference column order)."""
@@ -316,6 +332,19 @@ def _mlp_bwd(g, pk, x, h1, h2, draw, dev, need_dx=True):
     dx = _f32((M, w1.shape[1]), dev) if need_dx else None
     ops.linear_add_bwd(dh1, h1, HID, ACT_LRELU, SLOPE, x=x, k_real=k, dw=dw1, db=db1, w_bwd=w1t, dx=dx)
     return [g.unpack_dw1([dw1]), db1, dw2, db2, dw3, db3], dx
+
+
+def _action_term(action, w):
+    """a . w^T of the action columns `w` [256][A padded to 4] of a first layer over all S*B rows, without bias: action [B,S,A] ->
+    (the padded input [S,B,Kpad], the term [S*B, 256]), both time-major.  One s2p_linear_fwd."""
+    dev = action.device
+    B, S, A = action.shape
+    k = w.shape[1]
+    x = _f32((S, B, k), dev, True)
+    x[:, :, :A] = action.transpose(0, 1)
+    r = _f32((S * B, HID), dev)
+    ops.linear_fwd_into(x.view(S * B, k), w, None, HID, r)
+    return x, r
 
 
 class _GaussFn(torch.autograd.Function):
@@ -399,14 +428,13 @@ class _PosteriorFn(torch.autograd.Function):
         dev = feat.device
         B, T, _ = feat.shape
         S, A = T - 1, action.shape[2]
-        ka, kb = p1["g1"][1][0].shape[1], p2["g1"][1][0].shape[1]
-        xa, xb = _f32((S, B, ka), dev, True), _f32((S, B, kb), dev, True)
+        ka = p1["g1"][1][0].shape[1]
+        xa = _f32((S, B, ka), dev, True)
         xa[:, :, :FEAT] = feat[:, 1:].transpose(0, 1)
         xa[:, :, FEAT:FEAT + A] = action.transpose(0, 1)
-        xb[:, :, :A] = action.transpose(0, 1)
-        ra, rb = _f32((S * B, HID), dev), _f32((S * B, HID), dev)
+        ra = _f32((S * B, HID), dev)
         ops.linear_fwd_into(xa.view(S * B, ka), p1["g1"][1][0], None, HID, ra)
-        ops.linear_fwd_into(xb.view(S * B, kb), p2["g1"][1][0], None, HID, rb)
+        xb, rb = _action_term(action, p2["g1"][1][0])
         return xa, xb, ra, rb
 
     @staticmethod
@@ -574,7 +602,7 @@ class LatentModel(nn.Module):
                     nn.init.xavier_uniform_(p, gain=1.0)
         self.to(dev)
         self.chain_state_bytes = 0              # bytes the last sample_posterior kept for its backward (0 under no_grad)
-        self.fused_chain = False                # True: a no-grad sample_posterior runs its chain as ONE launch (SPEC.md N3h)
+        self.fused_chain = False                # True: a no-grad sample_posterior, and predict, run their chain as ONE launch (SPEC.md N3h, N3i)
 
     @property
     def device(self):
@@ -614,6 +642,68 @@ class LatentModel(nn.Module):
         mean, std = self._prior(actions_, z2_post_)
         m0, s0 = _f32((B, 1, Z1), self.device, True), torch.ones((B, 1, Z1), dtype=torch.float32, device=self.device)
         return torch.cat([m0, mean.reshape(B, S, Z1)], dim=1), torch.cat([s0, std.reshape(B, S, Z1)], dim=1)
+
+    @torch.no_grad()
+    def predict(self, z0, actions_, noise=None, sample=True):
+        """Open-loop rollout of the generative model (SPEC.md N3i): z0 [B,288] = z1(0) | z2(0), actions_ [B,H,A] = a(0..H-1), noise
+        [B,H,288] = the eps of z1(h) | z2(h) (None: drawn on the device; sample False: zeros, the mean rollout) ->
+        (z1_mean [B,H,32], z1_std [B,H,32], z [B,H,288]) of the steps h = 1..H in the slots h - 1.  z1_prior and z2_prior are fed
+        their own samples; z1(0) is not read.  Always without grad.  Both first layers are (chain columns + hoisted action term) +
+        bias, so H = 1 equals sample_prior within rounding, not bitwise.  With `fused_chain` the H steps are one launch
+        (s2p_prior_chain_fwd), else 8 per step; the two are bitwise equal."""
+        dev = self.device
+        z0 = z0.to(dev, torch.float32)
+        actions_ = actions_.to(dev, torch.float32).contiguous()
+        if z0.dim() != 2 or z0.shape[1] != Z1 + Z2 or actions_.dim() != 3 or actions_.shape[0] != z0.shape[0] or \
+                actions_.shape[2] != self.action_dim:
+            raise ValueError("z0 [B,z1_dim+z2_dim] and actions_ [B,H,A] are needed")
+        B, H, A = actions_.shape
+        if not sample:
+            noise = _f32((B, H, Z1 + Z2), dev, True)
+        elif noise is None:
+            noise = torch.randn((B, H, Z1 + Z2), dtype=torch.float32, device=dev)
+        noise = noise.to(dev, torch.float32).contiguous()
+        if noise.shape != (B, H, Z1 + Z2):
+            raise ValueError("noise is [B,H,z1_dim+z2_dim]")
+        mean, std, z = _f32((B, H, Z1), dev), _f32((B, H, Z1), dev), _f32((B, H, Z1 + Z2), dev)
+        if B == 0 or H == 0:
+            return mean, std, z
+        g1, g2 = self.z1_prior, self.z2_prior
+        p1, p2 = g1.packed(), g2.packed()
+        rc = _action_term(actions_, g1.packed_cols(Z2, Z2 + A))[1]
+        rb = _action_term(actions_, p2["g1"][1][0])[1]
+        w1a, w1b = p1["g1"][0][0], p2["g1"][0][0]              # [256][pad4(256 + A)]: the z2 columns are read in place; [256][288]
+        # xz = z1(h) | z2(h-1), the input row of both first layers: the per-layer path writes it, the fused one reads z2(0) from it
+        xz = _f32((B, Z1 + Z2), dev).copy_(z0)
+        if self.fused_chain:
+            ops.prior_chain_fwd(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], mean, std, z)
+            return mean, std, z
+        h1, h2 = _f32((B, HID), dev), _f32((B, HID), dev)
+        rawa, rawb = _f32((B, g1.Npad), dev), _f32((B, g2.Npad), dev)
+        for s in range(H):
+            r = slice(s * B, (s + 1) * B)
+            ops.linear_fwd_into(xz[:, Z1:], w1a, p1["b1"], HID, h1, ACT_LRELU, SLOPE, add=rc[r])
+            _mlp_tail_fwd(g1, p1, h1, h2, rawa)
+            ops.gauss_head_fwd(rawa, Z1, eps=noise[:, s, :Z1], mean=mean[:, s], std=std[:, s], z=z[:, s, :Z1], z2=xz[:, :Z1])
+            ops.linear_fwd_into(xz, w1b, p2["b1"], HID, h1, ACT_LRELU, SLOPE, add=rb[r])
+            _mlp_tail_fwd(g2, p2, h1, h2, rawb)
+            ops.gauss_head_fwd(rawb, Z2, eps=noise[:, s, Z1:], z=z[:, s, Z1:], z2=xz[:, Z1:])
+        return mean, std, z
+
+    def predict_reward(self, z0, z, actions_):
+        """Reward head on [z(h-1) | a(h-1) | z(h)], h = 1..H, with z(0) = z0 [B,288], z [B,H,288] (predict's), actions_ [B,H,A] ->
+        (mean [B,H], std [B,H])."""
+        dev = self.device
+        z0, z = z0.to(dev, torch.float32), z.to(dev, torch.float32)
+        actions_ = actions_.to(dev, torch.float32)
+        B, H, A = actions_.shape
+        if z0.shape != (B, Z1 + Z2) or z.shape != (B, H, Z1 + Z2) or A != self.action_dim:
+            raise ValueError("z0 [B,z1_dim+z2_dim], z [B,H,z1_dim+z2_dim] and actions_ [B,H,A] are needed")
+        k = 2 * (Z1 + Z2) + A
+        pad = _f32((B, H, pad_to(k, 4) - k), dev, True)
+        x = torch.cat([torch.cat([z0[:, None], z[:, :-1]], dim=1), actions_, z, pad], dim=-1).reshape(B * H, -1)
+        mean, std = _GaussFn.apply(x, self.reward, *self.reward.layer_params())
+        return mean.reshape(B, H), std.reshape(B, H)
 
     def calculate_loss(self, state_, action_, reward_, done_, noise=None):
         dev = self.device
