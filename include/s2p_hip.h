@@ -347,6 +347,28 @@ int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const float* ra, 
 int s2p_prior_chain_fwd(const float* z2_0, int z2_0_pitch, const float* rc, const float* rb, const float* eps, int eps_pitch,
                         const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z, int z_pitch,
                         int B, int H, void* stream);
+/* Closed-loop rollout (SPEC.md N3j): a deterministic tanh policy inside the loop of s2p_prior_chain_fwd, B rows and H steps in ONE
+ * launch.  For h = 0..H-1, z(0) = z0:
+ *   a(h) = tanh(last_fc(relu(fc1(relu(fc0(z(h)))))));  (mu1, sd1) = z1_prior([z2(h) | a(h)]),  z1(h+1) = mu1 + eps1 sd1;
+ *   (mu2, sd2) = z2_prior([z1(h+1) | z2(h) | a(h)]),  z2(h+1) = mu2 + eps2 sd2;   slot h holds a(h) and z(h+1).
+ * BITWISE the per-layer path: the policy layers as s2p_linear_fwd (relu, relu, tanh on the first A rows of w3), the two action
+ * terms as s2p_linear_fwd of a(h) [B][pad4(A)] on wc / wb without bias, then the step of s2p_prior_chain_fwd.
+ *   z0     [B][z0_pitch >= 288] = z1(0) | z2(0), 16-byte aligned, the pitch a multiple of 4 floats
+ *   eps    [B][H][eps_pitch >= 288], the noise of z1(h+1) | z2(h+1) in slot h
+ *   mlps   HOST array of 2: z1_prior with k1 == 256 (read in place, as s2p_prior_chain_fwd), z2_prior with k1 == 288
+ *   wc, wb [256][row >= pad4(A)]: the action columns of z1_prior's and z2_prior's first layers, zero-padded, 16-byte aligned
+ *   policy HOST struct: w1 [W][w1_row >= 288], w2 [W][W], w3 [>= A][W] (the last_fc rows first), biases; W = width, a multiple of
+ *          128 from 128 to 1024; 1 <= A <= 8; the weights 16-byte aligned
+ *   act    [B][H][act_pitch >= A]: exactly A columns are written;  mean, std, z as for s2p_prior_chain_fwd.  Nothing else is written.
+ * A negative size is refused; B == 0 (or H == 0) is a successful no-op that looks at no pointer; a NULL pointer, another k1, an
+ * unsupported W or A, a short pitch, a short or odd w*_row and a misaligned operand are refused before the launch.              */
+typedef struct {
+  const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3;
+  int32_t w1_row, width;
+} s2p_policy_mlp;
+int s2p_imagine_chain_fwd(const float* z0, int z0_pitch, const float* eps, int eps_pitch, const s2p_chain_mlp* mlps, const float* wc,
+                          int wc_row, const float* wb, int wb_row, int A, const s2p_policy_mlp* policy, float* act, int act_pitch,
+                          float* mean, int mean_pitch, float* std, int std_pitch, float* z, int z_pitch, int B, int H, void* stream);
 /* KL(p || q) of diagonal Gaussians, value and all four gradients in one pass (slac/utils.py:66-69):
  *   loss[0] += scale * sum 0.5 ((sp/sq)^2 + ((mp-mq)/sq)^2 - 1 - log (sp/sq)^2),  d* = scale * dKL/d*  (overwritten; any NULL).
  * p: [B][T][p_pitch >= D].  const_first == 0: q is [B][T][q_pitch]; const_first != 0: q is [B][T-1][q_pitch] and holds the

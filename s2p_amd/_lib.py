@@ -61,6 +61,12 @@ class ChainMlp(ctypes.Structure):
                 ("k1", ctypes.c_int32), ("w1_row", ctypes.c_int32)]
 
 
+class PolicyMlp(ctypes.Structure):
+    """s2p_policy_mlp: the packed layers of a two-hidden-layer tanh policy for the closed-loop chain (w3 / b3: the last_fc rows first)."""
+    _fields_ = [("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("w3", c_void_p), ("b3", c_void_p),
+                ("w1_row", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
 class MlpBwdGroup(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("dpre", c_void_p), ("w", c_void_p), ("dw", c_void_p), ("db", c_void_p), ("pre_prev", c_void_p),
                 ("dprev", c_void_p), ("x_pitch", ctypes.c_int32), ("dpre_pitch", ctypes.c_int32), ("prev_pitch", ctypes.c_int32),
@@ -120,6 +126,8 @@ SIGNATURES = {
     "s2p_posterior_chain_fwd": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int, c_int, c_int,
                                 _P],
     "s2p_prior_chain_fwd": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
+    "s2p_imagine_chain_fwd": [_P, c_int, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, c_int, ctypes.POINTER(PolicyMlp),
+                              _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
     "s2p_linear_add_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int, _P, _P,
                            c_int, c_int, _P, c_int, _P],
     "s2p_gauss_kl": [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int, _P, _P, c_int, _P],

@@ -30,6 +30,12 @@
 // The open-loop PRIOR chain (SPEC.md N3i; s2p_prior_chain_fwd) is the same kernel design around the same step: chain_step() below is
 // the posterior chain's t >= 1 body, and the prior chain runs it H times from z2(0) with z1_prior's weights in place of
 // z1_posterior's and the action term rc in place of ra.  It is bitwise its own per-layer path for the same reason.
+//
+// The closed-loop IMAGINATION chain (SPEC.md N3j; s2p_imagine_chain_fwd) puts a deterministic tanh policy in front of that step: the
+// three policy layers read xz = z(h), a(h) goes to global memory and to a 16 x 8 LDS tile, and the action terms of the two first
+// layers are one MFMA chunk per column tile whose accumulator IS the additive value of ChainHidden (ChainAddRegs): they never leave
+// the registers.  The policy's hidden activations ([16][W + 4], W <= 1 024) are the big LDS tiles; h1 / h2 of the latent half alias
+// their heads -- the halves never overlap in time.  LDS: xz 18 688 + 2 x 65 792 + action tile 512 = 150 784 bytes, static.
 #include "gauss_dev.h"
 
 namespace {
@@ -95,6 +101,11 @@ __device__ __forceinline__ void chain_gemm(const float* xr, const float* const (
   }
 }
 
+// The additive term of a ChainHidden first layer in registers: v[q][r] is the value for column tile q, accumulator register r, of the
+// lane that holds it -- the layout of `acc` in ChainHidden::run.
+template <int NT>
+struct ChainAddRegs { float v[NT][4]; };
+
 // A hidden layer: ys[16][CH_H_P] = lrelu(xs[16][K] . w[256][w_row]^T (+ add) + bias); wave v owns the column tiles v and v + 8.
 // ask(): everything that does not depend on the previous layer -- the first weights, the bias, the additive term -- is asked for
 // BEFORE the barrier that ends the previous layer; run() after it.
@@ -117,6 +128,21 @@ struct ChainHidden {
         const int gm = row0 + 4 * j + r;
         av[q][r] = (ADD && gm < B) ? add[(size_t)gm * CH_HID + n] : 0.f;
       }
+    }
+    chain_load_w<K, NT, U>(wr, 0, w0);
+  }
+
+  // the same with the additive values handed over in registers (the closed-loop chain's action term)
+  __device__ __forceinline__ void ask(const float* w, int w_row, const float* bias, const ChainAddRegs<NT>& add, int, int) {
+    static_assert(ADD, "an additive term for a layer without one");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int n = 16 * (wave + q * CH_WAVES) + i;
+      wr[q] = w + (size_t)n * w_row + 4 * j;
+      bv[q] = bias[n];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) av[q][r] = add.v[q][r];
     }
     chain_load_w<K, NT, U>(wr, 0, w0);
   }
@@ -218,9 +244,10 @@ __device__ __forceinline__ void chain_mlp(const ChainArgs& a, const s2p_chain_ml
 // One chain step, shared by the posterior chain (t >= 1) and the prior chain (every step): the z1 MLP `ma` on xz[:, 32:288] =
 // z2(t-1) with its first layer `a1` already asked for, then the z2 MLP `mb` on xz = z1(t) | z2(t-1) with the additive term `add_b`.
 // Results go to slot t of eps / mean / std / z.  `next()` asks for whatever follows the step, before the step's last barrier.
-template <typename Next>
+// `add_b`: a global pointer ([B][256] rows of this step) or the values in registers (ChainAddRegs).
+template <typename Add, typename Next>
 __device__ __forceinline__ void chain_step(const ChainArgs& a, const s2p_chain_mlp& ma, const s2p_chain_mlp& mb, ChainHidden<CH_Z2, true>& a1,
-                                           ChainHidden<CH_Z, true>& b1, const float* add_b, int t, int row0, float* xz, float* h1, float* h2,
+                                           ChainHidden<CH_Z, true>& b1, const Add add_b, int t, int row0, float* xz, float* h1, float* h2,
                                            Next next) {
   chain_mlp<CH_Z1>(a, ma, a1, xz + CH_Z1, t, 0, row0, xz, h1, h2, [&] { b1.ask(mb.w1, mb.w1_row, mb.b1, add_b, row0, a.B); });
   chain_mlp<CH_Z2>(a, mb, b1, xz, t, CH_Z1, row0, xz, h1, h2, next);
@@ -270,6 +297,133 @@ __global__ __launch_bounds__(CH_THREADS) void prior_chain_kernel(const ChainArgs
   chain_load_rows(a.feat, a.feat_pitch, row0, a.B, xz);
   for (int s = 0; s < a.T; ++s)
     chain_step(a, a.m[0], a.m[1], a1, b1, a.rb + (size_t)s * a.B * CH_HID, s, row0, xz, h1, h2, [&] { ask_a1(s + 1); });
+}
+// ---- the closed-loop imagination chain (SPEC.md N3j) ---------------------------------------------------------------------------------
+constexpr int IM_WMAX = 1024, IM_AP = 8;                   // widest policy hidden layer; columns of the LDS action tile (A <= 8)
+constexpr int IM_P_MAX = IM_WMAX + S2P_CHAIN_PAD;
+
+struct ImagineArgs {
+  ChainArgs c;                                             // feat / ra / rb unused; m[0] / m[1] = z1_prior / z2_prior; T = H
+  const float* z0; const float* wc; const float* wb; float* act;
+  int z0_pitch, wc_row, wb_row, act_pitch, A;
+  s2p_policy_mlp p;
+};
+
+// One 16 x 16 tile of x[16][16 nc] . w^T: lin_mfma_chunk over the chunks 0 .. nc - 1 in ascending order from 0 (what lin_fwd_kernel
+// does for an element; its zero chunks past K add nothing).  nc is a run-time value (the policy's width): blocks of 8 chunks, the
+// next block's operands load while this one is multiplied.  xr / wr: this lane's LDS activation row and weight row at k = 4 j;
+// wok false (a column past N): zero weights, as lin_fwd_kernel feeds them.
+__device__ __forceinline__ f32x4 policy_gemm(const float* xr, const float* wr, int nc, bool wok) {
+  constexpr int U = 8;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f}, xa[U], wa[U], xb[U], wb[U];
+  auto load = [&](f32x4 (&xv)[U], f32x4 (&wv)[U], int c0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (c0 + u < nc) {
+        xv[u] = *(const f32x4*)(xr + 16 * (c0 + u));
+        wv[u] = wok ? *(const f32x4*)(wr + 16 * (c0 + u)) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+  };
+  auto mul = [&](const f32x4 (&xv)[U], const f32x4 (&wv)[U], int c0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (c0 + u < nc) acc = lin_mfma_chunk(xv[u], wv[u], acc);
+  };
+  load(xa, wa, 0);
+  for (int c0 = 0; c0 < nc; c0 += 2 * U) {
+    load(xb, wb, c0 + U);
+    __builtin_amdgcn_sched_barrier(0);
+    mul(xa, wa, c0);
+    __builtin_amdgcn_sched_barrier(0);
+    load(xa, wa, c0 + 2 * U);
+    __builtin_amdgcn_sched_barrier(0);
+    mul(xb, wb, c0 + U);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return acc;
+}
+
+// A policy hidden layer: ys[16][yp] = relu(xs[16][16 nc] . w[W][w_row]^T + bias); wave v owns the column tiles v, v + 8, ... one at a time
+__device__ __forceinline__ void policy_hidden(const float* xs, int xp, int nc, const float* w, int w_row, const float* bias, int W, int row0,
+                                              int B, float* ys, int yp) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+  for (int t = wave; t < W / 16; t += CH_WAVES) {
+    const int n = 16 * t + i;
+    const float b = bias[n];
+    const f32x4 acc = policy_gemm(xs + i * xp + 4 * j, w + (size_t)n * w_row + 4 * j, nc, true);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 4 * j + r;
+      const float v = act_fwd(acc[r] + b, S2P_ACT_RELU, 0.f);
+      ys[row * yp + n] = row0 + row < B ? v : 0.f;
+    }
+  }
+}
+
+// a(h) = tanh(last_fc(hs)): one column tile (A <= 8 of its 16 columns), wave 0.  -> act slot h and the LDS tile at[16][IM_AP], whose
+// columns >= A and rows >= B are zeros.
+__device__ __forceinline__ void policy_last(const ImagineArgs& g, const float* hs, int hp, int h, int row0, float* at) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+  if (wave != 0) return;
+  const bool nok = i < g.A;
+  const int W = g.p.width;
+  const float b = nok ? g.p.b3[i] : 0.f;
+  const f32x4 acc = policy_gemm(hs + i * hp + 4 * j, g.p.w3 + (size_t)(nok ? i : 0) * W + 4 * j, W / 16, nok);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = 4 * j + r, gm = row0 + row;
+    const bool ok = nok && gm < g.c.B;
+    const float v = ok ? act_fwd(acc[r] + b, S2P_ACT_TANH, 0.f) : 0.f;
+    if (i < IM_AP) at[row * IM_AP + i] = v;
+    if (ok) g.act[((size_t)gm * g.c.T + h) * g.act_pitch + i] = v;
+  }
+}
+
+// The action term of a 256-wide first layer for the column tiles this wave owns there: ONE k-chunk of a(h) [16][pad4(A)] x the
+// action columns w[256][w_row], zero-filled past pad4(A), from a zero accumulator, then + 0 (s2p_linear_fwd without bias).
+template <int NT>
+__device__ __forceinline__ void chain_action_term(const float* at, const float* w, int w_row, int kp, ChainAddRegs<NT>& out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const bool kok = 4 * j < kp;
+  const f32x4 xv = kok ? *(const f32x4*)(at + i * IM_AP + 4 * j) : zero;
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int n = 16 * (wave + q * CH_WAVES) + i;
+    const f32x4 wv = kok ? *(const f32x4*)(w + (size_t)n * w_row + 4 * j) : zero;
+    const f32x4 acc = lin_mfma_chunk(xv, wv, zero);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out.v[q][r] = acc[r] + 0.f;
+  }
+}
+
+// z(0) -> xz, then H times: a(h) = policy(z(h)), the two action terms, chain_step.  Slot h holds a(h) and z(h+1).
+__global__ __launch_bounds__(CH_THREADS) void imagine_chain_kernel(const ImagineArgs g) {
+  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], pa[CH_ROWS * IM_P_MAX], pb[CH_ROWS * IM_P_MAX], at[CH_ROWS * IM_AP];
+  const ChainArgs& a = g.c;
+  const int row0 = blockIdx.x * CH_ROWS, W = g.p.width, pp = W + S2P_CHAIN_PAD, kp = (g.A + 3) / 4 * 4;
+  ChainHidden<CH_Z2, true> a1;
+  ChainHidden<CH_Z, true> b1;
+  for (int idx = threadIdx.x; idx < CH_ROWS * (CH_Z / 4); idx += CH_THREADS) {
+    const int row = idx / (CH_Z / 4), c4 = idx % (CH_Z / 4), gm = row0 + row;
+    const f32x4 v = gm < a.B ? *(const f32x4*)(g.z0 + (size_t)gm * g.z0_pitch + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    *(f32x4*)(xz + row * CH_XZ_P + 4 * c4) = v;
+  }
+  for (int s = 0; s < a.T; ++s) {
+    __syncthreads();                                       // xz = z(s); the latent half is done with h1 / h2 (= pa / pb)
+    policy_hidden(xz, CH_XZ_P, CH_Z / 16, g.p.w1, g.p.w1_row, g.p.b1, W, row0, a.B, pa, pp);
+    __syncthreads();
+    policy_hidden(pa, pp, W / 16, g.p.w2, W, g.p.b2, W, row0, a.B, pb, pp);
+    __syncthreads();
+    policy_last(g, pb, pp, s, row0, at);
+    __syncthreads();
+    ChainAddRegs<ChainHidden<CH_Z2, true>::NT> ta;
+    ChainAddRegs<ChainHidden<CH_Z, true>::NT> tb;
+    chain_action_term(at, g.wc, g.wc_row, kp, ta);
+    chain_action_term(at, g.wb, g.wb_row, kp, tb);
+    a1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, ta, row0, a.B);
+    chain_step(a, a.m[0], a.m[1], a1, b1, tb, s, row0, xz, pa, pb, [] {});
+  }
 }
 }  // namespace
 
@@ -328,5 +482,49 @@ extern "C" int s2p_prior_chain_fwd(const float* z2_0, int z2_0_pitch, const floa
   a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z; a.z_pitch = z_pitch; a.B = B; a.T = H;
   hipLaunchKernelGGL(prior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
   S2P_CHECK_LAUNCH("prior_chain_kernel");
+  return 0;
+}
+
+extern "C" int s2p_imagine_chain_fwd(const float* z0, int z0_pitch, const float* eps, int eps_pitch, const s2p_chain_mlp* mlps,
+                                     const float* wc, int wc_row, const float* wb, int wb_row, int A, const s2p_policy_mlp* policy,
+                                     float* act, int act_pitch, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
+                                     int z_pitch, int B, int H, void* stream) {
+  const char* who = "s2p_imagine_chain_fwd";
+  static const int k1[2] = {CH_Z2, CH_Z};
+  static const char* const name[2] = {"z1_prior", "z2_prior"};
+  S2P_REQUIRE(B >= 0 && H >= 0, "%s: negative size", who);
+  if (B == 0 || H == 0) return 0;
+  S2P_REQUIRE(z0 && eps && mlps && wc && wb && policy && act && mean && std && z,
+              "%s: null pointer (z0, eps, mlps, wc, wb, policy, act, mean, std and z are required)", who);
+  S2P_REQUIRE(A >= 1 && A <= IM_AP, "%s: action width %d, 1 .. 8 is built", who, A);
+  const int kp = (A + 3) / 4 * 4;
+  S2P_REQUIRE(z0_pitch >= CH_Z && eps_pitch >= CH_Z && act_pitch >= A && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
+              "%s: a pitch is below its row (z0 288, eps 288, act A, mean 32, std 32, z 288)", who);
+  S2P_REQUIRE(s2p_al16(z0) && z0_pitch % 4 == 0, "%s: z0 must be 16-byte aligned, its pitch a multiple of 4 floats", who);
+  S2P_REQUIRE(wc_row >= kp && wc_row % 4 == 0 && wb_row >= kp && wb_row % 4 == 0,
+              "%s: wc_row and wb_row must be multiples of 4 floats and at least A padded to 4", who);
+  S2P_REQUIRE(s2p_al16(wc) && s2p_al16(wb), "%s: wc and wb must be 16-byte aligned", who);
+  ImagineArgs g{};
+  for (int i = 0; i < 2; ++i) {
+    const s2p_chain_mlp& m = mlps[i];
+    S2P_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name[i]);
+    S2P_REQUIRE(m.k1 == k1[i], "%s: %s: the first layer's K is %d, %d is built", who, name[i], (int)m.k1, k1[i]);
+    S2P_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name[i]);
+    S2P_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name[i]);
+    g.c.m[i] = m;
+  }
+  const s2p_policy_mlp& p = *policy;
+  S2P_REQUIRE(p.w1 && p.b1 && p.w2 && p.b2 && p.w3 && p.b3, "%s: policy: null operand", who);
+  S2P_REQUIRE(p.width >= 128 && p.width <= IM_WMAX && p.width % 128 == 0,
+              "%s: policy: hidden width %d, multiples of 128 from 128 to 1024 are built", who, (int)p.width);
+  S2P_REQUIRE(p.w1_row >= CH_Z && p.w1_row % 4 == 0, "%s: policy: w1_row must be a multiple of 4 floats and at least K", who);
+  S2P_REQUIRE(s2p_al16(p.w1) && s2p_al16(p.w2) && s2p_al16(p.w3), "%s: policy: the weights must be 16-byte aligned", who);
+  g.p = p; g.z0 = z0; g.z0_pitch = z0_pitch; g.wc = wc; g.wc_row = wc_row; g.wb = wb; g.wb_row = wb_row; g.A = A; g.act = act;
+  g.act_pitch = act_pitch;
+  ChainArgs& a = g.c;
+  a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean; a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z;
+  a.z_pitch = z_pitch; a.B = B; a.T = H;
+  hipLaunchKernelGGL(imagine_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, g);
+  S2P_CHECK_LAUNCH("imagine_chain_kernel");
   return 0;
 }

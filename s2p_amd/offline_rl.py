@@ -148,6 +148,30 @@ class CriticSLAC:
             out.update(_export(net, self.packed[name], self.flat_of(name), name + "."))
         return out
 
+    @torch.no_grad()
+    def q_min(self, z, a):
+        """min(qf1, qf2)([z | a]) -> [B], forward only: both networks are the two groups of one s2p_mlp_linear_fwd launch per layer."""
+        z, a = z.to(self.device, torch.float32), a.to(self.device, torch.float32)
+        qf1 = self.nets["qf1"]
+        if z.dim() != 2 or a.dim() != 2 or z.shape[0] != a.shape[0] or z.shape[1] + a.shape[1] != qf1.input_size:
+            raise ValueError("z [B,Z] and a [B,A] with Z + A = %d are needed" % qf1.input_size)
+        B, f = z.shape[0], torch.float32
+        if B == 0:
+            return torch.zeros(0, dtype=f, device=self.device)
+        if getattr(self, "_qmin", (None,))[0] != B:
+            xp = torch.zeros(B, self.packed["qf1"].off[0][2], dtype=f, device=self.device)
+            nets = []
+            for name in ("qf1", "qf2"):
+                hs = [torch.empty(B, h, dtype=f, device=self.device) for h in qf1.hidden_sizes]
+                nets.append(Net(name, self.packed[name], B).bind(self.flat, None, xp, torch.empty(B, 1, dtype=f, device=self.device), act=hs))
+            self._qmin = (B, nets, fwd_tables(fwd_plan(nets)))      # the table holds bare addresses: the entry keeps the buffers alive
+        _, nets, table = self._qmin
+        xp = nets[0].x
+        xp[:, :z.shape[1]] = z
+        xp[:, z.shape[1]:qf1.input_size] = a
+        run(table)
+        return torch.minimum(nets[0].out[:, 0], nets[1].out[:, 0])
+
     def grads(self):
         """Reference name -> gradient of the last step's critic loss (qf1, qf2, vf: the targets have none)."""
         out = OrderedDict()

@@ -708,6 +708,31 @@ def prior_chain_fwd(z2_0, rc, rb, eps, mlps, mean, std, z):
                                     std.stride(1), ptr(z), z.stride(1), B, H, stream()), "s2p_prior_chain_fwd")
 
 
+def policy_mlp(policy):
+    """The s2p_policy_mlp of a two-hidden-layer TanhGaussianPolicy: its packed layers in place (the last layer's first A rows are
+    `last_fc`).  ValueError for a shape outside what s2p_imagine_chain_fwd is built for."""
+    pk, hs = policy.packed, policy.hidden_sizes
+    if policy.obs_dim != 288 or len(hs) != 2 or hs[0] != hs[1] or hs[0] % 128 or not 128 <= hs[0] <= 1024 or not 1 <= policy.action_dim <= 8:
+        raise ValueError("the fused imagination chain is built for obs_dim 288, two hidden layers of one width W (a multiple of 128, "
+                         "128 <= W <= 1024) and 1 <= action_dim <= 8; got obs_dim %d, hidden_sizes %s, action_dim %d"
+                         % (policy.obs_dim, hs, policy.action_dim))
+    w, b = [pk.w(policy.flat, li) for li in range(3)], [pk.b(policy.flat, li) for li in range(3)]
+    return _lib.PolicyMlp(ptr(w[0]), ptr(b[0]), ptr(w[1]), ptr(b[1]), ptr(w[2]), ptr(b[2]), w[0].shape[1], hs[0])
+
+
+def imagine_chain_fwd(z0, eps, mlps, wc, wb, A, policy, act, mean, std, z):
+    """The whole closed-loop rollout in one launch (s2p_imagine_chain_fwd).  z0: a [B, 288] view; eps, act, mean, std, z: [B, H, C]
+    views as for posterior_chain_fwd; mlps: the chain_mlp() structs of z1_prior (k1 = 256) and z2_prior; wc, wb: their action
+    columns [256][pad4(A)]; policy: a policy_mlp() struct."""
+    B, H = eps.shape[:2]
+    _chain_views(B, H, eps, act, mean, std, z)
+    zp, zs = _view2(z0)
+    arr = (_lib.ChainMlp * 2)(*mlps)
+    check(lib().s2p_imagine_chain_fwd(zp, zs, ptr(eps), eps.stride(1), arr, ptr(wc), wc.shape[1], ptr(wb), wb.shape[1], A,
+                                      ctypes.byref(policy), ptr(act), act.stride(1), ptr(mean), mean.stride(1), ptr(std),
+                                      std.stride(1), ptr(z), z.stride(1), B, H, stream()), "s2p_imagine_chain_fwd")
+
+
 def posterior_chain_fwd(feat0, ra, rb, eps, mlps, mean, std, z):
     """The whole no-grad posterior chain in one launch (s2p_posterior_chain_fwd).  feat0: the [B, 256] view feat[:, 0]; ra, rb
     [(T-1)*B, 256] contiguous (None when T == 1); eps, mean, std, z: [B, T, C] views with unit stride in C and stride(0) =

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import ACT_LRELU, ACT_NONE, EPI_MUL_ACTGRAD, chunk_elems
+from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EPI_MUL_ACTGRAD, chunk_elems
 from .ops import ConvGeom, pad_to
 from .slac_buffer import FrameBatch
 
@@ -602,7 +602,7 @@ class LatentModel(nn.Module):
                     nn.init.xavier_uniform_(p, gain=1.0)
         self.to(dev)
         self.chain_state_bytes = 0              # bytes the last sample_posterior kept for its backward (0 under no_grad)
-        self.fused_chain = False                # True: a no-grad sample_posterior, and predict, run their chain as ONE launch (SPEC.md N3h, N3i)
+        self.fused_chain = False                # True: a no-grad sample_posterior, predict and imagine run their chain as ONE launch (SPEC.md N3h-N3j)
 
     @property
     def device(self):
@@ -689,6 +689,66 @@ class LatentModel(nn.Module):
             _mlp_tail_fwd(g2, p2, h1, h2, rawb)
             ops.gauss_head_fwd(rawb, Z2, eps=noise[:, s, Z1:], z=z[:, s, Z1:], z2=xz[:, Z1:])
         return mean, std, z
+
+    @torch.no_grad()
+    def imagine(self, policy, z0, horizon, noise=None, sample=True):
+        """Closed-loop rollout (SPEC.md N3j): the deterministic policy tanh(mean) reads z(h) and the generative model steps on its
+        action.  policy: a `TanhGaussianPolicy` with obs_dim 288 and two hidden layers; z0 [B,288] = z1(0) | z2(0) (z1(0) IS read);
+        noise [B,H,288] as in `predict` -> (actions [B,H,A], z1_mean [B,H,32], z1_std [B,H,32], z [B,H,288]); slot h holds a(h) and
+        z(h+1).  Always without grad.  With `fused_chain` the H steps are one launch (s2p_imagine_chain_fwd; ValueError for a policy
+        outside its built shapes), else 13 per step; the two are bitwise equal, and `predict(z0, actions, noise)` returns bitwise
+        this z1_mean, z1_std and z."""
+        dev, A, H = self.device, self.action_dim, int(horizon)
+        z0 = z0.to(dev, torch.float32)
+        if z0.dim() != 2 or z0.shape[1] != Z1 + Z2 or H < 0:
+            raise ValueError("z0 [B,z1_dim+z2_dim] and horizon >= 0 are needed")
+        hs = getattr(policy, "hidden_sizes", None)
+        if getattr(policy, "obs_dim", None) != Z1 + Z2 or getattr(policy, "action_dim", None) != A or hs is None or len(hs) != 2:
+            raise ValueError("a TanhGaussianPolicy with obs_dim %d, action_dim %d and two hidden layers is needed" % (Z1 + Z2, A))
+        if policy.device is None or policy.device.type != dev.type:
+            raise ValueError("the policy and the latent model share a HIP device")
+        B = z0.shape[0]
+        if not sample:
+            noise = _f32((B, H, Z1 + Z2), dev, True)
+        elif noise is None:
+            noise = torch.randn((B, H, Z1 + Z2), dtype=torch.float32, device=dev)
+        noise = noise.to(dev, torch.float32).contiguous()
+        if noise.shape != (B, H, Z1 + Z2):
+            raise ValueError("noise is [B,H,z1_dim+z2_dim]")
+        Ap = pad_to(A, 4)
+        act = _f32((B, H, Ap), dev, True)
+        mean, std, z = _f32((B, H, Z1), dev), _f32((B, H, Z1), dev), _f32((B, H, Z1 + Z2), dev)
+        if B == 0 or H == 0:
+            return act[..., :A], mean, std, z
+        g1, g2 = self.z1_prior, self.z2_prior
+        p1, p2 = g1.packed(), g2.packed()
+        wc, wb = g1.packed_cols(Z2, Z2 + A), p2["g1"][1][0]
+        w1a, w1b = p1["g1"][0][0], p2["g1"][0][0]
+        xz = _f32((B, Z1 + Z2), dev).copy_(z0)
+        if self.fused_chain:
+            ops.imagine_chain_fwd(xz, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], wc, wb, A, ops.policy_mlp(policy), act,
+                                  mean, std, z)
+            return act[..., :A], mean, std, z
+        pk, fl = policy.packed, policy.flat
+        pw, pb = [pk.w(fl, li) for li in range(3)], [pk.b(fl, li) for li in range(3)]
+        q1, q2 = _f32((B, hs[0]), dev), _f32((B, hs[1]), dev)
+        rc, rb = _f32((B, HID), dev), _f32((B, HID), dev)
+        h1, h2 = _f32((B, HID), dev), _f32((B, HID), dev)
+        rawa, rawb = _f32((B, g1.Npad), dev), _f32((B, g2.Npad), dev)
+        for s in range(H):
+            a = act[:, s]                                                                # [B, pad4(A)] view, pitch H * pad4(A)
+            ops.linear_fwd_into(xz, pw[0], pb[0], hs[0], q1, ACT_RELU)
+            ops.linear_fwd_into(q1, pw[1], pb[1], hs[1], q2, ACT_RELU)
+            ops.linear_fwd_into(q2, pw[2], pb[2], A, a, ACT_TANH)
+            ops.linear_fwd_into(a, wc, None, HID, rc)
+            ops.linear_fwd_into(a, wb, None, HID, rb)
+            ops.linear_fwd_into(xz[:, Z1:], w1a, p1["b1"], HID, h1, ACT_LRELU, SLOPE, add=rc)
+            _mlp_tail_fwd(g1, p1, h1, h2, rawa)
+            ops.gauss_head_fwd(rawa, Z1, eps=noise[:, s, :Z1], mean=mean[:, s], std=std[:, s], z=z[:, s, :Z1], z2=xz[:, :Z1])
+            ops.linear_fwd_into(xz, w1b, p2["b1"], HID, h1, ACT_LRELU, SLOPE, add=rb)
+            _mlp_tail_fwd(g2, p2, h1, h2, rawb)
+            ops.gauss_head_fwd(rawb, Z2, eps=noise[:, s, Z1:], z=z[:, s, Z1:], z2=xz[:, Z1:])
+        return act[..., :A], mean, std, z
 
     def predict_reward(self, z0, z, actions_):
         """Reward head on [z(h-1) | a(h-1) | z(h)], h = 1..H, with z(0) = z0 [B,288], z [B,H,288] (predict's), actions_ [B,H,A] ->
