@@ -134,13 +134,17 @@ int s2p_conv2d_dgrad_mat(const s2p_conv_desc* d, const void* dy, const void* w_b
 int s2p_conv2d_mat_is_fused(const s2p_conv_desc* d, int dgrad, int has_gb);
 /* Which kernel family s2p_conv2d_fwd_ws (dgrad == 0) / s2p_conv2d_dgrad_ws (dgrad == 1) run this problem on, with
  * epi == S2P_EPI_STORE and no fused norm: the S2P_CONV_PATH_* id of the plan's first launch; for S2P_CONV_PATH_HALO the
- * kernel variant (S2P_HALO_*) rides in bits 8 and up.  has_workspace: the caller passes a scratch of the size the
- * workspace query asks for (0: none).  A dry run of the dispatcher -- nothing is dereferenced or launched; -1 for a
- * descriptor the conv entry points refuse.  For tests and tools: which path a shape takes is not part of the contract. */
+ * kernel variant (S2P_HALO_*) rides in bits 8 and up, for S2P_CONV_PATH_THIN the kernel behind it
+ * (S2P_THIN_*).  has_workspace: the caller passes a scratch of the size the workspace query asks for (0: none).  A dry
+ * run of the dispatcher -- nothing is dereferenced or launched; -1 for a descriptor the conv entry points refuse.  The
+ * query plans with S2P_ACT_NONE: a call with S2P_ACT_SWISH keeps the row-streaming kernel out (it then runs the tiled or
+ * the lanes-per-pixel kernel), which the query does not tell.  For tests and tools: which path a shape takes is not part
+ * of the contract. */
 enum { S2P_CONV_PATH_THIN = 0, S2P_CONV_PATH_THIN4 = 1, S2P_CONV_PATH_THIN_CIN = 2, S2P_CONV_PATH_THIN_ROWS = 3,
        S2P_CONV_PATH_PLANE = 4, S2P_CONV_PATH_PLANEG = 5, S2P_CONV_PATH_HALO = 6, S2P_CONV_PATH_SPLITK = 7,
        S2P_CONV_PATH_DMA = 8, S2P_CONV_PATH_PHASES = 9, S2P_CONV_PATH_GENERIC = 10 };
 enum { S2P_HALO_S9_176_PIPE = 0, S2P_HALO_S9_176 = 1, S2P_HALO_S9_320 = 2, S2P_HALO_R_176 = 3, S2P_HALO_R_320 = 4 };
+enum { S2P_THIN_LANES = 0, S2P_THIN_TILED, S2P_THIN_ROWS, S2P_THIN_HEAD, S2P_THIN_HEAD_MFMA };
 int s2p_conv2d_path(const s2p_conv_desc* d, int dgrad, int has_workspace);
 /* dw (fp32) [groups][Cout][KH*KW][Cin_real] for transposed==0,
  *           [groups][Cin][KH*KW][Cout_real] for transposed==1  (= channels-last physical

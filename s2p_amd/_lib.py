@@ -15,10 +15,12 @@ _SO = os.path.join(_HERE, "csrc", "libs2p_hip.so")     # (tools/uselib.py points
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SWISH = 0, 1, 2, 3, 4
 EPI_STORE, EPI_ADD, EPI_MUL_ACTGRAD = 0, 1, 2
-# s2p_conv2d_path: the dispatcher's path of a conv problem; for PATH_HALO the kernel variant is in bits 8 and up (halo_path)
+# s2p_conv2d_path: the dispatcher's path of a conv problem; for PATH_HALO the kernel variant is in bits 8 and up (halo_path), for
+# PATH_THIN the kernel behind it (thin_path)
 (PATH_THIN, PATH_THIN4, PATH_THIN_CIN, PATH_THIN_ROWS, PATH_PLANE, PATH_PLANEG, PATH_HALO, PATH_SPLITK, PATH_DMA, PATH_PHASES,
  PATH_GENERIC) = range(11)
 HALO_S9_176_PIPE, HALO_S9_176, HALO_S9_320, HALO_R_176, HALO_R_320 = range(5)
+THIN_LANES, THIN_TILED, THIN_ROWS, THIN_HEAD, THIN_HEAD_MFMA = range(5)
 
 c_int, c_float, c_void_p, c_int64 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64
 
@@ -228,6 +230,11 @@ def lib():
 def halo_path(kind):
     """The s2p_conv2d_path answer for the halo-resident kernel in variant `kind` (HALO_*)."""
     return PATH_HALO | (kind << 8)
+
+
+def thin_path(kind):
+    """The s2p_conv2d_path answer for the thin-Cout forward on kernel `kind` (THIN_*)."""
+    return PATH_THIN | (kind << 8)
 
 
 def check(rc, what):

@@ -1595,6 +1595,7 @@ extern "C" int s2p_conv2d_path(const s2p_conv_desc* d, int dgrad, int has_worksp
   ConvPlan P;
   if (dgrad ? conv_plan_dgrad(d, op, NormWant{}, sc, P) : conv_plan_fwd(d, op, NormWant{}, sc, P)) return -1;
   const int path = (int)P.path;
+  if (P.path == ConvPath::Thin) return path | (s2p_thin_kind(d, op.act) << 8);
   return P.path == ConvPath::Halo ? path | ((int)P.items[0].c.halo << 8) : path;
 }
 extern "C" size_t s2p_conv2d_dgrad_workspace(const s2p_conv_desc* d) {

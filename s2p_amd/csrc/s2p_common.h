@@ -231,6 +231,7 @@ __device__ __forceinline__ void s2p_dma16_so(i32x4 rsrc, unsigned lds_dst, int v
 
 // thin-Cout direct convolutions (thin_conv.hip)
 bool s2p_thin_applicable(const s2p_conv_desc* d);
+int s2p_thin_kind(const s2p_conv_desc* d, int act);      // S2P_THIN_*: the kernel s2p_thin_fwd launches (also s2p_conv2d_path's answer)
 int s2p_thin_fwd(const s2p_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act, float slope,
                  hipStream_t st);
 int s2p_thin_wgrad(const s2p_conv_desc* d, const void* x, const void* dy, float* dw, int cin_real, void* ws, size_t ws_bytes, hipStream_t st);
@@ -268,8 +269,9 @@ int s2p_wgrad_slabg(const s2p_conv_desc* d, const void* x, const void* dy, float
 bool s2p_head_wgrad_supported(const s2p_conv_desc* d, int cin_real, int cout_real);
 size_t s2p_head_wgrad_workspace(const s2p_conv_desc* d);
 bool s2p_head_fwd_applicable(const s2p_conv_desc* d);
+bool s2p_head_fwd_mfma(const s2p_conv_desc* d);           // the MFMA form (else the shuffle form); asked by s2p_thin_kind only
 int s2p_head_fwd(const s2p_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act, float slope,
-                 hipStream_t st);
+                 bool mfma, hipStream_t st);
 int s2p_head_wgrad(const s2p_conv_desc* d, const void* x, const void* dy, float* dw, float* db, int cin_real,
                    void* workspace, size_t workspace_bytes, hipStream_t st);
 

@@ -162,13 +162,24 @@ bool s2p_thin_applicable(const s2p_conv_desc* d) {
          d->Cin / 8 <= 64 && d->y_pitch % 8 == 0 && (long long)d->Cout * d->KH * d->KW * d->Cin * 2 <= 64 * 1024;
 }
 
+// Which kernel s2p_thin_fwd launches (S2P_THIN_*): the one selection, shared by the launcher and by s2p_conv2d_path.
+int s2p_thin_kind(const s2p_conv_desc* d, int act) {
+  static const int no_head = s2p_env_set("S2P_NO_HEAD_FWD");          // A/B switch (diagnostics build only)
+  if (!no_head && s2p_head_fwd_applicable(d)) return s2p_head_fwd_mfma(d) ? S2P_THIN_HEAD_MFMA : S2P_THIN_HEAD;
+  static const int no_rows = s2p_env_set("S2P_NO_THIN_ROWS");         // A/B switch (diagnostics build only)
+  if (!no_rows && act != S2P_ACT_SWISH && s2p_thin_rows_applicable(d)) return S2P_THIN_ROWS;
+  return tiled_applicable(d) ? S2P_THIN_TILED : S2P_THIN_LANES;
+}
+
 int s2p_thin_fwd(const s2p_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act, float slope,
                  hipStream_t st) {
-  static const int no_head = s2p_env_set("S2P_NO_HEAD_FWD");          // A/B switch (diagnostics build only)
-  if (!no_head && s2p_head_fwd_applicable(d)) return s2p_head_fwd(d, x, w, bias, y, act, slope, st);
-  static const int no_rows = s2p_env_set("S2P_NO_THIN_ROWS");         // A/B switch (diagnostics build only)
-  if (!no_rows && act != S2P_ACT_SWISH && s2p_thin_rows_applicable(d)) return s2p_thin_rows_fwd(d, x, w, bias, y, act, slope, st);
-  if (tiled_applicable(d)) return s2p_thin_tiled_fwd(d, x, w, bias, y, act, slope, st);
+  switch (s2p_thin_kind(d, act)) {
+    case S2P_THIN_HEAD_MFMA: return s2p_head_fwd(d, x, w, bias, y, act, slope, true, st);
+    case S2P_THIN_HEAD: return s2p_head_fwd(d, x, w, bias, y, act, slope, false, st);
+    case S2P_THIN_ROWS: return s2p_thin_rows_fwd(d, x, w, bias, y, act, slope, st);
+    case S2P_THIN_TILED: return s2p_thin_tiled_fwd(d, x, w, bias, y, act, slope, st);
+    default: break;                                                   // S2P_THIN_LANES: below
+  }
   ThinArgs a{};
   fill_args(a, d);
   a.x = (const __bf16*)x; a.w = (const __bf16*)w; a.bias = bias; a.y = (__bf16*)y; a.act = act; a.slope = slope;

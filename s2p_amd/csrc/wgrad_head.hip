@@ -379,13 +379,16 @@ bool s2p_head_fwd_applicable(const s2p_conv_desc* d) {
          d->H >= 1 && d->W >= 1;
 }
 
+// the MFMA form holds an image's H*W x 16 per-tap products in LDS (256 rows); larger maps of <= 16 rows take the shuffle form
+bool s2p_head_fwd_mfma(const s2p_conv_desc* d) { return !S2P_DIAG_SWITCH(13) && d->H * d->W <= 256; }
+
 int s2p_head_fwd(const s2p_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act, float slope,
-                 hipStream_t st) {
+                 bool mfma, hipStream_t st) {
   HeadFwdArgs a{};
   a.x = (const __bf16*)x; a.w = (const __bf16*)w; a.bias = bias; a.y = (__bf16*)y;
   a.N = d->N; a.H = d->H; a.W = d->W; a.x_pitch = d->x_pitch; a.Ho = d->Ho; a.Wo = d->Wo; a.y_pitch = d->y_pitch;
   a.pad = d->pad; a.act = act; a.slope = slope;
-  if (!S2P_DIAG_SWITCH(13) && d->H * d->W <= 256) {
+  if (mfma) {
     hipLaunchKernelGGL(head_fwd_mfma_kernel, dim3(d->N), dim3(64 * cdiv(d->H * d->W, 16)), 0, st, a);
     S2P_CHECK_LAUNCH("head_fwd_mfma_kernel");
     return 0;

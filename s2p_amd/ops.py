@@ -118,8 +118,9 @@ def conv_fwd(geom, x, w_fwd, bias, cin_pad, y_pitch=None, act=ACT_NONE, slope=0.
 
 
 def conv_path(geom, dtype, x_shape, cin_pad, dgrad=False, workspace=True):
-    """The dispatcher's path (_lib.PATH_*; _lib.halo_path(kind) for the halo-resident kernel) of conv_fwd / conv_dgrad on an input of
-    `x_shape` = (N, H, W, x_pitch): a dry run on the host, nothing is launched.  workspace=False: as called without a scratch."""
+    """The dispatcher's path (_lib.PATH_*; _lib.halo_path(kind) for the halo-resident kernel, _lib.thin_path(kind) for the thin-Cout
+    forward) of conv_fwd / conv_dgrad on an input of `x_shape` = (N, H, W, x_pitch): a dry run on the host, nothing is launched.
+    workspace=False: as called without a scratch."""
     N, H, W, xp = x_shape
     ce = chunk_elems(dtype)
     d = geom.desc(dtype, N, H, W, cin_pad, xp, pad_to(geom.cout * geom.groups if geom.groups > 1 else geom.cout, ce))

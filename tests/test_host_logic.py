@@ -103,8 +103,8 @@ def test_fused_norm_dispatch_is_host_logic():
 
 def test_conv_path_query_is_host_logic():
     """`s2p_conv2d_path` is a dry run of the conv dispatcher as well: it names the kernel family of a problem's first launch (and the
-    variant of the halo-resident kernel) without a GPU, with and without the caller's scratch.  tests/test_kernels_gpu.py asserts
-    through it that its conv cases reach the kernels their comments name."""
+    variant of the halo-resident kernel, the kernel behind the thin-Cout forward) without a GPU, with and without the caller's scratch.
+    tests/test_kernels_gpu.py asserts through it that its conv cases reach the kernels their comments name."""
     import ctypes
     from s2p_amd import ops
     L = _lib.lib()
@@ -131,6 +131,14 @@ def test_conv_path_query_is_host_logic():
     assert path(256, 128, 3, 2, 1, 2, 5, 5, tr=True) == _lib.PATH_PHASES
     assert path(3, 64, 7, 1, 3, 2, 20, 20, refl=True) == _lib.PATH_THIN4
     assert path(3, 64, 7, 1, 3, 2, 20, 20, refl=True, ws=0) != _lib.PATH_THIN4       # needs the caller's scratch
+    # PATH_THIN is five kernels: the one s2p_thin_fwd launches rides in bits 8 and up (the query plans with ACT_NONE)
+    T = _lib.thin_path
+    assert path(512, 1, 4, 1, 2, 3, 13, 13) == T(_lib.THIN_HEAD_MFMA)                # H * W <= 256
+    assert path(512, 1, 4, 1, 2, 3, 16, 17) == T(_lib.THIN_HEAD)                     # H <= 16
+    assert path(512, 1, 4, 1, 2, 2, 17, 17) == T(_lib.THIN_LANES)
+    assert path(64, 3, 7, 1, 3, 2, 12, 12, refl=True) == T(_lib.THIN_ROWS)
+    assert path(64, 2, 7, 1, 3, 1, 33, 37, refl=True) == T(_lib.THIN_TILED)
+    assert path(64, 4, 7, 1, 3, 1, 33, 37, refl=True) == T(_lib.THIN_LANES)          # four channels: over the tiled kernel's LDS
     # 50 K steps on 3 workgroups: K-split where the caller offers scratch, the halo-resident kernel (two slabs of run-time taps) without
     assert path(128, 72, 5, 1, 2, 2, 8, 10) == _lib.PATH_SPLITK
     assert path(128, 72, 5, 1, 2, 2, 8, 10, ws=0) == H(_lib.HALO_R_176)

@@ -69,15 +69,15 @@ CONV_CASES = [
     (72, 128, 3, 1, 1, False, False, 9, 11, 3),    # the DGRAD is the pipelined form: flipped taps of the transposed pack, two slabs (Cout padded to 128)
     (64, 72, 5, 1, 2, False, False, 8, 10, 2),     # 25 run-time taps, window of 172 positions (two halo buffers)
     (128, 64, 3, 2, 1, False, False, 13, 21, 3),   # LDS-DMA kernel on the 64-row weight tile (forward, 2 pixel tiles); dgrad: merged phases, 128 rows
-    (64, 3, 7, 1, 3, False, True, 40, 36, 2),      # out conv at a size that takes the spatially tiled MFMA path (ragged tiles)
-    (32, 2, 5, 1, 2, False, False, 33, 37, 1),     # tiled path, zero padding, Cout=2, K=5
-    (64, 3, 7, 1, 3, False, True, 84, 84, 2),      # out conv, row-streaming path: 3 waves, several row bands
+    (64, 3, 7, 1, 3, False, True, 40, 36, 2),      # out conv, row-streaming path (s2p_thin_rows_applicable takes it before the tiled kernel): 2 waves, 6 bands of 7 rows (the last 5); wgrad: thin_rows7_wgrad_kernel, 2 bands of 20
+    (32, 2, 5, 1, 2, False, False, 33, 37, 1),     # spatially tiled MFMA path (ragged tiles), zero padding, Cout=2, K=5
+    (64, 3, 7, 1, 3, False, True, 84, 84, 2),      # out conv, row-streaming path: 4 waves, 12 bands of 7 rows (band = KS at this batch: tests/test_thin_conv_layers_gpu.py runs the longer bands)
     (64, 3, 7, 1, 3, False, True, 9, 130, 1),      # row-streaming path: two column strips, one short band
     (64, 3, 7, 1, 3, False, False, 30, 40, 3),     # row-streaming path with zero padding
     (3, 64, 3, 1, 1, False, False, 84, 84, 2),     # VGG conv1_1: the dgrad is the row-streaming kernel over dy with flipped taps
-    (3, 64, 3, 1, 1, False, False, 9, 35, 3),      # ... two waves, one short band
+    (3, 64, 3, 1, 1, False, False, 9, 35, 3),      # ... two waves, three bands of 3 rows
     (3, 200, 3, 1, 1, False, False, 21, 21, 2),    # conditioning conv 3 -> many: thin-input forward kernel, 4 channel blocks (ragged)
-    (3, 64, 7, 1, 3, False, True, 84, 84, 1),      # stem at the train size: thin-input forward kernel, several tiles per wave
+    (3, 64, 7, 1, 3, False, True, 84, 84, 1),      # stem at the train size: thin-input forward kernel, 221 tiles on 224 waves: one tile per wave, the last half full (several tiles per wave: tests/test_thin_conv_layers_gpu.py)
     (3, 64, 7, 1, 3, False, False, 30, 40, 3),     # stem-like with zero padding: weight gradient on the row-streaming kernel with exchanged operands (2 bands of 18 rows)
     (3, 64, 7, 1, 3, False, True, 25, 31, 2),      # ... reflect padding, one band of 31 -> two of 16 rows (the second short)
     (256, 128, 3, 1, 1, False, False, 19, 21, 8),  # plane-resident kernel (bf16): 8 half-slabs, XCD-aware (image, slab) order, H != W
