@@ -18,7 +18,10 @@
 // for before the barrier that ends the previous layer, then the next block loads while the current one is multiplied.  One CU's
 // fp32 MFMA rate bounds a 16-row step (13.4 MFLOP, ~52 k cycles), so more waves would only divide the same pipe; fewer (4) leave a
 // SIMD idle whenever its one wave waits for weights.  Measured: 425 us per chain at 512 threads, 451-459
-// at 256, 504 at 1 024 -- where 128 VGPRs per lane no longer hold the double-buffered operands.
+// at 256, 504 at 1 024 -- where the 128 VGPRs a lane then has no longer hold the double-buffered operands.  At 512 threads the three
+// kernels sit AT the register ceiling (hipcc -Rpass-analysis=kernel-resource-usage): 256 VGPRs per lane, occupancy 2, and a few
+// spilled registers -- 12 / 20 / 72 bytes of scratch per lane in the posterior / prior / imagination kernel.  Any edit of the device
+// code is judged by that table and by the assembly, not by how it reads.
 //
 // LDS (51 968 bytes of the CU's 160 KiB, static, nothing aliased):
 //   xz [16][292]  z1(t) | z2(t-1), the input row of both first layers (at t = 0 columns 32.. hold feat(0))
@@ -253,12 +256,13 @@ __device__ __forceinline__ void chain_step(const ChainArgs& a, const s2p_chain_m
   chain_mlp<CH_Z2>(a, mb, b1, xz, t, CH_Z1, row0, xz, h1, h2, next);
 }
 
-// src[16 rows][256] -> xz[:, 32:]; rows >= B are zeros, and so is every activation row derived from them
+// src[16 rows][W] -> xz[:, C0 : C0 + W]; rows >= B are zeros, and so is every activation row derived from them
+template <int C0, int W>
 __device__ __forceinline__ void chain_load_rows(const float* src, int pitch, int row0, int B, float* xz) {
-  for (int idx = threadIdx.x; idx < CH_ROWS * (CH_Z2 / 4); idx += CH_THREADS) {
-    const int row = idx / (CH_Z2 / 4), c4 = idx % (CH_Z2 / 4), gm = row0 + row;
+  for (int idx = threadIdx.x; idx < CH_ROWS * (W / 4); idx += CH_THREADS) {
+    const int row = idx / (W / 4), c4 = idx % (W / 4), gm = row0 + row;
     const f32x4 v = gm < B ? *(const f32x4*)(src + (size_t)gm * pitch + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    *(f32x4*)(xz + row * CH_XZ_P + CH_Z1 + 4 * c4) = v;
+    *(f32x4*)(xz + row * CH_XZ_P + C0 + 4 * c4) = v;
   }
 }
 
@@ -270,7 +274,7 @@ __global__ __launch_bounds__(CH_THREADS) void posterior_chain_kernel(const Chain
   ChainHidden<CH_Z2, true> a1;
   ChainHidden<CH_Z, true> b1;
   i1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, nullptr, row0, a.B);
-  chain_load_rows(a.feat, a.feat_pitch, row0, a.B, xz);          // feat(0) -> xz[:, 32:]
+  chain_load_rows<CH_Z1, CH_FEAT>(a.feat, a.feat_pitch, row0, a.B, xz);      // feat(0) -> xz[:, 32:]
   auto ask_a1 = [&](int t) {
     if (t < a.T) a1.ask(a.m[2].w1, a.m[2].w1_row, a.m[2].b1, a.ra + (size_t)(t - 1) * a.B * CH_HID, row0, a.B);
   };
@@ -294,7 +298,7 @@ __global__ __launch_bounds__(CH_THREADS) void prior_chain_kernel(const ChainArgs
     if (s < a.T) a1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, a.ra + (size_t)s * a.B * CH_HID, row0, a.B);
   };
   ask_a1(0);
-  chain_load_rows(a.feat, a.feat_pitch, row0, a.B, xz);
+  chain_load_rows<CH_Z1, CH_Z2>(a.feat, a.feat_pitch, row0, a.B, xz);
   for (int s = 0; s < a.T; ++s)
     chain_step(a, a.m[0], a.m[1], a1, b1, a.rb + (size_t)s * a.B * CH_HID, s, row0, xz, h1, h2, [&] { ask_a1(s + 1); });
 }
@@ -404,11 +408,7 @@ __global__ __launch_bounds__(CH_THREADS) void imagine_chain_kernel(const Imagine
   const int row0 = blockIdx.x * CH_ROWS, W = g.p.width, pp = W + S2P_CHAIN_PAD, kp = (g.A + 3) / 4 * 4;
   ChainHidden<CH_Z2, true> a1;
   ChainHidden<CH_Z, true> b1;
-  for (int idx = threadIdx.x; idx < CH_ROWS * (CH_Z / 4); idx += CH_THREADS) {
-    const int row = idx / (CH_Z / 4), c4 = idx % (CH_Z / 4), gm = row0 + row;
-    const f32x4 v = gm < a.B ? *(const f32x4*)(g.z0 + (size_t)gm * g.z0_pitch + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    *(f32x4*)(xz + row * CH_XZ_P + 4 * c4) = v;
-  }
+  chain_load_rows<0, CH_Z>(g.z0, g.z0_pitch, row0, a.B, xz);
   for (int s = 0; s < a.T; ++s) {
     __syncthreads();                                       // xz = z(s); the latent half is done with h1 / h2 (= pa / pb)
     policy_hidden(xz, CH_XZ_P, CH_Z / 16, g.p.w1, g.p.w1_row, g.p.b1, W, row0, a.B, pa, pp);
@@ -425,32 +425,51 @@ __global__ __launch_bounds__(CH_THREADS) void imagine_chain_kernel(const Imagine
     chain_step(a, a.m[0], a.m[1], a1, b1, tb, s, row0, xz, pa, pb, [] {});
   }
 }
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------
+struct ChainHeadSpec { int k1; const char* name; };        // the chain columns of a head's first layer, and the head's name in messages
+const ChainHeadSpec CH_POSTERIOR_HEADS[4] = {{CH_FEAT, "z1_posterior_init"}, {CH_Z1, "z2_prior_init"}, {CH_Z2, "z1_posterior"}, {CH_Z, "z2_prior"}};
+const ChainHeadSpec CH_PRIOR_HEADS[2] = {{CH_Z2, "z1_prior"}, {CH_Z, "z2_prior"}};
+
+// Checks `n` s2p_chain_mlps against `spec` and copies them into a.m.  0, or S2P_REQUIRE's value with the error text set.
+int chain_take_mlps(const char* who, const s2p_chain_mlp* mlps, const ChainHeadSpec* spec, int n, ChainArgs& a) {
+  for (int g = 0; g < n; ++g) {
+    const s2p_chain_mlp& m = mlps[g];
+    const char* name = spec[g].name;
+    S2P_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name);
+    S2P_REQUIRE(m.k1 == spec[g].k1, "%s: %s: the first layer's K is %d, %d is built", who, name, (int)m.k1, spec[g].k1);
+    S2P_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name);
+    S2P_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name);
+    a.m[g] = m;
+  }
+  return 0;
+}
+
+// Checks the [B, T, C] views every chain reads (eps) and writes (mean, std, z) and fills them, B and T into `a`.  Returns as above.
+int chain_take_views(const char* who, const float* eps, int eps_pitch, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
+                     int z_pitch, int B, int T, ChainArgs& a) {
+  S2P_REQUIRE(eps && mean && std && z, "%s: null pointer (eps, mean, std and z are required)", who);
+  S2P_REQUIRE(eps_pitch >= CH_Z && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
+              "%s: a pitch is below its row (eps 288, mean 32, std 32, z 288)", who);
+  a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean; a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z;
+  a.z_pitch = z_pitch; a.B = B; a.T = T;
+  return 0;
+}
 }  // namespace
 
 extern "C" int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
                                        int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std,
                                        int std_pitch, float* z, int z_pitch, int B, int T, void* stream) {
   const char* who = "s2p_posterior_chain_fwd";
-  static const int k1[4] = {CH_FEAT, CH_Z1, CH_Z2, CH_Z};
-  static const char* const name[4] = {"z1_posterior_init", "z2_prior_init", "z1_posterior", "z2_prior"};
   S2P_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
   if (B == 0 || T == 0) return 0;
-  S2P_REQUIRE(feat && eps && mlps && mean && std && z, "%s: null pointer (feat, eps, mlps, mean, std and z are required)", who);
+  S2P_REQUIRE(feat && mlps, "%s: null pointer (feat and mlps are required)", who);
   S2P_REQUIRE(T == 1 || (ra && rb), "%s: ra and rb are required when T > 1", who);
-  S2P_REQUIRE(feat_pitch >= CH_FEAT && eps_pitch >= CH_Z && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
-              "%s: a pitch is below its row (feat 256, eps 288, mean 32, std 32, z 288)", who);
-  S2P_REQUIRE(s2p_al16(feat) && feat_pitch % 4 == 0, "%s: feat must be 16-byte aligned, its pitch a multiple of 4 floats", who);
   ChainArgs a{};
-  for (int g = 0; g < (T > 1 ? 4 : 2); ++g) {
-    const s2p_chain_mlp& m = mlps[g];
-    S2P_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name[g]);
-    S2P_REQUIRE(m.k1 == k1[g], "%s: %s: the first layer's K is %d, %d is built", who, name[g], (int)m.k1, k1[g]);
-    S2P_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name[g]);
-    S2P_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name[g]);
-    a.m[g] = m;
-  }
-  a.feat = feat; a.feat_pitch = feat_pitch; a.ra = ra; a.rb = rb; a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean;
-  a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z; a.z_pitch = z_pitch; a.B = B; a.T = T;
+  if (int e = chain_take_views(who, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a)) return e;
+  S2P_REQUIRE(feat_pitch >= CH_FEAT, "%s: the pitch of feat is below its row of 256", who);
+  S2P_REQUIRE(s2p_al16(feat) && feat_pitch % 4 == 0, "%s: feat must be 16-byte aligned, its pitch a multiple of 4 floats", who);
+  if (int e = chain_take_mlps(who, mlps, CH_POSTERIOR_HEADS, T > 1 ? 4 : 2, a)) return e;
+  a.feat = feat; a.feat_pitch = feat_pitch; a.ra = ra; a.rb = rb;
   hipLaunchKernelGGL(posterior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
   S2P_CHECK_LAUNCH("posterior_chain_kernel");
   return 0;
@@ -460,26 +479,15 @@ extern "C" int s2p_prior_chain_fwd(const float* z2_0, int z2_0_pitch, const floa
                                    const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
                                    int z_pitch, int B, int H, void* stream) {
   const char* who = "s2p_prior_chain_fwd";
-  static const int k1[2] = {CH_Z2, CH_Z};
-  static const char* const name[2] = {"z1_prior", "z2_prior"};
   S2P_REQUIRE(B >= 0 && H >= 0, "%s: negative size", who);
   if (B == 0 || H == 0) return 0;
-  S2P_REQUIRE(z2_0 && rc && rb && eps && mlps && mean && std && z,
-              "%s: null pointer (z2_0, rc, rb, eps, mlps, mean, std and z are required)", who);
-  S2P_REQUIRE(z2_0_pitch >= CH_Z2 && eps_pitch >= CH_Z && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
-              "%s: a pitch is below its row (z2_0 256, eps 288, mean 32, std 32, z 288)", who);
-  S2P_REQUIRE(s2p_al16(z2_0) && z2_0_pitch % 4 == 0, "%s: z2_0 must be 16-byte aligned, its pitch a multiple of 4 floats", who);
+  S2P_REQUIRE(z2_0 && rc && rb && mlps, "%s: null pointer (z2_0, rc, rb and mlps are required)", who);
   ChainArgs a{};
-  for (int g = 0; g < 2; ++g) {
-    const s2p_chain_mlp& m = mlps[g];
-    S2P_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name[g]);
-    S2P_REQUIRE(m.k1 == k1[g], "%s: %s: the first layer's K is %d, %d is built", who, name[g], (int)m.k1, k1[g]);
-    S2P_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name[g]);
-    S2P_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name[g]);
-    a.m[g] = m;
-  }
-  a.feat = z2_0; a.feat_pitch = z2_0_pitch; a.ra = rc; a.rb = rb; a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean;
-  a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z; a.z_pitch = z_pitch; a.B = B; a.T = H;
+  if (int e = chain_take_views(who, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, H, a)) return e;
+  S2P_REQUIRE(z2_0_pitch >= CH_Z2, "%s: the pitch of z2_0 is below its row of 256", who);
+  S2P_REQUIRE(s2p_al16(z2_0) && z2_0_pitch % 4 == 0, "%s: z2_0 must be 16-byte aligned, its pitch a multiple of 4 floats", who);
+  if (int e = chain_take_mlps(who, mlps, CH_PRIOR_HEADS, 2, a)) return e;
+  a.feat = z2_0; a.feat_pitch = z2_0_pitch; a.ra = rc; a.rb = rb;
   hipLaunchKernelGGL(prior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
   S2P_CHECK_LAUNCH("prior_chain_kernel");
   return 0;
@@ -490,29 +498,19 @@ extern "C" int s2p_imagine_chain_fwd(const float* z0, int z0_pitch, const float*
                                      float* act, int act_pitch, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
                                      int z_pitch, int B, int H, void* stream) {
   const char* who = "s2p_imagine_chain_fwd";
-  static const int k1[2] = {CH_Z2, CH_Z};
-  static const char* const name[2] = {"z1_prior", "z2_prior"};
   S2P_REQUIRE(B >= 0 && H >= 0, "%s: negative size", who);
   if (B == 0 || H == 0) return 0;
-  S2P_REQUIRE(z0 && eps && mlps && wc && wb && policy && act && mean && std && z,
-              "%s: null pointer (z0, eps, mlps, wc, wb, policy, act, mean, std and z are required)", who);
+  S2P_REQUIRE(z0 && mlps && wc && wb && policy && act, "%s: null pointer (z0, mlps, wc, wb, policy and act are required)", who);
   S2P_REQUIRE(A >= 1 && A <= IM_AP, "%s: action width %d, 1 .. 8 is built", who, A);
   const int kp = (A + 3) / 4 * 4;
-  S2P_REQUIRE(z0_pitch >= CH_Z && eps_pitch >= CH_Z && act_pitch >= A && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
-              "%s: a pitch is below its row (z0 288, eps 288, act A, mean 32, std 32, z 288)", who);
+  ImagineArgs g{};
+  if (int e = chain_take_views(who, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, H, g.c)) return e;
+  S2P_REQUIRE(z0_pitch >= CH_Z && act_pitch >= A, "%s: a pitch is below its row (z0 288, act A)", who);
   S2P_REQUIRE(s2p_al16(z0) && z0_pitch % 4 == 0, "%s: z0 must be 16-byte aligned, its pitch a multiple of 4 floats", who);
   S2P_REQUIRE(wc_row >= kp && wc_row % 4 == 0 && wb_row >= kp && wb_row % 4 == 0,
               "%s: wc_row and wb_row must be multiples of 4 floats and at least A padded to 4", who);
   S2P_REQUIRE(s2p_al16(wc) && s2p_al16(wb), "%s: wc and wb must be 16-byte aligned", who);
-  ImagineArgs g{};
-  for (int i = 0; i < 2; ++i) {
-    const s2p_chain_mlp& m = mlps[i];
-    S2P_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name[i]);
-    S2P_REQUIRE(m.k1 == k1[i], "%s: %s: the first layer's K is %d, %d is built", who, name[i], (int)m.k1, k1[i]);
-    S2P_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name[i]);
-    S2P_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name[i]);
-    g.c.m[i] = m;
-  }
+  if (int e = chain_take_mlps(who, mlps, CH_PRIOR_HEADS, 2, g.c)) return e;
   const s2p_policy_mlp& p = *policy;
   S2P_REQUIRE(p.w1 && p.b1 && p.w2 && p.b2 && p.w3 && p.b3, "%s: policy: null operand", who);
   S2P_REQUIRE(p.width >= 128 && p.width <= IM_WMAX && p.width % 128 == 0,
@@ -521,9 +519,6 @@ extern "C" int s2p_imagine_chain_fwd(const float* z0, int z0_pitch, const float*
   S2P_REQUIRE(s2p_al16(p.w1) && s2p_al16(p.w2) && s2p_al16(p.w3), "%s: policy: the weights must be 16-byte aligned", who);
   g.p = p; g.z0 = z0; g.z0_pitch = z0_pitch; g.wc = wc; g.wc_row = wc_row; g.wb = wb; g.wb_row = wb_row; g.A = A; g.act = act;
   g.act_pitch = act_pitch;
-  ChainArgs& a = g.c;
-  a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean; a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z;
-  a.z_pitch = z_pitch; a.B = B; a.T = H;
   hipLaunchKernelGGL(imagine_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, g);
   S2P_CHECK_LAUNCH("imagine_chain_kernel");
   return 0;

@@ -694,19 +694,25 @@ def _chain_views(B, T, *ts):
             raise ValueError("[B, T, C] fp32 views whose rows (b, t) are evenly pitched are needed")
 
 
+def _chain_operands(src, eps, mlps, n_mlps, mean, std, z, terms=(), steps=0, more=()):
+    """What the three chain wrappers share.  Checks eps, mean, std, z and `more` as [B, T, C] views (_chain_views) and the hoisted
+    `terms` as contiguous fp32 [steps*B, 256] (None passes: the entry point says when a term may be absent).  -> the (pointer, pitch)
+    of the 2-D view `src`, the array of `n_mlps` ChainMlp, and the argument tail of all three entry points, mean .. stream."""
+    B, T = eps.shape[:2]
+    _chain_views(B, T, eps, mean, std, z, *more)
+    for r in terms:
+        if r is not None and (not r.is_contiguous() or r.dtype != torch.float32 or r.shape != (steps * B, 256)):
+            raise ValueError("the hoisted terms are contiguous fp32 [%d*B, 256]" % steps)
+    tail = (ptr(mean), mean.stride(1), ptr(std), std.stride(1), ptr(z), z.stride(1), B, T, stream())
+    return _view2(src), (_lib.ChainMlp * n_mlps)(*mlps), tail
+
+
 def prior_chain_fwd(z2_0, rc, rb, eps, mlps, mean, std, z):
     """The whole open-loop prior rollout in one launch (s2p_prior_chain_fwd).  z2_0: a [B, 256] view (a column slice of z(0) is read
     in place); rc, rb [H*B, 256] contiguous, time-major; eps, mean, std, z: [B, H, C] views as for posterior_chain_fwd; mlps: the
     chain_mlp() structs of z1_prior (k1 = 256) and z2_prior."""
-    B, H = eps.shape[:2]
-    _chain_views(B, H, eps, mean, std, z)
-    zp, zs = _view2(z2_0)
-    for r in (rc, rb):
-        if not r.is_contiguous() or r.dtype != torch.float32 or r.shape != (H * B, 256):
-            raise ValueError("rc / rb are contiguous fp32 [H*B, 256]")
-    arr = (_lib.ChainMlp * 2)(*mlps)
-    check(lib().s2p_prior_chain_fwd(zp, zs, ptr(rc), ptr(rb), ptr(eps), eps.stride(1), arr, ptr(mean), mean.stride(1), ptr(std),
-                                    std.stride(1), ptr(z), z.stride(1), B, H, stream()), "s2p_prior_chain_fwd")
+    (zp, zs), arr, tail = _chain_operands(z2_0, eps, mlps, 2, mean, std, z, terms=(rc, rb), steps=eps.shape[1])
+    check(lib().s2p_prior_chain_fwd(zp, zs, ptr(rc), ptr(rb), ptr(eps), eps.stride(1), arr, *tail), "s2p_prior_chain_fwd")
 
 
 def policy_mlp(policy):
@@ -725,28 +731,17 @@ def imagine_chain_fwd(z0, eps, mlps, wc, wb, A, policy, act, mean, std, z):
     """The whole closed-loop rollout in one launch (s2p_imagine_chain_fwd).  z0: a [B, 288] view; eps, act, mean, std, z: [B, H, C]
     views as for posterior_chain_fwd; mlps: the chain_mlp() structs of z1_prior (k1 = 256) and z2_prior; wc, wb: their action
     columns [256][pad4(A)]; policy: a policy_mlp() struct."""
-    B, H = eps.shape[:2]
-    _chain_views(B, H, eps, act, mean, std, z)
-    zp, zs = _view2(z0)
-    arr = (_lib.ChainMlp * 2)(*mlps)
+    (zp, zs), arr, tail = _chain_operands(z0, eps, mlps, 2, mean, std, z, more=(act,))
     check(lib().s2p_imagine_chain_fwd(zp, zs, ptr(eps), eps.stride(1), arr, ptr(wc), wc.shape[1], ptr(wb), wb.shape[1], A,
-                                      ctypes.byref(policy), ptr(act), act.stride(1), ptr(mean), mean.stride(1), ptr(std),
-                                      std.stride(1), ptr(z), z.stride(1), B, H, stream()), "s2p_imagine_chain_fwd")
+                                      ctypes.byref(policy), ptr(act), act.stride(1), *tail), "s2p_imagine_chain_fwd")
 
 
 def posterior_chain_fwd(feat0, ra, rb, eps, mlps, mean, std, z):
     """The whole no-grad posterior chain in one launch (s2p_posterior_chain_fwd).  feat0: the [B, 256] view feat[:, 0]; ra, rb
     [(T-1)*B, 256] contiguous (None when T == 1); eps, mean, std, z: [B, T, C] views with unit stride in C and stride(0) =
     T * stride(1) (a slice of a wider [B, T, W] buffer is written in place); mlps: four chain_mlp() structs."""
-    B, T = eps.shape[:2]
-    _chain_views(B, T, eps, mean, std, z)
-    fp, fs = _view2(feat0)
-    for r in (ra, rb):
-        if r is not None and (not r.is_contiguous() or r.dtype != torch.float32 or r.shape != ((T - 1) * B, 256)):
-            raise ValueError("ra / rb are contiguous fp32 [(T-1)*B, 256]")
-    arr = (_lib.ChainMlp * 4)(*mlps)
-    check(lib().s2p_posterior_chain_fwd(fp, fs, ptr(ra), ptr(rb), ptr(eps), eps.stride(1), arr, ptr(mean), mean.stride(1), ptr(std),
-                                        std.stride(1), ptr(z), z.stride(1), B, T, stream()), "s2p_posterior_chain_fwd")
+    (fp, fs), arr, tail = _chain_operands(feat0, eps, mlps, 4, mean, std, z, terms=(ra, rb), steps=eps.shape[1] - 1)
+    check(lib().s2p_posterior_chain_fwd(fp, fs, ptr(ra), ptr(rb), ptr(eps), eps.stride(1), arr, *tail), "s2p_posterior_chain_fwd")
 
 
 def gauss_head_bwd(raw, D, draw, eps=None, dmean=None, dstd=None, dz=None, dz2=None):

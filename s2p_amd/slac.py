@@ -347,6 +347,20 @@ def _action_term(action, w):
     return x, r
 
 
+def _chain_step(g1, p1, g2, p2, bufa, bufb, add_a, add_b, noise, mean, std, z, t, xz, xz_next):
+    """One step of a latent chain, 8 launches: the z1 head (g1, p1) on xz[:, Z1:] = z2(t-1) plus the row term add_a, then the z2 head
+    (g2, p2) on xz = z1(t) | z2(t-1) plus add_b.  Both read the chain columns of their first layer in place (p["g1"][0]).  Results go
+    to slot t of mean, std [B,T,32] and z [B,T,288] with the eps of noise [B,T,288], z1(t) to xz[:, :Z1] and z2(t) to the z2 columns
+    of the next step's input row xz_next (None: there is no next step).  bufa / bufb: each head's (h1, h2, raw)."""
+    (h1a, h2a, rawa), (h1b, h2b, rawb) = bufa, bufb
+    ops.linear_fwd_into(xz[:, Z1:], p1["g1"][0][0], p1["b1"], HID, h1a, ACT_LRELU, SLOPE, add=add_a)
+    _mlp_tail_fwd(g1, p1, h1a, h2a, rawa)
+    ops.gauss_head_fwd(rawa, Z1, eps=noise[:, t, :Z1], mean=mean[:, t], std=std[:, t], z=z[:, t, :Z1], z2=xz[:, :Z1])
+    ops.linear_fwd_into(xz, p2["g1"][0][0], p2["b1"], HID, h1b, ACT_LRELU, SLOPE, add=add_b)
+    _mlp_tail_fwd(g2, p2, h1b, h2b, rawb)
+    ops.gauss_head_fwd(rawb, Z2, eps=noise[:, t, Z1:], z=z[:, t, Z1:], z2=xz_next[:, Z1:] if xz_next is not None else None)
+
+
 class _GaussFn(torch.autograd.Function):
     """A Gaussian head on rows that are all known up front (z1_prior, reward): x [M, Kpad] -> mean, std [M, D]."""
 
@@ -407,14 +421,9 @@ class _PosteriorFn(torch.autograd.Function):
             h1b, h2b, rawb = _f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g2.Npad), dev)
             for t in range(1, T):
                 s, r = slot(t), slice((t - 1) * B, t * B)
-                # q(z1(t) | feat(t), z2(t-1), a(t-1))
-                ops.linear_fwd_into(xz[s][:, Z1:], p1["g1"][0][0], p1["b1"], HID, h1a[s], ACT_LRELU, SLOPE, add=ra[r])
-                _mlp_tail_fwd(g1, p1, h1a[s], h2a[s], rawa[s])
-                ops.gauss_head_fwd(rawa[s], Z1, eps=noise[:, t, :Z1], mean=mean[:, t], std=std[:, t], z=z[:, t, :Z1], z2=xz[s][:, :Z1])
-                # q(z2(t) | z1(t), z2(t-1), a(t-1))
-                ops.linear_fwd_into(xz[s], p2["g1"][0][0], p2["b1"], HID, h1b[s], ACT_LRELU, SLOPE, add=rb[r])
-                _mlp_tail_fwd(g2, p2, h1b[s], h2b[s], rawb[s])
-                ops.gauss_head_fwd(rawb[s], Z2, eps=noise[:, t, Z1:], z=z[:, t, Z1:], z2=xz[slot(t + 1)][:, Z1:] if t < S else None)
+                # q(z1(t) | feat(t), z2(t-1), a(t-1)), q(z2(t) | z1(t), z2(t-1), a(t-1))
+                _chain_step(g1, p1, g2, p2, (h1a[s], h2a[s], rawa[s]), (h1b[s], h2b[s], rawb[s]), ra[r], rb[r], noise, mean, std, z, t,
+                            xz[s], xz[slot(t + 1)] if t < S else None)
             sv = (xa, xb, h1a, h2a, rawa, h1b, h2b, rawb)
         ctx.model, ctx.packs, ctx.A = model, (pi1, pi2, p1, p2), A
         ctx.saved = (feat, noise, z, xz, a0, b0, sv) if keep else None
@@ -643,6 +652,31 @@ class LatentModel(nn.Module):
         m0, s0 = _f32((B, 1, Z1), self.device, True), torch.ones((B, 1, Z1), dtype=torch.float32, device=self.device)
         return torch.cat([m0, mean.reshape(B, S, Z1)], dim=1), torch.cat([s0, std.reshape(B, S, Z1)], dim=1)
 
+    def _rollout_start(self, z0, H, noise, sample):
+        """What `predict` and `imagine` share before they diverge: z0 [B,288] and the noise [B,H,288] (None: drawn on the device;
+        sample False: zeros) on the device, the outputs (mean, std [B,H,32], z [B,H,288]), and -- None for an empty batch -- the two
+        heads z1_prior / z2_prior, their packs, their action columns wc / wb [256][pad4(A)], and xz [B,288] = z0."""
+        dev, A = self.device, self.action_dim
+        z0 = z0.to(dev, torch.float32)
+        if z0.dim() != 2 or z0.shape[1] != Z1 + Z2 or H < 0:
+            raise ValueError("z0 [B,z1_dim+z2_dim] and a horizon >= 0 are needed")
+        B = z0.shape[0]
+        if not sample:
+            noise = _f32((B, H, Z1 + Z2), dev, True)
+        elif noise is None:
+            noise = torch.randn((B, H, Z1 + Z2), dtype=torch.float32, device=dev)
+        noise = noise.to(dev, torch.float32).contiguous()
+        if noise.shape != (B, H, Z1 + Z2):
+            raise ValueError("noise is [B,H,z1_dim+z2_dim]")
+        out = _f32((B, H, Z1), dev), _f32((B, H, Z1), dev), _f32((B, H, Z1 + Z2), dev)
+        if B == 0 or H == 0:
+            return noise, out, None
+        g1, g2 = self.z1_prior, self.z2_prior
+        p1, p2 = g1.packed(), g2.packed()
+        # xz = z1(h) | z2(h-1), the input row of both first layers: the per-layer path writes it, the fused one reads z(0) from it
+        xz = _f32((B, Z1 + Z2), dev).copy_(z0)
+        return noise, out, (g1, g2, p1, p2, g1.packed_cols(Z2, Z2 + A), p2["g1"][1][0], xz)
+
     @torch.no_grad()
     def predict(self, z0, actions_, noise=None, sample=True):
         """Open-loop rollout of the generative model (SPEC.md N3i): z0 [B,288] = z1(0) | z2(0), actions_ [B,H,A] = a(0..H-1), noise
@@ -651,43 +685,23 @@ class LatentModel(nn.Module):
         their own samples; z1(0) is not read.  Always without grad.  Both first layers are (chain columns + hoisted action term) +
         bias, so H = 1 equals sample_prior within rounding, not bitwise.  With `fused_chain` the H steps are one launch
         (s2p_prior_chain_fwd), else 8 per step; the two are bitwise equal."""
-        dev = self.device
-        z0 = z0.to(dev, torch.float32)
-        actions_ = actions_.to(dev, torch.float32).contiguous()
-        if z0.dim() != 2 or z0.shape[1] != Z1 + Z2 or actions_.dim() != 3 or actions_.shape[0] != z0.shape[0] or \
-                actions_.shape[2] != self.action_dim:
+        actions_ = actions_.to(self.device, torch.float32).contiguous()
+        if actions_.dim() != 3 or actions_.shape[:1] != z0.shape[:1] or actions_.shape[2] != self.action_dim:
             raise ValueError("z0 [B,z1_dim+z2_dim] and actions_ [B,H,A] are needed")
         B, H, A = actions_.shape
-        if not sample:
-            noise = _f32((B, H, Z1 + Z2), dev, True)
-        elif noise is None:
-            noise = torch.randn((B, H, Z1 + Z2), dtype=torch.float32, device=dev)
-        noise = noise.to(dev, torch.float32).contiguous()
-        if noise.shape != (B, H, Z1 + Z2):
-            raise ValueError("noise is [B,H,z1_dim+z2_dim]")
-        mean, std, z = _f32((B, H, Z1), dev), _f32((B, H, Z1), dev), _f32((B, H, Z1 + Z2), dev)
-        if B == 0 or H == 0:
+        noise, (mean, std, z), st = self._rollout_start(z0, H, noise, sample)
+        if st is None:
             return mean, std, z
-        g1, g2 = self.z1_prior, self.z2_prior
-        p1, p2 = g1.packed(), g2.packed()
-        rc = _action_term(actions_, g1.packed_cols(Z2, Z2 + A))[1]
-        rb = _action_term(actions_, p2["g1"][1][0])[1]
-        w1a, w1b = p1["g1"][0][0], p2["g1"][0][0]              # [256][pad4(256 + A)]: the z2 columns are read in place; [256][288]
-        # xz = z1(h) | z2(h-1), the input row of both first layers: the per-layer path writes it, the fused one reads z2(0) from it
-        xz = _f32((B, Z1 + Z2), dev).copy_(z0)
+        g1, g2, p1, p2, wc, wb, xz = st
+        rc, rb = _action_term(actions_, wc)[1], _action_term(actions_, wb)[1]
         if self.fused_chain:
             ops.prior_chain_fwd(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], mean, std, z)
             return mean, std, z
-        h1, h2 = _f32((B, HID), dev), _f32((B, HID), dev)
-        rawa, rawb = _f32((B, g1.Npad), dev), _f32((B, g2.Npad), dev)
+        h1, h2 = _f32((B, HID), self.device), _f32((B, HID), self.device)
+        bufa, bufb = (h1, h2, _f32((B, g1.Npad), self.device)), (h1, h2, _f32((B, g2.Npad), self.device))
         for s in range(H):
             r = slice(s * B, (s + 1) * B)
-            ops.linear_fwd_into(xz[:, Z1:], w1a, p1["b1"], HID, h1, ACT_LRELU, SLOPE, add=rc[r])
-            _mlp_tail_fwd(g1, p1, h1, h2, rawa)
-            ops.gauss_head_fwd(rawa, Z1, eps=noise[:, s, :Z1], mean=mean[:, s], std=std[:, s], z=z[:, s, :Z1], z2=xz[:, :Z1])
-            ops.linear_fwd_into(xz, w1b, p2["b1"], HID, h1, ACT_LRELU, SLOPE, add=rb[r])
-            _mlp_tail_fwd(g2, p2, h1, h2, rawb)
-            ops.gauss_head_fwd(rawb, Z2, eps=noise[:, s, Z1:], z=z[:, s, Z1:], z2=xz[:, Z1:])
+            _chain_step(g1, p1, g2, p2, bufa, bufb, rc[r], rb[r], noise, mean, std, z, s, xz, xz)
         return mean, std, z
 
     @torch.no_grad()
@@ -699,32 +713,17 @@ class LatentModel(nn.Module):
         outside its built shapes), else 13 per step; the two are bitwise equal, and `predict(z0, actions, noise)` returns bitwise
         this z1_mean, z1_std and z."""
         dev, A, H = self.device, self.action_dim, int(horizon)
-        z0 = z0.to(dev, torch.float32)
-        if z0.dim() != 2 or z0.shape[1] != Z1 + Z2 or H < 0:
-            raise ValueError("z0 [B,z1_dim+z2_dim] and horizon >= 0 are needed")
         hs = getattr(policy, "hidden_sizes", None)
         if getattr(policy, "obs_dim", None) != Z1 + Z2 or getattr(policy, "action_dim", None) != A or hs is None or len(hs) != 2:
             raise ValueError("a TanhGaussianPolicy with obs_dim %d, action_dim %d and two hidden layers is needed" % (Z1 + Z2, A))
         if policy.device is None or policy.device.type != dev.type:
             raise ValueError("the policy and the latent model share a HIP device")
-        B = z0.shape[0]
-        if not sample:
-            noise = _f32((B, H, Z1 + Z2), dev, True)
-        elif noise is None:
-            noise = torch.randn((B, H, Z1 + Z2), dtype=torch.float32, device=dev)
-        noise = noise.to(dev, torch.float32).contiguous()
-        if noise.shape != (B, H, Z1 + Z2):
-            raise ValueError("noise is [B,H,z1_dim+z2_dim]")
-        Ap = pad_to(A, 4)
-        act = _f32((B, H, Ap), dev, True)
-        mean, std, z = _f32((B, H, Z1), dev), _f32((B, H, Z1), dev), _f32((B, H, Z1 + Z2), dev)
-        if B == 0 or H == 0:
+        noise, (mean, std, z), st = self._rollout_start(z0, H, noise, sample)
+        B = z.shape[0]
+        act = _f32((B, H, pad_to(A, 4)), dev, True)
+        if st is None:
             return act[..., :A], mean, std, z
-        g1, g2 = self.z1_prior, self.z2_prior
-        p1, p2 = g1.packed(), g2.packed()
-        wc, wb = g1.packed_cols(Z2, Z2 + A), p2["g1"][1][0]
-        w1a, w1b = p1["g1"][0][0], p2["g1"][0][0]
-        xz = _f32((B, Z1 + Z2), dev).copy_(z0)
+        g1, g2, p1, p2, wc, wb, xz = st
         if self.fused_chain:
             ops.imagine_chain_fwd(xz, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], wc, wb, A, ops.policy_mlp(policy), act,
                                   mean, std, z)
@@ -734,7 +733,7 @@ class LatentModel(nn.Module):
         q1, q2 = _f32((B, hs[0]), dev), _f32((B, hs[1]), dev)
         rc, rb = _f32((B, HID), dev), _f32((B, HID), dev)
         h1, h2 = _f32((B, HID), dev), _f32((B, HID), dev)
-        rawa, rawb = _f32((B, g1.Npad), dev), _f32((B, g2.Npad), dev)
+        bufa, bufb = (h1, h2, _f32((B, g1.Npad), dev)), (h1, h2, _f32((B, g2.Npad), dev))
         for s in range(H):
             a = act[:, s]                                                                # [B, pad4(A)] view, pitch H * pad4(A)
             ops.linear_fwd_into(xz, pw[0], pb[0], hs[0], q1, ACT_RELU)
@@ -742,12 +741,7 @@ class LatentModel(nn.Module):
             ops.linear_fwd_into(q2, pw[2], pb[2], A, a, ACT_TANH)
             ops.linear_fwd_into(a, wc, None, HID, rc)
             ops.linear_fwd_into(a, wb, None, HID, rb)
-            ops.linear_fwd_into(xz[:, Z1:], w1a, p1["b1"], HID, h1, ACT_LRELU, SLOPE, add=rc)
-            _mlp_tail_fwd(g1, p1, h1, h2, rawa)
-            ops.gauss_head_fwd(rawa, Z1, eps=noise[:, s, :Z1], mean=mean[:, s], std=std[:, s], z=z[:, s, :Z1], z2=xz[:, :Z1])
-            ops.linear_fwd_into(xz, w1b, p2["b1"], HID, h1, ACT_LRELU, SLOPE, add=rb)
-            _mlp_tail_fwd(g2, p2, h1, h2, rawb)
-            ops.gauss_head_fwd(rawb, Z2, eps=noise[:, s, Z1:], z=z[:, s, Z1:], z2=xz[:, Z1:])
+            _chain_step(g1, p1, g2, p2, bufa, bufb, rc, rb, noise, mean, std, z, s, xz, xz)
         return act[..., :A], mean, std, z
 
     def predict_reward(self, z0, z, actions_):

@@ -5,7 +5,7 @@ reward sum beside the model's.  The `latent_z` policy input only: the policy rea
 import numpy as np
 import torch
 
-from .slac import Z1, Z2
+from .slac_predict import filter_context, gather
 
 
 def discounted(rewards, discount):
@@ -13,23 +13,6 @@ def discounted(rewards, discount):
     r = torch.as_tensor(rewards).to(torch.float64)
     g = float(discount) ** torch.arange(r.shape[1], dtype=torch.float64, device=r.device)
     return (r * g).sum(dim=1)
-
-
-def _start(latent, frames_u8_nhwc, actions, context, sample, posterior_noise):
-    """Encoder + sample_posterior on the first `context` + 1 frames and `context` actions, as `slac_predict.open_loop`: z(context)."""
-    dev = latent.device
-    frames = torch.as_tensor(frames_u8_nhwc)
-    actions = torch.as_tensor(actions).to(dev, torch.float32)
-    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
-        raise ValueError("frames_u8_nhwc is uint8 [B,C+1,H,W,3]")
-    B = frames.shape[0]
-    if context < 1 or frames.shape[1] < context + 1 or actions.dim() != 3 or actions.shape[0] != B or actions.shape[1] < context:
-        raise ValueError("frames [B,>=context+1,...] and actions [B,>=context,A] with context >= 1 are needed")
-    feat = latent.encoder(frames[:, :context + 1].to(dev))
-    if posterior_noise is None and not sample:
-        posterior_noise = torch.zeros((B, context + 1, Z1 + Z2), dtype=torch.float32, device=dev)
-    _, _, z1, z2 = latent.sample_posterior(feat, actions[:, :context], posterior_noise)
-    return torch.cat([z1[:, -1], z2[:, -1]], dim=-1), actions
 
 
 @torch.no_grad()
@@ -43,7 +26,7 @@ def imagined_returns(latent, policy, frames_u8_nhwc, actions, horizon, discount=
     H = int(horizon)
     if H < 1:
         raise ValueError("horizon >= 1")
-    z0, _ = _start(latent, frames_u8_nhwc, actions, int(context), sample, posterior_noise)
+    z0, _ = filter_context(latent, frames_u8_nhwc, actions, int(context), sample, posterior_noise)
     act, z1_mean, z1_std, z = latent.imagine(policy, z0, H, noise, sample)
     r_mean, r_std = latent.predict_reward(z0, z, act)
     out = dict(z0=z0, actions=act, z=z, z1_mean=z1_mean, z1_std=z1_std, reward_mean=r_mean, reward_std=r_std,
@@ -61,12 +44,11 @@ def behaviour(latent, data, starts, context, horizon, discount=0.99, noise=None,
     states z(context) rolled under the dataset's recorded next `horizon` actions through `predict`.  -> dict: z0, actions [n,H,A]
     (the recorded ones), z, reward_mean, reward_std, returns fp64 [n] (the model's, under those actions) and data_returns fp64 [n] =
     sum_h discount^h rewards[start + context + h], the dataset's own."""
-    from .slac_predict import gather
     context, H = int(context), int(horizon)
     if H < 1:
         raise ValueError("horizon >= 1")
     frames, actions, rewards = gather(data, starts, context + H)
-    z0, actions = _start(latent, frames, actions, context, sample, posterior_noise)
+    z0, actions = filter_context(latent, frames, actions, context, sample, posterior_noise)
     future = actions[:, context:].contiguous()
     _, _, z = latent.predict(z0, future, noise, sample)
     r_mean, r_std = latent.predict_reward(z0, z, future)

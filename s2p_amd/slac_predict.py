@@ -55,30 +55,42 @@ def _nchw01(u8):
     return (x.float() / 255.0).contiguous()
 
 
-@torch.no_grad()
-def open_loop(latent, frames_u8_nhwc, actions, rewards=None, context=8, noise=None, sample=True, posterior_noise=None):
-    """frames_u8_nhwc [B,L+1,100,100,3], actions [B,L,A], rewards [B,L] or None.  The encoder and `sample_posterior` see the first
-    `context` + 1 frames and `context` actions; z0 = z(context); `predict(z0, actions[:, context:], noise, sample)` rolls the
-    H = L - `context` remaining steps; the decoder's mean, clamped to [0, 1], is the predicted frame.  -> dict of device tensors:
-    z0 [B,288], z1_mean, z1_std [B,H,32], z [B,H,288], frames [B,H,3,100,100], psnr, ssim [B,H] of the prediction and
-    baseline_psnr, baseline_ssim [B,H] of repeating the last context frame (data_range 1; PSNR of identical frames is +inf),
-    reward_mean, reward_std [B,H], and with `rewards` reward_abs_err [B,H].  `posterior_noise` [B,context+1,288] fixes the
-    filtering pass (None: drawn, or zeros when `sample` is False, so that a mean rollout is a function of its inputs alone)."""
+def filter_context(latent, frames_u8_nhwc, actions, context, sample, posterior_noise):
+    """The filtering pass before a rollout: the encoder and `sample_posterior` see the first `context` + 1 frames and `context`
+    actions (longer ones are cut).  `posterior_noise` [B,context+1,288] fixes the pass (None: drawn, or zeros when `sample` is False,
+    so that a mean rollout is a function of its inputs alone).  -> z0 = z(context) [B,288] and the actions on the device."""
     dev = latent.device
     frames = torch.as_tensor(frames_u8_nhwc)
     actions = torch.as_tensor(actions).to(dev, torch.float32)
     if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
         raise ValueError("frames_u8_nhwc is uint8 [B,L+1,H,W,3]")
-    B, L = frames.shape[0], frames.shape[1] - 1
-    H = L - context
-    if context < 1 or H < 1 or actions.dim() != 3 or actions.shape[:2] != (B, L):
-        raise ValueError("frames [B,L+1,...] and actions [B,L,A] with L > context >= 1 are needed")
-    frames = frames.to(dev)
-    feat = latent.encoder(frames[:, :context + 1])
+    B = frames.shape[0]
+    if context < 1 or frames.shape[1] < context + 1 or actions.dim() != 3 or actions.shape[0] != B or actions.shape[1] < context:
+        raise ValueError("frames [B,>=context+1,...] and actions [B,>=context,A] with context >= 1 are needed")
+    feat = latent.encoder(frames[:, :context + 1].to(dev))
     if posterior_noise is None and not sample:
         posterior_noise = torch.zeros((B, context + 1, Z1 + Z2), dtype=torch.float32, device=dev)
     _, _, z1, z2 = latent.sample_posterior(feat, actions[:, :context], posterior_noise)
-    z0 = torch.cat([z1[:, -1], z2[:, -1]], dim=-1)
+    return torch.cat([z1[:, -1], z2[:, -1]], dim=-1), actions
+
+
+@torch.no_grad()
+def open_loop(latent, frames_u8_nhwc, actions, rewards=None, context=8, noise=None, sample=True, posterior_noise=None):
+    """frames_u8_nhwc [B,L+1,100,100,3], actions [B,L,A], rewards [B,L] or None.  z0 = z(context) of `filter_context` (which takes
+    `posterior_noise`); `predict(z0, actions[:, context:], noise, sample)` rolls the H = L - `context` remaining steps; the
+    decoder's mean, clamped to [0, 1], is the predicted frame.  -> dict of device tensors:
+    z0 [B,288], z1_mean, z1_std [B,H,32], z [B,H,288], frames [B,H,3,100,100], psnr, ssim [B,H] of the prediction and
+    baseline_psnr, baseline_ssim [B,H] of repeating the last context frame (data_range 1; PSNR of identical frames is +inf),
+    reward_mean, reward_std [B,H], and with `rewards` reward_abs_err [B,H]."""
+    dev = latent.device
+    frames, actions = torch.as_tensor(frames_u8_nhwc), torch.as_tensor(actions)
+    if frames.dim() != 5 or actions.dim() != 3 or actions.shape[:2] != (frames.shape[0], frames.shape[1] - 1) or \
+            frames.shape[1] - 1 <= context:
+        raise ValueError("frames [B,L+1,...] and actions [B,L,A] with L > context >= 1 are needed")
+    frames = frames.to(dev)
+    z0, actions = filter_context(latent, frames, actions, context, sample, posterior_noise)
+    B, L = actions.shape[:2]
+    H = L - context
     future = actions[:, context:].contiguous()
     z1_mean, z1_std, z = latent.predict(z0, future, noise, sample)
     pred = latent.decoder(z)[0].clamp_(0.0, 1.0)

@@ -18,6 +18,7 @@ import slac_buffer_ref as SB
 import slac_imagine_ref as IR
 import slac_latent_ref as R
 from guard_region import Region
+from slac_chain_util import build_model, count_calls, model_cache
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -26,13 +27,6 @@ Z1, Z2, Z = 32, 256, 288
 BS, HS, AS, WS = (1, 15, 16, 17, 33), (1, 2, 5), (6, 1), (128, 256)
 NAME = "s2p_imagine_chain_fwd"
 OUT = ("actions", "mean", "std", "z")
-
-
-def _build(A, dtype=torch.float32):
-    from s2p_amd.slac import LatentModel
-    m = LatentModel((3, 100, 100), (A,), image_size=100, dtype=dtype)
-    m.load_state_dict(R.full_state_dict(R.make_params(A)), strict=True)
-    return m
 
 
 def _make_policy(W, A, sd=None):
@@ -44,13 +38,7 @@ def _make_policy(W, A, sd=None):
 @pytest.fixture(scope="module")
 def models(hip_device):
     """action width -> a LatentModel with the seeded weights of tests/slac_latent_ref.py; built once, left with fused_chain False."""
-    cache = {}
-
-    def get(A):
-        if A not in cache:
-            cache[A] = _build(A)
-        return cache[A]
-    return get
+    return model_cache()
 
 
 @pytest.fixture(scope="module")
@@ -94,26 +82,6 @@ def _predict(m, fused, z0, actions, noise):
         return [t.clone() for t in out]
     finally:
         m.fused_chain = False
-
-
-def _count(fn):
-    """C-ABI calls per entry point during fn()."""
-    from s2p_amd import _lib
-    L, counts, orig = _lib.lib(), {}, {}
-    for name in _lib.SIGNATURES:
-        f = getattr(L, name)
-        orig[name] = f
-
-        def wrap(*a, _f=f, _n=name):
-            counts[_n] = counts.get(_n, 0) + 1
-            return _f(*a)
-        setattr(L, name, wrap)
-    try:
-        fn()
-    finally:
-        for name, f in orig.items():
-            setattr(L, name, f)
-    return counts
 
 
 def _widths(A):
@@ -366,7 +334,7 @@ def test_q_min(hip_device, golden):
     z, a = torch.randn(33, Z, generator=g), torch.rand(33, IR.A, generator=g) * 2 - 1
     qs = [{k: v.double() for k, v in IR.make_q_params(i).items()} for i in range(2)]
     want = IR.q_min(qs, z.double(), a.double())
-    counts = _count(lambda: critic.q_min(z.cuda(), a.cuda()))
+    counts = count_calls(lambda: critic.q_min(z.cuda(), a.cuda()))
     got = critic.q_min(z.cuda(), a.cuda()).clone()
     ref = max(float(max(golden["%s.bootstrap.ref32_err" % r] for r in IR.ROLLOUTS)), FLOOR)
     err = R.rel_max(got, want)
@@ -384,7 +352,7 @@ def test_call_counts(models, policies):
     m, po = models(6), policies(256, 6)
     z0, noise = _inputs(17, 5)
     _imagine(m, po, False, z0, noise)                                         # (packs are built on first use)
-    per_layer, fused = _count(lambda: _imagine(m, po, False, z0, noise)), _count(lambda: _imagine(m, po, True, z0, noise))
+    per_layer, fused = count_calls(lambda: _imagine(m, po, False, z0, noise)), count_calls(lambda: _imagine(m, po, True, z0, noise))
     print("library calls, per-layer:", per_layer, " fused:", fused)
     assert fused == {NAME: 1}
     assert per_layer == {"s2p_linear_fwd": 9 * 5, "s2p_linear_add_fwd": 2 * 5, "s2p_gauss_head_fwd": 2 * 5}
@@ -461,7 +429,7 @@ def test_imagined_returns_bf16_stacks(models, policies, real_windows):
     of the bf16 encoder (1e-1, R.rel_max) of the fp32 model's."""
     po = policies(256, SB.A)
     ref = _returns(models(SB.A), po, None, real_windows, True)
-    got = _returns(_build(SB.A, torch.bfloat16), po, None, real_windows, True)
+    got = _returns(build_model(SB.A, torch.bfloat16), po, None, real_windows, True)
     assert all(bool(torch.isfinite(v).all()) for v in got.values())
     err = R.rel_max(got["z"], ref["z"])
     print("bf16 stacks: z deviates from the fp32 model's by %.3e" % err)

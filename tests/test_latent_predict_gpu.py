@@ -19,6 +19,7 @@ import slac_buffer_ref as SB
 import slac_latent_ref as R
 import slac_predict_ref as PR
 from guard_region import Region
+from slac_chain_util import build_model, count_calls, model_cache
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -30,23 +31,10 @@ LN2 = 0.6931472
 OUT = ("mean", "std", "z")
 
 
-def _build(A, dtype=torch.float32):
-    from s2p_amd.slac import LatentModel
-    m = LatentModel((3, 100, 100), (A,), image_size=100, dtype=dtype)
-    m.load_state_dict(R.full_state_dict(R.make_params(A)), strict=True)
-    return m
-
-
 @pytest.fixture(scope="module")
 def models(hip_device):
     """action width -> a LatentModel with the seeded weights of tests/slac_latent_ref.py; built once, left with fused_chain False."""
-    cache = {}
-
-    def get(A):
-        if A not in cache:
-            cache[A] = _build(A)
-        return cache[A]
-    return get
+    return model_cache()
 
 
 @pytest.fixture(scope="module")
@@ -68,26 +56,6 @@ def _predict(m, fused, z0, actions, noise=None, sample=True):
         return [t.clone() for t in out]
     finally:
         m.fused_chain = False
-
-
-def _count(fn):
-    """C-ABI calls per entry point during fn()."""
-    from s2p_amd import _lib
-    L, counts, orig = _lib.lib(), {}, {}
-    for name in _lib.SIGNATURES:
-        f = getattr(L, name)
-        orig[name] = f
-
-        def wrap(*a, _f=f, _n=name):
-            counts[_n] = counts.get(_n, 0) + 1
-            return _f(*a)
-        setattr(L, name, wrap)
-    try:
-        fn()
-    finally:
-        for name, f in orig.items():
-            setattr(L, name, f)
-    return counts
 
 
 # ---- 1. bitwise against the per-layer path -------------------------------------------------------------------------------------------
@@ -212,7 +180,7 @@ def test_both_softplus_branches(hip_device, bias, head, D):
     1e-5 floor.  z1_prior's std is an output; z2_prior's shows in z2 = mean + eps * std, so eps = 1 against eps = 0 at the first
     step (the same mean in both runs).  softplus(0) = ln 2 separates the branches."""
     A, B, H = 6, 17, 2
-    m = _build(A)
+    m = build_model(A)
     with torch.no_grad():
         getattr(m, head).net._modules["4"].bias[D:] = bias
     z0, actions, noise = _inputs(B, H, A)
@@ -295,7 +263,7 @@ def test_pinned_parity(models, golden, capsys):
 def test_call_counts(models):
     m = models(6)
     args = _inputs(17, 9, 6)
-    per_layer, fused = _count(lambda: _predict(m, False, *args)), _count(lambda: _predict(m, True, *args))
+    per_layer, fused = count_calls(lambda: _predict(m, False, *args)), count_calls(lambda: _predict(m, True, *args))
     print("library calls, per-layer:", per_layer, " fused:", fused)
     assert fused == {NAME: 1, "s2p_linear_fwd": 2}
     assert per_layer == {"s2p_linear_add_fwd": 18, "s2p_gauss_head_fwd": 18, "s2p_linear_fwd": 2 + 36}
@@ -380,7 +348,7 @@ def test_open_loop_bf16_stacks(models, real_windows):
     _, frames, actions, rewards = real_windows
     pn, n = _noises(frames.shape[0])
     ref = open_loop(models(SB.A), frames, actions, rewards, context=CONTEXT, noise=n, posterior_noise=pn)
-    got = open_loop(_build(SB.A, torch.bfloat16), frames, actions, rewards, context=CONTEXT, noise=n, posterior_noise=pn)
+    got = open_loop(build_model(SB.A, torch.bfloat16), frames, actions, rewards, context=CONTEXT, noise=n, posterior_noise=pn)
     torch.cuda.synchronize()
     assert all(bool(torch.isfinite(v).all()) for k, v in got.items() if k != "baseline_psnr")
     err = R.rel_max(got["z"], ref["z"])

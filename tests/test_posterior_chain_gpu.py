@@ -16,6 +16,7 @@ import iql_ref as IR
 import slac_buffer_ref as SB
 import slac_latent_ref as R
 from guard_region import Region
+from slac_chain_util import count_calls, model_cache
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -29,16 +30,7 @@ LN2 = 0.6931472
 @pytest.fixture(scope="module")
 def models(hip_device):
     """action width -> a LatentModel with the seeded weights of tests/slac_latent_ref.py; built once, left with fused_chain False."""
-    from s2p_amd.slac import LatentModel
-    cache = {}
-
-    def get(A):
-        if A not in cache:
-            m = LatentModel((3, 100, 100), (A,), image_size=100)
-            m.load_state_dict(R.full_state_dict(R.make_params(A)), strict=True)
-            cache[A] = m
-        return cache[A]
-    return get
+    return model_cache()
 
 
 def _inputs(B, T, A, seed=0):
@@ -57,26 +49,6 @@ def _posterior(m, fused, feat, action, noise):
         return [t.clone() for t in out]
     finally:
         m.fused_chain = False
-
-
-def _count(fn):
-    """C-ABI calls per entry point during fn() (tests/tools/bench_slac_latent.py: count_launches)."""
-    from s2p_amd import _lib
-    L, counts, orig = _lib.lib(), {}, {}
-    for name in _lib.SIGNATURES:
-        f = getattr(L, name)
-        orig[name] = f
-
-        def wrap(*a, _f=f, _n=name):
-            counts[_n] = counts.get(_n, 0) + 1
-            return _f(*a)
-        setattr(L, name, wrap)
-    try:
-        fn()
-    finally:
-        for name, f in orig.items():
-            setattr(L, name, f)
-    return counts
 
 
 # ---- 1. bitwise against the unfused path -------------------------------------------------------------------------------------------
@@ -230,7 +202,7 @@ def test_grad_mode_runs_the_per_layer_path(models):
                 z = m.sample_posterior(m.encoder(state), action, noise)[3]
                 assert z.grad_fn is not None and m.chain_state_bytes > 0
                 sum(m.calculate_loss(state, action, reward, done, noise)).backward()
-            calls[fused] = _count(step)
+            calls[fused] = count_calls(step)
             torch.cuda.synchronize()
             named = dict(m.named_parameters())
             grads[fused] = {k: named[k].grad.clone() for k in heads}
@@ -245,7 +217,7 @@ def test_grad_mode_runs_the_per_layer_path(models):
 def test_one_chain_call_replaces_the_per_layer_calls(models):
     m = models(6)
     args = _inputs(17, 9, 6)
-    unfused, fused = _count(lambda: _posterior(m, False, *args)), _count(lambda: _posterior(m, True, *args))
+    unfused, fused = count_calls(lambda: _posterior(m, False, *args)), count_calls(lambda: _posterior(m, True, *args))
     print("library calls, unfused:", unfused, " fused:", fused)
     assert fused.get(NAME) == 1 and NAME not in unfused
     assert "s2p_linear_add_fwd" not in fused and "s2p_gauss_head_fwd" not in fused and fused.get("s2p_linear_fwd", 0) <= 2
@@ -288,7 +260,7 @@ def test_prepare_batch_and_an_iql_step(hip_device, algo, form):
             _fused(algo, on)
             batch = buf.random_batch(len(IDXES), idxes=IDXES, frames=form)
             assert isinstance(batch["observations"], FeatureBatch if form == "features" else FrameBatch)
-            calls[on] = _count(lambda: outs.__setitem__(on, [t.clone() for t in algo.prepare_batch(batch["observations"], batch["actions"], noise)]))
+            calls[on] = count_calls(lambda: outs.__setitem__(on, [t.clone() for t in algo.prepare_batch(batch["observations"], batch["actions"], noise)]))
             q = [Qfunction(hidden_sizes=[64, 64], output_size=1, input_size=Z + A8) for _ in range(4)]
             critic = CriticSLAC(q[0], q[1], q[2], q[3], vf=Vfunction(hidden_sizes=[64, 64], output_size=1, input_size=Z), device=hip_device)
             policy = TanhGaussianPolicy(hidden_sizes=[64, 64], obs_dim=P, action_dim=A8, device=hip_device)
@@ -328,7 +300,7 @@ def test_latent_z_actor_on_a_replayed_environment(hip_device, algo):
                     out.append(a.copy())
                     actor.observe(np.stack([e.step(a[k])[0] for k, e in enumerate(envs)]), a)
                 acts[on] = np.stack(out)
-            calls[on] = _count(run)
+            calls[on] = count_calls(run)
     finally:
         _fused(algo, False)
     assert calls[True].get(NAME) == 3 and NAME not in calls[False]

@@ -20,8 +20,9 @@ for p in ("", "tests", os.path.join("tests", "tools")):
     sys.path.insert(0, os.path.join(ROOT, p))
 import bench_actor  # noqa: E402
 from bench_feature_cache import out, timed  # noqa: E402
-from bench_posterior_chain import CU_FP32_MFMA_FLOPS_PER_CYCLE, MACS_PER_ROW_STEP, both, count_calls, report  # noqa: E402
+from bench_posterior_chain import CU_FP32_MFMA_FLOPS_PER_CYCLE, MACS_PER_ROW_STEP, both, report  # noqa: E402
 from s2p_amd import ops  # noqa: E402
+from slac_chain_util import count_calls  # noqa: E402
 from s2p_amd.slac import LatentModel, _action_term  # noqa: E402
 from s2p_amd.slac_predict import open_loop  # noqa: E402
 

@@ -26,7 +26,8 @@ import bench_actor  # noqa: E402
 import bench_cql  # noqa: E402
 import bench_iql  # noqa: E402
 from bench_feature_cache import datasets, out, timed  # noqa: E402
-from s2p_amd import _lib, ops  # noqa: E402
+from s2p_amd import ops  # noqa: E402
+from slac_chain_util import count_calls  # noqa: E402
 from s2p_amd.actor import SlacActor  # noqa: E402
 from s2p_amd.offline_rl import TanhGaussianPolicy  # noqa: E402
 from s2p_amd.slac import _PosteriorFn  # noqa: E402
@@ -36,24 +37,6 @@ S, A, H, W, C, B, FEAT, Z = 8, 6, 100, 100, 3, 256, 256, 288
 MACS_PER_ROW = (256 * 256 + 256 * 256 + 256 * 64) + (32 * 256 + 256 * 256 + 256 * 512)            # t = 0
 MACS_PER_ROW_STEP = (256 * 256 + 256 * 256 + 256 * 64) + (288 * 256 + 256 * 256 + 256 * 512)      # t >= 1
 CU_FP32_MFMA_FLOPS_PER_CYCLE = 256                                                                # 4 SIMDs x v_mfma_f32_16x16x4_f32
-
-
-def count_calls(fn):
-    L, counts, orig = _lib.lib(), {}, {}
-    for name in _lib.SIGNATURES:
-        f = getattr(L, name)
-        orig[name] = f
-
-        def wrap(*a, _f=f, _n=name):
-            counts[_n] = counts.get(_n, 0) + 1
-            return _f(*a)
-        setattr(L, name, wrap)
-    try:
-        fn()
-    finally:
-        for name, f in orig.items():
-            setattr(L, name, f)
-    return counts
 
 
 def both(latent, make):

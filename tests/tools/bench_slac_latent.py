@@ -8,7 +8,7 @@ R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in ("", "oracle", "tests"): sys.path.insert(0, os.path.join(R, p))
 import torch
 import slac_latent_ref as REF
-from s2p_amd import _lib, ops
+from slac_chain_util import count_calls
 from s2p_amd.slac import LatentModel
 
 B, S, A = 32, 8, 6
@@ -23,22 +23,6 @@ def timed(fn):
         for _ in range(ITERS): fn()
         torch.cuda.synchronize(); out.append((time.perf_counter() - t) / ITERS * 1e3)
     return statistics.median(out), min(out), max(out)
-
-
-def count_launches(fn):
-    """C-ABI calls per call of fn (every one of these entry points is one launch at these sizes, except s2p_linear_add_bwd /
-    s2p_linear_bwd with both a weight gradient and a dgrad: two)."""
-    L, counts, orig = _lib.lib(), {}, {}
-    for name in _lib.SIGNATURES:
-        f = getattr(L, name); orig[name] = f
-        def wrap(*a, _f=f, _n=name):
-            counts[_n] = counts.get(_n, 0) + 1
-            return _f(*a)
-        setattr(L, name, wrap)
-    try: fn()
-    finally:
-        for name, f in orig.items(): setattr(L, name, f)
-    return counts
 
 
 g = torch.Generator().manual_seed(0)
@@ -66,15 +50,15 @@ for dt in (torch.float32, torch.bfloat16):
     print("%-8s calculate_loss + backward + Adam.step:              %.3f ms [%.3f, %.3f]" % ((name,) + timed(train)))
     if dt == torch.float32:
         feat = m.encoder(frames).detach()
-        c1 = count_launches(lambda: m.sample_posterior(feat, action))
+        c1 = count_calls(lambda: m.sample_posterior(feat, action))
         m2 = LatentModel((3, 100, 100), (A,), image_size=100, dtype=dt); m2.load_state_dict(REF.full_state_dict(params))
         f2 = torch.cat([feat, feat[:, -1:]], dim=1); a2 = torch.cat([action, action[:, -1:]], dim=1)
-        c2 = count_launches(lambda: m2.sample_posterior(f2, a2))
+        c2 = count_calls(lambda: m2.sample_posterior(f2, a2))
         print("chain launches per time step, forward: %d (C-ABI calls at S=9 minus S=8)" % (sum(c2.values()) - sum(c1.values())))
         z = m.sample_posterior(feat.requires_grad_(True), action)
-        cb1 = count_launches(lambda: (z[2].sum() + z[3].sum() + z[0].sum()).backward())
+        cb1 = count_calls(lambda: (z[2].sum() + z[3].sum() + z[0].sum()).backward())
         z = m2.sample_posterior(f2.requires_grad_(True), a2)
-        cb2 = count_launches(lambda: (z[2].sum() + z[3].sum() + z[0].sum()).backward())
+        cb2 = count_calls(lambda: (z[2].sum() + z[3].sum() + z[0].sum()).backward())
         print("chain launches per time step, backward: %d" % (sum(cb2.values()) - sum(cb1.values())))
 
 # yardstick: the same model in plain torch ops on the same GPU
