@@ -373,6 +373,36 @@ typedef struct {
 int s2p_imagine_chain_fwd(const float* z0, int z0_pitch, const float* eps, int eps_pitch, const s2p_chain_mlp* mlps, const float* wc,
                           int wc_row, const float* wb, int wb_row, int A, const s2p_policy_mlp* policy, float* act, int act_pitch,
                           float* mean, int mean_pitch, float* std, int std_pitch, float* z, int z_pitch, int B, int H, void* stream);
+/* The posterior chain under grad (SPEC.md N3k): s2p_posterior_chain_fwd that also stores what the backward reads, and the
+ * sequential part of that backward, ONE launch each, one workgroup per 16 batch rows.  Both are BITWISE the per-layer path.
+ * s2p_chain_state: the activations of the chain for B rows and S = T - 1 steps, every buffer dense fp32, 16-byte aligned:
+ *   a0_*, b0_*  (h1 [B][256], h2 [B][256], raw [B][64 | 512]) of z1_posterior_init and z2_prior_init at t = 0
+ *   h1a, h2a [S][B][256], rawa [S][B][64]; h1b, h2b [S][B][256], rawb [S][B][512]: z1_posterior and z2_prior at t = 1..S in slot t - 1;
+ *   raw = [mean | raw_std], the last layer's acc + bias
+ *   xz [S][B][288]: slot t - 1 = z1(t) | z2(t-1), the input rows of both first layers
+ * s2p_chain_grads: what the backward chain writes, time-major like the state: drawa [S][B][64], drawb [S][B][512], dh2a, dh1a, dh2b,
+ *   dh1b [S][B][256] (the gradient at each layer's OUTPUT, before its activation derivative) and dxz [S][B][288], slot t - 1 = the
+ *   gradient at z1(t) | z2(t-1) from the steps t .. S (without dz).
+ * s2p_chain_mlp_bwd: the transposed packs of one chain MLP: w1t [k1][w1t_row >= 256] (row k = column k of the first layer's chain
+ *   columns), w2t [256][256], w3t [256][2 D], all 16-byte aligned, w1t_row a multiple of 4 floats.
+ * s2p_posterior_chain_fwd_save: the arguments and refusals of s2p_posterior_chain_fwd, and a HOST `state` whose t = 0 buffers (and,
+ *   with T > 1, chain buffers) are written for the rows < B; a NULL or misaligned one is refused.  mean, std, z as without it.
+ * s2p_posterior_chain_bwd: the steps t = T-1 .. 1 of the backward.  eps, dz [B][T][pitch >= 288], dmean, dstd [B][T][pitch >= 32]
+ *   (rows (b, t) at (b * T + t) * pitch; slot 0 is not read); mlps: HOST array of 2, z1_posterior (k1 256) and z2_prior (k1 288);
+ *   state: h1a .. rawb are read; grads: all seven are written, nothing else is.  A negative size, a NULL pointer, another k1, a short
+ *   pitch, a short or odd w1t_row and a misaligned operand are refused; B == 0 and T < 2 are no-ops that look at no pointer.     */
+typedef struct {
+  float* a0_h1; float* a0_h2; float* a0_raw; float* b0_h1; float* b0_h2; float* b0_raw;
+  float* h1a; float* h2a; float* rawa; float* h1b; float* h2b; float* rawb; float* xz;
+} s2p_chain_state;
+typedef struct { float* drawa; float* dh2a; float* dh1a; float* drawb; float* dh2b; float* dh1b; float* dxz; } s2p_chain_grads;
+typedef struct { const float* w1t; const float* w2t; const float* w3t; int32_t k1, w1t_row; } s2p_chain_mlp_bwd;
+int s2p_posterior_chain_fwd_save(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
+                                 int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch,
+                                 float* z, int z_pitch, const s2p_chain_state* state, int B, int T, void* stream);
+int s2p_posterior_chain_bwd(const float* eps, int eps_pitch, const float* dmean, int dmean_pitch, const float* dstd, int dstd_pitch,
+                            const float* dz, int dz_pitch, const s2p_chain_mlp_bwd* mlps, const s2p_chain_state* state,
+                            const s2p_chain_grads* grads, int B, int T, void* stream);
 /* KL(p || q) of diagonal Gaussians, value and all four gradients in one pass (slac/utils.py:66-69):
  *   loss[0] += scale * sum 0.5 ((sp/sq)^2 + ((mp-mq)/sq)^2 - 1 - log (sp/sq)^2),  d* = scale * dKL/d*  (overwritten; any NULL).
  * p: [B][T][p_pitch >= D].  const_first == 0: q is [B][T][q_pitch]; const_first != 0: q is [B][T-1][q_pitch] and holds the

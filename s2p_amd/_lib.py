@@ -63,6 +63,22 @@ class ChainMlp(ctypes.Structure):
                 ("k1", ctypes.c_int32), ("w1_row", ctypes.c_int32)]
 
 
+class ChainState(ctypes.Structure):
+    """s2p_chain_state: the activations the posterior chain keeps for its backward (t = 0: a0_*, b0_*; t >= 1 time-major: the rest)."""
+    _fields_ = [(n, c_void_p) for n in ("a0_h1", "a0_h2", "a0_raw", "b0_h1", "b0_h2", "b0_raw", "h1a", "h2a", "rawa", "h1b", "h2b", "rawb",
+                                        "xz")]
+
+
+class ChainGrads(ctypes.Structure):
+    """s2p_chain_grads: what s2p_posterior_chain_bwd writes, time-major."""
+    _fields_ = [(n, c_void_p) for n in ("drawa", "dh2a", "dh1a", "drawb", "dh2b", "dh1b", "dxz")]
+
+
+class ChainMlpBwd(ctypes.Structure):
+    """s2p_chain_mlp_bwd: the transposed packs of one chain MLP (k1: the chain columns of its first layer = the rows of w1t)."""
+    _fields_ = [("w1t", c_void_p), ("w2t", c_void_p), ("w3t", c_void_p), ("k1", ctypes.c_int32), ("w1t_row", ctypes.c_int32)]
+
+
 class PolicyMlp(ctypes.Structure):
     """s2p_policy_mlp: the packed layers of a two-hidden-layer tanh policy for the closed-loop chain (w3 / b3: the last_fc rows first)."""
     _fields_ = [("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("w3", c_void_p), ("b3", c_void_p),
@@ -127,6 +143,10 @@ SIGNATURES = {
     "s2p_linear_add_fwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_float, _P, c_int, c_int, _P],
     "s2p_posterior_chain_fwd": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int, c_int, c_int,
                                 _P],
+    "s2p_posterior_chain_fwd_save": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int,
+                                     ctypes.POINTER(ChainState), c_int, c_int, _P],
+    "s2p_posterior_chain_bwd": [_P, c_int, _P, c_int, _P, c_int, _P, c_int, ctypes.POINTER(ChainMlpBwd), ctypes.POINTER(ChainState),
+                                ctypes.POINTER(ChainGrads), c_int, c_int, _P],
     "s2p_prior_chain_fwd": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
     "s2p_imagine_chain_fwd": [_P, c_int, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, c_int, ctypes.POINTER(PolicyMlp),
                               _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],

@@ -1,8 +1,9 @@
 // The SLAC latent model's Gaussian heads and likelihood terms (SPEC.md N3b; rlkit/torch/slac/network/latent.py:174-311), all fp32.
 // The posterior chain is 9 strictly sequential time steps of two 3-layer MLPs at M = batch rows: latency-bound like the state path
-// (linear_small.hip).  With grad enabled a layer stays one short launch (the backward needs every activation in memory); a call
-// that keeps no backward state can run the whole chain as ONE launch instead (gauss_chain.hip, LatentModel.fused_chain), built from
-// the same device functions (gauss_dev.h) and bitwise equal.  The chain's linear layers, with the additive term that takes the
+// (linear_small.hip).  By default a layer is one short launch.  A call that keeps no backward state can run the whole chain as ONE
+// launch instead (gauss_chain.hip, LatentModel.fused_chain), and one that does keep it as one launch that also stores every
+// activation, with the sequential part of its backward as one more (LatentModel.fused_chain_grad): all built from the same device
+// functions (gauss_dev.h) and bitwise equal.  The chain's linear layers, with the additive term that takes the
 // part of a first layer's input the chain does not produce, are in linear_small.hip.  This file holds the heads and the three
 // losses, so that NO torch.cat / chunk / stack / element-wise kernel runs between the per-layer launches:
 //   gauss_head_{fwd,bwd}_kernel : [mean | raw] -> mean, std = softplus(raw) + 1e-5, z = mean + eps * std, every output with its own
@@ -42,16 +43,15 @@ __global__ __launch_bounds__(256) void gauss_head_bwd_kernel(const HeadArgs a) {
   const long long total = (long long)a.M * a.D;
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
     const int m = (int)(idx / a.D), d = (int)(idx - (long long)m * a.D);
-    float gz = 0.f;
-    if (a.dz) gz = a.dz[(size_t)m * a.dz_pitch + d];
-    if (a.dz2) gz += a.dz2[(size_t)m * a.dz2_pitch + d];
-    float gm = gz, gs = 0.f;
-    if (a.dmean) gm += a.dmean[(size_t)m * a.dmean_pitch + d];
-    if (a.dstd) gs = a.dstd[(size_t)m * a.dstd_pitch + d];
-    if (a.eps) gs = __builtin_fmaf(gz, a.eps[(size_t)m * a.eps_pitch + d], gs);
+    const GaussHeadGrad g = gauss_head_grad(a.dz, a.dz ? a.dz[(size_t)m * a.dz_pitch + d] : 0.f,
+                                            a.dz2, a.dz2 ? a.dz2[(size_t)m * a.dz2_pitch + d] : 0.f,
+                                            a.dmean, a.dmean ? a.dmean[(size_t)m * a.dmean_pitch + d] : 0.f,
+                                            a.dstd, a.dstd ? a.dstd[(size_t)m * a.dstd_pitch + d] : 0.f,
+                                            a.eps, a.eps ? a.eps[(size_t)m * a.eps_pitch + d] : 0.f,
+                                            a.raw[(size_t)m * a.raw_pitch + a.D + d]);
     float* o = a.draw + (size_t)m * a.draw_pitch;
-    o[d] = gm;
-    o[a.D + d] = gs * gauss_sigmoid(a.raw[(size_t)m * a.raw_pitch + a.D + d]);
+    o[d] = g.dmu;
+    o[a.D + d] = g.draw_std;
   }
 }
 

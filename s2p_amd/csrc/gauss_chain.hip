@@ -39,6 +39,11 @@
 // layers are one MFMA chunk per column tile whose accumulator IS the additive value of ChainHidden (ChainAddRegs): they never leave
 // the registers.  The policy's hidden activations ([16][W + 4], W <= 1 024) are the big LDS tiles; h1 / h2 of the latent half alias
 // their heads -- the halves never overlap in time.  LDS: xz 18 688 + 2 x 65 792 + action tile 512 = 150 784 bytes, static.
+//
+// The posterior chain UNDER GRAD (SPEC.md N3k): s2p_posterior_chain_fwd_save is the posterior kernel with a ChainSaveT<true> at every
+// MLP -- h1, h2, raw = acc + bias and the chain's input rows go to global memory as the per-layer path keeps them -- in a kernel of
+// its own, so that the three kernels above keep their generated code; s2p_posterior_chain_bwd (further down) is the sequential part
+// of the backward, per step two head backwards and six input gradients, on the same 16-rows-per-workgroup design.
 #include "gauss_dev.h"
 
 namespace {
@@ -62,6 +67,23 @@ struct ChainArgs {
   int feat_pitch, eps_pitch, mean_pitch, std_pitch, z_pitch, B, T;
   s2p_chain_mlp m[4];                                      // z1_posterior_init, z2_prior_init, z1_posterior, z2_prior
 };                                                         // (prior chain: feat = z2(0), ra = rc, T = H, m = z1_prior, z2_prior)
+
+// What the training form of the posterior chain (SPEC.md N3k) stores of one MLP at one time step, beside what every chain stores:
+// h1, h2 [B][256], raw [B][2 D] = acc + bias of the last layer, and the sample at its place in the saved input rows xz ([B][288] rows
+// of the step that reads it; nullptr: no step does).  ChainSaveT<false> holds nothing and every use of it is compiled out.
+template <bool SAVE>
+struct ChainSaveT {
+  static constexpr bool on = false;
+  __device__ __forceinline__ ChainSaveT() {}
+  __device__ __forceinline__ ChainSaveT(float*, float*, float*, float*) {}
+};
+template <>
+struct ChainSaveT<true> {
+  static constexpr bool on = true;
+  float *h1, *h2, *raw, *xz;
+  __device__ __forceinline__ ChainSaveT(float* h1_, float* h2_, float* raw_, float* xz_) : h1(h1_), h2(h2_), raw(raw_), xz(xz_) {}
+};
+using ChainNoSave = ChainSaveT<false>;
 
 // The weights of NT column tiles for one block of k-chunks; wr: this lane's weight rows, already at k = 4 j.
 template <int K, int NT, int U>
@@ -150,7 +172,9 @@ struct ChainHidden {
     chain_load_w<K, NT, U>(wr, 0, w0);
   }
 
-  __device__ __forceinline__ void run(const float* xs, int xp, int row0, int B, float* ys) {
+  // gy (the SAVE variant): the layer's output of the rows < B also to global memory, [B][256]
+  template <bool SAVE = false>
+  __device__ __forceinline__ void run(const float* xs, int xp, int row0, int B, float* ys, float* gy = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
     f32x4 acc[NT];
 #pragma unroll
@@ -166,6 +190,7 @@ struct ChainHidden {
         if (ADD) v += av[q][r];
         v = act_fwd(v + bv[q], S2P_ACT_LRELU, CH_SLOPE);
         ys[row * CH_H_P + n] = row0 + row < B ? v : 0.f;
+        if constexpr (SAVE) { if (row0 + row < B) gy[(size_t)(row0 + row) * CH_HID + n] = v; }
       }
     }
   }
@@ -200,7 +225,8 @@ struct ChainHead {
     chain_load_w<CH_HID, NT, U>(wr, 0, w0);
   }
 
-  __device__ __forceinline__ void run(const ChainArgs& a, const float* hs, int t, int off, int row0, float* xz) {
+  template <typename Save = ChainNoSave>
+  __device__ __forceinline__ void run(const ChainArgs& a, const float* hs, int t, int off, int row0, float* xz, const Save sv = Save()) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
     if (idle()) return;
     f32x4 acc[NT];
@@ -214,10 +240,14 @@ struct ChainHead {
       for (int r = 0; r < 4; ++r) {
         const int row = 4 * j + r, gm = row0 + row;
         const bool ok = gm < a.B;
-        const float mu = acc[2 * p][r] + bm[p], sd = gauss_head_std(acc[2 * p + 1][r] + bs[p]);
+        const float mu = acc[2 * p][r] + bm[p], rs = acc[2 * p + 1][r] + bs[p], sd = gauss_head_std(rs);
         const float zv = gauss_head_sample(ev[p][r], sd, mu);
         xz[row * CH_XZ_P + off + d] = ok ? zv : 0.f;
         if (!ok) continue;
+        if constexpr (Save::on) {
+          sv.raw[(size_t)gm * (2 * D) + d] = mu; sv.raw[(size_t)gm * (2 * D) + D + d] = rs;
+          if (sv.xz) sv.xz[(size_t)gm * CH_Z + off + d] = zv;
+        }
         const size_t bt = (size_t)gm * a.T + t;
         if (D == CH_Z1) { a.mean[bt * a.mean_pitch + d] = mu; a.std[bt * a.std_pitch + d] = sd; }
         a.z[bt * a.z_pitch + off + d] = zv;
@@ -228,19 +258,22 @@ struct ChainHead {
 
 // Layers 2 and 3 of a Gaussian MLP whose first layer `l1` has been asked for: input xs, output z(t)[:, off : off + D].  Before its
 // last barrier it asks for the first layer of the NEXT MLP through `next()`.
-template <int D, typename L1, typename Next>
+// `sv`: where the SAVE variant stores this MLP's h1, h2, raw and sample (ChainNoSave: nowhere).
+template <int D, typename L1, typename Next, typename Save = ChainNoSave>
 __device__ __forceinline__ void chain_mlp(const ChainArgs& a, const s2p_chain_mlp& m, L1& l1, const float* xs, int t, int off, int row0,
-                                          float* xz, float* h1, float* h2, Next next) {
+                                          float* xz, float* h1, float* h2, Next next, const Save sv = Save()) {
   ChainHidden<CH_HID, false> l2;
   ChainHead<D> l3;
   __syncthreads();
-  l1.run(xs, CH_XZ_P, row0, a.B, h1);
+  if constexpr (Save::on) l1.template run<true>(xs, CH_XZ_P, row0, a.B, h1, sv.h1);
+  else l1.run(xs, CH_XZ_P, row0, a.B, h1);
   l2.ask(m.w2, CH_HID, m.b2, nullptr, row0, a.B);
   __syncthreads();
-  l2.run(h1, CH_H_P, row0, a.B, h2);
+  if constexpr (Save::on) l2.template run<true>(h1, CH_H_P, row0, a.B, h2, sv.h2);
+  else l2.run(h1, CH_H_P, row0, a.B, h2);
   l3.ask(a, m.w3, m.b3, t, off, row0);
   __syncthreads();
-  l3.run(a, h2, t, off, row0, xz);
+  l3.run(a, h2, t, off, row0, xz, sv);
   next();
 }
 
@@ -248,12 +281,13 @@ __device__ __forceinline__ void chain_mlp(const ChainArgs& a, const s2p_chain_ml
 // z2(t-1) with its first layer `a1` already asked for, then the z2 MLP `mb` on xz = z1(t) | z2(t-1) with the additive term `add_b`.
 // Results go to slot t of eps / mean / std / z.  `next()` asks for whatever follows the step, before the step's last barrier.
 // `add_b`: a global pointer ([B][256] rows of this step) or the values in registers (ChainAddRegs).
-template <typename Add, typename Next>
+// `sa` / `sb`: the two MLPs' ChainSaveT.
+template <typename Add, typename Next, typename Save = ChainNoSave>
 __device__ __forceinline__ void chain_step(const ChainArgs& a, const s2p_chain_mlp& ma, const s2p_chain_mlp& mb, ChainHidden<CH_Z2, true>& a1,
                                            ChainHidden<CH_Z, true>& b1, const Add add_b, int t, int row0, float* xz, float* h1, float* h2,
-                                           Next next) {
-  chain_mlp<CH_Z1>(a, ma, a1, xz + CH_Z1, t, 0, row0, xz, h1, h2, [&] { b1.ask(mb.w1, mb.w1_row, mb.b1, add_b, row0, a.B); });
-  chain_mlp<CH_Z2>(a, mb, b1, xz, t, CH_Z1, row0, xz, h1, h2, next);
+                                           Next next, const Save sa = Save(), const Save sb = Save()) {
+  chain_mlp<CH_Z1>(a, ma, a1, xz + CH_Z1, t, 0, row0, xz, h1, h2, [&] { b1.ask(mb.w1, mb.w1_row, mb.b1, add_b, row0, a.B); }, sa);
+  chain_mlp<CH_Z2>(a, mb, b1, xz, t, CH_Z1, row0, xz, h1, h2, next, sb);
 }
 
 // src[16 rows][W] -> xz[:, C0 : C0 + W]; rows >= B are zeros, and so is every activation row derived from them
@@ -284,6 +318,35 @@ __global__ __launch_bounds__(CH_THREADS) void posterior_chain_kernel(const Chain
   // q(z1(t) | feat(t), z2(t-1), a(t-1)), q(z2(t) | z1(t), z2(t-1), a(t-1)): the feat / action columns arrive as ra / rb
   for (int t = 1; t < a.T; ++t)
     chain_step(a, a.m[2], a.m[3], a1, b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, t, row0, xz, h1, h2, [&] { ask_a1(t + 1); });
+}
+
+// The training form of the posterior chain (SPEC.md N3k): the kernel above, every MLP with a ChainSaveT<true> that names where its
+// h1, h2, raw and sample go in `s` -- everything _PosteriorFn.backward reads.  A kernel of its own and not a template of the one
+// above: that one sits at the register ceiling and keeps its generated code.
+__global__ __launch_bounds__(CH_THREADS) void posterior_chain_save_kernel(const ChainArgs a, const s2p_chain_state s) {
+  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
+  using Sv = ChainSaveT<true>;
+  const int row0 = blockIdx.x * CH_ROWS;
+  const size_t B = a.B;
+  ChainHidden<CH_FEAT, false> i1;
+  ChainHidden<CH_Z1, false> j1;
+  ChainHidden<CH_Z2, true> a1;
+  ChainHidden<CH_Z, true> b1;
+  i1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, nullptr, row0, a.B);
+  chain_load_rows<CH_Z1, CH_FEAT>(a.feat, a.feat_pitch, row0, a.B, xz);
+  auto ask_a1 = [&](int t) {
+    if (t < a.T) a1.ask(a.m[2].w1, a.m[2].w1_row, a.m[2].b1, a.ra + (size_t)(t - 1) * a.B * CH_HID, row0, a.B);
+  };
+  chain_mlp<CH_Z1>(a, a.m[0], i1, xz + CH_Z1, 0, 0, row0, xz, h1, h2, [&] { j1.ask(a.m[1].w1, a.m[1].w1_row, a.m[1].b1, nullptr, row0, a.B); },
+                   Sv(s.a0_h1, s.a0_h2, s.a0_raw, nullptr));
+  chain_mlp<CH_Z2>(a, a.m[1], j1, xz, 0, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(1); },
+                   Sv(s.b0_h1, s.b0_h2, s.b0_raw, a.T > 1 ? s.xz : nullptr));          // z2(0) -> xz[0][:, 32:]
+  for (int t = 1; t < a.T; ++t) {
+    const size_t r = (size_t)(t - 1) * B;                  // the first row of slot t - 1 in the time-major state
+    chain_step(a, a.m[2], a.m[3], a1, b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, t, row0, xz, h1, h2, [&] { ask_a1(t + 1); },
+               Sv(s.h1a + r * CH_HID, s.h2a + r * CH_HID, s.rawa + r * 2 * CH_Z1, s.xz + r * CH_Z),      // z1(t) -> xz[t-1][:, :32]
+               Sv(s.h1b + r * CH_HID, s.h2b + r * CH_HID, s.rawb + r * 2 * CH_Z2, t + 1 < a.T ? s.xz + (r + B) * CH_Z : nullptr));
+  }
 }
 
 // The open-loop prior chain (SPEC.md N3i): z2(0) -> xz[:, 32:], then H steps of p(z1(h) | z2(h-1), a(h-1)), p(z2(h) | z1(h), z2(h-1),
@@ -425,6 +488,140 @@ __global__ __launch_bounds__(CH_THREADS) void imagine_chain_kernel(const Imagine
     chain_step(a, a.m[0], a.m[1], a1, b1, tb, s, row0, xz, pa, pb, [] {});
   }
 }
+// ---- the backward of the posterior chain's steps (SPEC.md N3k) -----------------------------------------------------------------------
+// The loop "for t = S .. 1" of _PosteriorFn.backward as ONE launch: per step the two head backwards and the six input gradients
+// that ARE sequential (every weight gradient is a batched launch after the chain and reads what this kernel leaves in global
+// memory).  The forward's argument holds: rows never meet, so a workgroup owns 16 rows and every column, workgroup barriers only.
+// Bitwise the per-layer path: a dgrad element is lin_fwd_kernel's through lin_dgrad_args -- lin_mfma_chunk over the k-chunks of the
+// reduction (512, 256 or 64) in ascending order from 0, operand dy * act_grad_from_out(y) (ONE multiply, done here by the lane that
+// stores dy into the LDS tile), epilogue acc + 0 or (acc + dx_old) + 0 -- and a head element is gauss_head_grad (gauss_dev.h).
+// Weights: the transposed packs, from L2 straight into the MFMA registers (chain_gemm).  LDS, static, nothing aliased, 84 992 bytes:
+//   dr [16][516] draw of the head in flight      ta, tb [16][260] dh2 . act', dh1 . act'      dx [16][292] the gradient at xz
+struct ChainBwdArgs {
+  const float* eps; const float* dmean; const float* dstd; const float* dz;
+  int eps_pitch, dmean_pitch, dstd_pitch, dz_pitch, B, T;
+  s2p_chain_mlp_bwd m[2];                                  // z1_posterior, z2_prior
+  s2p_chain_state s;
+  s2p_chain_grads g;
+};
+constexpr int CH_DR_P = 2 * CH_Z2 + S2P_CHAIN_PAD;
+
+// One input gradient: o[16][NO] = xs[16][K] . w[NO][w_row]^T, xs = dy . act'(y) already.  Wave v owns the column tiles v, v + 8, ...
+// -> global `go` (pitch gp) as it is, and the LDS tile `os` (pitch op): as it is, or with PRE times act'(ya) for the dgrad below
+// (ya [B][256]: the saved OUTPUT of the layer this gradient arrives at).  ACC: (acc + os) + 0, the accumulating dgrad.
+// ask(): the first weights and ya, before the barrier that ends the previous stage; run() after it.
+template <int K, int NO, bool ACC, bool PRE>
+struct ChainDgrad {
+  static constexpr int TILES = NO / 16, NT = (TILES + CH_WAVES - 1) / CH_WAVES, U = ch_u(NT);
+  const float* wr[NT];
+  f32x4 w0[NT][U];
+  float yv[NT][4];
+
+  static __device__ __forceinline__ bool has(int q) { return (int)(threadIdx.x >> 6) + q * CH_WAVES < TILES; }   // (wave-uniform)
+
+  __device__ __forceinline__ void ask(const float* w, int w_row, const float* ya, int row0, int B) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int n = 16 * (has(q) ? wave + q * CH_WAVES : wave) + i;            // (a wave without tile q multiplies tile 0 again, unused)
+      wr[q] = w + (size_t)n * w_row + 4 * j;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gm = row0 + 4 * j + r;
+        yv[q][r] = (PRE && gm < B) ? ya[(size_t)gm * CH_HID + n] : 0.f;
+      }
+    }
+    chain_load_w<K, NT, U>(wr, 0, w0);
+  }
+
+  __device__ __forceinline__ void run(const float* xs, int xp, int row0, int B, float* go, int gp, float* os, int op) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    f32x4 acc[NT];
+#pragma unroll
+    for (int q = 0; q < NT; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    chain_gemm<K, NT, U>(xs + i * xp + 4 * j, wr, w0, acc);
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      if (!has(q)) continue;
+      const int n = 16 * (wave + q * CH_WAVES) + i;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 4 * j + r, gm = row0 + row;
+        float v = acc[q][r];
+        if (ACC) v += os[row * op + n];
+        v = v + 0.f;                                       // (lin_fwd_kernel's "+ bias" without one: -0 becomes +0)
+        if (gm < B) go[(size_t)gm * gp + n] = v;
+        if (PRE) v *= act_grad_from_out(yv[q][r], S2P_ACT_LRELU, CH_SLOPE);
+        os[row * op + n] = gm < B ? v : 0.f;
+      }
+    }
+  }
+};
+
+// The head backward of D columns at step t: -> draw [B][2 D] of slot t - 1 in global memory and dr[:, : 2 D].  WIDE (the z2 head):
+// no dmean / dstd, and the carried gradient dx[:, 32:] only when `carry`; else (z1): dmean, dstd and dx[:, :32], just written.
+template <int D, bool WIDE>
+__device__ __forceinline__ void chain_head_bwd(const ChainBwdArgs& a, const float* raw, float* draw, int t, bool carry, int row0,
+                                               const float* dx, float* dr) {
+  constexpr int off = WIDE ? CH_Z1 : 0;
+  for (int e = threadIdx.x; e < CH_ROWS * D; e += CH_THREADS) {
+    const int row = e / D, d = e % D, gm = row0 + row;
+    GaussHeadGrad g = {0.f, 0.f};
+    if (gm < a.B) {
+      const size_t bt = (size_t)gm * a.T + t;
+      const float dzv = a.dz[bt * a.dz_pitch + off + d], ev = a.eps[bt * a.eps_pitch + off + d], dz2 = dx[row * CH_XZ_P + off + d];
+      const float rs = raw[(size_t)gm * (2 * D) + D + d];
+      if (WIDE) g = gauss_head_grad(true, dzv, carry, dz2, false, 0.f, false, 0.f, true, ev, rs);
+      else g = gauss_head_grad(true, dzv, true, dz2, true, a.dmean[bt * a.dmean_pitch + d], true, a.dstd[bt * a.dstd_pitch + d], true, ev, rs);
+      draw[(size_t)gm * (2 * D) + d] = g.dmu;
+      draw[(size_t)gm * (2 * D) + D + d] = g.draw_std;
+    }
+    dr[row * CH_DR_P + d] = g.dmu;
+    dr[row * CH_DR_P + D + d] = g.draw_std;
+  }
+}
+
+__global__ __launch_bounds__(CH_THREADS) void posterior_chain_bwd_kernel(const ChainBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float dr[CH_ROWS * CH_DR_P], ta[CH_ROWS * CH_H_P], tb[CH_ROWS * CH_H_P], dx[CH_ROWS * CH_XZ_P];
+  const int row0 = blockIdx.x * CH_ROWS, B = a.B, S = a.T - 1;
+  const s2p_chain_mlp_bwd& ma = a.m[0];
+  const s2p_chain_mlp_bwd& mb = a.m[1];
+  for (int e = threadIdx.x; e < CH_ROWS * CH_XZ_P; e += CH_THREADS) dx[e] = 0.f;   // (read at t = S only as an operand that is not added)
+  __syncthreads();
+  for (int t = S; t >= 1; --t) {
+    const size_t r = (size_t)(t - 1) * B;                  // the first row of slot t - 1
+    // the z2 MLP: head, 512 -> 256, 256 -> 256, 256 -> 288
+    ChainDgrad<2 * CH_Z2, CH_HID, false, true> b3;
+    ChainDgrad<CH_HID, CH_HID, false, true> b2;
+    ChainDgrad<CH_HID, CH_Z, false, false> b1;
+    chain_head_bwd<CH_Z2, true>(a, a.s.rawb + r * 2 * CH_Z2, a.g.drawb + r * 2 * CH_Z2, t, t < S, row0, dx, dr);
+    b3.ask(mb.w3t, 2 * CH_Z2, a.s.h2b + r * CH_HID, row0, B);
+    __syncthreads();
+    b3.run(dr, CH_DR_P, row0, B, a.g.dh2b + r * CH_HID, CH_HID, ta, CH_H_P);
+    b2.ask(mb.w2t, CH_HID, a.s.h1b + r * CH_HID, row0, B);
+    __syncthreads();
+    b2.run(ta, CH_H_P, row0, B, a.g.dh1b + r * CH_HID, CH_HID, tb, CH_H_P);
+    b1.ask(mb.w1t, mb.w1t_row, nullptr, row0, B);
+    __syncthreads();
+    b1.run(tb, CH_H_P, row0, B, a.g.dxz + r * CH_Z, CH_Z, dx, CH_XZ_P);
+    __syncthreads();
+    // the z1 MLP: head, 64 -> 256, 256 -> 256, 256 -> 256 added to dxz[:, 32:], the gradient at z2(t-1) that step t - 1 takes up
+    ChainDgrad<2 * CH_Z1, CH_HID, false, true> a3;
+    ChainDgrad<CH_HID, CH_HID, false, true> a2;
+    ChainDgrad<CH_HID, CH_Z2, true, false> a1;
+    chain_head_bwd<CH_Z1, false>(a, a.s.rawa + r * 2 * CH_Z1, a.g.drawa + r * 2 * CH_Z1, t, true, row0, dx, dr);
+    a3.ask(ma.w3t, 2 * CH_Z1, a.s.h2a + r * CH_HID, row0, B);
+    __syncthreads();
+    a3.run(dr, CH_DR_P, row0, B, a.g.dh2a + r * CH_HID, CH_HID, ta, CH_H_P);
+    a2.ask(ma.w2t, CH_HID, a.s.h1a + r * CH_HID, row0, B);
+    __syncthreads();
+    a2.run(ta, CH_H_P, row0, B, a.g.dh1a + r * CH_HID, CH_HID, tb, CH_H_P);
+    a1.ask(ma.w1t, ma.w1t_row, nullptr, row0, B);
+    __syncthreads();
+    a1.run(tb, CH_H_P, row0, B, a.g.dxz + r * CH_Z + CH_Z1, CH_Z, dx + CH_Z1, CH_XZ_P);
+    __syncthreads();
+  }
+}
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 struct ChainHeadSpec { int k1; const char* name; };        // the chain columns of a head's first layer, and the head's name in messages
 const ChainHeadSpec CH_POSTERIOR_HEADS[4] = {{CH_FEAT, "z1_posterior_init"}, {CH_Z1, "z2_prior_init"}, {CH_Z2, "z1_posterior"}, {CH_Z, "z2_prior"}};
@@ -454,7 +651,79 @@ int chain_take_views(const char* who, const float* eps, int eps_pitch, float* me
   a.z_pitch = z_pitch; a.B = B; a.T = T;
   return 0;
 }
+
+// The operand checks of the posterior chain, for both of its forms.  0 with `a` filled, or S2P_REQUIRE's value with the error text set.
+int posterior_chain_take(const char* who, const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
+                         int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
+                         int z_pitch, int B, int T, ChainArgs& a) {
+  S2P_REQUIRE(feat && mlps, "%s: null pointer (feat and mlps are required)", who);
+  S2P_REQUIRE(T == 1 || (ra && rb), "%s: ra and rb are required when T > 1", who);
+  if (int e = chain_take_views(who, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a)) return e;
+  S2P_REQUIRE(feat_pitch >= CH_FEAT, "%s: the pitch of feat is below its row of 256", who);
+  S2P_REQUIRE(s2p_al16(feat) && feat_pitch % 4 == 0, "%s: feat must be 16-byte aligned, its pitch a multiple of 4 floats", who);
+  if (int e = chain_take_mlps(who, mlps, CH_POSTERIOR_HEADS, T > 1 ? 4 : 2, a)) return e;
+  a.feat = feat; a.feat_pitch = feat_pitch; a.ra = ra; a.rb = rb;
+  return 0;
+}
+
+// every buffer of `n` is given and 16-byte aligned
+bool chain_bufs_ok(float* const* p, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!p[i] || !s2p_al16(p[i])) return false;
+  return true;
+}
 }  // namespace
+
+extern "C" int s2p_posterior_chain_fwd_save(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
+                                            int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std,
+                                            int std_pitch, float* z, int z_pitch, const s2p_chain_state* state, int B, int T,
+                                            void* stream) {
+  const char* who = "s2p_posterior_chain_fwd_save";
+  S2P_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
+  if (B == 0 || T == 0) return 0;
+  ChainArgs a{};
+  if (int e = posterior_chain_take(who, feat, feat_pitch, ra, rb, eps, eps_pitch, mlps, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a))
+    return e;
+  S2P_REQUIRE(state, "%s: null pointer (state is required)", who);
+  float* const bufs[13] = {state->a0_h1, state->a0_h2, state->a0_raw, state->b0_h1, state->b0_h2, state->b0_raw, state->h1a,
+                           state->h2a, state->rawa, state->h1b, state->h2b, state->rawb, state->xz};
+  S2P_REQUIRE(chain_bufs_ok(bufs, T > 1 ? 13 : 6), "%s: state: a buffer is NULL or not 16-byte aligned", who);
+  hipLaunchKernelGGL(posterior_chain_save_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a, *state);
+  S2P_CHECK_LAUNCH("posterior_chain_save_kernel");
+  return 0;
+}
+
+extern "C" int s2p_posterior_chain_bwd(const float* eps, int eps_pitch, const float* dmean, int dmean_pitch, const float* dstd,
+                                       int dstd_pitch, const float* dz, int dz_pitch, const s2p_chain_mlp_bwd* mlps,
+                                       const s2p_chain_state* state, const s2p_chain_grads* grads, int B, int T, void* stream) {
+  const char* who = "s2p_posterior_chain_bwd";
+  S2P_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
+  if (B == 0 || T < 2) return 0;                           // (T == 1: the chain has no step)
+  S2P_REQUIRE(eps && dmean && dstd && dz && mlps && state && grads,
+              "%s: null pointer (eps, dmean, dstd, dz, mlps, state and grads are required)", who);
+  S2P_REQUIRE(eps_pitch >= CH_Z && dz_pitch >= CH_Z && dmean_pitch >= CH_Z1 && dstd_pitch >= CH_Z1,
+              "%s: a pitch is below its row (eps 288, dz 288, dmean 32, dstd 32)", who);
+  ChainBwdArgs a{};
+  for (int g = 0; g < 2; ++g) {
+    const s2p_chain_mlp_bwd& m = mlps[g];
+    const char* name = CH_POSTERIOR_HEADS[2 + g].name;
+    S2P_REQUIRE(m.w1t && m.w2t && m.w3t, "%s: %s: null operand", who, name);
+    S2P_REQUIRE(m.k1 == CH_POSTERIOR_HEADS[2 + g].k1, "%s: %s: the first layer's K is %d, %d is built", who, name, (int)m.k1,
+                CH_POSTERIOR_HEADS[2 + g].k1);
+    S2P_REQUIRE(m.w1t_row >= CH_HID && m.w1t_row % 4 == 0, "%s: %s: w1t_row must be a multiple of 4 floats and at least 256", who, name);
+    S2P_REQUIRE(s2p_al16(m.w1t) && s2p_al16(m.w2t) && s2p_al16(m.w3t), "%s: %s: the weights must be 16-byte aligned", who, name);
+    a.m[g] = m;
+  }
+  float* const sb[6] = {state->h1a, state->h2a, state->rawa, state->h1b, state->h2b, state->rawb};
+  S2P_REQUIRE(chain_bufs_ok(sb, 6), "%s: state: a chain buffer is NULL or not 16-byte aligned", who);
+  float* const gb[7] = {grads->drawa, grads->dh2a, grads->dh1a, grads->drawb, grads->dh2b, grads->dh1b, grads->dxz};
+  S2P_REQUIRE(chain_bufs_ok(gb, 7), "%s: grads: a buffer is NULL or not 16-byte aligned", who);
+  a.eps = eps; a.eps_pitch = eps_pitch; a.dmean = dmean; a.dmean_pitch = dmean_pitch; a.dstd = dstd; a.dstd_pitch = dstd_pitch; a.dz = dz;
+  a.dz_pitch = dz_pitch; a.B = B; a.T = T; a.s = *state; a.g = *grads;
+  hipLaunchKernelGGL(posterior_chain_bwd_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
+  S2P_CHECK_LAUNCH("posterior_chain_bwd_kernel");
+  return 0;
+}
 
 extern "C" int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
                                        int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std,
@@ -462,14 +731,9 @@ extern "C" int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const 
   const char* who = "s2p_posterior_chain_fwd";
   S2P_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
   if (B == 0 || T == 0) return 0;
-  S2P_REQUIRE(feat && mlps, "%s: null pointer (feat and mlps are required)", who);
-  S2P_REQUIRE(T == 1 || (ra && rb), "%s: ra and rb are required when T > 1", who);
   ChainArgs a{};
-  if (int e = chain_take_views(who, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a)) return e;
-  S2P_REQUIRE(feat_pitch >= CH_FEAT, "%s: the pitch of feat is below its row of 256", who);
-  S2P_REQUIRE(s2p_al16(feat) && feat_pitch % 4 == 0, "%s: feat must be 16-byte aligned, its pitch a multiple of 4 floats", who);
-  if (int e = chain_take_mlps(who, mlps, CH_POSTERIOR_HEADS, T > 1 ? 4 : 2, a)) return e;
-  a.feat = feat; a.feat_pitch = feat_pitch; a.ra = ra; a.rb = rb;
+  if (int e = posterior_chain_take(who, feat, feat_pitch, ra, rb, eps, eps_pitch, mlps, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a))
+    return e;
   hipLaunchKernelGGL(posterior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
   S2P_CHECK_LAUNCH("posterior_chain_kernel");
   return 0;

@@ -14,8 +14,10 @@
 // layer is two short launches (wgrad + bias grad; dgrad) -- no act_bwd pass, no atomics, fixed summation order.
 // (One launch per layer, not one per chain: a layer needs every output COLUMN of the previous one, and on this chip a kernel
 // boundary (~1.5 us, hipGraph) is cheaper than an in-kernel grid barrier (~4-7 us).  That holds wherever the rows of a layer are
-// spread over workgroups: the state path, and the SLAC posterior chain with grad enabled.  The no-grad posterior chain can give a
-// workgroup 16 rows and ALL columns and then needs workgroup barriers only: gauss_chain.hip runs it as one launch.)
+// spread over workgroups: the state path, and the SLAC posterior chain as it runs by default.  The chain's batch rows never meet, so
+// it can also give a workgroup 16 rows and ALL columns and then needs workgroup barriers only: gauss_chain.hip runs the no-grad
+// chains as one launch, and with LatentModel.fused_chain_grad the chain under grad as one launch forward and one backward, whose
+// dgrad elements are this file's lin_fwd_kernel through lin_dgrad_args, bit for bit.)
 //
 // The SLAC Gaussian MLPs' variant of a layer is here too (s2p_linear_add_fwd / s2p_linear_add_bwd): the same forward kernel with an
 // additive [M][N] term in its epilogue, y = act(f(x) . W^T + add + bias).  The part of a first layer's pre-activation that does not

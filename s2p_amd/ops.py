@@ -744,6 +744,44 @@ def posterior_chain_fwd(feat0, ra, rb, eps, mlps, mean, std, z):
     check(lib().s2p_posterior_chain_fwd(fp, fs, ptr(ra), ptr(rb), ptr(eps), eps.stride(1), arr, *tail), "s2p_posterior_chain_fwd")
 
 
+def _dense(ts):
+    for t in ts:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("the chain state and its gradients are contiguous fp32 buffers")
+    return [ptr(t) for t in ts]
+
+
+def chain_state(a0, b0, sv=None):
+    """The s2p_chain_state of what _PosteriorFn keeps: a0, b0 = (h1, h2, raw) of the two t = 0 heads, sv = (h1a, h2a, rawa, h1b,
+    h2b, rawb, xz), time-major (None when T == 1: the chain has no step)."""
+    return _lib.ChainState(*(_dense(tuple(a0) + tuple(b0)) + (_dense(sv) if sv is not None else [None] * 7)))
+
+
+def posterior_chain_fwd_save(feat0, ra, rb, eps, mlps, mean, std, z, state):
+    """posterior_chain_fwd that also fills `state` (a chain_state()) with everything the backward reads: one launch
+    (s2p_posterior_chain_fwd_save), bitwise the per-layer path."""
+    (fp, fs), arr, tail = _chain_operands(feat0, eps, mlps, 4, mean, std, z, terms=(ra, rb), steps=eps.shape[1] - 1)
+    check(lib().s2p_posterior_chain_fwd_save(fp, fs, ptr(ra), ptr(rb), ptr(eps), eps.stride(1), arr, *tail[:6], ctypes.byref(state),
+                                             *tail[6:]), "s2p_posterior_chain_fwd_save")
+
+
+def chain_mlp_bwd(pk):
+    """The s2p_chain_mlp_bwd of a Gaussian.packed() dict: the transposes of the chain columns of the first layer, of w2 and of w3."""
+    _, w1t, k = pk["g1"][0]
+    return _lib.ChainMlpBwd(ptr(w1t), ptr(pk["w2t"]), ptr(pk["w3t"]), k, w1t.shape[1])
+
+
+def posterior_chain_bwd(eps, dmean, dstd, dz, mlps, state, grads):
+    """The steps t = T-1 .. 1 of the posterior chain's backward in one launch (s2p_posterior_chain_bwd).  eps, dz [B, T, 288],
+    dmean, dstd [B, T, 32] views as for posterior_chain_fwd; mlps: the chain_mlp_bwd() of z1_posterior and z2_prior; state: a
+    chain_state(); grads = (drawa, dh2a, dh1a, drawb, dh2b, dh1b, dxz), contiguous and time-major: all of them are written."""
+    B, T = eps.shape[:2]
+    _chain_views(B, T, eps, dmean, dstd, dz)
+    check(lib().s2p_posterior_chain_bwd(ptr(eps), eps.stride(1), ptr(dmean), dmean.stride(1), ptr(dstd), dstd.stride(1), ptr(dz),
+                                        dz.stride(1), (_lib.ChainMlpBwd * 2)(*mlps), ctypes.byref(state),
+                                        ctypes.byref(_lib.ChainGrads(*_dense(grads))), B, T, stream()), "s2p_posterior_chain_bwd")
+
+
 def gauss_head_bwd(raw, D, draw, eps=None, dmean=None, dstd=None, dz=None, dz2=None):
     """draw[:, :2D] = [dmean + dz + dz2 | (dstd + (dz + dz2) * eps) * sigmoid(raw_std)]."""
     views = [_view2(t) for t in (raw, eps, dmean, dstd, dz, dz2, draw)]

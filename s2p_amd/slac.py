@@ -393,7 +393,9 @@ class _PosteriorFn(torch.autograd.Function):
     Per time step the chain is 8 launches forward (2 x (3 layers + head)) and 8 backward (2 x (head + 3 dgrads)): the
     feature / action columns of the two first layers are one batched GEMM before the chain, every weight gradient and the
     feature / action gradients are batched launches after it.  With `model.fused_chain` a call that keeps no backward state
-    (keep False) runs the hoisted GEMMs and then the whole chain as one launch (_fused; SPEC.md N3h), bitwise the same."""
+    (keep False) runs the hoisted GEMMs and then the whole chain as one launch (_fused; SPEC.md N3h), bitwise the same.  With
+    `model.fused_chain_grad` a call that does keep it runs the chain as one launch that also stores that state (_fused_save), and the
+    8 S sequential launches of the backward as one (SPEC.md N3k), bitwise the same again."""
 
     @staticmethod
     def forward(ctx, feat, action, noise, model, keep, *params):
@@ -408,6 +410,9 @@ class _PosteriorFn(torch.autograd.Function):
         mean, std = _f32((B, T, Z1), dev), _f32((B, T, Z1), dev)
         if model.fused_chain and not keep:
             return _PosteriorFn._fused(ctx, model, feat, action, noise, (pi1, pi2, p1, p2), mean, std, z)
+        ctx.fused = bool(keep and model.fused_chain_grad)                  # the backward follows what the forward did
+        if ctx.fused:
+            return _PosteriorFn._fused_save(ctx, model, feat, action, noise, (pi1, pi2, p1, p2), mean, std, z)
         # t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
         xz = _f32((Tn, B, Z1 + Z2), dev)                               # [slot(t)] = z1(t) | z2(t-1): the chain's input rows
         a0 = _mlp_fwd(gi1, pi1, feat[:, 0], B, dev)
@@ -460,6 +465,30 @@ class _PosteriorFn(torch.autograd.Function):
         return mean, std, z
 
     @staticmethod
+    def _fused_save(ctx, model, feat, action, noise, packs, mean, std, z):
+        """Backward state is wanted and `model.fused_chain_grad` is set: the hoisted terms, then the whole chain as ONE launch that
+        also fills the buffers forward() keeps (s2p_posterior_chain_fwd_save; SPEC.md N3k) -- the same tensors in the same layout,
+        bitwise."""
+        dev = feat.device
+        B, T, _ = feat.shape
+        S, Tn = T - 1, max(T - 1, 1)
+        gs = (model.z1_posterior_init, model.z2_prior_init, model.z1_posterior, model.z2_prior)
+        xz = _f32((Tn, B, Z1 + Z2), dev)
+        a0, b0 = [(_f32((B, HID), dev), _f32((B, HID), dev), _f32((B, g.Npad), dev)) for g in gs[:2]]
+        sv = ra = rb = None
+        if S > 0:
+            xa, xb, ra, rb = _PosteriorFn._hoisted(feat, action, packs[2], packs[3])
+            (h1a, h2a, rawa), (h1b, h2b, rawb) = [(_f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g.Npad), dev))
+                                                  for g in gs[2:]]
+            sv = (xa, xb, h1a, h2a, rawa, h1b, h2b, rawb)
+        ops.posterior_chain_fwd_save(feat[:, 0], ra, rb, noise, [ops.chain_mlp(p) for p in packs], mean, std, z,
+                                     ops.chain_state(a0, b0, sv[2:] + (xz,) if sv else None))
+        ctx.model, ctx.packs, ctx.A = model, packs, action.shape[2]
+        ctx.saved = (feat, noise, z, xz, a0, b0, sv)
+        model.chain_state_bytes = sum(t.numel() * 4 for t in (xz,) + a0 + b0 + (sv or ()))
+        return mean, std, z
+
+    @staticmethod
     def backward(ctx, dmean, dstd, dz):
         model, A = ctx.model, ctx.A
         pi1, pi2, p1, p2 = ctx.packs
@@ -478,7 +507,12 @@ class _PosteriorFn(torch.autograd.Function):
             dxz = _f32((S, B, Z1 + Z2), dev)                           # gradient at z1(t) | z2(t-1), slot t - 1
             drawa, dh2a, dh1a = _f32((S, B, g1.Npad), dev), _f32((S, B, HID), dev), _f32((S, B, HID), dev)
             drawb, dh2b, dh1b = _f32((S, B, g2.Npad), dev), _f32((S, B, HID), dev), _f32((S, B, HID), dev)
-            for t in range(S, 0, -1):
+            steps = range(S, 0, -1)
+            if ctx.fused:                                              # the loop below as ONE launch (s2p_posterior_chain_bwd)
+                ops.posterior_chain_bwd(noise, dmean, dstd, dz, [ops.chain_mlp_bwd(p1), ops.chain_mlp_bwd(p2)],
+                                        ops.chain_state(a0, b0, sv[2:] + (xz,)), (drawa, dh2a, dh1a, drawb, dh2b, dh1b, dxz))
+                steps = ()
+            for t in steps:
                 s = t - 1
                 ops.gauss_head_bwd(rawb[s], Z2, drawb[s], eps=noise[:, t, Z1:], dz=dz[:, t, Z1:], dz2=dxz[t][:, Z1:] if t < S else None)
                 _mlp_tail_dgrad(g2, p2, drawb[s], h2b[s], dh2b[s], h1b[s], dh1b[s])
@@ -612,6 +646,7 @@ class LatentModel(nn.Module):
         self.to(dev)
         self.chain_state_bytes = 0              # bytes the last sample_posterior kept for its backward (0 under no_grad)
         self.fused_chain = False                # True: a no-grad sample_posterior, predict and imagine run their chain as ONE launch (SPEC.md N3h-N3j)
+        self.fused_chain_grad = False           # True: a grad-mode sample_posterior runs its chain as ONE launch forward, ONE backward (SPEC.md N3k)
 
     @property
     def device(self):

@@ -2,13 +2,14 @@
 
   python train_iql.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --latent_dir DIR --steps N
                       --out DIR [--freeze_slac [--cache_features]] [--slac_policy_input_type feature_action|latent_z] [--bf16]
-                      [--fused_chain] [--seed S]
+                      [--fused_chain] [--fused_chain_grad] [--seed S]
 
 Loads `latent.pth` from --latent_dir (written by train_latent.py), fills the buffer as the reference's `load_data_in_buffer` does,
 runs `IQLTrainer.train_from_torch` N times in the shipped configuration (`examples/iql/mujoco_finetune.py:91-119`) and writes
 `critic.pth` / `policy.pth` with the reference's keys, plus `encoder.pth` / `latent.pth`.  With --freeze_slac the encoder never
 changes: --cache_features encodes every stored frame once and samples cached features (SPEC.md N3g).  --fused_chain runs the
-no-grad posterior chain of every step's `prepare_batch` as one launch (SPEC.md N3h; the same numbers, bit for bit)."""
+no-grad posterior chain of every step's `prepare_batch` as one launch (SPEC.md N3h; the same numbers, bit for bit), --fused_chain_grad
+the chain that `update_latent` trains through as one launch forward and one backward (SPEC.md N3k; bit for bit again)."""
 import argparse
 import os
 
@@ -35,6 +36,8 @@ def parse_args(argv=None, extend=None):
                     help="with --freeze_slac: encode every stored frame once and sample cached features, not frames")
     ap.add_argument("--fused_chain", action="store_true",
                     help="run the no-grad posterior chain of prepare_batch as one launch (bitwise the same result)")
+    ap.add_argument("--fused_chain_grad", action="store_true",
+                    help="run the posterior chain of update_latent as one launch forward and one backward (bitwise the same result)")
     ap.add_argument("--slac_policy_input_type", choices=["feature_action", "latent_z"], default="feature_action")
     ap.add_argument("--bf16", action="store_true", help="bf16 conv stacks of the latent model (the IQL networks stay fp32)")
     ap.add_argument("--seed", type=int, default=0)
@@ -89,7 +92,7 @@ def main(argv=None):
     algo = SlacAlgorithm((C,) + real["image_observations"].shape[1:3], (A,), 1, "cuda:0", a.seed, batch_size_sac=a.batch_size,
                          batch_size_latent=a.batch_size_latent, buffer_size=max(rows, 1), num_sequences=a.num_sequences,
                          dtype=torch.bfloat16 if a.bf16 else torch.float32, frame_capacity=2 * rows + a.num_sequences + 1,
-                         fused_chain=a.fused_chain)
+                         fused_chain=a.fused_chain, fused_chain_grad=a.fused_chain_grad)
     algo.latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
     algo.load_data_in_buffer(real)
     if gen is not None:

@@ -1,10 +1,11 @@
 """Train the SLAC latent model on real (and generated) frames from the device-resident replay buffer (SPEC.md N3c).
 
   python train_latent.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --steps N --out DIR
-                         [--bf16] [--seed S]
+                         [--bf16] [--seed S] [--fused_chain_grad]
 
 Loads the file(s) as the reference's `load_data_in_buffer` does (`rlkit/torch/slac/algo.py:154-416`), runs `update_latent` N times
-and writes `encoder.pth` / `latent.pth` with the reference's keys."""
+and writes `encoder.pth` / `latent.pth` with the reference's keys.  --fused_chain_grad runs the posterior chain of every update as
+one launch forward and one launch backward instead of 8 per time step and direction (SPEC.md N3k; the same numbers, bit for bit)."""
 import argparse
 
 import torch
@@ -13,7 +14,7 @@ from s2p_amd.data import load_arrays
 from s2p_amd.slac_algo import UNCERTAINTY_TYPES, SlacAlgorithm
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--real", required=True, help="dataset of real transitions (.npz, or .hdf5 with h5py)")
     ap.add_argument("--gen", help="generated dataset (all_state_1step_random_action) made from the real one")
@@ -26,7 +27,13 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--num_sequences", type=int, default=8)
     ap.add_argument("--log_every", type=int, default=100)
-    a = ap.parse_args(argv)
+    ap.add_argument("--fused_chain_grad", action="store_true",
+                    help="run the posterior chain of every update as one launch forward and one backward (bitwise the same result)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_latent.py needs a HIP device (no CPU fallback)")
     real = load_arrays(a.real)
@@ -37,7 +44,8 @@ def main(argv=None):
     # observations it windows over
     algo = SlacAlgorithm((C,) + real["image_observations"].shape[1:3], (real["actions"].shape[1],), 1, "cuda:0", a.seed,
                          batch_size_latent=a.batch_size, buffer_size=max(rows, 1), num_sequences=a.num_sequences,
-                         dtype=torch.bfloat16 if a.bf16 else torch.float32, frame_capacity=2 * rows + a.num_sequences + 1)
+                         dtype=torch.bfloat16 if a.bf16 else torch.float32, frame_capacity=2 * rows + a.num_sequences + 1,
+                         fused_chain_grad=a.fused_chain_grad)
     algo.load_data_in_buffer(real)
     if gen is not None:
         algo.load_data_in_buffer(gen, data_num=len(gen["actions"]), uncertainty_type=a.uncertainty_type,
