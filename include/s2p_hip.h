@@ -489,6 +489,22 @@ int s2p_feature_window_gather(const float* feat, int64_t n_slots, int feat_pitch
                               const int64_t* win, int B, const float* action_, const float* reward_, const float* done_, int A,
                               float* feature_, float* fa, float* next_fa, int fa_pitch, float* action_seq, float* action_last,
                               int action_last_pitch, float* reward, float* terminal, void* stream);
+/* S2P training set on the device (SPEC.md N1d): frame numbers -> the batch the generator's train step takes, in one launch.
+ *   pool    uint8 [n_frames][H][W][C]          the dataset's image_observations as stored (NHWC)
+ *   states  fp32  [n_frames][S]                its observations
+ *   idx     int64 [B]                          device array of frame numbers t
+ *   prev    fp32  [B][C][out_h][out_w]         frame t     (NCHW)
+ *   image   fp32  [B][C][out_h][out_w]         frame t + 1.  Nullable.
+ *   state   fp32  [B][S]                       states[t + 1].  Nullable.
+ * Value: (float)u8 / 127.5f - 1.0f, the quotient and the difference each rounded in fp32 (torch's `.float() / 127.5 - 1.0`).
+ * Resize: torch's `nearest`: source row = min((int)floorf(y * ((float)H / (float)out_h)), H - 1), columns likewise; out == source
+ * size is the identity.  A row with t < 0 or t + 1 >= n_frames writes zeros to all its outputs and dereferences nothing; all byte
+ * offsets are 64-bit.  B == 0 is a successful no-op that looks at no pointer.  Refused before the launch: a negative size, C < 1,
+ * H, W, out_h or out_w < 1, a null pool / idx / prev, a null states with a state output, an fp32 pointer that is not 4-byte aligned.
+ * C == 3 with out_w % 4 == 0, a 4-byte aligned pool, H * W * 3 a multiple of 4 and 16-byte aligned prev / image makes 4 pixels per
+ * thread step from whole dwords with one 16-byte store per plane; anything else takes a one-pixel-per-thread path.               */
+int s2p_frame_pair_gather(const void* pool, int64_t n_frames, int H, int W, int C, const float* states, int S, const int64_t* idx,
+                          int B, int out_h, int out_w, float* prev, float* image, float* state, void* stream);
 /* generic cast copy between dtypes (n elements)                                         */
 int s2p_cast(int src_dtype, const void* src, int dst_dtype, void* dst, int64_t n, void* stream);
 

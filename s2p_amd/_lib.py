@@ -169,6 +169,7 @@ SIGNATURES = {
     "s2p_window_gather_u8": [c_int, _P, c_int64, c_int64, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P],
     "s2p_feature_window_gather": [_P, c_int64, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, c_int,
                                   _P, _P, _P],
+    "s2p_frame_pair_gather": [_P, c_int64, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P],
     "s2p_l1_loss": [c_int, _P, _P, c_int64, c_float, _P, _P, c_int, _P],
     "s2p_l1_loss_multi": [c_int, ctypes.POINTER(L1Job), c_int, _P],
     "s2p_hinge_loss": [c_int, _P, c_int64, c_int, c_float, _P, _P, _P],

@@ -193,3 +193,132 @@ extern "C" int s2p_feature_window_gather(const float* feat, int64_t n_slots, int
   S2P_CHECK_LAUNCH("feature_window_gather_kernel");
   return 0;
 }
+
+// S2P training set (SPEC.md N1d): frame numbers t -> the (previous image, next image, next state) triples of those frames, out of the
+// dataset's uint8 NHWC frames and fp32 states as stored, in the form the generator's train step takes: fp32 NCHW in [-1,1], nearest-
+// resized to out_h x out_w.  This is S2PDataset.__getitem__ + the default collate, bit for bit.  Output frame (b, which) is block-uniform:
+// blockIdx.y = which (0: frame t -> prev, 1: frame t+1 -> image), blockIdx.z strides over b, so the index load and its range check are
+// scalar work once per workgroup.  A row with t < 0 or t + 1 >= n_frames is never dereferenced: all its outputs are zeros.
+
+// (float)u8 / 127.5f - 1.0f with the quotient and the difference rounded on their own, as torch's `.float() / 127.5 - 1.0` does: the
+// quotient passes through a register the compiler cannot see through, so it can neither fold the division into the subtraction nor
+// replace it by a multiplication
+__device__ __forceinline__ float pair_value(unsigned byte) {
+  float q = (float)byte / 127.5f;
+  asm volatile("" : "+v"(q));
+  return q - 1.0f;
+}
+// torch's `nearest` source index: min((int)floorf(dst * scale), size - 1), scale = (float)in / (float)out formed by the launcher
+__device__ __forceinline__ int pair_nearest(int dst, float scale, int size) {
+  const int s = (int)floorf((float)dst * scale);
+  return s < size - 1 ? s : size - 1;
+}
+__device__ __forceinline__ void pair_copy_state(const float* states, int S, long long t, bool ok, float* state, int b) {
+  for (int j = threadIdx.x; j < S; j += 256) state[(size_t)b * S + j] = ok ? states[(size_t)(t + 1) * S + j] : 0.f;
+}
+
+// C == 3, out_w % 4 == 0, a frame a whole number of dwords in a 4-byte aligned pool, 16-byte aligned outputs, frames below 2^31 bytes:
+// a thread step makes 4 neighbouring output pixels of a row = one 16-byte store into each of the three planes.  RESIZE false (out ==
+// source size): the 12 source bytes are 3 whole dwords and the quad number is both offsets, no division.  RESIZE true: a pixel's 3
+// bytes are cut out of the 2 dwords that hold them (the second index is clamped to the frame: it is then not needed).
+template <bool RESIZE>
+__global__ __launch_bounds__(256) void frame_pair_rgb4_kernel(const unsigned char* pool, long long n_frames, int H, int W,
+                                                              const float* states, int S, const long long* idx, int B, int oh, int ow,
+                                                              float sh, float sw, float* prev, float* image, float* state) {
+  const int which = blockIdx.y;
+  const unsigned quads = (unsigned)oh * (unsigned)ow / 4u, qw = (unsigned)ow / 4u;
+  const size_t plane = (size_t)oh * ow;
+  const unsigned frame_dwords = (unsigned)H * (unsigned)W * 3u / 4u;
+  for (int b = blockIdx.z; b < B; b += gridDim.z) {
+    const long long t = idx[b];
+    const bool ok = t >= 0 && t < n_frames - 1;                   // (t + 1 could overflow)
+    if (state && which == 0 && blockIdx.x == 0) pair_copy_state(states, S, t, ok, state, b);
+    const unsigned* src = (const unsigned*)(pool + (size_t)(ok ? t + which : 0) * (size_t)frame_dwords * 4);
+    float* dst = (which ? image : prev) + (size_t)b * 3 * plane;
+    for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < quads; q += gridDim.x * 256u) {
+      f32x4 o[3];
+      if (!ok) {
+        o[0] = o[1] = o[2] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      } else if (!RESIZE) {
+        const unsigned d[3] = {src[3 * q], src[3 * q + 1], src[3 * q + 2]};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int byte = 3 * k + c;
+            o[c][k] = pair_value((d[byte >> 2] >> (8 * (byte & 3))) & 0xffu);
+          }
+      } else {
+        const unsigned y = q / qw, x0 = (q - y * qw) * 4u;
+        const unsigned row = (unsigned)pair_nearest((int)y, sh, H) * (unsigned)W;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const unsigned at = (row + (unsigned)pair_nearest((int)(x0 + k), sw, W)) * 3u;      // first byte of the source pixel
+          const unsigned i0 = at >> 2, i1 = i0 + 1 < frame_dwords ? i0 + 1 : frame_dwords - 1;
+          const unsigned long long two = ((unsigned long long)src[i1] << 32) | src[i0];
+          const unsigned px = (unsigned)(two >> (8 * (at & 3u)));
+#pragma unroll
+          for (int c = 0; c < 3; ++c) o[c][k] = pair_value((px >> (8 * c)) & 0xffu);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) *(f32x4*)(dst + c * plane + (size_t)q * 4) = o[c];
+    }
+  }
+}
+
+// any C, any sizes, any alignment of the pool, 4-byte aligned outputs: one thread per output pixel, bytes in, one float per plane out
+__global__ __launch_bounds__(256) void frame_pair_kernel(const unsigned char* pool, long long n_frames, int H, int W, int C,
+                                                         const float* states, int S, const long long* idx, int B, int oh, int ow,
+                                                         float sh, float sw, float* prev, float* image, float* state) {
+  const int which = blockIdx.y;
+  const long long plane = (long long)oh * ow;
+  for (int b = blockIdx.z; b < B; b += gridDim.z) {
+    const long long t = idx[b];
+    const bool ok = t >= 0 && t < n_frames - 1;                   // (t + 1 could overflow)
+    if (state && which == 0 && blockIdx.x == 0) pair_copy_state(states, S, t, ok, state, b);
+    const unsigned char* src = pool + (size_t)(ok ? t + which : 0) * (size_t)H * (size_t)W * (size_t)C;
+    float* dst = (which ? image : prev) + (size_t)b * (size_t)C * (size_t)plane;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < plane; p += (long long)gridDim.x * 256) {
+      const int y = (int)(p / ow), x = (int)(p - (long long)y * ow);
+      const size_t at = ((size_t)pair_nearest(y, sh, H) * (size_t)W + (size_t)pair_nearest(x, sw, W)) * (size_t)C;
+      for (int c = 0; c < C; ++c) dst[(size_t)c * plane + p] = ok ? pair_value(src[at + c]) : 0.f;
+    }
+  }
+}
+
+extern "C" int s2p_frame_pair_gather(const void* pool, int64_t n_frames, int H, int W, int C, const float* states, int S,
+                                     const int64_t* idx, int B, int out_h, int out_w, float* prev, float* image, float* state,
+                                     void* stream) {
+  S2P_REQUIRE(n_frames >= 0 && H >= 0 && W >= 0 && S >= 0 && B >= 0 && out_h >= 0 && out_w >= 0, "s2p_frame_pair_gather: negative size");
+  S2P_REQUIRE(C >= 1, "s2p_frame_pair_gather: C < 1");
+  if (B == 0) return 0;                                                // nothing to gather: no pointer is looked at
+  S2P_REQUIRE(H >= 1 && W >= 1 && out_h >= 1 && out_w >= 1, "s2p_frame_pair_gather: empty frame");
+  S2P_REQUIRE(pool && idx && prev, "s2p_frame_pair_gather: null pointer (pool, idx and prev are required)");
+  if (S == 0) state = nullptr;
+  S2P_REQUIRE(!state || states, "s2p_frame_pair_gather: null states");
+  S2P_REQUIRE((((uintptr_t)prev | (uintptr_t)image | (uintptr_t)state | (uintptr_t)states) & 3) == 0,
+              "s2p_frame_pair_gather: prev, image, state and states must be 4-byte aligned");
+  const long long frame_bytes = (long long)H * W * C, plane = (long long)out_h * out_w;
+  const bool same = out_h == H && out_w == W;
+  const bool fast = C == 3 && out_w % 4 == 0 && frame_bytes % 4 == 0 && frame_bytes < 0x7fffffffLL && plane < 0x7fffffffLL &&
+                    ((uintptr_t)pool & 3) == 0 && (((uintptr_t)prev | (uintptr_t)image) & 15) == 0;
+  const float sh = (float)H / (float)out_h, sw = (float)W / (float)out_w;       // torch's scales: fp32 quotients
+  const long long items = fast ? plane / 4 : plane;                   // thread steps per frame
+  long long gx = (items + 255) / 256; if (gx > 64) gx = 64;
+  const dim3 grid((unsigned)gx, image ? 2u : 1u, (unsigned)(B < 65535 ? B : 65535));
+  const unsigned char* p8 = (const unsigned char*)pool;
+  const long long* ix = (const long long*)idx;
+  hipStream_t st = (hipStream_t)stream;
+  if (fast && same)
+    hipLaunchKernelGGL(frame_pair_rgb4_kernel<false>, grid, dim3(256), 0, st, p8, (long long)n_frames, H, W, states, S, ix, B, out_h, out_w,
+                       sh, sw, prev, image, state);
+  else if (fast)
+    hipLaunchKernelGGL(frame_pair_rgb4_kernel<true>, grid, dim3(256), 0, st, p8, (long long)n_frames, H, W, states, S, ix, B, out_h, out_w,
+                       sh, sw, prev, image, state);
+  else
+    hipLaunchKernelGGL(frame_pair_kernel, grid, dim3(256), 0, st, p8, (long long)n_frames, H, W, C, states, S, ix, B, out_h, out_w, sh, sw,
+                       prev, image, state);
+  S2P_CHECK_LAUNCH("frame_pair_kernel");
+  return 0;
+}

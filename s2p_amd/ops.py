@@ -617,6 +617,27 @@ def feature_window_gather(feat, table, win, action_, reward_, done_):
     return feature_, fa[:, :P], next_fa[:, :P], action_seq, action_last, reward, terminal
 
 
+def frame_pair_gather(pool, states, idx, size, prev, image=None, state=None):
+    """The (frame t, frame t+1, state t+1) triples of the frame numbers `idx` (device int64 [B]) out of the dataset's uint8 frames
+    `pool` [n_frames,H,W,C] and fp32 `states` [n_frames,S] in one launch (csrc/replay.hip): prev / image fp32 NCHW [B,C,h,w] =
+    u8 / 127.5 - 1 nearest-resized to `size` = (h, w), state [B,S]; image and state may be None.  The outputs are caller-owned and
+    contiguous.  The caller has range-checked `idx` (a row out of range comes out as zeros)."""
+    n_frames, H, W, C = pool.shape
+    (h, w), B = size, idx.numel()
+    if pool.dtype != torch.uint8 or states.dtype != torch.float32 or idx.dtype != torch.int64:
+        raise TypeError("pool is uint8, states fp32 and idx int64")
+    if states.dim() != 2 or states.shape[0] != n_frames:
+        raise ValueError("states is [n_frames,S]")
+    S = states.shape[1]
+    for t, shape in ((prev, (B, C, h, w)), (image, (B, C, h, w)), (state, (B, S))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError("prev / image are contiguous fp32 [B,C,h,w] and state is contiguous fp32 [B,S]")
+    if not (pool.is_contiguous() and states.is_contiguous() and idx.is_contiguous()):
+        raise ValueError("pool, states and idx must be contiguous")
+    check(lib().s2p_frame_pair_gather(ptr(pool), n_frames, H, W, C, ptr(states), S, ptr(idx), B, h, w, ptr(prev), ptr(image), ptr(state),
+                                      stream()), "s2p_frame_pair_gather")
+
+
 def transition_pack(obs, action, obs_mean, obs_std, out):
     """out[r] = [(obs[r] - obs_mean) / obs_std | action[r] | 0 ...] for every row of a dataset in one launch (csrc/transition.hip):
     the two operations separately rounded in fp32, i.e. numpy's `(obs - mean) / std` bit for bit.  obs [N,obs_dim], action [N,A] and

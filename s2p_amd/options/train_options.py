@@ -33,5 +33,8 @@ class TrainOptions(BaseOptions):
         parser.add_argument("--gan_mode", type=str, default="hinge", help="(hinge)")
         parser.add_argument("--netD", type=str, default="multiscale", help="(n_layers|multiscale)")
         parser.add_argument("--hip_graph", action="store_true", help="capture the G+D train step in a hipGraph")
+        parser.add_argument("--device_data", action="store_true",
+                            help="keep the whole dataset on the device (uint8 frames + fp32 states) and build every batch there with one "
+                                 "launch instead of DataLoader workers; same batches in the same order as --nThreads 0 (--nThreads is ignored)")
         self.isTrain = True
         return parser
