@@ -675,6 +675,30 @@ int s2p_mlp_linear_dgrad(const s2p_mlp_bwd_group* groups, int G, int N, int act_
 size_t s2p_mlp_linear_bwd_split_workspace(const s2p_mlp_bwd_group* groups, int G, int N, int S);
 int s2p_mlp_linear_bwd_split(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, int S, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* ---- bf16 compute for the wide grouped layers (SPEC.md N3l): s2p_mlp_linear_fwd / _bwd / _dgrad / _bwd_split with the
+ * products on the bf16 matrix cores.  Signatures, group tables and argument checks are those of the fp32 entry points; the
+ * workspace of _bwd_split_bf16 is that of s2p_mlp_linear_bwd_split_workspace.
+ *  - Every tensor stays fp32 in memory: x, w, bias, pre, act, dpre, dw, db, pre_prev, dprev.  Nothing is repacked and no shadow
+ *    copy of the weights exists: a state_dict, Adam, the Polyak update and the loss heads see what they see with the fp32 entries.
+ *  - Both operands of every product are rounded to bf16, round-to-nearest-even, when a tile loads them; the products are
+ *    summed in fp32 on v_mfma_f32_32x32x16_bf16:
+ *      pre   = sum_k bf16(x) bf16(w) + bias
+ *      dw    = sum_m bf16(dpre) bf16(x)
+ *      dprev = (sum_n bf16(dpre) bf16(w)) * [pre_prev > 0]
+ *  - The bias add, ReLU, the mask and all stores are fp32.  db = sum_m dpre is an fp32 sum of the UNROUNDED values in the fp32
+ *    kernel's order (bitwise the fp32 entry point's db).
+ *  - The MFMA-tile form only: N <= 16 is refused before any launch (the narrow last layers keep the fp32 dot-product kernels).
+ *  - K, x_pitch, N, dpre_pitch multiples of 4 and the operands 16-byte aligned, as for the fp32 entries, and no further demand:
+ *    a step of 16 along the summation index that is partly past its end loads zeros.
+ *  - No atomics, a fixed summation order: two identical calls give bitwise identical results.  _bwd_split_bf16 at S = 1 is bitwise
+ *    _bwd_bf16; _dgrad_bf16 is tile for tile the dprev of _bwd_bf16.  The split chunks are the fp32 entry's multiples of 16 rows:
+ *    one bf16 step of the weight tile.
+ *  - A group with rows == 0 is skipped; a size of 0 is a successful no-op that looks at no pointer.                            */
+int s2p_mlp_linear_fwd_bf16(const s2p_mlp_fwd_group* groups, int G, int N, int act, void* stream);
+int s2p_mlp_linear_bwd_bf16(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream);
+int s2p_mlp_linear_dgrad_bf16(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream);
+int s2p_mlp_linear_bwd_split_bf16(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, int S, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 /* Reparameterised TanhNormal sample and its log-probability from the pre-tanh value (rlkit/torch/distributions.py:339-386).
  * raw [M][raw_pitch >= 2 A] = (mu | raw log sigma), eps [M * rep][eps_pitch >= A], rep >= 1.  For the row m * rep + r:
  *   ls = clamp(raw log sigma[m], -20, 2),  u = mu[m] + exp(ls) * eps,  action = tanh(u),

@@ -193,6 +193,10 @@ SIGNATURES = {
     "s2p_mlp_linear_dgrad": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, _P],
     "s2p_mlp_linear_bwd_split_workspace": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int],
     "s2p_mlp_linear_bwd_split": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, c_int, _P, ctypes.c_size_t, _P],
+    "s2p_mlp_linear_fwd_bf16": [ctypes.POINTER(MlpFwdGroup), c_int, c_int, c_int, _P],
+    "s2p_mlp_linear_bwd_bf16": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, _P],
+    "s2p_mlp_linear_dgrad_bf16": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, _P],
+    "s2p_mlp_linear_bwd_split_bf16": [ctypes.POINTER(MlpBwdGroup), c_int, c_int, c_int, c_int, _P, ctypes.c_size_t, _P],
     "s2p_tanh_gauss_rsample": [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, c_int, _P],
     "s2p_tanh_gauss_rsample_bwd": [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int, _P],
     "s2p_sac_policy_head": [_P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P],

@@ -11,8 +11,8 @@ from collections import OrderedDict
 
 import torch
 
-from ._lib import check, lib, ptr, stream
-from .mlp import Net, bwd_plan, bwd_tables, fwd_plan, fwd_tables, run, split_chunks
+from ._lib import lib, ptr, stream
+from .mlp import Net, bwd_plan, bwd_tables, entry_point, fwd_plan, fwd_tables, split_chunks
 from .offline_rl import CriticSLAC, LatentTrainer, Qfunction, TanhGaussianPolicy, Vfunction  # noqa: F401  (re-exported)
 from .ops import pad_to
 
@@ -43,7 +43,7 @@ class CQLTrainer(LatentTrainer):
                  policy_eval_start=0, num_qs=2, min_q_version=3, temp=1.0, min_q_weight=1.0, max_q_backup=False,
                  deterministic_backup=True, num_random=10, with_lagrange=False, lagrange_thresh=0.0, image_rl=True, critic=None,
                  vf=None, curl_learning=False, slac_representation=True, slac_algo=None, freeze_slac=False, slac_update_period=1,
-                 slac_policy_input_type="feature_action", policy_weight_decay=0, q_weight_decay=0, generator=None):
+                 slac_policy_input_type="feature_action", policy_weight_decay=0, q_weight_decay=0, generator=None, mlp_compute="fp32"):
         for flag, what in ((with_lagrange, "with_lagrange"), (max_q_backup, "max_q_backup"), (num_qs != 2, "num_qs != 2"),
                            (min_q_version != 3, "min_q_version != 3"), (curl_learning, "the CURL branch"),
                            (not (image_rl and slac_representation), "the state-RL branch (image_rl and slac_representation only)"),
@@ -53,7 +53,7 @@ class CQLTrainer(LatentTrainer):
         if int(num_random) < 1 or not temp > 0:
             raise ValueError("num_random >= 1 and temp > 0")
         super().__init__(env, policy, critic, qf1, qf2, target_qf1, target_qf2, vf, qf_lr, policy_lr, slac_algo, freeze_slac,
-                         slac_update_period, slac_policy_input_type)
+                         slac_update_period, slac_policy_input_type, mlp_compute=mlp_compute)
         self.obs_dim, self.action_dim = self.qf1.input_size - policy.action_dim, policy.action_dim
         if self.qf1.output_size != 1 or self.obs_dim <= 0:
             raise ValueError("qf: (Z + A) -> 1")
@@ -71,7 +71,6 @@ class CQLTrainer(LatentTrainer):
         self.log_alpha_step = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.alpha = torch.ones(1, dtype=torch.float32, device=self.device)
         self._current_epoch = self._num_q_update_steps = self._num_policy_update_steps = 0
-        self.launches = OrderedDict()           # the last step's library calls and torch copies, by name
 
     @property
     def log_alpha(self):
@@ -117,14 +116,6 @@ class CQLTrainer(LatentTrainer):
         self._buf = {B: t}                      # (one batch size is kept: a new one replaces the tables and their buffers)
         return t
 
-    def _call(self, name, *args):
-        self.launches[name] = self.launches.get(name, 0) + 1
-        check(getattr(lib(), name)(*args), name)
-
-    def _adam(self, opt):
-        self.launches["s2p_adam_step_dev"] = self.launches.get("s2p_adam_step_dev", 0) + 1
-        opt.step()
-
     def _copy(self, dst, src):
         self.launches["torch copy"] = self.launches.get("torch copy", 0) + 1
         dst.copy_(src)
@@ -144,9 +135,6 @@ class CQLTrainer(LatentTrainer):
             if tuple(noise[k].shape) != want:
                 raise ValueError("noise[%r]: shape %s, expected %s" % (k, tuple(noise[k].shape), want))
             self._copy(t[k], noise[k].to(dev, torch.float32))
-
-    def _run(self, table, entry="s2p_mlp_linear_fwd"):
-        run(table, entry, self._call)
 
     def _rsample(self, raw, eps, M, rep, action, action_pitch, group, logp, logp_group):
         A = self.action_dim
@@ -213,9 +201,9 @@ class CQLTrainer(LatentTrainer):
                    ptr(t["dq_all"][0][B:]), M, ptr(t["q_target"]), ptr(t["std"]), st)
         for (gs, G, N, a), S in zip(t["critic_bwd"], t["critic_split"]):
             if S:
-                self._call("s2p_mlp_linear_bwd_split", gs, G, N, a, S, ptr(t["split_ws"]), t["split_ws"].numel() * 4, st)
+                self._call(entry_point("bwd_split", N, self.mlp_compute), gs, G, N, a, S, ptr(t["split_ws"]), t["split_ws"].numel() * 4, st)
             else:
-                self._call("s2p_mlp_linear_bwd", gs, G, N, a, st)
+                self._call(entry_point("bwd", N, self.mlp_compute), gs, G, N, a, st)
         self._adam(self.critic_optimizer)
         self._num_q_update_steps += 1
         self._update_latent(_latent)

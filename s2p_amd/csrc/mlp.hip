@@ -7,32 +7,35 @@
 // forms share the tiles, so what they write agrees bit for bit: the full backward; the input gradient alone (the CQL policy loss is
 // differentiated THROUGH the critics to the action, and the critics' gradient buffers must stay as they are); the full backward with
 // the rows of each weight tile split into chunks.  All fp32, no atomics, a fixed summation order: two identical calls give bitwise
-// identical results.
-#include "ens_tile.h"
+// identical results.  The s2p_mlp_linear_*_bf16 entry points (SPEC.md N3l) are the wide-layer kernels over the tiles of
+// ens_tile_bf16.h: the same tensors, tables, grids and checks, both operands of every product rounded to bf16 as a tile loads them.
+#include "ens_tile_bf16.h"
 
 #define MLP_MAX_G 8
 #define MLP_DOT_MAX_N 16
 struct MlpFwdArgs { EnsFwdTile g[MLP_MAX_G]; };
 struct MlpBwdArgs { EnsBwdTile g[MLP_MAX_G]; };              // the full backward and the input gradient alone (x, dw, db NULL there)
 
-// ---- wide layers: the MFMA wave tiles -------------------------------------------------------------------------------------------------
-template <int ACT> __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpFwdArgs a) {
+// ---- wide layers: the MFMA wave tiles, fp32 compute (ens_tile.h) or with BF16 the bf16 compute of ens_tile_bf16.h ---------------------
+template <int ACT, bool BF16> __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpFwdArgs a) {
   const EnsFwdTile t = a.g[blockIdx.z];
   const int wave = threadIdx.x >> 6, nb = blockIdx.x * 64, mb = blockIdx.y * 128 + wave * 32;
   if (mb >= t.B) return;                                     // (wave-uniform; a group of fewer rows than the widest one ends here)
-  ens_fwd_tile<ACT>(t, mb, nb);
+  if constexpr (BF16) ens_fwd_tile_bf16<ACT>(t, mb, nb);
+  else ens_fwd_tile<ACT>(t, mb, nb);
 }
 // input tile `id` of group view t (four waves = 128 rows per workgroup, row tiles outermost): nothing past the group's last tile.
 // tk = the group's tiles along K and the wave index come from the caller, which has both at hand for its weight tiles
-template <int ACT> __device__ __forceinline__ void mlp_input_tile(const EnsBwdTile& t, int id, int tk, int wave) {
+template <int ACT, bool BF16> __device__ __forceinline__ void mlp_input_tile(const EnsBwdTile& t, int id, int tk, int wave) {
   const int tm = (t.B + 127) / 128;
   if (id >= tm * tk) return;
   const int mb = (id / tk) * 128 + wave * 32;
   if (mb >= t.B) return;                                     // (wave-uniform)
-  ens_dgrad_tile<ACT>(t, mb, (id % tk) * 64);
+  if constexpr (BF16) ens_dgrad_tile_bf16<ACT>(t, mb, (id % tk) * 64);
+  else ens_dgrad_tile<ACT>(t, mb, (id % tk) * 64);
 }
 // grid x: the weight tiles of a group (four waves = four tiles per workgroup), then its input tiles; sized for the largest group
-template <int ACT> __global__ __launch_bounds__(256) void mlp_bwd_kernel(const MlpBwdArgs a) {
+template <int ACT, bool BF16> __global__ __launch_bounds__(256) void mlp_bwd_kernel(const MlpBwdArgs a) {
   const EnsBwdTile t = a.g[blockIdx.z];
   const int wave = threadIdx.x >> 6;
   if (t.B == 0) return;
@@ -40,17 +43,18 @@ template <int ACT> __global__ __launch_bounds__(256) void mlp_bwd_kernel(const M
   if ((int)blockIdx.x < w_blocks) {
     const int id = blockIdx.x * 4 + wave;
     if (id >= w_tiles) return;                               // (wave-uniform)
-    ens_wgrad_tile(t, (id / tk) * 32, (id % tk) * 64);
+    if constexpr (BF16) ens_wgrad_tile_bf16(t, (id / tk) * 32, (id % tk) * 64);
+    else ens_wgrad_tile(t, (id / tk) * 32, (id % tk) * 64);
     return;
   }
   if (!t.dprev) return;
-  mlp_input_tile<ACT>(t, blockIdx.x - w_blocks, tk, wave);
+  mlp_input_tile<ACT, BF16>(t, blockIdx.x - w_blocks, tk, wave);
 }
 // the input gradient alone: the input tiles of mlp_bwd_kernel
-template <int ACT> __global__ __launch_bounds__(256) void mlp_dgrad_kernel(const MlpBwdArgs a) {
+template <int ACT, bool BF16> __global__ __launch_bounds__(256) void mlp_dgrad_kernel(const MlpBwdArgs a) {
   const EnsBwdTile t = a.g[blockIdx.z];
   if (t.B == 0) return;
-  mlp_input_tile<ACT>(t, blockIdx.x, (t.K + 63) / 64, threadIdx.x >> 6);
+  mlp_input_tile<ACT, BF16>(t, blockIdx.x, (t.K + 63) / 64, threadIdx.x >> 6);
 }
 
 // ---- the grouped backward with the rows of each weight tile divided into S contiguous chunks: chunk s of a tile is one wave that
@@ -58,7 +62,7 @@ template <int ACT> __global__ __launch_bounds__(256) void mlp_dgrad_kernel(const
 //      adds the partials in the order s = 0 .. S - 1.  More waves for a launch whose weight tiles alone do not fill the chip, and
 //      S shorter summation chains.  The input tiles are those of mlp_bwd_kernel --------------------------------------------------------
 struct MlpSplitArgs { EnsBwdTile g[MLP_MAX_G]; float* ws[MLP_MAX_G]; int chunk[MLP_MAX_G]; int S; };
-template <int ACT> __global__ __launch_bounds__(256) void mlp_bwd_split_kernel(const MlpSplitArgs a) {
+template <int ACT, bool BF16> __global__ __launch_bounds__(256) void mlp_bwd_split_kernel(const MlpSplitArgs a) {
   EnsBwdTile t = a.g[blockIdx.z];
   const int wave = threadIdx.x >> 6;
   if (t.B == 0) return;
@@ -70,11 +74,12 @@ template <int ACT> __global__ __launch_bounds__(256) void mlp_bwd_split_kernel(c
     t.dw = a.ws[blockIdx.z] + (size_t)s * (nk + t.N);
     t.db = t.dw + nk;
     const int mb = s * a.chunk[blockIdx.z];                  // (a chunk past the last row sums nothing and writes zeros)
-    ens_wgrad_tile(t, (id / tk) * 32, (id % tk) * 64, mb, mb + a.chunk[blockIdx.z]);
+    if constexpr (BF16) ens_wgrad_tile_bf16(t, (id / tk) * 32, (id % tk) * 64, mb, mb + a.chunk[blockIdx.z]);
+    else ens_wgrad_tile(t, (id / tk) * 32, (id % tk) * 64, mb, mb + a.chunk[blockIdx.z]);
     return;
   }
   if (!t.dprev) return;
-  mlp_input_tile<ACT>(t, blockIdx.x - w_blocks * a.S, tk, wave);
+  mlp_input_tile<ACT, BF16>(t, blockIdx.x - w_blocks * a.S, tk, wave);
 }
 __global__ __launch_bounds__(256) void mlp_split_sum_kernel(const MlpSplitArgs a) {
   const EnsBwdTile t = a.g[blockIdx.z];
@@ -161,6 +166,14 @@ template <int ACT> __global__ __launch_bounds__(256) void mlp_dot_dgrad_kernel(c
     if ((act) == S2P_ACT_RELU) hipLaunchKernelGGL(kernel<ENS_ACT_RELU>, grid, dim3(256), 0, st, args); \
     else hipLaunchKernelGGL(kernel<ENS_ACT_NONE>, grid, dim3(256), 0, st, args); \
     S2P_CHECK_LAUNCH(#kernel); } while (0)
+// the same for a wide-layer kernel, on the fp32 tiles or (bf16 != 0) the bf16 tiles
+#define MLP_LAUNCH_TILE(kernel, bf16, act, grid, st, args) do { \
+    if (bf16) { \
+      if ((act) == S2P_ACT_RELU) hipLaunchKernelGGL((kernel<ENS_ACT_RELU, true>), grid, dim3(256), 0, st, args); \
+      else hipLaunchKernelGGL((kernel<ENS_ACT_NONE, true>), grid, dim3(256), 0, st, args); \
+    } else if ((act) == S2P_ACT_RELU) hipLaunchKernelGGL((kernel<ENS_ACT_RELU, false>), grid, dim3(256), 0, st, args); \
+    else hipLaunchKernelGGL((kernel<ENS_ACT_NONE, false>), grid, dim3(256), 0, st, args); \
+    S2P_CHECK_LAUNCH(#kernel); } while (0)
 
 // the head of a group table: 1 = go on, 0 = nothing to do, below 0 = refused
 static int mlp_header(const char* who, const void* groups, int G, int N, int act) {
@@ -170,6 +183,11 @@ static int mlp_header(const char* who, const void* groups, int G, int N, int act
   if (G > MLP_MAX_G) S2P_FAIL(-1, "%s: at most %d groups (G %d)", who, MLP_MAX_G, G);
   if (act != S2P_ACT_NONE && act != S2P_ACT_RELU) S2P_FAIL(-1, "%s: activation %d (none and relu only)", who, act);
   return 1;
+}
+// the bf16 entry points have the MFMA-tile form only
+static int mlp_bf16_wide(const char* who, int N) {
+  if (N <= MLP_DOT_MAX_N) S2P_FAIL(-1, "%s: the MFMA-tile form only: N above %d (N %d); narrow layers run on the fp32 entry point", who, MLP_DOT_MAX_N, N);
+  return 0;
 }
 // group g of a backward table -> its tile view; an empty group leaves *t as it is (B = 0: the kernels skip it).  `weights`: the
 // caller writes dw / db (x, dw, db required, dprev optional), else the input gradient alone (dprev required, x not looked at);
@@ -193,9 +211,10 @@ static int mlp_bwd_group(const char* who, int g, const s2p_mlp_bwd_group& s, int
   return 0;
 }
 
-extern "C" int s2p_mlp_linear_fwd(const s2p_mlp_fwd_group* groups, int G, int N, int act, void* stream) {
-  const char* who = "s2p_mlp_linear_fwd";
+// every entry point below is one function for both compute modes: `bf16` selects the tiles and refuses the narrow form
+static int mlp_fwd(const char* who, bool bf16, const s2p_mlp_fwd_group* groups, int G, int N, int act, void* stream) {
   if (const int h = mlp_header(who, groups, G, N, act); h <= 0) return h;
+  if (bf16) if (int rc = mlp_bf16_wide(who, N)) return rc;
   MlpFwdArgs a{};
   int rows = 0;
   for (int g = 0; g < G; ++g) {
@@ -212,13 +231,19 @@ extern "C" int s2p_mlp_linear_fwd(const s2p_mlp_fwd_group* groups, int G, int N,
   if (rows == 0) return 0;
   const hipStream_t st = (hipStream_t)stream;
   if (N <= MLP_DOT_MAX_N) MLP_LAUNCH_ACT(mlp_dot_fwd_kernel, act, dim3(cdiv(rows, 4), 1, G), st, a);
-  else MLP_LAUNCH_ACT(mlp_fwd_kernel, act, dim3(cdiv(N, 64), cdiv(rows, 128), G), st, a);
+  else MLP_LAUNCH_TILE(mlp_fwd_kernel, bf16, act, dim3(cdiv(N, 64), cdiv(rows, 128), G), st, a);
   return 0;
 }
+extern "C" int s2p_mlp_linear_fwd(const s2p_mlp_fwd_group* groups, int G, int N, int act, void* stream) {
+  return mlp_fwd("s2p_mlp_linear_fwd", false, groups, G, N, act, stream);
+}
+extern "C" int s2p_mlp_linear_fwd_bf16(const s2p_mlp_fwd_group* groups, int G, int N, int act, void* stream) {
+  return mlp_fwd("s2p_mlp_linear_fwd_bf16", true, groups, G, N, act, stream);
+}
 
-extern "C" int s2p_mlp_linear_bwd(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
-  const char* who = "s2p_mlp_linear_bwd";
+static int mlp_bwd(const char* who, bool bf16, const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
   if (const int h = mlp_header(who, groups, G, N, act_prev); h <= 0) return h;
+  if (bf16) if (int rc = mlp_bf16_wide(who, N)) return rc;
   const bool dot = N <= MLP_DOT_MAX_N;
   if (!dot && N % 4) S2P_FAIL(-1, "%s: N above %d must be a multiple of 4 (N %d)", who, MLP_DOT_MAX_N, N);
   MlpBwdArgs a{};
@@ -235,13 +260,19 @@ extern "C" int s2p_mlp_linear_bwd(const s2p_mlp_bwd_group* groups, int G, int N,
   if (blocks == 0) return 0;
   const hipStream_t st = (hipStream_t)stream;
   if (dot) MLP_LAUNCH_ACT(mlp_dot_bwd_kernel, act_prev, dim3(blocks, 1, G), st, a);
-  else MLP_LAUNCH_ACT(mlp_bwd_kernel, act_prev, dim3(blocks, 1, G), st, a);
+  else MLP_LAUNCH_TILE(mlp_bwd_kernel, bf16, act_prev, dim3(blocks, 1, G), st, a);
   return 0;
 }
+extern "C" int s2p_mlp_linear_bwd(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
+  return mlp_bwd("s2p_mlp_linear_bwd", false, groups, G, N, act_prev, stream);
+}
+extern "C" int s2p_mlp_linear_bwd_bf16(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
+  return mlp_bwd("s2p_mlp_linear_bwd_bf16", true, groups, G, N, act_prev, stream);
+}
 
-extern "C" int s2p_mlp_linear_dgrad(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
-  const char* who = "s2p_mlp_linear_dgrad";
+static int mlp_dgrad(const char* who, bool bf16, const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
   if (const int h = mlp_header(who, groups, G, N, act_prev); h <= 0) return h;
+  if (bf16) if (int rc = mlp_bf16_wide(who, N)) return rc;
   const bool dot = N <= MLP_DOT_MAX_N;
   if (!dot && N % 4) S2P_FAIL(-1, "%s: N above %d must be a multiple of 4 (N %d)", who, MLP_DOT_MAX_N, N);
   MlpBwdArgs a{};
@@ -256,8 +287,14 @@ extern "C" int s2p_mlp_linear_dgrad(const s2p_mlp_bwd_group* groups, int G, int 
   if (blocks == 0) return 0;
   const hipStream_t st = (hipStream_t)stream;
   if (dot) MLP_LAUNCH_ACT(mlp_dot_dgrad_kernel, act_prev, dim3(blocks, 1, G), st, a);
-  else MLP_LAUNCH_ACT(mlp_dgrad_kernel, act_prev, dim3(blocks, 1, G), st, a);
+  else MLP_LAUNCH_TILE(mlp_dgrad_kernel, bf16, act_prev, dim3(blocks, 1, G), st, a);
   return 0;
+}
+extern "C" int s2p_mlp_linear_dgrad(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
+  return mlp_dgrad("s2p_mlp_linear_dgrad", false, groups, G, N, act_prev, stream);
+}
+extern "C" int s2p_mlp_linear_dgrad_bf16(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, void* stream) {
+  return mlp_dgrad("s2p_mlp_linear_dgrad_bf16", true, groups, G, N, act_prev, stream);
 }
 
 static inline size_t mlp_split_floats(const s2p_mlp_bwd_group& s, int N, int S) {
@@ -269,9 +306,8 @@ extern "C" size_t s2p_mlp_linear_bwd_split_workspace(const s2p_mlp_bwd_group* gr
   for (int g = 0; g < G; ++g) n += mlp_split_floats(groups[g], N, S);
   return n * sizeof(float);
 }
-extern "C" int s2p_mlp_linear_bwd_split(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, int S, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  const char* who = "s2p_mlp_linear_bwd_split";
+static int mlp_bwd_split(const char* who, bool bf16, const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, int S, void* workspace,
+                         size_t workspace_bytes, void* stream) {
   if (const int h = mlp_header(who, groups, G, N, act_prev); h <= 0) return h;
   if (S < 1 || S > 64) S2P_FAIL(-1, "%s: S must be in [1, 64] (S %d)", who, S);
   if (N <= MLP_DOT_MAX_N || N % 4) S2P_FAIL(-1, "%s: the MFMA-tile form only: N above %d and a multiple of 4 (N %d)", who, MLP_DOT_MAX_N, N);
@@ -297,8 +333,16 @@ extern "C" int s2p_mlp_linear_bwd_split(const s2p_mlp_bwd_group* groups, int G, 
   if (workspace_bytes < off * sizeof(float))
     S2P_FAIL(-1, "%s: workspace of %zu bytes, %zu needed (s2p_mlp_linear_bwd_split_workspace)", who, workspace_bytes, off * sizeof(float));
   const hipStream_t st = (hipStream_t)stream;
-  MLP_LAUNCH_ACT(mlp_bwd_split_kernel, act_prev, dim3(blocks, 1, G), st, a);
+  MLP_LAUNCH_TILE(mlp_bwd_split_kernel, bf16, act_prev, dim3(blocks, 1, G), st, a);
   hipLaunchKernelGGL(mlp_split_sum_kernel, dim3(sum_blocks, 1, G), dim3(256), 0, st, a);
   S2P_CHECK_LAUNCH("mlp_split_sum_kernel");
   return 0;
+}
+extern "C" int s2p_mlp_linear_bwd_split(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, int S, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  return mlp_bwd_split("s2p_mlp_linear_bwd_split", false, groups, G, N, act_prev, S, workspace, workspace_bytes, stream);
+}
+extern "C" int s2p_mlp_linear_bwd_split_bf16(const s2p_mlp_bwd_group* groups, int G, int N, int act_prev, int S, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  return mlp_bwd_split("s2p_mlp_linear_bwd_split_bf16", true, groups, G, N, act_prev, S, workspace, workspace_bytes, stream);
 }

@@ -6,8 +6,8 @@ from collections import OrderedDict
 
 import torch
 
-from ._lib import check, lib, ptr, stream
-from .mlp import Net, bwd_plan, bwd_tables, fwd_plan, fwd_tables, run
+from ._lib import ptr, stream
+from .mlp import Net, bwd_plan, bwd_tables, fwd_plan, fwd_tables
 from .offline_rl import CriticSLAC, LatentTrainer, Qfunction, TanhGaussianPolicy, Vfunction  # noqa: F401  (re-exported)
 from .ops import pad_to
 
@@ -34,11 +34,11 @@ class IQLTrainer(LatentTrainer):
     def __init__(self, env, policy, qf1=None, qf2=None, vf=None, quantile=0.5, target_qf1=None, target_qf2=None, discount=0.99,
                  reward_scale=1.0, policy_lr=1e-3, qf_lr=1e-3, policy_weight_decay=0, q_weight_decay=0, policy_update_period=1,
                  q_update_period=1, clip_score=None, soft_target_tau=1e-2, target_update_period=1, beta=1.0, critic=None,
-                 slac_algo=None, freeze_slac=False, slac_update_period=1, slac_policy_input_type="feature_action"):
+                 slac_algo=None, freeze_slac=False, slac_update_period=1, slac_policy_input_type="feature_action", mlp_compute="fp32"):
         if policy_weight_decay or q_weight_decay or policy_update_period != 1 or q_update_period != 1:
             raise NotImplementedError("weight decay and update periods other than 1")
         super().__init__(env, policy, critic, qf1, qf2, target_qf1, target_qf2, vf, qf_lr, policy_lr, slac_algo, freeze_slac,
-                         slac_update_period, slac_policy_input_type, share_hidden=True)
+                         slac_update_period, slac_policy_input_type, share_hidden=True, mlp_compute=mlp_compute)
         self.quantile, self.discount, self.reward_scale, self.beta = float(quantile), float(discount), float(reward_scale), float(beta)
         self.clip_score = clip_score
         self.soft_target_tau, self.target_update_period = float(soft_target_tau), int(target_update_period)
@@ -75,7 +75,7 @@ class IQLTrainer(LatentTrainer):
     def _forward_backward(self, z, next_z, action, policy_input, rewards, terminals):
         """Every launch of a step up to the gradients; returns the tables (losses = [qf1, qf2, vf, policy])."""
         B, Z, A, dev, f = z.shape[0], self.obs_dim, self.action_dim, self.device, torch.float32
-        t, L = self._tables(B), lib()
+        t = self._tables(B)
         t["xq"][:, :Z] = z.to(dev, f)
         t["xq"][:, Z:Z + A] = action.to(dev, f)
         t["xv"][:B, :Z] = t["xq"][:, :Z]
@@ -85,28 +85,28 @@ class IQLTrainer(LatentTrainer):
         t["reward"].copy_(rewards.to(dev, f).reshape(B))
         t["terminal"].copy_(terminals.to(dev, f).reshape(B))
         st = stream()
-        run(t["fwd"])
+        self.launches = OrderedDict()
+        self._run(t["fwd"])
         clip = float("inf") if self.clip_score is None else float(self.clip_score)
         q, v = t["q"], t["v"]
-        check(L.s2p_iql_critic_head(ptr(q[0]), ptr(q[1]), ptr(q[2]), ptr(q[3]), ptr(v[:B]), ptr(v[B:]), ptr(t["reward"]),
-                                    ptr(t["terminal"]), B, self.reward_scale, self.discount, self.quantile, self.beta, clip,
-                                    ptr(t["losses"]), ptr(t["dq"][0]), ptr(t["dq"][1]), ptr(t["dv"]), ptr(t["weights"]), ptr(t["adv"]),
-                                    ptr(t["q_target"]), st), "s2p_iql_critic_head")
-        check(L.s2p_tanh_gauss_policy_head(ptr(t["raw"]), 2 * A, ptr(t["action"]), A, ptr(t["weights"]), B, A, ptr(t["losses"][3:]),
-                                           ptr(t["draw"]), 2 * A, None, st), "s2p_tanh_gauss_policy_head")
-        run(t["bwd"], "s2p_mlp_linear_bwd")
+        self._call("s2p_iql_critic_head", ptr(q[0]), ptr(q[1]), ptr(q[2]), ptr(q[3]), ptr(v[:B]), ptr(v[B:]), ptr(t["reward"]),
+                   ptr(t["terminal"]), B, self.reward_scale, self.discount, self.quantile, self.beta, clip, ptr(t["losses"]),
+                   ptr(t["dq"][0]), ptr(t["dq"][1]), ptr(t["dv"]), ptr(t["weights"]), ptr(t["adv"]), ptr(t["q_target"]), st)
+        self._call("s2p_tanh_gauss_policy_head", ptr(t["raw"]), 2 * A, ptr(t["action"]), A, ptr(t["weights"]), B, A, ptr(t["losses"][3:]),
+                   ptr(t["draw"]), 2 * A, None, st)
+        self._run(t["bwd"], "s2p_mlp_linear_bwd")
         return t
 
     @torch.no_grad()
     def train_from_latents(self, z, next_z, action, policy_input, rewards, terminals, _latent=False):
         """One IQL step on given latents: z, next_z [B, Z], action [B, A], policy_input [B, P], rewards / terminals [B] or [B, 1]."""
         t = self._forward_backward(z, next_z, action, policy_input, rewards, terminals)
-        self.critic_optimizer.step()
-        self.policy_optimizer.step()
+        self._adam(self.critic_optimizer)
+        self._adam(self.policy_optimizer)
         self._update_latent(_latent)
         if target_update_due(self._n_train_steps_total, self.target_update_period):
-            check(lib().s2p_soft_update(ptr(self.critic.target_flat), ptr(self.critic.flat), self.critic.n_target,
-                                        self.soft_target_tau, stream()), "s2p_soft_update")
+            self._call("s2p_soft_update", ptr(self.critic.target_flat), ptr(self.critic.flat), self.critic.n_target,
+                       self.soft_target_tau, stream())
         if self._need_to_update_eval_statistics:
             self._need_to_update_eval_statistics = False
             losses = t["losses"].cpu()

@@ -2,7 +2,9 @@
 a network's view for the grouped launches (`Net`), and ONE pair of table builders for every consumer (the IQL and CQL trainers, the
 policy's `act`).  A builder works in two steps.  `fwd_plan` / `bwd_plan` describe the launches -- which layer of which network is a
 group of which launch, with the launch's N and activation -- from shapes alone: no device, no pointer.  `fwd_tables` / `bwd_tables` turn a
-plan into the ctypes group tables `[(groups, G, N, act)]` that `run` hands to an s2p_mlp_linear_* entry point."""
+plan into the ctypes group tables `[(groups, G, N, act)]` that `run` hands to an s2p_mlp_linear_* entry point.  Which entry point
+is a separate, later choice: `entry_point` names it from the launch's kind, its N and the compute mode ("fp32", or "bf16": the wide
+layers on the bf16 matrix cores, SPEC.md N3l), so a table serves both modes."""
 from collections import namedtuple
 
 import torch
@@ -128,14 +130,34 @@ def bwd_tables(plan, with_weights=True):
     return _tables(plan, MlpBwdGroup, lambda n, li: _bwd_group(n, li, with_weights))
 
 
-def run(table, entry="s2p_mlp_linear_fwd", call=None):
-    """Every launch of a table through `entry`; `call(entry, *args)` instead of the plain checked call where the caller counts."""
-    st, fn = stream(), getattr(lib(), entry)
+COMPUTE_MODES = ("fp32", "bf16")
+ENTRY = dict(fwd="s2p_mlp_linear_fwd", bwd="s2p_mlp_linear_bwd", dgrad="s2p_mlp_linear_dgrad", bwd_split="s2p_mlp_linear_bwd_split")
+_KIND = {name: kind for kind, name in ENTRY.items()}
+
+
+def check_compute(compute):
+    if compute not in COMPUTE_MODES:
+        raise ValueError("mlp_compute %r (one of %s)" % (compute, ", ".join(COMPUTE_MODES)))
+    return compute
+
+
+def entry_point(kind, N, compute="fp32"):
+    """The entry point of a grouped launch of `kind` (fwd, bwd, dgrad, bwd_split) and output width N under a compute mode: the
+    `_bf16` entry (SPEC.md N3l: operands rounded to bf16 as a tile loads them, fp32 sums, every tensor fp32) for the MFMA-tile form
+    in mode "bf16", the fp32 entry otherwise -- the narrow layers (N <= 16) have no bf16 form."""
+    return ENTRY[kind] + "_bf16" if check_compute(compute) == "bf16" and N > 16 else ENTRY[kind]
+
+
+def run(table, entry="s2p_mlp_linear_fwd", call=None, compute="fp32"):
+    """Every launch of a table through `entry` -- for the four entries of `ENTRY`, through what `entry_point` names under `compute`;
+    `call(entry, *args)` instead of the plain checked call where the caller counts."""
+    st, kind = stream(), _KIND.get(entry)
     for gs, G, N, a in table:
+        name = entry_point(kind, N, compute) if kind else entry
         if call is not None:
-            call(entry, gs, G, N, a, st)
+            call(name, gs, G, N, a, st)
         else:
-            check(fn(gs, G, N, a, st), entry)
+            check(getattr(lib(), name)(gs, G, N, a, st), name)
 
 
 def split_chunks(tiles, rows, max_rows=1024, waves=1024, cap=8):

@@ -12,7 +12,7 @@ from collections import OrderedDict
 import torch
 
 from ._lib import check, lib, ptr, stream
-from .mlp import Net, Packed, fwd_plan, fwd_tables, run
+from .mlp import Net, Packed, check_compute, fwd_plan, fwd_tables, run
 
 LOG_SIG_MAX, LOG_SIG_MIN = 2.0, -20.0
 
@@ -280,11 +280,14 @@ class _Adam:
 class LatentTrainer:
     """What `IQLTrainer` and `CQLTrainer` share: the critic beside the policy on one HIP device, an Adam per flat buffer, the
     `state_dict` halves of both, and the SLAC side of `train_from_torch`.  `TRAINED` names the critic networks the critic loss
-    trains: they alone have gradients and optimizer state."""
+    trains: they alone have gradients and optimizer state.  `mlp_compute`: "fp32", or "bf16" for every wide grouped launch of the
+    step on the bf16 matrix cores (SPEC.md N3l; weights, gradients, Adam and the snapshots stay fp32).  `launches` counts the last
+    step's library calls by entry-point name."""
     TRAINED = ()
 
     def __init__(self, env, policy, critic, qf1, qf2, target_qf1, target_qf2, vf, qf_lr, policy_lr, slac_algo, freeze_slac,
-                 slac_update_period, slac_policy_input_type, share_hidden=False):
+                 slac_update_period, slac_policy_input_type, share_hidden=False, mlp_compute="fp32"):
+        self.mlp_compute = check_compute(mlp_compute)
         if slac_policy_input_type not in ("feature_action", "latent_z"):
             raise ValueError("slac_policy_input_type %r" % (slac_policy_input_type,))
         self.env, self.policy = env, policy
@@ -303,6 +306,19 @@ class LatentTrainer:
         self._n_train_steps_total = 0
         self._need_to_update_eval_statistics = True
         self._buf = {}
+        self.launches = OrderedDict()           # the last step's library calls (and, in CQL, torch copies), by name
+
+    # ---- counted launches -------------------------------------------------------------------------------------------------------
+    def _call(self, name, *args):
+        self.launches[name] = self.launches.get(name, 0) + 1
+        check(getattr(lib(), name)(*args), name)
+
+    def _adam(self, opt):
+        self.launches["s2p_adam_step_dev"] = self.launches.get("s2p_adam_step_dev", 0) + 1
+        opt.step()
+
+    def _run(self, table, entry="s2p_mlp_linear_fwd"):
+        run(table, entry, self._call, self.mlp_compute)
 
     # ---- the SLAC side of a step ------------------------------------------------------------------------------------------------
     def _policy_inputs(self, z, next_z, feature_action, next_feature_action):

@@ -3,12 +3,13 @@ counterpart of the reference's `run_cql_image.sh`.
 
   python train_cql.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --latent_dir DIR --steps N
                       --out DIR [--freeze_slac [--cache_features]] [--slac_policy_input_type feature_action|latent_z] [--bf16]
-                      [--fused_chain] [--fused_chain_grad] [--seed S]
+                      [--bf16_mlp] [--fused_chain] [--fused_chain_grad] [--seed S]
                       [--num_random R] [--min_q_weight W] [--temp T] [--policy_eval_start E] [--deterministic_backup]
 
 Loads `latent.pth` from --latent_dir (written by train_latent.py), fills the buffer as the reference's `load_data_in_buffer` does,
 runs `CQLTrainer.train_from_torch` N times in the shipped configuration (`examples/iql/mujoco_finetune.py:120-143`), writes
-`critic.pth` / `policy.pth` with the reference's keys plus `encoder.pth` / `latent.pth`, and reloads what it wrote."""
+`critic.pth` / `policy.pth` with the reference's keys plus `encoder.pth` / `latent.pth`, and reloads what it wrote.  --bf16_mlp runs
+the wide layers of the critics and the policy on the bf16 matrix cores (SPEC.md N3l); the written files are fp32 as always."""
 import os
 
 import torch
@@ -69,7 +70,8 @@ def main(argv=None):
     gen_noise = torch.Generator(device="cuda:0").manual_seed(a.seed)
     trainer = CQLTrainer(None, policy, critic=critic, slac_algo=algo, freeze_slac=a.freeze_slac, slac_policy_input_type=a.slac_policy_input_type,
                          num_random=a.num_random, min_q_weight=a.min_q_weight, temp=a.temp, policy_eval_start=a.policy_eval_start,
-                         deterministic_backup=a.deterministic_backup, generator=gen_noise, **CQL_KWARGS)
+                         deterministic_backup=a.deterministic_backup, generator=gen_noise, mlp_compute="bf16" if a.bf16_mlp else "fp32",
+                         **CQL_KWARGS)
     frames = sample_form(a, algo)
     for step in range(1, a.steps + 1):
         trainer.train_from_torch(algo.buffer.random_batch(a.batch_size, frames=frames))

@@ -2,14 +2,16 @@
 
   python train_iql.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --latent_dir DIR --steps N
                       --out DIR [--freeze_slac [--cache_features]] [--slac_policy_input_type feature_action|latent_z] [--bf16]
-                      [--fused_chain] [--fused_chain_grad] [--seed S]
+                      [--bf16_mlp] [--fused_chain] [--fused_chain_grad] [--seed S]
 
 Loads `latent.pth` from --latent_dir (written by train_latent.py), fills the buffer as the reference's `load_data_in_buffer` does,
 runs `IQLTrainer.train_from_torch` N times in the shipped configuration (`examples/iql/mujoco_finetune.py:91-119`) and writes
 `critic.pth` / `policy.pth` with the reference's keys, plus `encoder.pth` / `latent.pth`.  With --freeze_slac the encoder never
 changes: --cache_features encodes every stored frame once and samples cached features (SPEC.md N3g).  --fused_chain runs the
 no-grad posterior chain of every step's `prepare_batch` as one launch (SPEC.md N3h; the same numbers, bit for bit), --fused_chain_grad
-the chain that `update_latent` trains through as one launch forward and one backward (SPEC.md N3k; bit for bit again)."""
+the chain that `update_latent` trains through as one launch forward and one backward (SPEC.md N3k; bit for bit again).
+--bf16_mlp runs the wide layers of the IQL networks on the bf16 matrix cores (SPEC.md N3l): mixed precision, not the same numbers;
+the weights, Adam and the written files stay fp32."""
 import argparse
 import os
 
@@ -39,7 +41,11 @@ def parse_args(argv=None, extend=None):
     ap.add_argument("--fused_chain_grad", action="store_true",
                     help="run the posterior chain of update_latent as one launch forward and one backward (bitwise the same result)")
     ap.add_argument("--slac_policy_input_type", choices=["feature_action", "latent_z"], default="feature_action")
-    ap.add_argument("--bf16", action="store_true", help="bf16 conv stacks of the latent model (the IQL networks stay fp32)")
+    ap.add_argument("--bf16", action="store_true", help="bf16 conv stacks of the latent model (the IQL networks stay fp32: see --bf16_mlp)")
+    ap.add_argument("--bf16_mlp", action="store_true",
+                    help="bf16 matrix-core compute for the wide layers of the critics, vf and the policy, independent of --bf16: operands "
+                         "rounded to bf16 as a tile loads them, fp32 sums, fp32 master weights, heads and Adam; the written critic.pth / "
+                         "policy.pth are fp32 as always")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch_size", type=int, default=256)
     ap.add_argument("--batch_size_latent", type=int, default=32)
@@ -107,7 +113,7 @@ def main(argv=None):
     critic = CriticSLAC(q[0], q[1], q[2], q[3], vf=Vfunction(hidden_sizes=hid, output_size=1, input_size=Z))
     policy = TanhGaussianPolicy(hidden_sizes=hid, obs_dim=policy_input_dim(a, A), action_dim=A)
     trainer = IQLTrainer(None, policy, critic=critic, slac_algo=algo, freeze_slac=a.freeze_slac,
-                         slac_policy_input_type=a.slac_policy_input_type, **IQL_KWARGS)
+                         slac_policy_input_type=a.slac_policy_input_type, mlp_compute="bf16" if a.bf16_mlp else "fp32", **IQL_KWARGS)
     frames = sample_form(a, algo)
     for step in range(1, a.steps + 1):
         trainer.train_from_torch(algo.buffer.random_batch(a.batch_size, frames=frames))
