@@ -197,7 +197,12 @@ int s2p_channel_sum_ws(int dtype, const void* dy, int64_t pixels, int C, int pit
  * the three consumers below with the SAME (N,HW,C): per-split partial moments {mean_b, M2_b} about a pivot, merged
  * by the consumers in a fixed order (no atomics: bitwise reproducible; no cancellation for |mean| >> std).
  * The buffer is self-describing (it starts with its split geometry): a consumer may be called on a batch PREFIX
- * (N' <= N images of the same x) with the same buffer.  Consumers use mean and rstd = 1/sqrt(biased var + eps). */
+ * (N' <= N images of the same x) with the same buffer.  Consumers use mean and rstd = 1/sqrt(biased var + eps).
+ * Pitches may exceed C: every entry point of this section reads and writes channels [0, C) of a pixel only -- the pad
+ * columns at and beyond C of y, dx and dgb_img (beyond 2C there: gamma | beta) and everything outside [0, 2C) of a
+ * dgb_st row keep what they held.
+ * Every entry point of this section refuses (returns -1 and sets s2p_last_error, before any launch) N <= 0, HW <= 0
+ * and a NULL required pointer: x, stats, the output (y / dx), da for the backward, `sums` where the two kernels run. */
 int64_t s2p_in_stats_floats(int N, int HW, int C);
 int s2p_in_stats(int dtype, const void* x, int N, int HW, int C, int pitch, float eps,
                  float* stats, void* stream);

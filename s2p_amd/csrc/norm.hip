@@ -64,7 +64,8 @@ __device__ __forceinline__ float mat_value(float x, float mean, float rstd, floa
 
 // ------------------------------------------------------------------------------------------------
 // reductions: block = (channel slab of 64, image n, pixel split).  MODE 0: moments. MODE 1: backward sums.
-template <typename T, int MODE>
+// TANH (MODE 1 only): the tanh backward as an instantiation of its own, so that tanhf costs the relu / lrelu kernels no registers
+template <typename T, int MODE, bool TANH = false>
 __global__ __launch_bounds__(256) void in_reduce_kernel(const NormArgs a) {
   constexpr int CE = DT<T>::CE;
   constexpr int CS = 64;                 // channels per block
@@ -131,6 +132,19 @@ __global__ __launch_bounds__(256) void in_reduce_kernel(const NormArgs a) {
           const T* gp = (const T*)a.gb + ((size_t)n * a.HW + p) * a.gb_pitch + c0;
           gv.raw = *(const u32x4*)gp; bv.raw = *(const u32x4*)(gp + a.C);
         }
+        if constexpr (TANH) {                           // tanh' = 1 - tanh(v)^2, from the same tanhf as the forward
+#pragma unroll
+          for (int e = 0; e < CE; ++e) {
+            float gg = gs[e] + (a.gb ? gv.get(e) : 0.f);
+            float bb = bs[e] + (a.gb ? bv.get(e) : 0.f);
+            float xh;
+            const float t = tanhf(mat_value(xv.get(e), mean[e], rstd[e], gg, bb, xh));
+            float dy = dv.get(e) * (1.f - t * t);
+            float dxh = dy * gg;
+            q[0][e] += dxh; q[1][e] += dxh * xh; q[2][e] += dy * xh; q[3][e] += dy;
+          }
+          continue;
+        }
 #pragma unroll
         for (int e = 0; e < CE; ++e) {
           float gg = gs[e] + (a.gb ? gv.get(e) : 0.f);
@@ -182,7 +196,7 @@ __global__ __launch_bounds__(256) void in_reduce_kernel(const NormArgs a) {
 // Same thread geometry as the reductions: a thread owns one 16-byte channel chunk of one image and walks a pixel
 // stripe, so every per-(n,c) constant (mean, rstd, state gamma/beta, backward sums) is computed ONCE per workgroup and
 // the loop body is pure streaming: 16-B loads, a few FMAs per element, 16-B stores.
-template <typename T, int MODE>
+template <typename T, int MODE, bool TANH = false>    // TANH (MODE 1 only): see in_reduce_kernel
 __global__ __launch_bounds__(256) void in_apply_kernel(const NormArgs a) {
   constexpr int CE = DT<T>::CE;
   constexpr int CS = 64, NCH = CS / CE, PR = 256 / NCH;
@@ -219,7 +233,6 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const NormArgs a) {
   // activation selectors resolved once per thread: relu / lrelu / none are  v > 0 ? v : v * ns
   const float ns = a.act == S2P_ACT_RELU ? 0.f : (a.act == S2P_ACT_LRELU ? a.slope : 1.f);
   const bool act_generic = a.act == S2P_ACT_TANH || a.act == S2P_ACT_SWISH;
-  const bool g_tanh = a.act == S2P_ACT_TANH;
   float mean[CE], rstd[CE], gs[CE], bs[CE], s1[CE], s2[CE];
 #pragma unroll
   for (int e = 0; e < CE; ++e) {
@@ -251,9 +264,21 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const NormArgs a) {
       } else {
         const float dvv = dv.get(e);
         float dy = yv > 0.f ? dvv : dvv * ns;
-        if (g_tanh) dy = dvv * (1.f - yv * yv);
         float dxh = dy * gg;
         v0[e] = rstd[e] * (dxh - s1[e] - xh * s2[e]);
+        v1[e] = dy * xh;
+        v2[e] = dy;
+      }
+    }
+    if constexpr (MODE == 1 && TANH) {                // tanh' = 1 - tanh(v)^2 (in_reduce_kernel's)
+#pragma unroll
+      for (int e = 0; e < CE; ++e) {
+        float gg = gs[e] + (gbb ? gv.get(e) : 0.f);
+        float bb = bs[e] + (gbb ? bv.get(e) : 0.f);
+        float xh;
+        const float t = tanhf(mat_value(xv.get(e), mean[e], rstd[e], gg, bb, xh));
+        const float dy = dv.get(e) * (1.f - t * t);
+        v0[e] = rstd[e] * (dy * gg - s1[e] - xh * s2[e]);
         v1[e] = dy * xh;
         v2[e] = dy;
       }
@@ -549,13 +574,12 @@ __global__ __launch_bounds__(TH) void in_fused_bwd_kernel(const NormArgs a) {
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    o0.pack(v0); o1.pack(v1); o2.pack(v2);
-    if (a.res) {                                         // skip-connection gradient folded into the store (added to the ROUNDED dx, as before)
+    if (a.res) {                                         // skip-connection gradient folded into the store: fp32 add, ONE rounding (s2p_hip.h)
       Chunk<T> rv; rv.raw = *(const u32x4*)((const T*)a.res + img * a.res_pitch + cb0 + (p * a.res_pitch + lc));
 #pragma unroll
-      for (int e = 0; e < CE; ++e) v0[e] = o0.get(e) + rv.get(e);
-      o0.pack(v0);
+      for (int e = 0; e < CE; ++e) v0[e] += rv.get(e);
     }
+    o0.pack(v0); o1.pack(v1); o2.pack(v2);
     *(u32x4*)(yb + (p * a.y_pitch + lc)) = o0.raw;
     if (dgb) {
       *(u32x4*)(dgb + (p * a.dgb_pitch + lc)) = o1.raw;
@@ -638,7 +662,10 @@ static int launch_reduce(int dtype, NormArgs& a, hipStream_t st) {
   a.psplit = stats_splits(a.N, a.HW, a.C); a.rows_per_split = cdiv(a.HW, a.psplit);
   a.q_split = a.psplit;
   dim3 grid(slabs, a.N, a.psplit);
-  if (dtype == S2P_F32) hipLaunchKernelGGL((in_reduce_kernel<float, MODE>), grid, dim3(256), 0, st, a);
+  if (MODE == 1 && a.act == S2P_ACT_TANH) {
+    if (dtype == S2P_F32) hipLaunchKernelGGL((in_reduce_kernel<float, MODE, MODE == 1>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((in_reduce_kernel<__bf16, MODE, MODE == 1>), grid, dim3(256), 0, st, a);
+  } else if (dtype == S2P_F32) hipLaunchKernelGGL((in_reduce_kernel<float, MODE>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((in_reduce_kernel<__bf16, MODE>), grid, dim3(256), 0, st, a);
   S2P_CHECK_LAUNCH("in_reduce_kernel");
   return 0;
@@ -652,7 +679,10 @@ static int launch_apply(int dtype, NormArgs& a, hipStream_t st) {
   int maxps = cdiv(a.HW, 64); if (ps > maxps) ps = maxps; if (ps < 1) ps = 1;
   a.psplit = ps; a.rows_per_split = cdiv(a.HW, ps);
   dim3 grid(slabs, a.N, cdiv(a.HW, a.rows_per_split));
-  if (dtype == S2P_F32) hipLaunchKernelGGL((in_apply_kernel<float, MODE>), grid, dim3(256), 0, st, a);
+  if (MODE == 1 && a.act == S2P_ACT_TANH) {
+    if (dtype == S2P_F32) hipLaunchKernelGGL((in_apply_kernel<float, MODE, MODE == 1>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((in_apply_kernel<__bf16, MODE, MODE == 1>), grid, dim3(256), 0, st, a);
+  } else if (dtype == S2P_F32) hipLaunchKernelGGL((in_apply_kernel<float, MODE>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((in_apply_kernel<__bf16, MODE>), grid, dim3(256), 0, st, a);
   S2P_CHECK_LAUNCH("in_apply_kernel");
   return 0;
@@ -681,6 +711,7 @@ extern "C" int s2p_in_apply_fwd(int dtype, const void* x, int N, int HW, int C, 
                                 float slope, float eps, void* y, int y_pitch, void* stream) {
   int rc = norm_check("s2p_in_apply_fwd", dtype, C, pitch, gb_pitch, y_pitch); if (rc) return rc;
   S2P_CHECK_SLOPE("s2p_in_apply_fwd", act, slope);
+  if (!x || !stats || !y || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_apply_fwd: null pointer / empty problem");
   NormArgs a{}; a.x = x; a.stats = stats; a.gb = gb_img; a.gbst = gb_st; a.y = y;
   a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.gb_pitch = gb_pitch; a.gbst_pitch = gb_st_pitch;
   a.y_pitch = y_pitch; a.act = act; a.slope = slope; a.eps = eps;
@@ -759,6 +790,7 @@ extern "C" int s2p_in_bwd_reduce(int dtype, const void* da, int da_pitch, const 
                                  float* sums, void* stream) {
   int rc = norm_check("s2p_in_bwd_reduce", dtype, C, pitch, gb_pitch, da_pitch); if (rc) return rc;
   S2P_CHECK_ACT_FROM_OUT("s2p_in_bwd_reduce", act);
+  if (!da || !x || !stats || !sums || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_bwd_reduce: null pointer / empty problem");
   NormArgs a{}; a.x = x; a.da = da; a.stats = stats; a.gb = gb_img; a.gbst = gb_st; a.sums = sums;
   a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.da_pitch = da_pitch; a.gb_pitch = gb_pitch;
   a.gbst_pitch = gb_st_pitch; a.act = act; a.slope = slope; a.eps = eps;
@@ -772,6 +804,7 @@ extern "C" int s2p_in_bwd_apply(int dtype, const void* da, int da_pitch, const v
                                 float* dgb_st, int dgb_st_pitch, void* stream) {
   int rc = norm_check("s2p_in_bwd_apply", dtype, C, pitch, gb_pitch, da_pitch); if (rc) return rc;
   S2P_CHECK_ACT_FROM_OUT("s2p_in_bwd_apply", act);
+  if (!da || !x || !stats || !sums || !dx || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_bwd_apply: null pointer / empty problem");
   if (dx_pitch % (dtype == S2P_F32 ? 4 : 8) || dgb_pitch % (dtype == S2P_F32 ? 4 : 8))
     S2P_FAIL(-1, "s2p_in_bwd_apply: bad output pitch");
   if (dgb_st && dgb_st_pitch < 2 * C) S2P_FAIL(-1, "s2p_in_bwd_apply: dgb_st pitch < 2*C");
@@ -798,6 +831,7 @@ extern "C" int s2p_in_norm_bwd_res(int dtype, const void* da, int da_pitch, cons
                                    int dgb_pitch, float* dgb_st, int dgb_st_pitch, const void* res, int res_pitch, void* stream) {
   int rc = norm_check("s2p_in_norm_bwd", dtype, C, pitch, gb_pitch, da_pitch); if (rc) return rc;
   S2P_CHECK_ACT_FROM_OUT("s2p_in_norm_bwd", act);
+  if (!da || !x || !stats || !dx || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_norm_bwd: null pointer / empty problem");
   if (res && (res_pitch != dx_pitch || dx_pitch != C)) S2P_FAIL(-1, "s2p_in_norm_bwd_res: res must have the layout of dx (pitch == C)");
   const int maxhw = dtype == S2P_F32 ? 256 : 512;
   const bool simple_act = act == S2P_ACT_NONE || act == S2P_ACT_RELU || act == S2P_ACT_LRELU;
