@@ -254,6 +254,16 @@ int s2p_in_norm_bwd_res(int dtype, const void* da, int da_pitch, const void* x, 
                         const float* stats, const void* gb_img, int gb_pitch, const float* gb_st, int gb_st_pitch,
                         int act, float slope, float eps, float* sums, void* dx, int dx_pitch, void* dgb_img,
                         int dgb_pitch, float* dgb_st, int dgb_st_pitch, const void* res, int res_pitch, void* stream);
+/* Which launch form s2p_in_norm_fwd (backward == 0) / s2p_in_norm_bwd[_res] (backward != 0) take for this problem: PAIR = the two
+ * kernels (s2p_in_stats + s2p_in_apply_fwd / s2p_in_bwd_reduce + s2p_in_bwd_apply); F256 / F512 / F1024 = one fused launch of that
+ * many threads per (image, 64-channel slab); L<channels>X<chunks> = the register-resident large-plane forwards (bf16, plain
+ * InstanceNorm); F1024_CS32 = the 32-channel variant of F1024, selectable in the diagnostics build only.  has_gb_img: gamma | beta
+ * maps are passed; wants_dgb_img (backward only): their gradient is asked for.  A dry run of the entry points' own rule: no launch,
+ * no device access; -1 (s2p_last_error) for a bad dtype, N <= 0, HW <= 0 or a C the entry points refuse.  For tests and tools:
+ * which form a shape takes is not part of the contract. */
+enum { S2P_NORM_FORM_PAIR = 0, S2P_NORM_FORM_F256 = 1, S2P_NORM_FORM_F512 = 2, S2P_NORM_FORM_F1024 = 3, S2P_NORM_FORM_L64X28 = 4,
+       S2P_NORM_FORM_L32X14 = 5, S2P_NORM_FORM_L16X28 = 6, S2P_NORM_FORM_F1024_CS32 = 7 };
+int s2p_in_norm_form(int dtype, int N, int HW, int C, int has_gb_img, int wants_dgb_img, int act, int backward);
 
 /* Small fp32 linear layers of the state path (replaces F.linear + LeakyReLU and their autograd backward for the
  * StateMapping MLP and the per-norm state affine; batch M of a few dozen rows: latency-bound, csrc/linear_small.hip).

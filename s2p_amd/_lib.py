@@ -21,6 +21,10 @@ EPI_STORE, EPI_ADD, EPI_MUL_ACTGRAD = 0, 1, 2
  PATH_GENERIC) = range(11)
 HALO_S9_176_PIPE, HALO_S9_176, HALO_S9_320, HALO_R_176, HALO_R_320 = range(5)
 THIN_LANES, THIN_TILED, THIN_ROWS, THIN_HEAD, THIN_HEAD_MFMA = range(5)
+# s2p_in_norm_form: the launch form of an InstanceNorm problem (the reduce + apply pair, a fused launch of 256 / 512 / 1024 threads, a
+# large-plane forward of <channels per slab> x <chunks per thread>, the diagnostics-only 32-channel 1024-thread variant)
+(NORM_FORM_PAIR, NORM_FORM_F256, NORM_FORM_F512, NORM_FORM_F1024, NORM_FORM_L64X28, NORM_FORM_L32X14, NORM_FORM_L16X28,
+ NORM_FORM_F1024_CS32) = range(8)
 
 c_int, c_float, c_void_p, c_int64 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64
 
@@ -132,6 +136,7 @@ SIGNATURES = {
                         c_float, c_float, _P, _P, c_int, _P, c_int, _P, c_int, _P],
     "s2p_in_norm_bwd_res": [c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, c_int,
                             c_float, c_float, _P, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P],
+    "s2p_in_norm_form": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int],
     "s2p_in_stats_floats": [c_int, c_int, c_int],
     "s2p_in_bwd_sums_floats": [c_int, c_int, c_int],
     "s2p_linear_fwd": [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_float, _P, c_int, c_int, _P],

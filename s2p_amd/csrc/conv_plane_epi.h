@@ -6,6 +6,7 @@
 #pragma once
 #include "s2p_common.h"
 #include "conv_plane.h"
+#include "norm_stats.h"
 
 typedef Chunk<__bf16> PeChunk;
 constexpr int PE_ERS = 144;                  // epilogue staging row: 64 co x 2 B + 16
@@ -227,9 +228,9 @@ __device__ __forceinline__ void pe_norm_fwd(const PeTail& t, const PeOut& eo, Ro
   plane_sum(sacc, 1);
   if (tid < 64) {
     const int c = co_base + tid;
-    float* o = n.stats + 4 + ((size_t)t.img * t.Cout + c) * 2;  // norm.hip format: 4-word header, then [N][C][1 split]{mean, M2}
+    float* o = stats_slot(n.stats, t.img, t.Cout, c, 1, 0);    // one split: the plane
     o[0] = cst[tid] * inv; o[1] = cst[64 + tid];
-    if (c == 0 && t.img == 0) *(i32x4*)n.stats = (i32x4){1, HW, 0, 0};
+    if (c == 0 && t.img == 0) stats_store_header(n.stats, 1, HW);
     cst[2 * 64 + tid] = n.gbst ? 1.f + n.gbst[(size_t)t.img * n.gbst_pitch + c] : 1.f;
     cst[3 * 64 + tid] = n.gbst ? n.gbst[(size_t)t.img * n.gbst_pitch + t.Cout + c] : 0.f;
   }
@@ -252,9 +253,8 @@ __device__ __forceinline__ void pe_norm_fwd(const PeTail& t, const PeOut& eo, Ro
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float gg = gs[e] + gk.get(e), bb = bs[e] + bk.get(e);
-      const float xh = xf[k][e] * rstd[e];                      // (x - mean) * rstd
-      const float yv = __builtin_fmaf(xh, gg, bb);              // (norm.hip: mat_value)
-      ov[e] = lrelu_ns(yv, nns);
+      float xh;
+      ov[e] = lrelu_ns(mat_value_centred(xf[k][e], rstd[e], gg, bb, xh), nns);
     }
     o0.pack(ov);
     *(u32x4*)(y2 + (size_t)row * n.y2_pitch) = o0.raw;
@@ -292,17 +292,7 @@ __device__ __forceinline__ void pe_norm_bwd(const PeTail& t, const PeOut& eo, Ro
   float* cst = red + 4 * 8 * 64;                                // [6][64]: mean, rstd, 1 + gamma_st, beta_st, s1 / HW, s2 / HW
   if (tid < 64) {
     const int c = co_base + tid;
-    // merge the per-split partial moments (norm.hip: mean_rstd; S = 1 when a fused forward kernel wrote them)
-    const int S = ((const int*)n.stats)[0], rows = ((const int*)n.stats)[1];
-    const float* pm = n.stats + 4 + ((size_t)t.img * t.Cout + c) * S * 2;
-    const float inv = 1.f / (float)HW;
-    const float m0 = pm[0];
-    float m = 0.f;
-    for (int b = 1; b < S; ++b) { int nb = HW - b * rows; if (nb > rows) nb = rows; m += (float)nb * (pm[2 * b] - m0); }
-    m = m0 + m * inv;
-    float M2 = 0.f;
-    for (int b = 0; b < S; ++b) { int nb = HW - b * rows; if (nb > rows) nb = rows; const float dd = pm[2 * b] - m; M2 += pm[2 * b + 1] + (float)nb * dd * dd; }
-    cst[tid] = m; cst[64 + tid] = 1.f / sqrtf(M2 * inv + n.eps);
+    stats_mean_rstd(n.stats, t.img, t.Cout, c, HW, n.eps, cst[tid], cst[64 + tid]);   // (S = 1 when a fused forward kernel wrote them)
     cst[2 * 64 + tid] = n.gbst ? 1.f + n.gbst[(size_t)t.img * n.gbst_pitch + c] : 1.f;
     cst[3 * 64 + tid] = n.gbst ? n.gbst[(size_t)t.img * n.gbst_pitch + t.Cout + c] : 0.f;
   }
@@ -327,8 +317,8 @@ __device__ __forceinline__ void pe_norm_bwd(const PeTail& t, const PeOut& eo, Ro
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float gg = g1[e] + gk.get(e), bb = b1[e] + bk.get(e);
-        const float xh = (xv[k].get(e) - mm[e]) * rr[e];
-        const float yv = __builtin_fmaf(xh, gg, bb);            // (norm.hip: mat_value -- the forward's rounding)
+        float xh;
+        const float yv = mat_value(xv[k].get(e), mm[e], rr[e], gg, bb, xh);          // (the forward's rounding)
         const float dvv = dv[k].get(e);
         const float dy = yv > 0.f ? dvv : dvv * nneg;
         const float dxh = dy * gg;

@@ -3,15 +3,22 @@
 // stripe, then across stripes through LDS (fixed order), then across the workgroups of a plane by the CONSUMER,
 // again in a fixed order.  No atomics anywhere: results are bitwise reproducible run to run.
 //
-//   stats  : opaque fp32 buffer: a 4-word header {S, rows per split, 0, 0} followed by [N][C][S][2] per-split partial
-//            moments {mean_b, M2_b}.  A split accumulates sum(x-K), sum((x-K)^2) about a pivot K = its first pixel
+//   stats  : opaque fp32 buffer (norm_stats.h: its format and the helpers shared with the convs' fused norm tails): a header
+//            {S, rows per split, 0, 0} followed by [N][C][S][2] per-split partial moments {mean_b, M2_b}.  A split
+//            accumulates sum(x-K), sum((x-K)^2) about a pivot K = its first pixel
 //            (no cancellation for |mean| >> std), converts to (mean_b, M2_b); consumers merge the S partials with
 //            Chan's formula.  The header makes the buffer self-describing: a batch prefix (the first n images) is a
 //            valid stats buffer for that prefix whatever split count the consumer's own launch would pick.
 //   sums   : opaque fp32 buffer [N][C][S][4] of per-split backward sums, summed by the consumer in split order.
 //   y  = act( xhat * (1 + g_img + g_st) + (b_img + b_st) ),   xhat = (x - mean) * rstd
 #include "s2p_common.h"
+#include "norm_stats.h"
 #include <type_traits>
+
+// dL/dv of the tanh activation from dL/dy = d and the modulated value v: tanh' = 1 - tanh(v)^2, from the same tanhf as the forward.
+// (relu / lrelu / none stay spelled out in the two kernels below: in_reduce_kernel multiplies by the selected factor, in_apply_kernel
+// selects between the two products -- the same value, but not the same instructions)
+__device__ __forceinline__ float tanh_bwd_value(float d, float v) { const float t = tanhf(v); return d * (1.f - t * t); }
 
 struct NormArgs {
   const void* x; const void* da; const void* gb; const float* gbst; const float* stats; float* sums;
@@ -22,7 +29,6 @@ struct NormArgs {
   int psplit, rows_per_split;       // geometry of THIS launch
   int q_split;                      // geometry of the backward-sum partials (bwd apply merges q_split entries)
 };
-constexpr int STATS_HDR = 4;        // header words in front of the partial moments
 
 // split geometry of the reductions: aim at >= 1024 workgroups, at least 128 pixels per split
 static inline int stats_splits(int N, int HW, int C) {
@@ -31,35 +37,6 @@ static inline int stats_splits(int N, int HW, int C) {
   int maxps = cdiv(HW, 128); if (ps > maxps) ps = maxps; if (ps < 1) ps = 1;
   int rows = cdiv(HW, ps);
   return cdiv(HW, rows);
-}
-
-// merge the per-split partial moments of channel c of image n (fixed order: bitwise reproducible)
-__device__ __forceinline__ void mean_rstd(const NormArgs& a, int n, int c, float& mean, float& rstd) {
-  const int S = ((const int*)a.stats)[0], rows = ((const int*)a.stats)[1];
-  const float* p = a.stats + STATS_HDR + ((size_t)n * a.C + c) * S * 2;
-  const float inv = 1.f / (float)a.HW;
-  const float m0 = p[0];                               // merge about the first split's mean: the differences are O(std)
-  float m = 0.f;
-  for (int b = 1; b < S; ++b) {
-    int nb = a.HW - b * rows; if (nb > rows) nb = rows;
-    m += (float)nb * (p[2 * b] - m0);
-  }
-  m = m0 + m * inv;
-  float M2 = 0.f;
-  for (int b = 0; b < S; ++b) {
-    int nb = a.HW - b * rows; if (nb > rows) nb = rows;
-    const float d = p[2 * b] - m;
-    M2 += p[2 * b + 1] + (float)nb * d * d;
-  }
-  mean = m;
-  rstd = 1.f / sqrtf(M2 * inv + a.eps);
-}
-
-// the modulated value, written ONCE so that forward, backward-reduce and backward-apply round identically (the
-// backward re-derives the activation mask from it)
-__device__ __forceinline__ float mat_value(float x, float mean, float rstd, float gg, float bb, float& xh) {
-  xh = (x - mean) * rstd;
-  return __builtin_fmaf(xh, gg, bb);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -98,8 +75,8 @@ __global__ __launch_bounds__(256) void in_reduce_kernel(const NormArgs a) {
       const int c = blockIdx.x * CS + tid;
       float m = 0.f, r = 0.f, g1 = 1.f, b1 = 0.f;
       if (c < a.C) {
-        mean_rstd(a, n, c, m, r);
-        if (a.gbst) { g1 = 1.f + a.gbst[(size_t)n * a.gbst_pitch + c]; b1 = a.gbst[(size_t)n * a.gbst_pitch + a.C + c]; }
+        stats_mean_rstd(a.stats, n, a.C, c, a.HW, a.eps, m, r);
+        const StateAffine sa = state_affine(a.gbst, a.gbst_pitch, n, c, a.C); g1 = sa.g1; b1 = sa.b1;
       }
       cst[0][tid] = m; cst[1][tid] = r; cst[2][tid] = g1; cst[3][tid] = b1;
     }
@@ -132,26 +109,13 @@ __global__ __launch_bounds__(256) void in_reduce_kernel(const NormArgs a) {
           const T* gp = (const T*)a.gb + ((size_t)n * a.HW + p) * a.gb_pitch + c0;
           gv.raw = *(const u32x4*)gp; bv.raw = *(const u32x4*)(gp + a.C);
         }
-        if constexpr (TANH) {                           // tanh' = 1 - tanh(v)^2, from the same tanhf as the forward
-#pragma unroll
-          for (int e = 0; e < CE; ++e) {
-            float gg = gs[e] + (a.gb ? gv.get(e) : 0.f);
-            float bb = bs[e] + (a.gb ? bv.get(e) : 0.f);
-            float xh;
-            const float t = tanhf(mat_value(xv.get(e), mean[e], rstd[e], gg, bb, xh));
-            float dy = dv.get(e) * (1.f - t * t);
-            float dxh = dy * gg;
-            q[0][e] += dxh; q[1][e] += dxh * xh; q[2][e] += dy * xh; q[3][e] += dy;
-          }
-          continue;
-        }
 #pragma unroll
         for (int e = 0; e < CE; ++e) {
           float gg = gs[e] + (a.gb ? gv.get(e) : 0.f);
           float bb = bs[e] + (a.gb ? bv.get(e) : 0.f);
           float xh;
           float yv = mat_value(xv.get(e), mean[e], rstd[e], gg, bb, xh);
-          float dy = dv.get(e) * (yv > 0.f ? 1.f : gneg);
+          float dy = TANH ? tanh_bwd_value(dv.get(e), yv) : dv.get(e) * (yv > 0.f ? 1.f : gneg);
           float dxh = dy * gg;
           q[0][e] += dxh; q[1][e] += dxh * xh; q[2][e] += dy * xh; q[3][e] += dy;
         }
@@ -180,9 +144,9 @@ __global__ __launch_bounds__(256) void in_reduce_kernel(const NormArgs a) {
         const float nb = (float)(p_end - p_begin);
         const float d = tot[0] / nb;                       // mean_b - pivot
         float M2 = tot[1] - tot[0] * d;
-        float* o = (float*)a.stats + STATS_HDR + (((size_t)n * a.C + c) * a.psplit + blockIdx.z) * 2;
+        float* o = stats_slot((float*)a.stats, n, a.C, c, a.psplit, blockIdx.z);
         o[0] = cst[0][tid] + d; o[1] = M2 > 0.f ? M2 : 0.f;
-        if (c == 0 && n == 0 && blockIdx.z == 0) *(i32x4*)a.stats = (i32x4){a.psplit, a.rows_per_split, 0, 0};
+        if (c == 0 && n == 0 && blockIdx.z == 0) stats_store_header((float*)a.stats, a.psplit, a.rows_per_split);
       } else {
         float* o = a.sums + (((size_t)n * a.C + c) * a.psplit + blockIdx.z) * 4;
         *(f32x4*)o = (f32x4){tot[0], tot[1], tot[2], tot[3]};
@@ -212,8 +176,8 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const NormArgs a) {
     const int c = blockIdx.x * CS + tid;
     float m = 0.f, r = 0.f, g1 = 1.f, b1 = 0.f, q1 = 0.f, q2 = 0.f;
     if (c < a.C) {
-      mean_rstd(a, n, c, m, r);
-      if (a.gbst) { g1 = 1.f + a.gbst[(size_t)n * a.gbst_pitch + c]; b1 = a.gbst[(size_t)n * a.gbst_pitch + a.C + c]; }
+      stats_mean_rstd(a.stats, n, a.C, c, a.HW, a.eps, m, r);
+      const StateAffine sa = state_affine(a.gbst, a.gbst_pitch, n, c, a.C); g1 = sa.g1; b1 = sa.b1;
       if (MODE == 1) {
         const float* sm = a.sums + ((size_t)n * a.C + c) * a.q_split * 4;
         float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
@@ -263,22 +227,9 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const NormArgs a) {
         v0[e] = lrelu_ns(yv, ns);
       } else {
         const float dvv = dv.get(e);
-        float dy = yv > 0.f ? dvv : dvv * ns;
+        float dy = TANH ? tanh_bwd_value(dvv, yv) : (yv > 0.f ? dvv : dvv * ns);
         float dxh = dy * gg;
         v0[e] = rstd[e] * (dxh - s1[e] - xh * s2[e]);
-        v1[e] = dy * xh;
-        v2[e] = dy;
-      }
-    }
-    if constexpr (MODE == 1 && TANH) {                // tanh' = 1 - tanh(v)^2 (in_reduce_kernel's)
-#pragma unroll
-      for (int e = 0; e < CE; ++e) {
-        float gg = gs[e] + (gbb ? gv.get(e) : 0.f);
-        float bb = bs[e] + (gbb ? bv.get(e) : 0.f);
-        float xh;
-        const float t = tanhf(mat_value(xv.get(e), mean[e], rstd[e], gg, bb, xh));
-        const float dy = dv.get(e) * (1.f - t * t);
-        v0[e] = rstd[e] * (dy * gg - s1[e] - xh * s2[e]);
         v1[e] = dy * xh;
         v2[e] = dy;
       }
@@ -422,11 +373,11 @@ __global__ __launch_bounds__(TH, (MP > 14 || TH == 1024) ? 1 : 4) void in_fused_
   if (tid < CS) {
     const int c = slab * CS + tid;
     if (c < a.C) {
-      float* o = (float*)a.stats + STATS_HDR + ((size_t)n * a.C + c) * 2;
+      float* o = stats_slot((float*)a.stats, n, a.C, c, 1, 0);
       o[0] = cst[0][tid] * inv; o[1] = cst[1][tid];
-      if (c == 0 && n == 0) *(i32x4*)a.stats = (i32x4){1, a.HW, 0, 0};
-      cst[2][tid] = a.gbst ? 1.f + a.gbst[(size_t)n * a.gbst_pitch + c] : 1.f;
-      cst[3][tid] = a.gbst ? a.gbst[(size_t)n * a.gbst_pitch + a.C + c] : 0.f;
+      if (c == 0 && n == 0) stats_store_header((float*)a.stats, 1, a.HW);
+      const StateAffine sa = state_affine(a.gbst, a.gbst_pitch, n, c, a.C);
+      cst[2][tid] = sa.g1; cst[3][tid] = sa.b1;
     }
   }
   __syncthreads();
@@ -449,9 +400,8 @@ __global__ __launch_bounds__(TH, (MP > 14 || TH == 1024) ? 1 : 4) void in_fused_
     for (int e = 0; e < CE; ++e) {
       float gg = gs[e] + ((GB && gbb) ? gv[k % MG].get(e) : 0.f);
       float bb = bs[e] + ((GB && gbb) ? bv[k % MG].get(e) : 0.f);
-      // mat_value's arithmetic, bit for bit: ((x - mean) * rstd) * gg + bb
-      const float xh = (KEEP ? xf[KEEP ? k : 0][e] : xv[k].get(e) - mean[e]) * rstd[e];
-      ov[e] = lrelu_ns(__builtin_fmaf(xh, gg, bb), ns);
+      float xh;
+      ov[e] = lrelu_ns(mat_value_centred(KEEP ? xf[KEEP ? k : 0][e] : xv[k].get(e) - mean[e], rstd[e], gg, bb, xh), ns);
     }
     o0.pack(ov);
     *(u32x4*)(yb + (size_t)p * a.y_pitch) = o0.raw;
@@ -500,8 +450,8 @@ __global__ __launch_bounds__(TH) void in_fused_bwd_kernel(const NormArgs a) {
     const int c = slab * CS + tid;
     float m = 0.f, r = 0.f, g1 = 1.f, b1 = 0.f;
     if (c < a.C) {
-      mean_rstd(a, n, c, m, r);
-      if (a.gbst) { g1 = 1.f + a.gbst[(size_t)n * a.gbst_pitch + c]; b1 = a.gbst[(size_t)n * a.gbst_pitch + a.C + c]; }
+      stats_mean_rstd(a.stats, n, a.C, c, a.HW, a.eps, m, r);
+      const StateAffine sa = state_affine(a.gbst, a.gbst_pitch, n, c, a.C); g1 = sa.g1; b1 = sa.b1;
     }
     cst[0][tid] = m; cst[1][tid] = r; cst[2][tid] = g1; cst[3][tid] = b1;
   }
@@ -656,17 +606,85 @@ static int norm_check(const char* who, int dtype, int C, int p0, int p1, int p2)
   return 0;
 }
 
+// ---- NormArgs: one builder per direction.  A launch reads the fields of its own form only; what an entry point does not have is 0 ----
+static NormArgs fwd_args(const void* x, int N, int HW, int C, int pitch, const float* stats, const void* gb_img, int gb_pitch,
+                         const float* gb_st, int gb_st_pitch, int act, float slope, float eps, void* y, int y_pitch) {
+  NormArgs a{}; a.x = x; a.stats = stats; a.gb = gb_img; a.gbst = gb_st; a.y = y; a.act = act; a.slope = slope; a.eps = eps;
+  a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.gb_pitch = gb_pitch; a.gbst_pitch = gb_st_pitch; a.y_pitch = y_pitch;
+  return a;
+}
+// backward: the forward's operands, dL/dy, the outputs (dx in the place of y) and the optional skip gradient
+static NormArgs bwd_args(const void* da, int da_pitch, const void* x, int N, int HW, int C, int pitch, const float* stats,
+                         const void* gb_img, int gb_pitch, const float* gb_st, int gb_st_pitch, int act, float slope, float eps,
+                         const float* sums, void* dx, int dx_pitch, void* dgb_img, int dgb_pitch, float* dgb_st, int dgb_st_pitch,
+                         const void* res, int res_pitch) {
+  NormArgs a = fwd_args(x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps, dx, dx_pitch);
+  a.da = da; a.da_pitch = da_pitch; a.sums = (float*)sums; a.res = res; a.res_pitch = res_pitch;
+  a.dgb = dgb_img; a.dgb_pitch = dgb_pitch; a.dgbst = dgb_st; a.dgbst_pitch = dgb_st_pitch;
+  return a;
+}
+// what the launches that write dx / dgb_img / dgb_st refuse
+static int bwd_out_check(const char* who, int dtype, int C, int dx_pitch, int dgb_pitch, const float* dgb_st, int dgb_st_pitch) {
+  const int ce = dtype == S2P_F32 ? 4 : 8;
+  if (dx_pitch % ce || dgb_pitch % ce) S2P_FAIL(-1, "%s: bad output pitch", who);
+  if (dgb_st && dgb_st_pitch < 2 * C) S2P_FAIL(-1, "%s: dgb_st pitch < 2*C", who);
+  return 0;
+}
+
+// ---- launch forms (S2P_NORM_FORM_*, s2p_hip.h): norm_fwd_form / norm_bwd_form are the whole rule, and the only readers of the A/B
+// switches (diagnostics build; in the product build every switch is the constant 0 and they are pure functions of their arguments)
+static inline bool norm_simple_act(int act) { return act == S2P_ACT_NONE || act == S2P_ACT_RELU || act == S2P_ACT_LRELU; }   // tanh / swish: the pair
+static inline int norm_maxhw(int dtype) { return dtype == S2P_F32 ? 256 : 512; }          // largest plane of the fused small-plane kernels
+// plain InstanceNorm (no gamma / beta maps): 256 threads for planes of <= 256 (bf16) / 128 (fp32) pixels, 512 up to twice those; else 1024
+static inline int norm_small_form(int dtype, int HW, bool plain, bool use512) {
+  const int lim = dtype == S2P_F32 ? 128 : 256;
+  return (plain && HW <= lim) ? S2P_NORM_FORM_F256 : ((plain && HW <= 2 * lim && use512) ? S2P_NORM_FORM_F512 : S2P_NORM_FORM_F1024);
+}
+
+static int norm_fwd_form(int dtype, int N, int HW, int C, bool gb_img, int act) {
+  const bool no_fused = s2p_env_set("S2P_NO_FUSED_NORM"), simple = norm_simple_act(act);
+  if (dtype == S2P_BF16 && HW > norm_maxhw(dtype) && simple && !gb_img && S2P_DIAG_SWITCH(9) != 1 && !no_fused) {
+    // large planes, plain InstanceNorm: the register-resident form (see in_fused_fwd_kernel, MP)
+    // planes of <= 1792 pixels: 64-channel slabs at 28 chunks per thread, or -- when those are fewer workgroups than CUs (42x42 x 128 at
+    // N 64: 128) -- 32-channel slabs at 14 chunks (twice the workgroups, 56 VGPRs of payload: round 4 measured 16.9 vs 21.3 us on that
+    // plane and rejected the half slabs only because the SAME switch also halved the 84x84 planes' slabs, 51 vs 36 us)
+    int cs = (HW <= 28 * 64 && C % 64 == 0) ? 64 : ((HW <= 28 * 256 && C % 16 == 0) ? 16 : 0);
+    if (cs == 64 && HW <= 14 * 128 && C % 32 == 0 && N * (C / 64) < 256 && !S2P_DIAG_SWITCH(11)) cs = 32;
+    if (cs && N * (C / cs) >= 64)          // (a handful of workgroups: the two-kernel path spreads over more CUs)
+      return cs == 64 ? S2P_NORM_FORM_L64X28 : (cs == 32 ? S2P_NORM_FORM_L32X14 : S2P_NORM_FORM_L16X28);
+  }
+  if (HW > norm_maxhw(dtype) || !simple || no_fused) return S2P_NORM_FORM_PAIR;
+  const int form = norm_small_form(dtype, HW, !gb_img && !s2p_env_set("S2P_NORM_NO_SMALL"), !s2p_env_set("S2P_NORM_NO_512"));
+  // 32-channel slabs (twice the workgroups, two per CU) were measured and lost: 24.2 vs 20.5 us on the MAT norms -- the
+  // 64-byte half-line accesses cost more than the extra overlap buys.  Kept selectable in the diagnostics build only.
+  return (form == S2P_NORM_FORM_F1024 && s2p_env_set("S2P_NORM_CS32") && C % 32 == 0) ? S2P_NORM_FORM_F1024_CS32 : form;
+}
+
+static int norm_bwd_form(int dtype, int /*N*/, int HW, int C, bool gb_img, bool dgb_img, int act) {
+  if (HW > norm_maxhw(dtype) || !norm_simple_act(act) || s2p_env_set("S2P_NO_FUSED_NORM")) return S2P_NORM_FORM_PAIR;
+  const int form = norm_small_form(dtype, HW, !gb_img && !dgb_img && !s2p_env_set("S2P_NORM_NO_SMALL"), !s2p_env_set("S2P_NORM_NO_512"));
+  return (form == S2P_NORM_FORM_F1024 && s2p_env_set("S2P_NORM_CS32") && C % 32 == 0) ? S2P_NORM_FORM_F1024_CS32 : form;   // (see norm_fwd_form)
+}
+
+extern "C" int s2p_in_norm_form(int dtype, int N, int HW, int C, int has_gb_img, int wants_dgb_img, int act, int backward) {
+  int rc = norm_check("s2p_in_norm_form", dtype, C, 0, 0, 0); if (rc) return rc;
+  if (N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_norm_form: empty problem");
+  return backward ? norm_bwd_form(dtype, N, HW, C, has_gb_img != 0, wants_dgb_img != 0, act)
+                  : norm_fwd_form(dtype, N, HW, C, has_gb_img != 0, act);
+}
+
+// ---- one launch helper per kernel family: the tanh instantiation and the launch check once; the dtype ladder once for all of them -----
+#define NORM_LAUNCH(kernel, grid, threads, ...) do { \
+    if (dtype == S2P_F32) hipLaunchKernelGGL((kernel<float, __VA_ARGS__>), grid, dim3(threads), 0, st, a); \
+    else hipLaunchKernelGGL((kernel<__bf16, __VA_ARGS__>), grid, dim3(threads), 0, st, a); } while (0)
 template <int MODE>
 static int launch_reduce(int dtype, NormArgs& a, hipStream_t st) {
   int slabs = cdiv(a.C, 64);
   a.psplit = stats_splits(a.N, a.HW, a.C); a.rows_per_split = cdiv(a.HW, a.psplit);
   a.q_split = a.psplit;
   dim3 grid(slabs, a.N, a.psplit);
-  if (MODE == 1 && a.act == S2P_ACT_TANH) {
-    if (dtype == S2P_F32) hipLaunchKernelGGL((in_reduce_kernel<float, MODE, MODE == 1>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((in_reduce_kernel<__bf16, MODE, MODE == 1>), grid, dim3(256), 0, st, a);
-  } else if (dtype == S2P_F32) hipLaunchKernelGGL((in_reduce_kernel<float, MODE>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((in_reduce_kernel<__bf16, MODE>), grid, dim3(256), 0, st, a);
+  if (MODE == 1 && a.act == S2P_ACT_TANH) NORM_LAUNCH(in_reduce_kernel, grid, 256, MODE, MODE == 1);
+  else NORM_LAUNCH(in_reduce_kernel, grid, 256, MODE, false);
   S2P_CHECK_LAUNCH("in_reduce_kernel");
   return 0;
 }
@@ -679,14 +697,31 @@ static int launch_apply(int dtype, NormArgs& a, hipStream_t st) {
   int maxps = cdiv(a.HW, 64); if (ps > maxps) ps = maxps; if (ps < 1) ps = 1;
   a.psplit = ps; a.rows_per_split = cdiv(a.HW, ps);
   dim3 grid(slabs, a.N, cdiv(a.HW, a.rows_per_split));
-  if (MODE == 1 && a.act == S2P_ACT_TANH) {
-    if (dtype == S2P_F32) hipLaunchKernelGGL((in_apply_kernel<float, MODE, MODE == 1>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((in_apply_kernel<__bf16, MODE, MODE == 1>), grid, dim3(256), 0, st, a);
-  } else if (dtype == S2P_F32) hipLaunchKernelGGL((in_apply_kernel<float, MODE>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((in_apply_kernel<__bf16, MODE>), grid, dim3(256), 0, st, a);
+  if (MODE == 1 && a.act == S2P_ACT_TANH) NORM_LAUNCH(in_apply_kernel, grid, 256, MODE, MODE == 1);
+  else NORM_LAUNCH(in_apply_kernel, grid, 256, MODE, false);
   S2P_CHECK_LAUNCH("in_apply_kernel");
   return 0;
 }
+
+// the fused kernels: grid = (images, CS-channel slabs).  MP > 0: the large-plane forms, bf16 only
+#define S2P_FUSED_LABEL(kernel, MP) (MP ? kernel " (large planes)" : (TH != 1024 ? kernel " (small planes)" : kernel))
+template <int CS, int TH, bool GB, int MP = 0>
+static int launch_fused_fwd(int dtype, const NormArgs& a, hipStream_t st) {
+  const dim3 grid(a.N, cdiv(a.C, CS));
+  if constexpr (MP == 0) NORM_LAUNCH(in_fused_fwd_kernel, grid, TH, CS, TH, GB, 0);
+  else hipLaunchKernelGGL((in_fused_fwd_kernel<__bf16, CS, TH, GB, MP>), grid, dim3(TH), 0, st, a);
+  S2P_CHECK_LAUNCH(S2P_FUSED_LABEL("in_fused_fwd_kernel", MP));
+  return 0;
+}
+template <int CS, int TH, bool GB>
+static int launch_fused_bwd(int dtype, const NormArgs& a, hipStream_t st) {
+  const dim3 grid(a.N, cdiv(a.C, CS));
+  NORM_LAUNCH(in_fused_bwd_kernel, grid, TH, CS, TH, GB);
+  S2P_CHECK_LAUNCH(S2P_FUSED_LABEL("in_fused_bwd_kernel", 0));
+  return 0;
+}
+#undef S2P_FUSED_LABEL
+#undef NORM_LAUNCH
 
 extern "C" int64_t s2p_in_stats_floats(int N, int HW, int C) {
   if (N <= 0 || HW <= 0 || C <= 0) return 0;
@@ -702,7 +737,7 @@ extern "C" int s2p_in_stats(int dtype, const void* x, int N, int HW, int C, int 
                             void* stream) {
   int rc = norm_check("s2p_in_stats", dtype, C, pitch, 0, 0); if (rc) return rc;
   if (!x || !stats || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_stats: null pointer / empty problem");
-  NormArgs a{}; a.x = x; a.stats = stats; a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.eps = eps;
+  NormArgs a = fwd_args(x, N, HW, C, pitch, stats, nullptr, 0, nullptr, 0, S2P_ACT_NONE, 0.f, eps, nullptr, 0);
   return launch_reduce<0>(dtype, a, (hipStream_t)stream);
 }
 
@@ -712,76 +747,31 @@ extern "C" int s2p_in_apply_fwd(int dtype, const void* x, int N, int HW, int C, 
   int rc = norm_check("s2p_in_apply_fwd", dtype, C, pitch, gb_pitch, y_pitch); if (rc) return rc;
   S2P_CHECK_SLOPE("s2p_in_apply_fwd", act, slope);
   if (!x || !stats || !y || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_apply_fwd: null pointer / empty problem");
-  NormArgs a{}; a.x = x; a.stats = stats; a.gb = gb_img; a.gbst = gb_st; a.y = y;
-  a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.gb_pitch = gb_pitch; a.gbst_pitch = gb_st_pitch;
-  a.y_pitch = y_pitch; a.act = act; a.slope = slope; a.eps = eps;
+  NormArgs a = fwd_args(x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps, y, y_pitch);
   return launch_apply<0>(dtype, a, (hipStream_t)stream);
 }
 
-// the 256-thread form of the fused kernels: plain InstanceNorm (no gamma/beta maps) on planes of <= 256 (bf16) / 128 (fp32) pixels
-// (returns the workgroup size: 256, 512 for up to twice those planes, or 0: the 1024-thread form)
-static inline int small_plane(int dtype, int HW, const void* gb_img) {
-  static const int off = s2p_env_set("S2P_NORM_NO_SMALL");          // A/B switches (diagnostics build only)
-  static const int no512 = s2p_env_set("S2P_NORM_NO_512");
-  if (off || gb_img) return 0;
-  const int lim = dtype == S2P_F32 ? 128 : 256;
-  return HW <= lim ? 256 : (HW <= 2 * lim && !no512 ? 512 : 0);
-}
-
-// statistics + apply in one call: one fused launch for small planes, otherwise the two-kernel path
+// statistics + apply in one call: one fused launch where the form rule finds one, otherwise the two-kernel path
 extern "C" int s2p_in_norm_fwd(int dtype, const void* x, int N, int HW, int C, int pitch, const void* gb_img, int gb_pitch,
                                const float* gb_st, int gb_st_pitch, int act, float slope, float eps, void* y, int y_pitch,
                                float* stats, void* stream) {
   int rc = norm_check("s2p_in_norm_fwd", dtype, C, pitch, gb_pitch, y_pitch); if (rc) return rc;
   S2P_CHECK_SLOPE("s2p_in_norm_fwd", act, slope);
   if (!x || !y || !stats || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_norm_fwd: null pointer / empty problem");
-  const int maxhw = dtype == S2P_F32 ? 256 : 512;
-  const bool simple_act = act == S2P_ACT_NONE || act == S2P_ACT_RELU || act == S2P_ACT_LRELU;   // tanh / swish: two-kernel path
-  if (dtype == S2P_BF16 && HW > maxhw && simple_act && !gb_img && S2P_DIAG_SWITCH(9) != 1 && !s2p_env_set("S2P_NO_FUSED_NORM")) {
-    // large planes, plain InstanceNorm: the register-resident form (see in_fused_fwd_kernel, MP)
-    // planes of <= 1792 pixels: 64-channel slabs at 28 chunks per thread, or -- when those are fewer workgroups than CUs (42x42 x 128 at
-    // N 64: 128) -- 32-channel slabs at 14 chunks (twice the workgroups, 56 VGPRs of payload: round 4 measured 16.9 vs 21.3 us on that
-    // plane and rejected the half slabs only because the SAME switch also halved the 84x84 planes' slabs, 51 vs 36 us)
-    int cs = (HW <= 28 * 64 && C % 64 == 0) ? 64 : ((HW <= 28 * 256 && C % 16 == 0) ? 16 : 0);
-    if (cs == 64 && HW <= 14 * 128 && C % 32 == 0 && N * (C / 64) < 256 && !S2P_DIAG_SWITCH(11)) cs = 32;
-    if (cs && N * (C / cs) >= 64) {        // (a handful of workgroups: the two-kernel path spreads over more CUs)
-      NormArgs a{}; a.x = x; a.stats = stats; a.gbst = gb_st; a.y = y;
-      a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.gbst_pitch = gb_st_pitch; a.y_pitch = y_pitch; a.act = act; a.slope = slope; a.eps = eps;
-      const dim3 lg(N, C / cs);
-      if (cs == 64) hipLaunchKernelGGL((in_fused_fwd_kernel<__bf16, 64, 512, false, 28>), lg, dim3(512), 0, (hipStream_t)stream, a);
-      else if (cs == 32) hipLaunchKernelGGL((in_fused_fwd_kernel<__bf16, 32, 512, false, 14>), lg, dim3(512), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((in_fused_fwd_kernel<__bf16, 16, 512, false, 28>), lg, dim3(512), 0, (hipStream_t)stream, a);
-      S2P_CHECK_LAUNCH("in_fused_fwd_kernel (large planes)");
-      return 0;
-    }
-  }
-  if (HW > maxhw || !simple_act || s2p_env_set("S2P_NO_FUSED_NORM")) {
-    rc = s2p_in_stats(dtype, x, N, HW, C, pitch, eps, stats, stream); if (rc) return rc;
-    return s2p_in_apply_fwd(dtype, x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps, y, y_pitch, stream);
-  }
-  NormArgs a{}; a.x = x; a.stats = stats; a.gb = gb_img; a.gbst = gb_st; a.y = y;
-  a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.gb_pitch = gb_pitch; a.gbst_pitch = gb_st_pitch;
-  a.y_pitch = y_pitch; a.act = act; a.slope = slope; a.eps = eps;
-  // 32-channel slabs (twice the workgroups, two per CU) were measured and lost: 24.2 vs 20.5 us on the MAT norms -- the
-  // 64-byte half-line accesses cost more than the extra overlap buys.  Kept selectable in the diagnostics build only.
-  const bool half = s2p_env_set("S2P_NORM_CS32") && C % 32 == 0;
-  dim3 grid(N, cdiv(C, half ? 32 : 64));
+  const NormArgs a = fwd_args(x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps, y, y_pitch);
   hipStream_t st = (hipStream_t)stream;
-  if (const int th = small_plane(dtype, HW, gb_img)) {
-    const dim3 sg(N, cdiv(C, 64));
-    if (th == 256) { if (dtype == S2P_F32) hipLaunchKernelGGL((in_fused_fwd_kernel<float, 64, 256, false>), sg, dim3(256), 0, st, a);
-                     else hipLaunchKernelGGL((in_fused_fwd_kernel<__bf16, 64, 256, false>), sg, dim3(256), 0, st, a); }
-    else { if (dtype == S2P_F32) hipLaunchKernelGGL((in_fused_fwd_kernel<float, 64, 512, false>), sg, dim3(512), 0, st, a);
-           else hipLaunchKernelGGL((in_fused_fwd_kernel<__bf16, 64, 512, false>), sg, dim3(512), 0, st, a); }
-    S2P_CHECK_LAUNCH("in_fused_fwd_kernel (small planes)");
-    return 0;
+  switch (norm_fwd_form(dtype, N, HW, C, gb_img != nullptr, act)) {
+    case S2P_NORM_FORM_F256: return launch_fused_fwd<64, 256, false>(dtype, a, st);
+    case S2P_NORM_FORM_F512: return launch_fused_fwd<64, 512, false>(dtype, a, st);
+    case S2P_NORM_FORM_F1024: return launch_fused_fwd<64, 1024, true>(dtype, a, st);
+    case S2P_NORM_FORM_F1024_CS32: return launch_fused_fwd<32, 1024, true>(dtype, a, st);
+    case S2P_NORM_FORM_L64X28: return launch_fused_fwd<64, 512, false, 28>(dtype, a, st);
+    case S2P_NORM_FORM_L32X14: return launch_fused_fwd<32, 512, false, 14>(dtype, a, st);
+    case S2P_NORM_FORM_L16X28: return launch_fused_fwd<16, 512, false, 28>(dtype, a, st);
+    default: break;                                                       // S2P_NORM_FORM_PAIR
   }
-  if (dtype == S2P_F32) { if (half) hipLaunchKernelGGL((in_fused_fwd_kernel<float, 32>), grid, dim3(1024), 0, st, a);
-                          else hipLaunchKernelGGL((in_fused_fwd_kernel<float, 64>), grid, dim3(1024), 0, st, a); }
-  else { if (half) hipLaunchKernelGGL((in_fused_fwd_kernel<__bf16, 32>), grid, dim3(1024), 0, st, a);
-         else hipLaunchKernelGGL((in_fused_fwd_kernel<__bf16, 64>), grid, dim3(1024), 0, st, a); }
-  S2P_CHECK_LAUNCH("in_fused_fwd_kernel");
-  return 0;
+  rc = s2p_in_stats(dtype, x, N, HW, C, pitch, eps, stats, stream); if (rc) return rc;
+  return s2p_in_apply_fwd(dtype, x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps, y, y_pitch, stream);
 }
 
 extern "C" int s2p_in_bwd_reduce(int dtype, const void* da, int da_pitch, const void* x, int N, int HW, int C,
@@ -791,9 +781,8 @@ extern "C" int s2p_in_bwd_reduce(int dtype, const void* da, int da_pitch, const 
   int rc = norm_check("s2p_in_bwd_reduce", dtype, C, pitch, gb_pitch, da_pitch); if (rc) return rc;
   S2P_CHECK_ACT_FROM_OUT("s2p_in_bwd_reduce", act);
   if (!da || !x || !stats || !sums || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_bwd_reduce: null pointer / empty problem");
-  NormArgs a{}; a.x = x; a.da = da; a.stats = stats; a.gb = gb_img; a.gbst = gb_st; a.sums = sums;
-  a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.da_pitch = da_pitch; a.gb_pitch = gb_pitch;
-  a.gbst_pitch = gb_st_pitch; a.act = act; a.slope = slope; a.eps = eps;
+  NormArgs a = bwd_args(da, da_pitch, x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps, sums,
+                        nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0);
   return launch_reduce<1>(dtype, a, (hipStream_t)stream);
 }
 
@@ -805,14 +794,9 @@ extern "C" int s2p_in_bwd_apply(int dtype, const void* da, int da_pitch, const v
   int rc = norm_check("s2p_in_bwd_apply", dtype, C, pitch, gb_pitch, da_pitch); if (rc) return rc;
   S2P_CHECK_ACT_FROM_OUT("s2p_in_bwd_apply", act);
   if (!da || !x || !stats || !sums || !dx || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_bwd_apply: null pointer / empty problem");
-  if (dx_pitch % (dtype == S2P_F32 ? 4 : 8) || dgb_pitch % (dtype == S2P_F32 ? 4 : 8))
-    S2P_FAIL(-1, "s2p_in_bwd_apply: bad output pitch");
-  if (dgb_st && dgb_st_pitch < 2 * C) S2P_FAIL(-1, "s2p_in_bwd_apply: dgb_st pitch < 2*C");
-  NormArgs a{}; a.x = x; a.da = da; a.stats = stats; a.gb = gb_img; a.gbst = gb_st; a.sums = (float*)sums;
-  a.y = dx; a.dgb = dgb_img; a.dgbst = dgb_st; a.dgbst_pitch = dgb_st_pitch;
-  a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.da_pitch = da_pitch; a.gb_pitch = gb_pitch;
-  a.gbst_pitch = gb_st_pitch; a.y_pitch = dx_pitch; a.dgb_pitch = dgb_pitch; a.act = act; a.slope = slope;
-  a.eps = eps;
+  rc = bwd_out_check("s2p_in_bwd_apply", dtype, C, dx_pitch, dgb_pitch, dgb_st, dgb_st_pitch); if (rc) return rc;
+  NormArgs a = bwd_args(da, da_pitch, x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps, sums,
+                        dx, dx_pitch, dgb_img, dgb_pitch, dgb_st, dgb_st_pitch, nullptr, 0);
   return launch_apply<1>(dtype, a, (hipStream_t)stream);
 }
 
@@ -833,9 +817,8 @@ extern "C" int s2p_in_norm_bwd_res(int dtype, const void* da, int da_pitch, cons
   S2P_CHECK_ACT_FROM_OUT("s2p_in_norm_bwd", act);
   if (!da || !x || !stats || !dx || N <= 0 || HW <= 0) S2P_FAIL(-1, "s2p_in_norm_bwd: null pointer / empty problem");
   if (res && (res_pitch != dx_pitch || dx_pitch != C)) S2P_FAIL(-1, "s2p_in_norm_bwd_res: res must have the layout of dx (pitch == C)");
-  const int maxhw = dtype == S2P_F32 ? 256 : 512;
-  const bool simple_act = act == S2P_ACT_NONE || act == S2P_ACT_RELU || act == S2P_ACT_LRELU;
-  if (HW > maxhw || !simple_act || s2p_env_set("S2P_NO_FUSED_NORM")) {
+  const int form = norm_bwd_form(dtype, N, HW, C, gb_img != nullptr, dgb_img != nullptr, act);
+  if (form == S2P_NORM_FORM_PAIR) {
     if (!sums) S2P_FAIL(-1, "s2p_in_norm_bwd: the two-kernel path needs the `sums` workspace");
     rc = s2p_in_bwd_reduce(dtype, da, da_pitch, x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps,
                            sums, stream);
@@ -845,32 +828,16 @@ extern "C" int s2p_in_norm_bwd_res(int dtype, const void* da, int da_pitch, cons
     if (rc || !res) return rc;
     return s2p_add(dtype, dx, res, dx, (int64_t)N * HW * C, stream);          // two-kernel path: the residual is a third pass
   }
-  if (dx_pitch % (dtype == S2P_F32 ? 4 : 8) || dgb_pitch % (dtype == S2P_F32 ? 4 : 8))
-    S2P_FAIL(-1, "s2p_in_norm_bwd: bad output pitch");
-  if (dgb_st && dgb_st_pitch < 2 * C) S2P_FAIL(-1, "s2p_in_norm_bwd: dgb_st pitch < 2*C");
-  NormArgs a{}; a.x = x; a.da = da; a.stats = stats; a.gb = gb_img; a.gbst = gb_st;
-  a.y = dx; a.dgb = dgb_img; a.dgbst = dgb_st; a.dgbst_pitch = dgb_st_pitch;
-  a.N = N; a.HW = HW; a.C = C; a.x_pitch = pitch; a.da_pitch = da_pitch; a.gb_pitch = gb_pitch;
-  a.gbst_pitch = gb_st_pitch; a.y_pitch = dx_pitch; a.dgb_pitch = dgb_pitch; a.act = act; a.slope = slope; a.eps = eps;
-  a.res = res; a.res_pitch = res_pitch;
-  const bool half = s2p_env_set("S2P_NORM_CS32") && C % 32 == 0;
-  dim3 grid(N, cdiv(C, half ? 32 : 64));
+  rc = bwd_out_check("s2p_in_norm_bwd", dtype, C, dx_pitch, dgb_pitch, dgb_st, dgb_st_pitch); if (rc) return rc;
+  const NormArgs a = bwd_args(da, da_pitch, x, N, HW, C, pitch, stats, gb_img, gb_pitch, gb_st, gb_st_pitch, act, slope, eps, sums,
+                              dx, dx_pitch, dgb_img, dgb_pitch, dgb_st, dgb_st_pitch, res, res_pitch);
   hipStream_t st = (hipStream_t)stream;
-  if (const int th = dgb_img ? 0 : small_plane(dtype, HW, gb_img)) {
-    const dim3 sg(N, cdiv(C, 64));
-    if (th == 256) { if (dtype == S2P_F32) hipLaunchKernelGGL((in_fused_bwd_kernel<float, 64, 256, false>), sg, dim3(256), 0, st, a);
-                     else hipLaunchKernelGGL((in_fused_bwd_kernel<__bf16, 64, 256, false>), sg, dim3(256), 0, st, a); }
-    else { if (dtype == S2P_F32) hipLaunchKernelGGL((in_fused_bwd_kernel<float, 64, 512, false>), sg, dim3(512), 0, st, a);
-           else hipLaunchKernelGGL((in_fused_bwd_kernel<__bf16, 64, 512, false>), sg, dim3(512), 0, st, a); }
-    S2P_CHECK_LAUNCH("in_fused_bwd_kernel (small planes)");
-    return 0;
+  switch (form) {
+    case S2P_NORM_FORM_F256: return launch_fused_bwd<64, 256, false>(dtype, a, st);
+    case S2P_NORM_FORM_F512: return launch_fused_bwd<64, 512, false>(dtype, a, st);
+    case S2P_NORM_FORM_F1024_CS32: return launch_fused_bwd<32, 1024, true>(dtype, a, st);
+    default: return launch_fused_bwd<64, 1024, true>(dtype, a, st);     // S2P_NORM_FORM_F1024: the backward has no large-plane forms
   }
-  if (dtype == S2P_F32) { if (half) hipLaunchKernelGGL((in_fused_bwd_kernel<float, 32>), grid, dim3(1024), 0, st, a);
-                          else hipLaunchKernelGGL((in_fused_bwd_kernel<float, 64>), grid, dim3(1024), 0, st, a); }
-  else { if (half) hipLaunchKernelGGL((in_fused_bwd_kernel<__bf16, 32>), grid, dim3(1024), 0, st, a);
-         else hipLaunchKernelGGL((in_fused_bwd_kernel<__bf16, 64>), grid, dim3(1024), 0, st, a); }
-  S2P_CHECK_LAUNCH("in_fused_bwd_kernel");
-  return 0;
 }
 
 static void channel_sum_geom(int64_t pixels, int C, int& nb, int& rows) {

@@ -38,8 +38,9 @@ last chunk row, every register-slot boundary +- 1 and every split boundary +- 1 
 or counted twice in, the statistics changes the plane's rstd by a factor (HW 441: variance 1 vs 10.3); one dropped from a backward sum
 changes every dx of the plane by ~0.15.
 
-WHICH KERNEL RAN is unpinned but for word 0 of the statistics buffer (1 after a fused launch, S after the pair): test_case_geometry
-restates stats_splits, small_plane, the large-plane slab choice and the apply split in Python and asserts each named case's figures.
+WHICH KERNEL RAN is unpinned but for the header of the statistics buffer ({1, HW, 0, 0} after a fused launch, {S, rows, 0, 0} after the
+pair): test_case_geometry restates stats_splits, small_plane, the large-plane slab choice and the apply split in Python and asserts each
+named case's figures; test_form_rule_matches_library compares the restated form rule with the library's own (s2p_in_norm_form).
 Every call is made twice: outputs and the statistics buffer must be bit-identical.  Every output sits in a sentinel-filled allocation
 with 8 KiB bands (fp32 side buffers: guard_region.Region); pad columns and bands must keep the sentinel; input pads hold NaN.
 
@@ -111,6 +112,15 @@ def bwd_form(dtype, HW, gb, act):
     if HW > (256 if dtype == F32 else 512) or act not in SIMPLE:
         return "pair"
     return "f%d" % (small_plane(dtype, HW, gb) or 1024)           # (dgb_img is requested exactly where gb_img is given)
+
+
+FORM_NAME = {_lib.NORM_FORM_PAIR: "pair", _lib.NORM_FORM_F256: "f256", _lib.NORM_FORM_F512: "f512", _lib.NORM_FORM_F1024: "f1024",
+             _lib.NORM_FORM_L64X28: "L64x28", _lib.NORM_FORM_L32X14: "L32x14", _lib.NORM_FORM_L16X28: "L16x28"}
+
+
+def lib_form(dtype, N, HW, C, gb, act, backward):
+    """The library's own answer (s2p_in_norm_form: no launch, no device).  dgb_img is requested exactly where gb_img is given."""
+    return FORM_NAME[_lib.lib().s2p_in_norm_form(dtype_id(dtype), N, HW, C, int(gb), int(gb), act, int(backward))]
 
 
 def chunk_rows(dtype, form):
@@ -285,6 +295,35 @@ def test_case_geometry():
     # the batch prefix of test_batch_prefix, and the fused statistics of test_stats_across_forms
     assert stats_splits(64, 257, 512) == (2, 129) and stats_splits(32, 257, 512) == (3, 86)
     assert fwd_form(BF, 3, 400, 72, False, ACT_LRELU) == "f512" and stats_splits(3, 400, 72) == (4, 100)
+
+
+def test_form_rule_matches_library():
+    """Host only: the restated rule (fwd_form / bwd_form) against s2p_in_norm_form, for every case of the table and over a sweep with HW
+    on and either side of every threshold of the rule; what the query refuses."""
+    for cid, cs in CASES.items():
+        f, b = _forms(cs)
+        assert lib_form(cs.dtype, cs.N, cs.HW, cs.C, cs.gb, cs.act, False) == f, cid
+        if cs.bwd:
+            assert lib_form(cs.dtype, cs.N, cs.HW, cs.C, cs.gb, cs.act, True) == b, cid
+    n = 0
+    for dtype in (BF, F32):
+        for HW in [t + d for t in (128, 256, 512, 1792, 7168) for d in (-1, 0, 1)]:
+            for C in (8, 16, 32, 64, 72, 128, 1024, 4096):
+                for N in (1, 2, 4, 8, 64):
+                    for gb in (False, True):
+                        for act in ACT_NAME:
+                            key = (dtype, N, HW, C, gb, ACT_NAME[act])
+                            assert lib_form(dtype, N, HW, C, gb, act, False) == fwd_form(dtype, N, HW, C, gb, act), key
+                            assert lib_form(dtype, N, HW, C, gb, act, True) == bwd_form(dtype, HW, gb, act), key
+                            n += 1
+    assert n == 2 * 15 * 8 * 5 * 2 * 5
+    L = _lib.lib()
+    for bad in [(7, 2, 100, 64), (_lib.BF16, 0, 100, 64), (_lib.BF16, -1, 100, 64), (_lib.BF16, 2, 0, 64), (_lib.BF16, 2, -5, 64),
+                (_lib.BF16, 2, 100, 68), (_lib.F32, 2, 100, 6)]:
+        for backward in (0, 1):
+            assert L.s2p_in_norm_form(*bad, 0, 0, ACT_NONE, backward) == -1, bad
+            assert "s2p_in_norm_form" in L.s2p_last_error().decode(), bad
+    assert L.s2p_in_norm_form(_lib.F32, 2, 100, 68, 0, 0, ACT_NONE, 0) == _lib.NORM_FORM_F256
 
 
 # ---- operands, closed forms, bounds --------------------------------------------------------------------------------------------------
@@ -601,6 +640,10 @@ def test_parity(hip_device, cid):
     S = stats_splits(cs.N, cs.HW, cs.C)[0]
     if S > 1 or ff == "pair":
         assert _word0(stats) == (S if ff == "pair" else 1), (cid, ff, S)
+    # the whole header, against the library's own answer for the case: {1, HW, 0, 0} exactly when its forward form is not the pair
+    fused = cs.how == "norm" and lib_form(cs.dtype, cs.N, cs.HW, cs.C, cs.gb, cs.act, False) != "pair"
+    hdr = stats.bits("stats").view(torch.int32)[0, :4].tolist()
+    assert hdr == ([1, cs.HW, 0, 0] if fused else list(stats_splits(cs.N, cs.HW, cs.C)) + [0, 0]), (cid, hdr)
     _check("gpu", ff, cid, "y", y, k.f.y, _tol(k.f.y, k.dy, cs.dtype))
     if not cs.bwd:
         return
