@@ -32,12 +32,17 @@ def parse_args(argv=None):
     ap.add_argument("--slac_policy_input_type", choices=["feature_action", "latent_z"], default="feature_action")
     ap.add_argument("--fused_chain", action="store_true",
                     help="latent_z: run the posterior chain of every acting step as one launch (bitwise the same result)")
+    ap.add_argument("--bf16_chain", action="store_true",
+                    help="with --fused_chain: bf16 matrix-core compute inside the fused no-grad latent chain (SPEC.md N3m), independent of --bf16 and "
+                         "--bf16_mlp: weights and LDS activations rounded to bf16, fp32 sums, heads and outputs; mixed precision, not the same numbers")
     ap.add_argument("--reset_w_same_obs", action="store_true", help="pad a new episode's window with its first frame, not with zero frames")
     ap.add_argument("--bf16", action="store_true", help="bf16 conv stack of the encoder (the policy stays fp32)")
     ap.add_argument("--num_sequences", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0, help="seeds the posterior noise of latent_z")
     ap.add_argument("--out", help="write the per-episode arrays to this .npz")
     a = ap.parse_args(argv)
+    if a.bf16_chain and not a.fused_chain:
+        ap.error("--bf16_chain needs --fused_chain: the bf16 compute mode exists only in the fused chain kernels")
     if a.episodes < 0 or a.max_path_length < 1 or not 1 <= a.num_envs <= 16:
         ap.error("--episodes >= 0, --max_path_length >= 1 and 1 <= --num_envs <= 16")
     return a
@@ -96,6 +101,7 @@ def main(argv=None):
     latent = LatentModel(state_shape, (A,), dtype=torch.bfloat16 if a.bf16 else torch.float32, device="cuda:0")
     latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
     latent.fused_chain = a.fused_chain
+    latent.chain_compute = "bf16" if a.bf16_chain else "fp32"
     algo = types.SimpleNamespace(latent=latent, state_shape=state_shape, action_shape=(A,), num_sequences=a.num_sequences)
     actor = SlacActor(policy, algo, a.num_envs, a.slac_policy_input_type, a.reset_w_same_obs)
     out = run_episodes(make_envs(a), actor, a.episodes, a.max_path_length)

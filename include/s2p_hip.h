@@ -418,6 +418,24 @@ int s2p_posterior_chain_fwd_save(const float* feat, int feat_pitch, const float*
 int s2p_posterior_chain_bwd(const float* eps, int eps_pitch, const float* dmean, int dmean_pitch, const float* dstd, int dstd_pitch,
                             const float* dz, int dz_pitch, const s2p_chain_mlp_bwd* mlps, const s2p_chain_state* state,
                             const s2p_chain_grads* grads, int B, int T, void* stream);
+/* The two fused no-grad chains in bf16 compute (SPEC.md N3m; csrc/gauss_chain_bf16.hip): the arguments, no-ops and refusals of
+ * s2p_posterior_chain_fwd and s2p_prior_chain_fwd, ONE launch each.  Every tensor stays fp32 except the weight operands:
+ * s2p_chain_mlp_bf16 holds w1 [256][w1_row >= k1] (the CHAIN columns of the first layer only; for z1_prior a pack of its 256 z2
+ * columns), w2 [256][256] and w3 [2 D][256] as bf16 bits, each the fp32 parameter rounded to nearest even, 16-byte aligned, w1_row in
+ * bf16 elements and a multiple of 8; the biases are fp32.  Per layer: both operands bf16 (the activations are rounded where the kernel
+ * writes them to LDS), acc = the fp32 sum of the exact products on v_mfma_f32_16x16x32_bf16 with k ascending in steps of 32 and K never
+ * split, then (acc + add) + bias or acc + bias, LeakyReLU 0.2 and the head in fp32 as in the fp32 chains; z is stored unrounded.  A
+ * row's values do not depend on B; two identical calls are bitwise equal.  Nothing but mean, std and z is written.            */
+typedef struct {
+  const uint16_t* w1; const float* b1; const uint16_t* w2; const float* b2; const uint16_t* w3; const float* b3;
+  int32_t k1, w1_row;
+} s2p_chain_mlp_bf16;
+int s2p_posterior_chain_fwd_bf16(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
+                                 int eps_pitch, const s2p_chain_mlp_bf16* mlps, float* mean, int mean_pitch, float* std,
+                                 int std_pitch, float* z, int z_pitch, int B, int T, void* stream);
+int s2p_prior_chain_fwd_bf16(const float* z2_0, int z2_0_pitch, const float* rc, const float* rb, const float* eps, int eps_pitch,
+                             const s2p_chain_mlp_bf16* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
+                             int z_pitch, int B, int H, void* stream);
 /* KL(p || q) of diagonal Gaussians, value and all four gradients in one pass (slac/utils.py:66-69):
  *   loss[0] += scale * sum 0.5 ((sp/sq)^2 + ((mp-mq)/sq)^2 - 1 - log (sp/sq)^2),  d* = scale * dKL/d*  (overwritten; any NULL).
  * p: [B][T][p_pitch >= D].  const_first == 0: q is [B][T][q_pitch]; const_first != 0: q is [B][T-1][q_pitch] and holds the

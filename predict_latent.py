@@ -2,7 +2,7 @@
 next H actions after `context` frames it has seen, and how far are they from what happened?
 
   python predict_latent.py --data FILE --latent_dir DIR --out pred.npz [--context 8] [--horizon 8] [--windows 64] [--stride N]
-                           [--batch 64] [--mean] [--seed 0] [--bf16] [--fused_chain] [--frames]
+                           [--batch 64] [--mean] [--seed 0] [--bf16] [--fused_chain] [--bf16_chain] [--frames]
 
 Takes up to --windows stretches of --context + --horizon transitions from the trajectories of --data (`s2p_amd.slac_predict.windows`;
 starts --stride rows apart, default no overlap), filters the first --context + 1 frames of each with the posterior, rolls the
@@ -11,7 +11,7 @@ frame and of the copy-the-last-context-frame baseline against the true frame, an
 those columns (`psnr`, `ssim`, `baseline_psnr`, `baseline_ssim`, `reward_abs_err`, each [H]), the per-window values behind them
 (`window_*` [n,H]), `reward_mean`, `reward_std` [n,H], `z` [n,H,288] and the windows' `starts`; with --frames also the predicted
 `frames` as uint8 [n,H,100,100,3].  --mean rolls the means (no noise anywhere); --fused_chain runs every chain as one launch
-(bitwise the same result)."""
+(bitwise the same result); --bf16_chain gives those launches bf16 operands (SPEC.md N3m: mixed precision, not the same numbers)."""
 import argparse
 import os
 
@@ -35,8 +35,13 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--bf16", action="store_true", help="bf16 conv stacks of the encoder and the decoder")
     ap.add_argument("--fused_chain", action="store_true", help="posterior and prior chain as one launch each (bitwise the same result)")
+    ap.add_argument("--bf16_chain", action="store_true",
+                    help="with --fused_chain: bf16 matrix-core compute inside the fused no-grad latent chain (SPEC.md N3m), independent of --bf16 and "
+                         "--bf16_mlp: weights and LDS activations rounded to bf16, fp32 sums, heads and outputs; mixed precision, not the same numbers")
     ap.add_argument("--frames", action="store_true", help="also write the predicted frames")
     a = ap.parse_args(argv)
+    if a.bf16_chain and not a.fused_chain:
+        ap.error("--bf16_chain needs --fused_chain: the bf16 compute mode exists only in the fused chain kernels")
     if a.horizon < 1 or a.context < 1:
         ap.error("--horizon >= 1 and --context >= 1")
     if a.windows < 1 or a.batch < 1 or (a.stride is not None and a.stride < 1):
@@ -63,6 +68,7 @@ def main(argv=None):
     latent = LatentModel((3, 100, 100), (A,), dtype=torch.bfloat16 if a.bf16 else torch.float32, device="cuda:0")
     latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
     latent.fused_chain = a.fused_chain
+    latent.chain_compute = "bf16" if a.bf16_chain else "fp32"
     keep = ("z", "reward_mean", "reward_std") + COLUMNS + (("frames",) if a.frames else ())
     parts = {k: [] for k in keep}
     for lo in range(0, len(starts), a.batch):

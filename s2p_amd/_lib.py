@@ -67,6 +67,11 @@ class ChainMlp(ctypes.Structure):
                 ("k1", ctypes.c_int32), ("w1_row", ctypes.c_int32)]
 
 
+class ChainMlpBf16(ctypes.Structure):
+    """s2p_chain_mlp_bf16: ChainMlp with the three weight operands as bf16 bits (w1_row in bf16 elements); the biases stay fp32."""
+    _fields_ = ChainMlp._fields_
+
+
 class ChainState(ctypes.Structure):
     """s2p_chain_state: the activations the posterior chain keeps for its backward (t = 0: a0_*, b0_*; t >= 1 time-major: the rest)."""
     _fields_ = [(n, c_void_p) for n in ("a0_h1", "a0_h2", "a0_raw", "b0_h1", "b0_h2", "b0_raw", "h1a", "h2a", "rawa", "h1b", "h2b", "rawb",
@@ -153,6 +158,10 @@ SIGNATURES = {
     "s2p_posterior_chain_bwd": [_P, c_int, _P, c_int, _P, c_int, _P, c_int, ctypes.POINTER(ChainMlpBwd), ctypes.POINTER(ChainState),
                                 ctypes.POINTER(ChainGrads), c_int, c_int, _P],
     "s2p_prior_chain_fwd": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
+    "s2p_posterior_chain_fwd_bf16": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlpBf16), _P, c_int, _P, c_int, _P, c_int, c_int,
+                                     c_int, _P],
+    "s2p_prior_chain_fwd_bf16": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlpBf16), _P, c_int, _P, c_int, _P, c_int, c_int, c_int,
+                                 _P],
     "s2p_imagine_chain_fwd": [_P, c_int, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, c_int, ctypes.POINTER(PolicyMlp),
                               _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
     "s2p_linear_add_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int, _P, _P,

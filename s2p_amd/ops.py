@@ -709,14 +709,23 @@ def chain_mlp(pk, group=0, k1=None):
                          w1.shape[1])
 
 
+def chain_mlp_bf16(pk):
+    """The s2p_chain_mlp_bf16 of a Gaussian.packed_bf16() dict."""
+    w1 = pk["w1"]
+    for w in (w1, pk["w2"], pk["w3"]):
+        if w.dtype != torch.bfloat16 or not w.is_contiguous():
+            raise ValueError("the weight operands of a bf16 chain are contiguous torch.bfloat16 packs")
+    return _lib.ChainMlpBf16(ptr(w1), ptr(pk["b1"]), ptr(pk["w2"]), ptr(pk["b2"]), ptr(pk["w3"]), ptr(pk["b3"]), w1.shape[1], w1.shape[1])
+
+
 def _chain_views(B, T, *ts):
     for t in ts:
         if t.dtype != torch.float32 or t.shape[:2] != (B, T) or t.stride(2) != 1 or (B > 1 and T > 0 and t.stride(0) != T * t.stride(1)):
             raise ValueError("[B, T, C] fp32 views whose rows (b, t) are evenly pitched are needed")
 
 
-def _chain_operands(src, eps, mlps, n_mlps, mean, std, z, terms=(), steps=0, more=()):
-    """What the three chain wrappers share.  Checks eps, mean, std, z and `more` as [B, T, C] views (_chain_views) and the hoisted
+def _chain_operands(src, eps, mlps, n_mlps, mean, std, z, terms=(), steps=0, more=(), mlp_type=_lib.ChainMlp):
+    """What the chain wrappers share.  Checks eps, mean, std, z and `more` as [B, T, C] views (_chain_views) and the hoisted
     `terms` as contiguous fp32 [steps*B, 256] (None passes: the entry point says when a term may be absent).  -> the (pointer, pitch)
     of the 2-D view `src`, the array of `n_mlps` ChainMlp, and the argument tail of all three entry points, mean .. stream."""
     B, T = eps.shape[:2]
@@ -725,7 +734,7 @@ def _chain_operands(src, eps, mlps, n_mlps, mean, std, z, terms=(), steps=0, mor
         if r is not None and (not r.is_contiguous() or r.dtype != torch.float32 or r.shape != (steps * B, 256)):
             raise ValueError("the hoisted terms are contiguous fp32 [%d*B, 256]" % steps)
     tail = (ptr(mean), mean.stride(1), ptr(std), std.stride(1), ptr(z), z.stride(1), B, T, stream())
-    return _view2(src), (_lib.ChainMlp * n_mlps)(*mlps), tail
+    return _view2(src), (mlp_type * n_mlps)(*mlps), tail
 
 
 def prior_chain_fwd(z2_0, rc, rb, eps, mlps, mean, std, z):
@@ -734,6 +743,13 @@ def prior_chain_fwd(z2_0, rc, rb, eps, mlps, mean, std, z):
     chain_mlp() structs of z1_prior (k1 = 256) and z2_prior."""
     (zp, zs), arr, tail = _chain_operands(z2_0, eps, mlps, 2, mean, std, z, terms=(rc, rb), steps=eps.shape[1])
     check(lib().s2p_prior_chain_fwd(zp, zs, ptr(rc), ptr(rb), ptr(eps), eps.stride(1), arr, *tail), "s2p_prior_chain_fwd")
+
+
+def prior_chain_fwd_bf16(z2_0, rc, rb, eps, mlps, mean, std, z):
+    """prior_chain_fwd in bf16 compute (s2p_prior_chain_fwd_bf16; SPEC.md N3m): the same fp32 tensors, mlps: the chain_mlp_bf16()
+    structs of z1_prior (its z2-column pack) and z2_prior."""
+    (zp, zs), arr, tail = _chain_operands(z2_0, eps, mlps, 2, mean, std, z, terms=(rc, rb), steps=eps.shape[1], mlp_type=_lib.ChainMlpBf16)
+    check(lib().s2p_prior_chain_fwd_bf16(zp, zs, ptr(rc), ptr(rb), ptr(eps), eps.stride(1), arr, *tail), "s2p_prior_chain_fwd_bf16")
 
 
 def policy_mlp(policy):
@@ -763,6 +779,14 @@ def posterior_chain_fwd(feat0, ra, rb, eps, mlps, mean, std, z):
     T * stride(1) (a slice of a wider [B, T, W] buffer is written in place); mlps: four chain_mlp() structs."""
     (fp, fs), arr, tail = _chain_operands(feat0, eps, mlps, 4, mean, std, z, terms=(ra, rb), steps=eps.shape[1] - 1)
     check(lib().s2p_posterior_chain_fwd(fp, fs, ptr(ra), ptr(rb), ptr(eps), eps.stride(1), arr, *tail), "s2p_posterior_chain_fwd")
+
+
+def posterior_chain_fwd_bf16(feat0, ra, rb, eps, mlps, mean, std, z):
+    """posterior_chain_fwd in bf16 compute (s2p_posterior_chain_fwd_bf16; SPEC.md N3m): the same fp32 tensors, mlps: four
+    chain_mlp_bf16() structs."""
+    (fp, fs), arr, tail = _chain_operands(feat0, eps, mlps, 4, mean, std, z, terms=(ra, rb), steps=eps.shape[1] - 1,
+                                          mlp_type=_lib.ChainMlpBf16)
+    check(lib().s2p_posterior_chain_fwd_bf16(fp, fs, ptr(ra), ptr(rb), ptr(eps), eps.stride(1), arr, *tail), "s2p_posterior_chain_fwd_bf16")
 
 
 def _dense(ts):

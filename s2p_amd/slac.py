@@ -234,6 +234,7 @@ class Gaussian(nn.Module):
         self.net.add_module("4", _Lin(HID, self.N))
         self._pack_key, self._packed = None, None
         self._cols_key, self._cols = None, {}
+        self._bf16_key, self._bf16 = None, {}
 
     def layer_params(self):
         out = []
@@ -266,6 +267,27 @@ class Gaussian(nn.Module):
                        w3t=w3p.t().contiguous(), b3=b3p)
         self._pack_key, self._packed = key, out
         return out
+
+    def packed_bf16(self, k1=None):
+        """The operands of the bf16-compute chains (SPEC.md N3m), beside packed() and under its key rule: w1 [256][k1] = the chain
+        operand of the first layer, i.e. the first column group (`k1`: only its leading k1 columns, as a pack of their own -- z1_prior's
+        256 z2 columns in the prior chain), w2 [256][256], w3 [2 D][256].  Each is the fp32 parameter `.to(torch.bfloat16)` (round to
+        nearest even); the biases are packed()'s fp32 ones.  The other column groups stay in the hoisted fp32 GEMMs."""
+        ps = self.layer_params()
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if key != self._bf16_key:
+            self._bf16_key, self._bf16 = key, {}
+        if k1 not in self._bf16:
+            pk = self.packed()
+            with torch.no_grad():
+                w1, _, w2, _, w3, _ = [p.detach().float() for p in ps]
+                w = torch.cat([w1[:, a:b] for a, b in self.groups[0]], dim=1)
+                w = w if k1 is None else w[:, :k1]
+                if w.shape[1] % 8:
+                    raise ValueError("a bf16 chain operand has a multiple of 8 columns, not %d" % w.shape[1])
+                bf = lambda t: t.to(torch.bfloat16).contiguous()
+                self._bf16[k1] = dict(w1=bf(w), b1=pk["b1"], w2=bf(w2), b2=pk["b2"], w3=bf(w3), b3=pk["b3"])
+        return self._bf16[k1]
 
     def packed_cols(self, lo, hi):
         """net.0.weight[:, lo:hi] as a GEMM operand of its own, [256][(hi - lo) padded to 4] with a zero pad, beside packed() and
@@ -454,12 +476,16 @@ class _PosteriorFn(torch.autograd.Function):
     @staticmethod
     def _fused(ctx, model, feat, action, noise, packs, mean, std, z):
         """No backward state is wanted: the hoisted terms as in forward(), then the whole chain as ONE launch
-        (s2p_posterior_chain_fwd; bitwise the per-layer path)."""
+        (s2p_posterior_chain_fwd; bitwise the per-layer path) -- or, with `model.chain_compute == "bf16"`, its bf16-compute twin."""
         pi1, pi2, p1, p2 = packs
         ra = rb = None
         if feat.shape[1] > 1:
             _, _, ra, rb = _PosteriorFn._hoisted(feat, action, p1, p2)
-        ops.posterior_chain_fwd(feat[:, 0], ra, rb, noise, [ops.chain_mlp(p) for p in packs], mean, std, z)
+        if model.bf16_chain():                                         # SPEC.md N3m: the same launch count, bf16 operands
+            heads = (model.z1_posterior_init, model.z2_prior_init, model.z1_posterior, model.z2_prior)
+            ops.posterior_chain_fwd_bf16(feat[:, 0], ra, rb, noise, [ops.chain_mlp_bf16(g.packed_bf16()) for g in heads], mean, std, z)
+        else:
+            ops.posterior_chain_fwd(feat[:, 0], ra, rb, noise, [ops.chain_mlp(p) for p in packs], mean, std, z)
         ctx.model, ctx.packs, ctx.A, ctx.saved = model, packs, action.shape[2], None
         model.chain_state_bytes = 0
         return mean, std, z
@@ -647,10 +673,18 @@ class LatentModel(nn.Module):
         self.chain_state_bytes = 0              # bytes the last sample_posterior kept for its backward (0 under no_grad)
         self.fused_chain = False                # True: a no-grad sample_posterior, predict and imagine run their chain as ONE launch (SPEC.md N3h-N3j)
         self.fused_chain_grad = False           # True: a grad-mode sample_posterior runs its chain as ONE launch forward, ONE backward (SPEC.md N3k)
+        self.chain_compute = "fp32"             # "bf16": the fused no-grad chains of sample_posterior and predict multiply in bf16 (SPEC.md N3m)
 
     @property
     def device(self):
         return self.encoder.device
+
+    def bf16_chain(self):
+        """Whether a fused no-grad chain that is about to run multiplies in bf16 (SPEC.md N3m); ValueError for an unknown `chain_compute`.
+        Read only there: with grad, on the per-layer path and in `imagine` the attribute changes nothing."""
+        if self.chain_compute not in ("fp32", "bf16"):
+            raise ValueError("chain_compute is 'fp32' or 'bf16', not %r" % (self.chain_compute,))
+        return self.chain_compute == "bf16"
 
     def _chain_params(self):
         return (self.z1_posterior_init.layer_params() + self.z2_prior_init.layer_params() + self.z1_posterior.layer_params() +
@@ -719,7 +753,8 @@ class LatentModel(nn.Module):
         (z1_mean [B,H,32], z1_std [B,H,32], z [B,H,288]) of the steps h = 1..H in the slots h - 1.  z1_prior and z2_prior are fed
         their own samples; z1(0) is not read.  Always without grad.  Both first layers are (chain columns + hoisted action term) +
         bias, so H = 1 equals sample_prior within rounding, not bitwise.  With `fused_chain` the H steps are one launch
-        (s2p_prior_chain_fwd), else 8 per step; the two are bitwise equal."""
+        (s2p_prior_chain_fwd), else 8 per step; the two are bitwise equal.  `chain_compute == "bf16"` gives the fused launch bf16
+        operands (SPEC.md N3m): mixed precision, not the same numbers."""
         actions_ = actions_.to(self.device, torch.float32).contiguous()
         if actions_.dim() != 3 or actions_.shape[:1] != z0.shape[:1] or actions_.shape[2] != self.action_dim:
             raise ValueError("z0 [B,z1_dim+z2_dim] and actions_ [B,H,A] are needed")
@@ -730,7 +765,11 @@ class LatentModel(nn.Module):
         g1, g2, p1, p2, wc, wb, xz = st
         rc, rb = _action_term(actions_, wc)[1], _action_term(actions_, wb)[1]
         if self.fused_chain:
-            ops.prior_chain_fwd(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], mean, std, z)
+            if self.bf16_chain():
+                ops.prior_chain_fwd_bf16(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp_bf16(g1.packed_bf16(k1=Z2)),
+                                                                     ops.chain_mlp_bf16(g2.packed_bf16())], mean, std, z)
+            else:
+                ops.prior_chain_fwd(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], mean, std, z)
             return mean, std, z
         h1, h2 = _f32((B, HID), self.device), _f32((B, HID), self.device)
         bufa, bufb = (h1, h2, _f32((B, g1.Npad), self.device)), (h1, h2, _f32((B, g2.Npad), self.device))

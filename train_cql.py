@@ -3,7 +3,7 @@ counterpart of the reference's `run_cql_image.sh`.
 
   python train_cql.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --latent_dir DIR --steps N
                       --out DIR [--freeze_slac [--cache_features]] [--slac_policy_input_type feature_action|latent_z] [--bf16]
-                      [--bf16_mlp] [--fused_chain] [--fused_chain_grad] [--seed S]
+                      [--bf16_mlp] [--fused_chain] [--fused_chain_grad] [--bf16_chain] [--seed S]
                       [--num_random R] [--min_q_weight W] [--temp T] [--policy_eval_start E] [--deterministic_backup]
 
 Loads `latent.pth` from --latent_dir (written by train_latent.py), fills the buffer as the reference's `load_data_in_buffer` does,
@@ -49,7 +49,8 @@ def main(argv=None):
     algo = SlacAlgorithm((C,) + real["image_observations"].shape[1:3], (A,), 1, "cuda:0", a.seed, batch_size_sac=a.batch_size,
                          batch_size_latent=a.batch_size_latent, buffer_size=max(rows, 1), num_sequences=a.num_sequences,
                          dtype=torch.bfloat16 if a.bf16 else torch.float32, frame_capacity=2 * rows + a.num_sequences + 1,
-                         fused_chain=a.fused_chain, fused_chain_grad=a.fused_chain_grad)
+                         fused_chain=a.fused_chain, fused_chain_grad=a.fused_chain_grad,
+                         chain_compute="bf16" if a.bf16_chain else "fp32")
     algo.latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
     algo.load_data_in_buffer(real)
     if gen is not None:

@@ -2,7 +2,7 @@
 
   python train_iql.py --real FILE [--gen FILE --uncertainty_type T --uncertainty_penalty_lambda L] --latent_dir DIR --steps N
                       --out DIR [--freeze_slac [--cache_features]] [--slac_policy_input_type feature_action|latent_z] [--bf16]
-                      [--bf16_mlp] [--fused_chain] [--fused_chain_grad] [--seed S]
+                      [--bf16_mlp] [--fused_chain] [--fused_chain_grad] [--bf16_chain] [--seed S]
 
 Loads `latent.pth` from --latent_dir (written by train_latent.py), fills the buffer as the reference's `load_data_in_buffer` does,
 runs `IQLTrainer.train_from_torch` N times in the shipped configuration (`examples/iql/mujoco_finetune.py:91-119`) and writes
@@ -11,7 +11,8 @@ changes: --cache_features encodes every stored frame once and samples cached fea
 no-grad posterior chain of every step's `prepare_batch` as one launch (SPEC.md N3h; the same numbers, bit for bit), --fused_chain_grad
 the chain that `update_latent` trains through as one launch forward and one backward (SPEC.md N3k; bit for bit again).
 --bf16_mlp runs the wide layers of the IQL networks on the bf16 matrix cores (SPEC.md N3l): mixed precision, not the same numbers;
-the weights, Adam and the written files stay fp32."""
+the weights, Adam and the written files stay fp32.  --bf16_chain (with --fused_chain) does the same inside the fused no-grad posterior
+chain (SPEC.md N3m): bf16 operands, fp32 sums, heads and latents."""
 import argparse
 import os
 
@@ -40,6 +41,9 @@ def parse_args(argv=None, extend=None):
                     help="run the no-grad posterior chain of prepare_batch as one launch (bitwise the same result)")
     ap.add_argument("--fused_chain_grad", action="store_true",
                     help="run the posterior chain of update_latent as one launch forward and one backward (bitwise the same result)")
+    ap.add_argument("--bf16_chain", action="store_true",
+                    help="with --fused_chain: bf16 matrix-core compute inside the fused no-grad latent chain (SPEC.md N3m), independent of --bf16 and "
+                         "--bf16_mlp: weights and LDS activations rounded to bf16, fp32 sums, heads and outputs; mixed precision, not the same numbers")
     ap.add_argument("--slac_policy_input_type", choices=["feature_action", "latent_z"], default="feature_action")
     ap.add_argument("--bf16", action="store_true", help="bf16 conv stacks of the latent model (the IQL networks stay fp32: see --bf16_mlp)")
     ap.add_argument("--bf16_mlp", action="store_true",
@@ -59,6 +63,8 @@ def parse_args(argv=None, extend=None):
         ap.error("--steps >= 0 and --batch_size >= 1")
     if a.uncertainty_type and not a.gen:
         ap.error("--uncertainty_type applies to a --gen dataset")
+    if a.bf16_chain and not a.fused_chain:
+        ap.error("--bf16_chain needs --fused_chain: the bf16 compute mode exists only in the fused chain kernels")
     if a.cache_features and not a.freeze_slac:
         ap.error("--cache_features needs --freeze_slac: a feature is a constant of the run only while the encoder is not trained")
     return a
@@ -98,7 +104,8 @@ def main(argv=None):
     algo = SlacAlgorithm((C,) + real["image_observations"].shape[1:3], (A,), 1, "cuda:0", a.seed, batch_size_sac=a.batch_size,
                          batch_size_latent=a.batch_size_latent, buffer_size=max(rows, 1), num_sequences=a.num_sequences,
                          dtype=torch.bfloat16 if a.bf16 else torch.float32, frame_capacity=2 * rows + a.num_sequences + 1,
-                         fused_chain=a.fused_chain, fused_chain_grad=a.fused_chain_grad)
+                         fused_chain=a.fused_chain, fused_chain_grad=a.fused_chain_grad,
+                         chain_compute="bf16" if a.bf16_chain else "fp32")
     algo.latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
     algo.load_data_in_buffer(real)
     if gen is not None:
