@@ -41,14 +41,13 @@ static void launch_u8_chw(const void* x, int N, int C, int HW, void* y, int pitc
 
 extern "C" int s2p_u8_chw_to_nhwc01(int dtype, const void* x, int N, int C, int H, int W, void* y, int y_pitch, void* stream) {
   const char* who = "s2p_u8_chw_to_nhwc01";
-  ACTOR_REQUIRE(dtype == S2P_F32 || dtype == S2P_BF16, "%s: bad dtype", who);
+  ACTOR_REQUIRE(s2p_is_dtype(dtype), "%s: bad dtype", who);
   ACTOR_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0 && y_pitch >= 0, "%s: negative size", who);
   if (N == 0 || H == 0 || W == 0 || (C == 0 && y_pitch == 0)) return 0;         // nothing to write: no pointer is looked at
   ACTOR_REQUIRE(y_pitch >= C, "%s: pitch shorter than the row (C %d, y_pitch %d)", who, C, y_pitch);
   ACTOR_REQUIRE((C == 0 || x) && y, "%s: null pointer", who);
   ACTOR_REQUIRE(N <= 65535 && (int64_t)H * W < ((int64_t)1 << 29), "%s: at most 65535 frames of fewer than 2^29 pixels", who);
-  if (dtype == S2P_F32) launch_u8_chw<float>(x, N, C, H * W, y, y_pitch, (hipStream_t)stream);
-  else launch_u8_chw<__bf16>(x, N, C, H * W, y, y_pitch, (hipStream_t)stream);
+  s2p_with_dtype(dtype, [&](auto tag) { launch_u8_chw<decltype(tag)>(x, N, C, H * W, y, y_pitch, (hipStream_t)stream); });
   S2P_CHECK_LAUNCH("u8_chw_to_nhwc01_kernel");
   return 0;
 }

@@ -1335,8 +1335,8 @@ static int plan_scatter_problem(const Geo& G, bool bf16, const ConvOperands& op,
 
 static int check_desc(const s2p_conv_desc* d, const char* who) {
   if (!d) S2P_FAIL(-1, "%s: null desc", who);
-  if (d->dtype != S2P_F32 && d->dtype != S2P_BF16) S2P_FAIL(-1, "%s: bad dtype %d", who, d->dtype);
-  int ce = d->dtype == S2P_F32 ? 4 : 8;
+  if (!s2p_is_dtype(d->dtype)) S2P_FAIL(-1, "%s: bad dtype %d", who, d->dtype);
+  const int ce = s2p_chunk_elems(d->dtype);
   if (d->Cin % ce || d->x_pitch % ce || d->y_pitch % ce || d->x_gstride % ce || d->y_gstride % ce)
     S2P_FAIL(-1, "%s: Cin/pitches must be multiples of %d elements (Cin=%d xp=%d yp=%d)", who, ce, d->Cin,
              d->x_pitch, d->y_pitch);
@@ -1358,7 +1358,7 @@ static int conv_plan_fwd(const s2p_conv_desc* d, const ConvOperands& op, const N
     if (sc.any && sc.bytes >= need) { P.path = ConvPath::Thin4; P.ws_bytes = need; return 0; }      // no scratch: the next path
   }
   if (!sw.no_thin_cin && s2p_thin_cin_fwd_applicable(d, op.act, op.epi)) { P.path = ConvPath::ThinCin; return 0; }
-  const int ce = d->dtype == S2P_F32 ? 4 : 8;
+  const int ce = s2p_chunk_elems(d->dtype);
   Geo G{d->N, d->H, d->W, d->Cin, d->x_pitch, d->x_gstride, d->Ho, d->Wo, d->Cout,
         /*Cst*/ d->groups == 1 ? ((d->Cout + ce - 1) / ce * ce <= d->y_pitch ? (d->Cout + ce - 1) / ce * ce : d->Cout)
                                : d->Cout,
@@ -1376,7 +1376,7 @@ static int conv_plan_fwd(const s2p_conv_desc* d, const ConvOperands& op, const N
 static int conv_plan_dgrad(const s2p_conv_desc* d, const ConvOperands& op, const NormWant& want, const ScratchAvail& sc, ConvPlan& P) {
   int rc = check_desc(d, "s2p_conv2d_dgrad");
   if (rc) return rc;
-  const int ce = d->dtype == S2P_F32 ? 4 : 8;
+  const int ce = s2p_chunk_elems(d->dtype);
   const int cout_pad = P.cout_pad = (d->Cout + ce - 1) / ce * ce;       // channels of dy actually gathered
   if (cout_pad > d->y_pitch) S2P_FAIL(-1, "s2p_conv2d_dgrad: dy pitch %d < padded Cout %d", d->y_pitch, cout_pad);
   if (!ConvSwitches::no_thin4() && op.epi == S2P_EPI_STORE && s2p_thin4_dgrad_applicable(d, cout_pad)) {      // 7x7, <= 4 output channels (the generator's output conv)

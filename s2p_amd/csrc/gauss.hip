@@ -220,25 +220,22 @@ __global__ __launch_bounds__(256) void gauss_ll_image_kernel(const T* mu, int pi
 
 extern "C" int s2p_gauss_ll_image(int dtype, const void* mu, int pitch, const void* target, int target_u8, int N, int C, int HW,
                                   float sigma, float scale, float* loss, void* dmu, void* stream) {
-  S2P_REQUIRE(dtype == S2P_F32 || dtype == S2P_BF16, "s2p_gauss_ll_image: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_gauss_ll_image: bad dtype");
   S2P_REQUIRE(N >= 0 && C >= 0 && HW >= 0, "s2p_gauss_ll_image: negative size");
   if (N == 0 || C == 0 || HW == 0) return 0;
-  const int ce = dtype == S2P_F32 ? 4 : 8;
+  const int ce = s2p_chunk_elems(dtype);
   S2P_REQUIRE(mu && target && loss, "s2p_gauss_ll_image: null pointer");
   S2P_REQUIRE(pitch >= C && pitch % ce == 0, "s2p_gauss_ll_image: pitch must be a multiple of %d and at least C", ce);
-  S2P_REQUIRE(s2p_al16(mu) && s2p_al16(dmu), "s2p_gauss_ll_image: mu and dmu must be 16-byte aligned");
+  S2P_REQUIRE(s2p_al16(mu, dmu), "s2p_gauss_ll_image: mu and dmu must be 16-byte aligned");
   S2P_REQUIRE(target_u8 || ((uintptr_t)target & 3) == 0, "s2p_gauss_ll_image: an fp32 target must be 4-byte aligned");
   S2P_REQUIRE(sigma > 0.f, "s2p_gauss_ll_image: sigma must be positive");
   const long long pixels = (long long)N * HW;
   const dim3 g(gauss_grid(pixels, 512));                   // one atomicAdd per workgroup on the loss word (see s2p_l1_loss)
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == S2P_F32) {
-    if (target_u8) hipLaunchKernelGGL((gauss_ll_image_kernel<float, 1>), g, dim3(256), 0, st, (const float*)mu, pitch, target, pixels, HW, C, sigma, scale, loss, (float*)dmu);
-    else hipLaunchKernelGGL((gauss_ll_image_kernel<float, 0>), g, dim3(256), 0, st, (const float*)mu, pitch, target, pixels, HW, C, sigma, scale, loss, (float*)dmu);
-  } else {
-    if (target_u8) hipLaunchKernelGGL((gauss_ll_image_kernel<__bf16, 1>), g, dim3(256), 0, st, (const __bf16*)mu, pitch, target, pixels, HW, C, sigma, scale, loss, (__bf16*)dmu);
-    else hipLaunchKernelGGL((gauss_ll_image_kernel<__bf16, 0>), g, dim3(256), 0, st, (const __bf16*)mu, pitch, target, pixels, HW, C, sigma, scale, loss, (__bf16*)dmu);
-  }
+  s2p_with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto kernel = target_u8 ? gauss_ll_image_kernel<T, 1> : gauss_ll_image_kernel<T, 0>;
+    hipLaunchKernelGGL(kernel, g, dim3(256), 0, (hipStream_t)stream, (const T*)mu, pitch, target, pixels, HW, C, sigma, scale, loss, (T*)dmu);
+  });
   S2P_CHECK_LAUNCH("gauss_ll_image_kernel");
   return 0;
 }

@@ -21,10 +21,7 @@ static inline int grid_for(long long total, int cap = 4096) {
 // A negative size or an unknown dtype is refused.  A call that covers no element is a successful no-op: nothing is launched and no
 // pointer is looked at (an empty tensor may well have a null data pointer).  Otherwise null pointers are refused, and so are pointers
 // that are not 16-byte aligned wherever the kernel moves whole 16-byte chunks unconditionally (include/s2p_hip.h says which).
-static inline bool is_dtype(int dtype) { return dtype == S2P_F32 || dtype == S2P_BF16; }
-static inline bool host_al16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
-}
+// The dtype is validated first, so every launch goes through s2p_with_dtype (s2p_common.h) and is written once.
 
 // ---- positional encoding ---------------------------------------------------------------------------
 __global__ void posenc_kernel(const float* s, int N, int S, int L, float* out, int pitch) {
@@ -129,42 +126,36 @@ __global__ void avgpool_bwd_kernel(const T* dy, int N, int H, int W, int C, T* d
   }
 }
 extern "C" int s2p_avgpool3x3s2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_avgpool3x3s2_fwd: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_avgpool3x3s2_fwd: bad dtype");
   S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0, "s2p_avgpool3x3s2_fwd: negative size");
   if ((long long)N * H * W * C == 0) return 0;
   S2P_REQUIRE(x && y, "s2p_avgpool3x3s2_fwd: null pointer");
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  const int ce = dtype == S2P_F32 ? 4 : 8;
-  const bool chunks = C % ce == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+  const int ce = s2p_chunk_elems(dtype);
+  const bool chunks = C % ce == 0 && s2p_al16(x, y);
   long long total = (long long)N * Ho * Wo * (chunks ? C / ce : C);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == S2P_F32) {
-    if (chunks) hipLaunchKernelGGL((avgpool_fwd_kernel<float, 4>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)x, N, H, W, C, (float*)y, Ho, Wo);
-    else hipLaunchKernelGGL((avgpool_fwd_kernel<float, 1>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)x, N, H, W, C, (float*)y, Ho, Wo);
-  } else if (dtype == S2P_BF16) {
-    if (chunks) hipLaunchKernelGGL((avgpool_fwd_kernel<__bf16, 8>), dim3(grid_for(total)), dim3(256), 0, st, (const __bf16*)x, N, H, W, C, (__bf16*)y, Ho, Wo);
-    else hipLaunchKernelGGL((avgpool_fwd_kernel<__bf16, 1>), dim3(grid_for(total)), dim3(256), 0, st, (const __bf16*)x, N, H, W, C, (__bf16*)y, Ho, Wo);
-  } else S2P_FAIL(-1, "s2p_avgpool3x3s2_fwd: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto kernel = chunks ? avgpool_fwd_kernel<T, DT<T>::CE> : avgpool_fwd_kernel<T, 1>;
+    hipLaunchKernelGGL(kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, N, H, W, C, (T*)y, Ho, Wo);
+  });
   S2P_CHECK_LAUNCH("avgpool_fwd_kernel");
   return 0;
 }
 extern "C" int s2p_avgpool3x3s2_bwd(int dtype, const void* dy, int N, int H, int W, int C, void* dx, int accumulate, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_avgpool3x3s2_bwd: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_avgpool3x3s2_bwd: bad dtype");
   S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0, "s2p_avgpool3x3s2_bwd: negative size");
   if ((long long)N * H * W * C == 0) return 0;
   S2P_REQUIRE(dy && dx, "s2p_avgpool3x3s2_bwd: null pointer");
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  const int ce = dtype == S2P_F32 ? 4 : 8;
-  const bool chunks = C % ce == 0 && (((uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
+  const int ce = s2p_chunk_elems(dtype);
+  const bool chunks = C % ce == 0 && s2p_al16(dy, dx);
   long long total = (long long)N * H * W * (chunks ? C / ce : C);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == S2P_F32) {
-    if (chunks) hipLaunchKernelGGL((avgpool_bwd_kernel<float, 4>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)dy, N, H, W, C, (float*)dx, Ho, Wo, accumulate);
-    else hipLaunchKernelGGL((avgpool_bwd_kernel<float, 1>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)dy, N, H, W, C, (float*)dx, Ho, Wo, accumulate);
-  } else if (dtype == S2P_BF16) {
-    if (chunks) hipLaunchKernelGGL((avgpool_bwd_kernel<__bf16, 8>), dim3(grid_for(total)), dim3(256), 0, st, (const __bf16*)dy, N, H, W, C, (__bf16*)dx, Ho, Wo, accumulate);
-    else hipLaunchKernelGGL((avgpool_bwd_kernel<__bf16, 1>), dim3(grid_for(total)), dim3(256), 0, st, (const __bf16*)dy, N, H, W, C, (__bf16*)dx, Ho, Wo, accumulate);
-  } else S2P_FAIL(-1, "s2p_avgpool3x3s2_bwd: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto kernel = chunks ? avgpool_bwd_kernel<T, DT<T>::CE> : avgpool_bwd_kernel<T, 1>;
+    hipLaunchKernelGGL(kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, N, H, W, C, (T*)dx, Ho, Wo, accumulate);
+  });
   S2P_CHECK_LAUNCH("avgpool_bwd_kernel");
   return 0;
 }
@@ -259,32 +250,30 @@ __global__ void maxpool_bwd_kernel(const T* dy, const T* x, int N, int H, int W,
   }
 }
 extern "C" int s2p_maxpool2x2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_maxpool2x2_fwd: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_maxpool2x2_fwd: bad dtype");
   S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0, "s2p_maxpool2x2_fwd: negative size");
-  int Ho = H / 2, Wo = W / 2, ce = dtype == S2P_F32 ? 4 : 8;
+  int Ho = H / 2, Wo = W / 2, ce = s2p_chunk_elems(dtype);
   if (C % ce) S2P_FAIL(-1, "s2p_maxpool2x2_fwd: C must be a multiple of %d", ce);
   long long total = (long long)N * Ho * Wo * (C / ce);
   if (total == 0) return 0;
   S2P_REQUIRE(x && y, "s2p_maxpool2x2_fwd: null pointer");
-  S2P_REQUIRE(host_al16(x, y), "s2p_maxpool2x2_fwd: x and y must be 16-byte aligned");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, N, H, W, C, (float*)y, Ho, Wo);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(maxpool_fwd_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, N, H, W, C, (__bf16*)y, Ho, Wo);
-  else S2P_FAIL(-1, "s2p_maxpool2x2_fwd: bad dtype");
+  S2P_REQUIRE(s2p_al16(x, y), "s2p_maxpool2x2_fwd: x and y must be 16-byte aligned");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, N, H, W, C, (T*)y, Ho, Wo); });
   S2P_CHECK_LAUNCH("maxpool_fwd_kernel");
   return 0;
 }
 extern "C" int s2p_maxpool2x2_bwd(int dtype, const void* dy, const void* x, int N, int H, int W, int C, void* dx, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_maxpool2x2_bwd: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_maxpool2x2_bwd: bad dtype");
   S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0, "s2p_maxpool2x2_bwd: negative size");
-  int Ho = H / 2, Wo = W / 2, ce = dtype == S2P_F32 ? 4 : 8;
+  int Ho = H / 2, Wo = W / 2, ce = s2p_chunk_elems(dtype);
   if (C % ce) S2P_FAIL(-1, "s2p_maxpool2x2_bwd: C must be a multiple of %d", ce);
   long long total = (long long)N * H * W * (C / ce);
   if (total == 0) return 0;
   S2P_REQUIRE(x && dx && (dy || (long long)Ho * Wo == 0), "s2p_maxpool2x2_bwd: null pointer");
-  S2P_REQUIRE(host_al16(dy, x, dx), "s2p_maxpool2x2_bwd: dy, x and dx must be 16-byte aligned");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)x, N, H, W, C, (float*)dx, Ho, Wo);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(maxpool_bwd_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy, (const __bf16*)x, N, H, W, C, (__bf16*)dx, Ho, Wo);
-  else S2P_FAIL(-1, "s2p_maxpool2x2_bwd: bad dtype");
+  S2P_REQUIRE(s2p_al16(dy, x, dx), "s2p_maxpool2x2_bwd: dy, x and dx must be 16-byte aligned");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)x, N, H, W, C, (T*)dx, Ho, Wo); });
   S2P_CHECK_LAUNCH("maxpool_bwd_kernel");
   return 0;
 }
@@ -303,15 +292,14 @@ __global__ void resize_kernel(const T* x, int N, int H, int W, int C, T* y, int 
   }
 }
 extern "C" int s2p_resize_nearest(int dtype, const void* x, int N, int H, int W, int C, void* y, int Ho, int Wo, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_resize_nearest: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_resize_nearest: bad dtype");
   S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0 && Ho >= 0 && Wo >= 0, "s2p_resize_nearest: negative size");
   long long total = (long long)N * Ho * Wo * C;
   if (total == 0) return 0;
   S2P_REQUIRE(H > 0 && W > 0, "s2p_resize_nearest: empty input plane");
   S2P_REQUIRE(x && y, "s2p_resize_nearest: null pointer");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(resize_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, N, H, W, C, (float*)y, Ho, Wo);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(resize_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, N, H, W, C, (__bf16*)y, Ho, Wo);
-  else S2P_FAIL(-1, "s2p_resize_nearest: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(resize_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, N, H, W, C, (T*)y, Ho, Wo); });
   S2P_CHECK_LAUNCH("resize_kernel");
   return 0;
 }
@@ -360,30 +348,28 @@ __global__ void nhwc_to_nchw_kernel(const T* x, int pitch, int c_off, int N, int
   }
 }
 extern "C" int s2p_nchw_to_nhwc(int dtype, const float* x, int N, int C, int H, int W, void* y, int y_pitch, int c_off, int zero_pad, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_nchw_to_nhwc: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_nchw_to_nhwc: bad dtype");
   S2P_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0 && c_off >= 0 && y_pitch >= 0, "s2p_nchw_to_nhwc: negative size");
   if (c_off + C > y_pitch) S2P_FAIL(-1, "s2p_nchw_to_nhwc: channels exceed pitch");
   long long total = (long long)N * H * W;                                   // one thread per pixel
   if (total == 0 || (zero_pad ? y_pitch : C) == 0) return 0;
   S2P_REQUIRE(y && (x || C == 0), "s2p_nchw_to_nhwc: null pointer");
   // zero_pad with a pitch of whole chunks stores 16 bytes at a time
-  S2P_REQUIRE(!(zero_pad && y_pitch % (dtype == S2P_F32 ? 4 : 8) == 0) || host_al16(y), "s2p_nchw_to_nhwc: y must be 16-byte aligned");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, N, C, H, W, (float*)y, y_pitch, c_off, zero_pad);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, N, C, H, W, (__bf16*)y, y_pitch, c_off, zero_pad);
-  else S2P_FAIL(-1, "s2p_nchw_to_nhwc: bad dtype");
+  S2P_REQUIRE(!(zero_pad && y_pitch % s2p_chunk_elems(dtype) == 0) || s2p_al16(y), "s2p_nchw_to_nhwc: y must be 16-byte aligned");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, N, C, H, W, (T*)y, y_pitch, c_off, zero_pad); });
   S2P_CHECK_LAUNCH("nchw_to_nhwc_kernel");
   return 0;
 }
 extern "C" int s2p_nhwc_to_nchw(int dtype, const void* x, int x_pitch, int c_off, int N, int C, int H, int W, float* y, int accumulate, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_nhwc_to_nchw: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_nhwc_to_nchw: bad dtype");
   S2P_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0 && c_off >= 0, "s2p_nhwc_to_nchw: negative size");
   S2P_REQUIRE(c_off + C <= x_pitch, "s2p_nhwc_to_nchw: channels exceed pitch");
   long long total = (long long)N * C * H * W;
   if (total == 0) return 0;
   S2P_REQUIRE(x && y, "s2p_nhwc_to_nchw: null pointer");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, x_pitch, c_off, N, C, H, W, y, accumulate);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, x_pitch, c_off, N, C, H, W, y, accumulate);
-  else S2P_FAIL(-1, "s2p_nhwc_to_nchw: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, x_pitch, c_off, N, C, H, W, y, accumulate); });
   S2P_CHECK_LAUNCH("nhwc_to_nchw_kernel");
   return 0;
 }
@@ -393,16 +379,14 @@ __global__ void cast_kernel(const S* s, D* d, long long n) {
   GRID_STRIDE(idx, n) d[idx] = from_f32<D>(to_f32(s[idx]));
 }
 extern "C" int s2p_cast(int sd, const void* src, int dd, void* dst, int64_t n, void* stream) {
-  S2P_REQUIRE(is_dtype(sd) && is_dtype(dd), "s2p_cast: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(sd) && s2p_is_dtype(dd), "s2p_cast: bad dtype");
   S2P_REQUIRE(n >= 0, "s2p_cast: negative size");
   if (n == 0) return 0;
   S2P_REQUIRE(src && dst, "s2p_cast: null pointer");
-  dim3 g(grid_for(n)), b(256); hipStream_t st = (hipStream_t)stream;
-  if (sd == S2P_F32 && dd == S2P_BF16) hipLaunchKernelGGL((cast_kernel<float, __bf16>), g, b, 0, st, (const float*)src, (__bf16*)dst, (long long)n);
-  else if (sd == S2P_BF16 && dd == S2P_F32) hipLaunchKernelGGL((cast_kernel<__bf16, float>), g, b, 0, st, (const __bf16*)src, (float*)dst, (long long)n);
-  else if (sd == S2P_F32 && dd == S2P_F32) hipLaunchKernelGGL((cast_kernel<float, float>), g, b, 0, st, (const float*)src, (float*)dst, (long long)n);
-  else if (sd == S2P_BF16 && dd == S2P_BF16) hipLaunchKernelGGL((cast_kernel<__bf16, __bf16>), g, b, 0, st, (const __bf16*)src, (__bf16*)dst, (long long)n);
-  else S2P_FAIL(-1, "s2p_cast: bad dtype");
+  s2p_with_dtype(sd, [&](auto stag) {
+    s2p_with_dtype(dd, [&](auto dtag) { using S = decltype(stag); using D = decltype(dtag);
+      hipLaunchKernelGGL((cast_kernel<S, D>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const S*)src, (D*)dst, (long long)n); });
+  });
   S2P_CHECK_LAUNCH("cast_kernel");
   return 0;
 }
@@ -440,19 +424,18 @@ __global__ void reflect_fold_kernel(const T* dxp, int N, int H, int W, int C, in
   }
 }
 extern "C" int s2p_reflect_pad_bwd(int dtype, const void* dxp, int N, int H, int W, int C, int pad, void* dx, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_reflect_pad_bwd: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_reflect_pad_bwd: bad dtype");
   S2P_REQUIRE(N >= 0 && H >= 0 && W >= 0 && C >= 0 && pad >= 0, "s2p_reflect_pad_bwd: negative size");
-  const int ce = dtype == S2P_F32 ? 4 : 8;
+  const int ce = s2p_chunk_elems(dtype);
   if (C % ce) S2P_FAIL(-1, "s2p_reflect_pad_bwd: C (the NHWC pitch) must be a multiple of %d", ce);
   long long total = (long long)N * H * W * (C / ce);
   if (total == 0) return 0;
   // (reflection needs pad < H, W as F.pad does; the kernel folds at most one reflection per side and axis)
   S2P_REQUIRE(pad < H && pad < W, "s2p_reflect_pad_bwd: pad %d must be smaller than H %d and W %d", pad, H, W);
   S2P_REQUIRE(dxp && dx, "s2p_reflect_pad_bwd: null pointer");
-  S2P_REQUIRE(host_al16(dxp, dx), "s2p_reflect_pad_bwd: dxp and dx must be 16-byte aligned");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(reflect_fold_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)dxp, N, H, W, C, pad, (float*)dx);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(reflect_fold_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dxp, N, H, W, C, pad, (__bf16*)dx);
-  else S2P_FAIL(-1, "s2p_reflect_pad_bwd: bad dtype");
+  S2P_REQUIRE(s2p_al16(dxp, dx), "s2p_reflect_pad_bwd: dxp and dx must be 16-byte aligned");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(reflect_fold_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)dxp, N, H, W, C, pad, (T*)dx); });
   S2P_CHECK_LAUNCH("reflect_fold_kernel");
   return 0;
 }
@@ -499,7 +482,7 @@ __global__ void l1_loss_kernel(const T* a, const T* b, long long count, float sc
   block_atomic_add(s * scale, loss);
 }
 extern "C" int s2p_l1_loss(int dtype, const void* a, const void* b, int64_t count, float scale, float* loss_out, void* grad_a, int accumulate, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_l1_loss: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_l1_loss: bad dtype");
   S2P_REQUIRE(count >= 0, "s2p_l1_loss: negative count");
   if (count == 0) return 0;
   if (!a || !b || !loss_out) S2P_FAIL(-1, "s2p_l1_loss: null pointer");
@@ -507,9 +490,8 @@ extern "C" int s2p_l1_loss(int dtype, const void* a, const void* b, int64_t coun
   // MI355X (2048 workgroups = a 29 us floor): 512 workgroups of 16-byte loads still saturate HBM
   static const int l1_cap = s2p_env_int("S2P_L1_BLOCKS", 512);
   dim3 g(grid_for(count / 4, l1_cap));
-  if (dtype == S2P_F32) hipLaunchKernelGGL(l1_loss_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (long long)count, scale, loss_out, (float*)grad_a, accumulate);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(l1_loss_kernel<__bf16>, g, dim3(256), 0, (hipStream_t)stream, (const __bf16*)a, (const __bf16*)b, (long long)count, scale, loss_out, (__bf16*)grad_a, accumulate);
-  else S2P_FAIL(-1, "s2p_l1_loss: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(l1_loss_kernel<T>, g, dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, (long long)count, scale, loss_out, (T*)grad_a, accumulate); });
   S2P_CHECK_LAUNCH("l1_loss_kernel");
   return 0;
 }
@@ -557,13 +539,13 @@ __global__ __launch_bounds__(256) void l1_multi_kernel(const L1Multi m) {
 }
 extern "C" int s2p_l1_loss_multi(int dtype, const s2p_l1_job* jobs, int n_jobs, void* stream) {
   if (!jobs || n_jobs < 1 || n_jobs > S2P_L1_MAX_JOBS) S2P_FAIL(-1, "s2p_l1_loss_multi: 1..%d jobs", S2P_L1_MAX_JOBS);
-  const int ce = dtype == S2P_F32 ? 4 : 8;
+  const int ce = s2p_chunk_elems(dtype);
   L1Multi m{};
   m.n_jobs = n_jobs;
   for (int j = 0; j < n_jobs; ++j) {
     const s2p_l1_job& q = jobs[j];
     if (!q.a || !q.b || !q.loss_out || q.count <= 0) S2P_FAIL(-1, "s2p_l1_loss_multi: job %d: null pointer / empty", j);
-    if (((unsigned long long)q.a | (unsigned long long)q.b | (unsigned long long)q.grad_a) & 15ull || q.count % ce)
+    if (!s2p_al16(q.a, q.b, q.grad_a) || q.count % ce)
       S2P_FAIL(-1, "s2p_l1_loss_multi: job %d: pointers must be 16-byte aligned and count a multiple of %d", j, ce);
     m.a[j] = q.a; m.b[j] = q.b; m.g[j] = q.grad_a; m.count[j] = q.count; m.scale[j] = q.scale; m.loss[j] = q.loss_out;
     // one workgroup per 256 threads x 4 chunks x 4 rounds; same-address atomics retire at ~13 ns each: <= 512 workgroups per job
@@ -571,10 +553,9 @@ extern "C" int s2p_l1_loss_multi(int dtype, const s2p_l1_job* jobs, int n_jobs, 
     long long nb = (q.count / ce + 4095) / 4096; if (nb > cap) nb = cap; if (nb < 1) nb = 1;
     m.first[j + 1] = m.first[j] + (int)nb;
   }
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_l1_loss_multi: bad dtype");      // (after the jobs: an unknown id counts 8-element chunks above)
   dim3 g(m.first[n_jobs]);
-  if (dtype == S2P_F32) hipLaunchKernelGGL(l1_multi_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, m);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(l1_multi_kernel<__bf16>, g, dim3(256), 0, (hipStream_t)stream, m);
-  else S2P_FAIL(-1, "s2p_l1_loss_multi: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { hipLaunchKernelGGL(l1_multi_kernel<decltype(tag)>, g, dim3(256), 0, (hipStream_t)stream, m); });
   S2P_CHECK_LAUNCH("l1_multi_kernel");
   return 0;
 }
@@ -594,14 +575,13 @@ __global__ void hinge_kernel(const T* x, long long count, int mode, float scale,
   block_atomic_add(s * scale, loss);
 }
 extern "C" int s2p_hinge_loss(int dtype, const void* x, int64_t count, int mode, float scale, float* loss_out, void* grad_x, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_hinge_loss: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_hinge_loss: bad dtype");
   S2P_REQUIRE(count >= 0 && mode >= 0 && mode <= 2, "s2p_hinge_loss: bad count / mode");
   if (count == 0) return 0;
   if (!x || !loss_out) S2P_FAIL(-1, "s2p_hinge_loss: null pointer");
   dim3 g(grid_for(count, 256));                         // same-address atomic per workgroup: keep the grid small
-  if (dtype == S2P_F32) hipLaunchKernelGGL(hinge_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, (const float*)x, (long long)count, mode, scale, loss_out, (float*)grad_x);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(hinge_kernel<__bf16>, g, dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, (long long)count, mode, scale, loss_out, (__bf16*)grad_x);
-  else S2P_FAIL(-1, "s2p_hinge_loss: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(hinge_kernel<T>, g, dim3(256), 0, (hipStream_t)stream, (const T*)x, (long long)count, mode, scale, loss_out, (T*)grad_x); });
   S2P_CHECK_LAUNCH("hinge_kernel");
   return 0;
 }
@@ -631,17 +611,16 @@ __global__ void hinge_strided_kernel(const T* x, long long pixels, int pitch, in
 }
 extern "C" int s2p_hinge_loss_strided(int dtype, const void* x, int64_t pixels, int pitch, int mode, float scale, float* loss_out,
                                       void* grad_x, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_hinge_loss_strided: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_hinge_loss_strided: bad dtype");
   S2P_REQUIRE(pixels >= 0 && mode >= 0 && mode <= 2, "s2p_hinge_loss_strided: bad pixels / mode");
-  const int ce = dtype == S2P_F32 ? 4 : 8;
+  const int ce = s2p_chunk_elems(dtype);
   if (pitch < ce || pitch % ce) S2P_FAIL(-1, "s2p_hinge_loss_strided: pitch must be a multiple of %d", ce);
   if (pixels == 0) return 0;
   if (!x || !loss_out) S2P_FAIL(-1, "s2p_hinge_loss_strided: null pointer");
-  S2P_REQUIRE(host_al16(grad_x), "s2p_hinge_loss_strided: grad_x must be 16-byte aligned");      // whole chunks are stored
+  S2P_REQUIRE(s2p_al16(grad_x), "s2p_hinge_loss_strided: grad_x must be 16-byte aligned");      // whole chunks are stored
   dim3 g(grid_for(pixels, 256));                        // same-address atomic per workgroup: keep the grid small
-  if (dtype == S2P_F32) hipLaunchKernelGGL(hinge_strided_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, (const float*)x, (long long)pixels, pitch, mode, scale, loss_out, (float*)grad_x);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(hinge_strided_kernel<__bf16>, g, dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, (long long)pixels, pitch, mode, scale, loss_out, (__bf16*)grad_x);
-  else S2P_FAIL(-1, "s2p_hinge_loss_strided: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(hinge_strided_kernel<T>, g, dim3(256), 0, (hipStream_t)stream, (const T*)x, (long long)pixels, pitch, mode, scale, loss_out, (T*)grad_x); });
   S2P_CHECK_LAUNCH("hinge_strided_kernel");
   return 0;
 }
@@ -675,7 +654,7 @@ extern "C" int s2p_adam_step(float* p, const float* g, float* m, float* v, int64
   S2P_REQUIRE(n >= 0 && step >= 1, "s2p_adam_step: bad n / step");
   if (n == 0) return 0;
   if (!p || !g || !m || !v) S2P_FAIL(-1, "s2p_adam_step: null pointer");
-  if (!host_al16(p, g, m, v)) S2P_FAIL(-1, "s2p_adam_step: buffers must be 16-byte aligned");
+  if (!s2p_al16(p, g, m, v)) S2P_FAIL(-1, "s2p_adam_step: buffers must be 16-byte aligned");
   double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   long long n4 = (n + 3) / 4;
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, (long long)n,
@@ -736,7 +715,7 @@ extern "C" int s2p_adam_step_dev_part(float* p, const float* g, float* m, float*
   if (n == 0) return 0;                                       // (no tick either: an empty range is no part of a step)
   if (!p || !g || !m || !v || !step_dev) S2P_FAIL(-1, "s2p_adam_step_dev: null pointer");
   // the kernel moves 16-byte groups of p, g, m, v: a sub-range of the flat buffers must start at a multiple of 4 elements
-  if (!host_al16(p, g, m, v)) S2P_FAIL(-1, "s2p_adam_step_dev: buffers must be 16-byte aligned");
+  if (!s2p_al16(p, g, m, v)) S2P_FAIL(-1, "s2p_adam_step_dev: buffers must be 16-byte aligned");
   long long n4 = (n + 3) / 4;
   if (tick) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev);
   hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, (long long)n,
@@ -881,15 +860,14 @@ __global__ void act_bwd_kernel(const T* dy, const T* y, long long n, int act, fl
   GRID_STRIDE(idx, n) dx[idx] = from_f32<T>(to_f32(dy[idx]) * act_grad_from_out(to_f32(y[idx]), act, slope));
 }
 extern "C" int s2p_act_bwd(int dtype, const void* dy, const void* y, int64_t n, int act, float slope, void* dx, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_act_bwd: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_act_bwd: bad dtype");
   S2P_CHECK_ACT_FROM_OUT("s2p_act_bwd", act);
   S2P_REQUIRE(n >= 0, "s2p_act_bwd: negative size");
   if (n == 0) return 0;
   S2P_REQUIRE(dy && dx && (y || act == S2P_ACT_NONE), "s2p_act_bwd: null pointer");
   if (!y) y = dy;                                             // (act none: the kernel reads y without using it)
-  if (dtype == S2P_F32) hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)y, (long long)n, act, slope, (float*)dx);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(act_bwd_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy, (const __bf16*)y, (long long)n, act, slope, (__bf16*)dx);
-  else S2P_FAIL(-1, "s2p_act_bwd: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)y, (long long)n, act, slope, (T*)dx); });
   S2P_CHECK_LAUNCH("act_bwd_kernel");
   return 0;
 }
@@ -900,13 +878,12 @@ __global__ void scale_kernel(T* x, long long n, const float* scale) {
   GRID_STRIDE(idx, n) x[idx] = from_f32<T>(to_f32(x[idx]) * s);
 }
 extern "C" int s2p_scale(int dtype, void* x, int64_t n, const float* scale, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_scale: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_scale: bad dtype");
   S2P_REQUIRE(n >= 0, "s2p_scale: negative size");
   if (n == 0) return 0;
   S2P_REQUIRE(x && scale, "s2p_scale: null pointer");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(scale_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (float*)x, (long long)n, scale);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(scale_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (__bf16*)x, (long long)n, scale);
-  else S2P_FAIL(-1, "s2p_scale: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(scale_kernel<T>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (T*)x, (long long)n, scale); });
   S2P_CHECK_LAUNCH("scale_kernel");
   return 0;
 }
@@ -927,13 +904,12 @@ __global__ void add_kernel(const T* a, const T* b, T* out, long long n) {
     out[idx] = from_f32<T>(to_f32(a[idx]) + to_f32(b[idx]));
 }
 extern "C" int s2p_add(int dtype, const void* a, const void* b, void* out, int64_t n, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_add: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_add: bad dtype");
   S2P_REQUIRE(n >= 0, "s2p_add: negative size");
   if (n == 0) return 0;
   S2P_REQUIRE(a && b && out, "s2p_add: null pointer");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(add_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)out, (long long)n);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(add_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)a, (const __bf16*)b, (__bf16*)out, (long long)n);
-  else S2P_FAIL(-1, "s2p_add: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(add_kernel<T>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, (T*)out, (long long)n); });
   S2P_CHECK_LAUNCH("add_kernel");
   return 0;
 }
@@ -950,15 +926,14 @@ __global__ void copy_channels_kernel(const T* src, int sp, int so, T* dst, int d
 }
 extern "C" int s2p_copy_channels(int dtype, const void* src, int src_pitch, int src_off, void* dst, int dst_pitch, int dst_off,
                                  int C, int64_t pixels, int accumulate, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_copy_channels: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_copy_channels: bad dtype");
   S2P_REQUIRE(pixels >= 0 && C >= 0 && src_off >= 0 && dst_off >= 0, "s2p_copy_channels: negative size");
   S2P_REQUIRE(src_off + C <= src_pitch && dst_off + C <= dst_pitch, "s2p_copy_channels: channels exceed pitch");
   long long total = (long long)pixels * C;
   if (total == 0) return 0;
   S2P_REQUIRE(src && dst, "s2p_copy_channels: null pointer");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(copy_channels_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)src, src_pitch, src_off, (float*)dst, dst_pitch, dst_off, C, (long long)pixels, accumulate);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(copy_channels_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)src, src_pitch, src_off, (__bf16*)dst, dst_pitch, dst_off, C, (long long)pixels, accumulate);
-  else S2P_FAIL(-1, "s2p_copy_channels: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(copy_channels_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)src, src_pitch, src_off, (T*)dst, dst_pitch, dst_off, C, (long long)pixels, accumulate); });
   S2P_CHECK_LAUNCH("copy_channels_kernel");
   return 0;
 }
@@ -988,26 +963,24 @@ __global__ void nhwc_to_u8_kernel(const T* x, int pitch, long long pixels, int C
   }
 }
 extern "C" int s2p_u8_to_nhwc(int dtype, const void* x, int64_t pixels, int C, void* y, int y_pitch, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_u8_to_nhwc: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_u8_to_nhwc: bad dtype");
   S2P_REQUIRE(pixels >= 0 && C >= 0 && C <= y_pitch, "s2p_u8_to_nhwc: bad pixels / C / pitch");
   long long total = (long long)pixels * y_pitch;
   if (total == 0) return 0;
   if (!y || (!x && C)) S2P_FAIL(-1, "s2p_u8_to_nhwc: null pointer");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(u8_to_nhwc_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)x, (long long)pixels, C, (float*)y, y_pitch);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(u8_to_nhwc_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)x, (long long)pixels, C, (__bf16*)y, y_pitch);
-  else S2P_FAIL(-1, "s2p_u8_to_nhwc: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(u8_to_nhwc_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)x, (long long)pixels, C, (T*)y, y_pitch); });
   S2P_CHECK_LAUNCH("u8_to_nhwc_kernel");
   return 0;
 }
 extern "C" int s2p_nhwc_to_u8(int dtype, const void* x, int x_pitch, int64_t pixels, int C, void* y, void* stream) {
-  S2P_REQUIRE(is_dtype(dtype), "s2p_nhwc_to_u8: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_nhwc_to_u8: bad dtype");
   S2P_REQUIRE(pixels >= 0 && C >= 0 && C <= x_pitch, "s2p_nhwc_to_u8: bad pixels / C / pitch");
   long long total = (long long)pixels * C;
   if (total == 0) return 0;
   if (!x || !y) S2P_FAIL(-1, "s2p_nhwc_to_u8: null pointer");
-  if (dtype == S2P_F32) hipLaunchKernelGGL(nhwc_to_u8_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, x_pitch, (long long)pixels, C, (unsigned char*)y);
-  else if (dtype == S2P_BF16) hipLaunchKernelGGL(nhwc_to_u8_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, x_pitch, (long long)pixels, C, (unsigned char*)y);
-  else S2P_FAIL(-1, "s2p_nhwc_to_u8: bad dtype");
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(nhwc_to_u8_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, x_pitch, (long long)pixels, C, (unsigned char*)y); });
   S2P_CHECK_LAUNCH("nhwc_to_u8_kernel");
   return 0;
 }

@@ -600,8 +600,8 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const T* dy, long long
 
 // ------------------------------------------------------------------------------------------------
 static int norm_check(const char* who, int dtype, int C, int p0, int p1, int p2) {
-  if (dtype != S2P_F32 && dtype != S2P_BF16) S2P_FAIL(-1, "%s: bad dtype", who);
-  int ce = dtype == S2P_F32 ? 4 : 8;
+  if (!s2p_is_dtype(dtype)) S2P_FAIL(-1, "%s: bad dtype", who);
+  const int ce = s2p_chunk_elems(dtype);
   if (C % ce || p0 % ce || p1 % ce || p2 % ce) S2P_FAIL(-1, "%s: C / pitches must be multiples of %d", who, ce);
   return 0;
 }
@@ -625,7 +625,7 @@ static NormArgs bwd_args(const void* da, int da_pitch, const void* x, int N, int
 }
 // what the launches that write dx / dgb_img / dgb_st refuse
 static int bwd_out_check(const char* who, int dtype, int C, int dx_pitch, int dgb_pitch, const float* dgb_st, int dgb_st_pitch) {
-  const int ce = dtype == S2P_F32 ? 4 : 8;
+  const int ce = s2p_chunk_elems(dtype);
   if (dx_pitch % ce || dgb_pitch % ce) S2P_FAIL(-1, "%s: bad output pitch", who);
   if (dgb_st && dgb_st_pitch < 2 * C) S2P_FAIL(-1, "%s: dgb_st pitch < 2*C", who);
   return 0;
@@ -673,10 +673,10 @@ extern "C" int s2p_in_norm_form(int dtype, int N, int HW, int C, int has_gb_img,
                   : norm_fwd_form(dtype, N, HW, C, has_gb_img != 0, act);
 }
 
-// ---- one launch helper per kernel family: the tanh instantiation and the launch check once; the dtype ladder once for all of them -----
-#define NORM_LAUNCH(kernel, grid, threads, ...) do { \
-    if (dtype == S2P_F32) hipLaunchKernelGGL((kernel<float, __VA_ARGS__>), grid, dim3(threads), 0, st, a); \
-    else hipLaunchKernelGGL((kernel<__bf16, __VA_ARGS__>), grid, dim3(threads), 0, st, a); } while (0)
+// ---- one launch helper per kernel family: the tanh instantiation and the launch check once; the dtype dispatch (norm_check has
+// validated the id) once for all of them -----
+#define NORM_LAUNCH(kernel, grid, threads, ...) s2p_with_dtype(dtype, [&](auto tag) { \
+    hipLaunchKernelGGL((kernel<decltype(tag), __VA_ARGS__>), grid, dim3(threads), 0, st, a); })
 template <int MODE>
 static int launch_reduce(int dtype, NormArgs& a, hipStream_t st) {
   int slabs = cdiv(a.C, 64);
@@ -858,19 +858,15 @@ size_t s2p_channel_sum_ws_bytes(int64_t pixels, int C) {
 // db[c] += sum over pixels of dy[p][c].  ws == nullptr (or too small): fp32 atomics; otherwise partial sums + a fixed-order reduce.
 int s2p_channel_sum_det(int dtype, const void* dy, int64_t pixels, int C, int pitch, float* db, void* ws, size_t ws_bytes,
                         void* stream) {
-  if (dtype != S2P_F32 && dtype != S2P_BF16) S2P_FAIL(-1, "s2p_channel_sum: bad dtype");
-  int ce = dtype == S2P_F32 ? 4 : 8;
+  if (!s2p_is_dtype(dtype)) S2P_FAIL(-1, "s2p_channel_sum: bad dtype");
+  const int ce = s2p_chunk_elems(dtype);
   if (pitch % ce) S2P_FAIL(-1, "s2p_channel_sum: pitch must be a multiple of %d", ce);
   if (pixels <= 0) return 0;
   int nb, rows; channel_sum_geom(pixels, C, nb, rows);
   dim3 grid(cdiv(C, 64), nb);
   float* part = (ws && ws_bytes >= s2p_channel_sum_ws_bytes(pixels, C) && nb > 1) ? (float*)ws : nullptr;
-  if (dtype == S2P_F32)
-    hipLaunchKernelGGL(channel_sum_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy,
-                       (long long)pixels, C, pitch, db, rows, part);
-  else
-    hipLaunchKernelGGL(channel_sum_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy,
-                       (long long)pixels, C, pitch, db, rows, part);
+  s2p_with_dtype(dtype, [&](auto tag) { using T = decltype(tag);
+    hipLaunchKernelGGL(channel_sum_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)dy, (long long)pixels, C, pitch, db, rows, part); });
   S2P_CHECK_LAUNCH("channel_sum_kernel");
   if (part) {
     s2p_partial_reduce(part, nb, (long long)grid.x * 64, C, db, (hipStream_t)stream);

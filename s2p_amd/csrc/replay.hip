@@ -90,7 +90,7 @@ static void launch_gather(const void* pool, int64_t n_slots, int64_t fp, int C, 
 
 extern "C" int s2p_window_gather_u8(int dtype, const void* pool, int64_t n_slots, int64_t frame_pixels, int C, const int32_t* table, int T,
                                     const int64_t* win, int B, void* x, int x_pitch, void* u8_out, void* stream) {
-  S2P_REQUIRE(dtype == S2P_F32 || dtype == S2P_BF16, "s2p_window_gather_u8: bad dtype");
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_window_gather_u8: bad dtype");
   S2P_REQUIRE(n_slots >= 0 && frame_pixels >= 0 && C >= 0 && T >= 0 && B >= 0 && x_pitch >= 0, "s2p_window_gather_u8: negative size");
   S2P_REQUIRE(T <= 65535, "s2p_window_gather_u8: at most 65535 frames per window");
   if ((long long)B * T == 0 || frame_pixels == 0) return 0;            // nothing to gather: no pointer is looked at
@@ -98,9 +98,9 @@ extern "C" int s2p_window_gather_u8(int dtype, const void* pool, int64_t n_slots
   S2P_REQUIRE(!x || C <= x_pitch, "s2p_window_gather_u8: channels exceed pitch");
   if ((x ? x_pitch : C) == 0) return 0;
   S2P_REQUIRE(pool && table && win, "s2p_window_gather_u8: null pointer");
-  S2P_REQUIRE(((uintptr_t)x & 15) == 0, "s2p_window_gather_u8: x must be 16-byte aligned");
-  if (dtype == S2P_F32) launch_gather<float>(pool, n_slots, frame_pixels, C, table, T, win, B, x, x_pitch, u8_out, (hipStream_t)stream);
-  else launch_gather<__bf16>(pool, n_slots, frame_pixels, C, table, T, win, B, x, x_pitch, u8_out, (hipStream_t)stream);
+  S2P_REQUIRE(s2p_al16(x), "s2p_window_gather_u8: x must be 16-byte aligned");
+  s2p_with_dtype(dtype, [&](auto tag) {
+    launch_gather<decltype(tag)>(pool, n_slots, frame_pixels, C, table, T, win, B, x, x_pitch, u8_out, (hipStream_t)stream); });
   S2P_CHECK_LAUNCH("window_gather_kernel");
   return 0;
 }
@@ -174,7 +174,7 @@ extern "C" int s2p_feature_window_gather(const float* feat, int64_t n_slots, int
   S2P_REQUIRE(table && win, "s2p_feature_window_gather: null pointer");
   const bool rows = feature_ || fa || next_fa;
   S2P_REQUIRE(!rows || F == 0 || feat, "s2p_feature_window_gather: null feature table");
-  S2P_REQUIRE((((uintptr_t)feat | (uintptr_t)feature_ | (uintptr_t)fa | (uintptr_t)next_fa) & 15) == 0,
+  S2P_REQUIRE(s2p_al16(feat, feature_, fa, next_fa),
               "s2p_feature_window_gather: feat, feature_, fa and next_fa must be 16-byte aligned");
   if (fa || next_fa)
     S2P_REQUIRE(fa_pitch % 4 == 0 && (long long)(T - 1) * F + (long long)(T - 2) * A <= fa_pitch,
@@ -302,7 +302,7 @@ extern "C" int s2p_frame_pair_gather(const void* pool, int64_t n_frames, int H, 
   const long long frame_bytes = (long long)H * W * C, plane = (long long)out_h * out_w;
   const bool same = out_h == H && out_w == W;
   const bool fast = C == 3 && out_w % 4 == 0 && frame_bytes % 4 == 0 && frame_bytes < 0x7fffffffLL && plane < 0x7fffffffLL &&
-                    ((uintptr_t)pool & 3) == 0 && (((uintptr_t)prev | (uintptr_t)image) & 15) == 0;
+                    ((uintptr_t)pool & 3) == 0 && s2p_al16(prev, image);
   const float sh = (float)H / (float)out_h, sw = (float)W / (float)out_w;       // torch's scales: fp32 quotients
   const long long items = fast ? plane / 4 : plane;                   // thread steps per frame
   long long gx = (items + 255) / 256; if (gx > 64) gx = 64;

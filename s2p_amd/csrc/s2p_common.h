@@ -180,7 +180,17 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
-static inline bool s2p_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// every pointer 16-byte aligned (a null pointer counts as aligned)
+template <typename... P>
+static inline bool s2p_al16(const P*... p) { return ((uintptr_t(0) | ... | (uintptr_t)p) & 15) == 0; }
+
+// ---- dtype ids on the host: the one validity test, the host twin of DT<T>::CE, the one dtype dispatch ------------------------
+static inline bool s2p_is_dtype(int dtype) { return dtype == S2P_F32 || dtype == S2P_BF16; }
+static inline int s2p_chunk_elems(int dtype) { return dtype == S2P_F32 ? 4 : 8; }
+// f(float{}) or f(__bf16{}): the caller writes  using T = decltype(tag);  and launches kernel<T> once, with (const T*)x casts.
+// PRECONDITION: s2p_is_dtype(dtype) was required before the call -- an unknown id would run the bf16 instantiation.
+template <typename F>
+static inline void s2p_with_dtype(int dtype, F&& f) { if (dtype == S2P_F32) f(float{}); else f(__bf16{}); }
 
 // compute units of the current device (256 where there is none to ask: the workspace queries answer without a GPU)
 inline int s2p_num_cus() {

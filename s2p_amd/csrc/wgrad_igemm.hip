@@ -626,7 +626,7 @@ extern "C" size_t s2p_conv2d_wgrad_workspace(const s2p_conv_desc* d, int cin_rea
 
 // K split of the register-staged kernel (fp32): the launch and the scratch query below must agree
 static void wgrad_reg_splits(const s2p_conv_desc* d, int splitk, int& splits, int& steps_per_split) {
-  const int ce = d->dtype == S2P_F32 ? 4 : 8, BT = d->dtype == S2P_F32 ? 64 : 128, T = d->KH * d->KW;
+  const int ce = s2p_chunk_elems(d->dtype), BT = d->dtype == S2P_F32 ? 64 : 128, T = d->KH * d->KW;
   const int cout_pad = (d->Cout + ce - 1) / ce * ce;
   const int Ca = d->transposed ? d->Cin : cout_pad, Cb = d->transposed ? cout_pad : d->Cin;
   const long long M = d->transposed ? (long long)d->N * d->H * d->W : (long long)d->N * d->Ho * d->Wo;
@@ -660,8 +660,8 @@ extern "C" int s2p_conv2d_wgrad_ws(const s2p_conv_desc* d, const void* x, const 
                                    int cin_real, int cout_real, int64_t dw_gstride, int splitk, void* workspace,
                                    size_t workspace_bytes, void* stream) {
   if (!d || !x || !dy || !dw) S2P_FAIL(-1, "s2p_conv2d_wgrad: null pointer");
-  if (d->dtype != S2P_F32 && d->dtype != S2P_BF16) S2P_FAIL(-1, "s2p_conv2d_wgrad: bad dtype");
-  const int ce = d->dtype == S2P_F32 ? 4 : 8;
+  if (!s2p_is_dtype(d->dtype)) S2P_FAIL(-1, "s2p_conv2d_wgrad: bad dtype");
+  const int ce = s2p_chunk_elems(d->dtype);
   if (d->Cin % ce || d->x_pitch % ce || d->y_pitch % ce || d->x_gstride % ce || d->y_gstride % ce)
     S2P_FAIL(-1, "s2p_conv2d_wgrad: channel counts / pitches must be multiples of %d", ce);
   const int T = d->KH * d->KW;
@@ -782,8 +782,7 @@ extern "C" int s2p_conv2d_wgrad_ws(const s2p_conv_desc* d, const void* x, const 
     if (rc) return rc;
   }
   a.part = det ? (float*)workspace : nullptr;
-  if (d->dtype == S2P_F32) hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(wgrad_kernel<__bf16>, grid, dim3(256), 0, st, a);
+  s2p_with_dtype(d->dtype, [&](auto tag) { hipLaunchKernelGGL(wgrad_kernel<decltype(tag)>, grid, dim3(256), 0, st, a); });
   S2P_CHECK_LAUNCH("wgrad_kernel");
   if (det) {
     const long long n = (long long)a.Ca_real * a.dw_row;

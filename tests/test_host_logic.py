@@ -616,3 +616,63 @@ def test_bench_hbm_rows_from_the_committed_profiles():
     assert all(a["read_amplification"] >= 0.9 for a in h["read_amplification"])
     with pytest.raises(RuntimeError, match="library version"):
         b.hbm_rows(64, 84, ver + 1000)
+
+
+# ---- unknown dtype ids are refused before any launch ------------------------------------------------------------------------------------
+_D = object()                 # the dtype slot of a row
+_P = 0x10000                  # a non-null, 16-byte aligned placeholder: nothing is dereferenced before the dtype check
+_NORM_BWD = (_D, _P, 8, _P, 2, 16, 8, 8, _P, None, 0, None, 0, 0, 0.0, 1e-5, _P, _P, 8, None, 0, None, 0)   # ... (res, res_pitch,) stream
+# (export, arguments with non-empty sizes, the name the message carries).  Frozen from what the library answered before the dtype
+# dispatch moved into s2p_with_dtype (s2p_common.h): every entry point checks the dtype FIRST, except s2p_l1_loss_multi, which walks
+# its jobs (host structs; 8-element chunks for an unknown id) before it looks at the dtype -- its row passes a job that clears them.
+# The three wrappers answer under the name of the function they forward to.
+DTYPE_REFUSALS = [
+    ("s2p_avgpool3x3s2_fwd", (_D, _P, 2, 4, 4, 8, _P, None), "s2p_avgpool3x3s2_fwd"),
+    ("s2p_avgpool3x3s2_bwd", (_D, _P, 2, 4, 4, 8, _P, 0, None), "s2p_avgpool3x3s2_bwd"),
+    ("s2p_maxpool2x2_fwd", (_D, _P, 2, 4, 4, 8, _P, None), "s2p_maxpool2x2_fwd"),
+    ("s2p_maxpool2x2_bwd", (_D, _P, _P, 2, 4, 4, 8, _P, None), "s2p_maxpool2x2_bwd"),
+    ("s2p_resize_nearest", (_D, _P, 2, 4, 4, 8, _P, 8, 8, None), "s2p_resize_nearest"),
+    ("s2p_nchw_to_nhwc", (_D, _P, 2, 3, 4, 4, _P, 8, 0, 1, None), "s2p_nchw_to_nhwc"),
+    ("s2p_nhwc_to_nchw", (_D, _P, 8, 0, 2, 3, 4, 4, _P, 0, None), "s2p_nhwc_to_nchw"),
+    ("s2p_cast", (_D, _P, 0, _P, 16, None), "s2p_cast"),                 # the source id
+    ("s2p_cast", (1, _P, _D, _P, 16, None), "s2p_cast"),                 # the destination id
+    ("s2p_reflect_pad_bwd", (_D, _P, 2, 4, 4, 8, 1, _P, None), "s2p_reflect_pad_bwd"),
+    ("s2p_l1_loss", (_D, _P, _P, 16, 1.0, _P, _P, 0, None), "s2p_l1_loss"),
+    ("s2p_l1_loss_multi", (_D, "one job", 1, None), "s2p_l1_loss_multi"),
+    ("s2p_hinge_loss", (_D, _P, 16, 0, 1.0, _P, _P, None), "s2p_hinge_loss"),
+    ("s2p_hinge_loss_strided", (_D, _P, 16, 8, 0, 1.0, _P, _P, None), "s2p_hinge_loss_strided"),
+    ("s2p_act_bwd", (_D, _P, _P, 16, 1, 0.2, _P, None), "s2p_act_bwd"),
+    ("s2p_scale", (_D, _P, 16, _P, None), "s2p_scale"),
+    ("s2p_add", (_D, _P, _P, _P, 16, None), "s2p_add"),
+    ("s2p_copy_channels", (_D, _P, 8, 0, _P, 8, 0, 8, 16, 0, None), "s2p_copy_channels"),
+    ("s2p_u8_to_nhwc", (_D, _P, 16, 3, _P, 8, None), "s2p_u8_to_nhwc"),
+    ("s2p_nhwc_to_u8", (_D, _P, 8, 16, 3, _P, None), "s2p_nhwc_to_u8"),
+    ("s2p_channel_sum", (_D, _P, 16, 8, 8, _P, None), "s2p_channel_sum"),
+    ("s2p_channel_sum_ws", (_D, _P, 16, 8, 8, _P, _P, 1024, None), "s2p_channel_sum"),
+    ("s2p_in_stats", (_D, _P, 2, 16, 8, 8, 1e-5, _P, None), "s2p_in_stats"),
+    ("s2p_in_apply_fwd", (_D, _P, 2, 16, 8, 8, _P, None, 0, None, 0, 0, 0.0, 1e-5, _P, 8, None), "s2p_in_apply_fwd"),
+    ("s2p_in_norm_fwd", (_D, _P, 2, 16, 8, 8, None, 0, None, 0, 0, 0.0, 1e-5, _P, 8, _P, None), "s2p_in_norm_fwd"),
+    ("s2p_in_bwd_reduce", (_D, _P, 8, _P, 2, 16, 8, 8, _P, None, 0, None, 0, 0, 0.0, 1e-5, _P, None), "s2p_in_bwd_reduce"),
+    ("s2p_in_bwd_apply", _NORM_BWD + (None,), "s2p_in_bwd_apply"),
+    ("s2p_in_norm_bwd", _NORM_BWD + (None,), "s2p_in_norm_bwd"),
+    ("s2p_in_norm_bwd_res", _NORM_BWD + (None, 0, None), "s2p_in_norm_bwd"),
+    ("s2p_in_norm_form", (_D, 2, 16, 8, 0, 0, 0, 0), "s2p_in_norm_form"),
+    ("s2p_gauss_ll_image", (_D, _P, 8, _P, 0, 2, 3, 16, 1.0, 1.0, _P, _P, None), "s2p_gauss_ll_image"),
+    ("s2p_window_gather_u8", (_D, _P, 4, 16, 3, _P, 2, _P, 2, _P, 8, None, None), "s2p_window_gather_u8"),
+    ("s2p_u8_chw_to_nhwc01", (_D, _P, 2, 3, 4, 4, _P, 8, None), "s2p_u8_chw_to_nhwc01"),
+]
+
+
+def test_unknown_dtype_ids_are_refused_without_a_device():
+    """An id that is neither S2P_F32 nor S2P_BF16 must never reach a launch (the dispatch would run the bf16 instantiation): every
+    dtype-taking export answers -1 and "<name>: bad dtype", before any pointer is looked at."""
+    L = _lib.lib()
+    assert {n for n, _, _ in DTYPE_REFUSALS} <= set(_lib.SIGNATURES)
+    job = (_lib.L1Job * 1)(_lib.L1Job(_P, _P, _P, 16, 1.0, _P))          # aligned pointers, a count of whole chunks for either width
+    for name, args, who in DTYPE_REFUSALS:
+        assert len(args) == len(_lib.SIGNATURES[name]), name
+        for bad in (2, -1):
+            L.s2p_scale(0, None, -1, None, None)                          # (another message first: a stale text cannot pass)
+            call = [bad if a is _D else (job if isinstance(a, str) else a) for a in args]
+            assert getattr(L, name)(*call) == -1, (name, bad)
+            assert L.s2p_last_error() == (who + ": bad dtype").encode(), (name, bad, L.s2p_last_error())
