@@ -19,8 +19,10 @@ import types
 import numpy as np
 import torch
 
+from s2p_amd.latent_cli import add_chain_options, check_chain_options, load_latent, need_device, net_shape
 
-def parse_args(argv=None):
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--latent_dir", required=True, help="directory holding latent.pth")
     ap.add_argument("--policy_dir", required=True, help="directory holding policy.pth")
@@ -30,19 +32,20 @@ def parse_args(argv=None):
     ap.add_argument("--max_path_length", type=int, default=1000)
     ap.add_argument("--num_envs", type=int, default=4)
     ap.add_argument("--slac_policy_input_type", choices=["feature_action", "latent_z"], default="feature_action")
-    ap.add_argument("--fused_chain", action="store_true",
-                    help="latent_z: run the posterior chain of every acting step as one launch (bitwise the same result)")
-    ap.add_argument("--bf16_chain", action="store_true",
-                    help="with --fused_chain: bf16 matrix-core compute inside the fused no-grad latent chain (SPEC.md N3m), independent of --bf16 and "
-                         "--bf16_mlp: weights and LDS activations rounded to bf16, fp32 sums, heads and outputs; mixed precision, not the same numbers")
+    add_chain_options(ap, bf16_chain=True,
+                      fused_chain="latent_z: run the posterior chain of every acting step as one launch (bitwise the same result)")
     ap.add_argument("--reset_w_same_obs", action="store_true", help="pad a new episode's window with its first frame, not with zero frames")
-    ap.add_argument("--bf16", action="store_true", help="bf16 conv stack of the encoder (the policy stays fp32)")
+    add_chain_options(ap, bf16_help="bf16 conv stack of the encoder (the policy stays fp32)")
     ap.add_argument("--num_sequences", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0, help="seeds the posterior noise of latent_z")
     ap.add_argument("--out", help="write the per-episode arrays to this .npz")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
-    if a.bf16_chain and not a.fused_chain:
-        ap.error("--bf16_chain needs --fused_chain: the bf16 compute mode exists only in the fused chain kernels")
+    check_chain_options(ap, a)
     if a.episodes < 0 or a.max_path_length < 1 or not 1 <= a.num_envs <= 16:
         ap.error("--episodes >= 0, --max_path_length >= 1 and 1 <= --num_envs <= 16")
     return a
@@ -77,32 +80,18 @@ def make_envs(a):
     return [factory(**kwargs) for _ in range(a.num_envs)]
 
 
-def policy_shape(sd):
-    """(hidden sizes, obs_dim, action_dim) of a `policy.pth`."""
-    hidden = []
-    while "fc%d.weight" % len(hidden) in sd:
-        hidden.append(int(sd["fc%d.weight" % len(hidden)].shape[0]))
-    return hidden, int(sd["fc0.weight"].shape[1]), int(sd["last_fc.weight"].shape[0])
-
-
 def main(argv=None):
     a = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("evaluate_policy.py needs a HIP device (no CPU fallback)")
+    need_device("evaluate_policy.py")
     from s2p_amd.actor import SlacActor, run_episodes
     from s2p_amd.offline_rl import TanhGaussianPolicy
-    from s2p_amd.slac import LatentModel
     torch.manual_seed(a.seed)
     torch.cuda.manual_seed(a.seed)
     sd = torch.load(os.path.join(a.policy_dir, "policy.pth"), map_location="cpu")
-    hidden, obs_dim, A = policy_shape(sd)
+    hidden, obs_dim, A = net_shape(sd)
     policy = TanhGaussianPolicy(hidden_sizes=hidden, obs_dim=obs_dim, action_dim=A).load_state_dict(sd, strict=True)
     state_shape = (3, 100, 100)
-    latent = LatentModel(state_shape, (A,), dtype=torch.bfloat16 if a.bf16 else torch.float32, device="cuda:0")
-    latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
-    latent.fused_chain = a.fused_chain
-    latent.chain_compute = "bf16" if a.bf16_chain else "fp32"
-    algo = types.SimpleNamespace(latent=latent, state_shape=state_shape, action_shape=(A,), num_sequences=a.num_sequences)
+    algo = types.SimpleNamespace(latent=load_latent(a, state_shape, A), state_shape=state_shape, action_shape=(A,), num_sequences=a.num_sequences)
     actor = SlacActor(policy, algo, a.num_envs, a.slac_policy_input_type, a.reset_w_same_obs)
     out = run_episodes(make_envs(a), actor, a.episodes, a.max_path_length)
     print("Average Returns %.6f" % out["average_return"])

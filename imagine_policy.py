@@ -19,10 +19,12 @@ import os
 import numpy as np
 import torch
 
+from s2p_amd.latent_cli import add_chain_options, load_latent, need_device, net_shape
+
 Z = 288
 
 
-def parse_args(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", required=True, help="dataset file (.npz / .hdf5) with image_observations, image_observations_tp1, actions, rewards, timeouts")
     ap.add_argument("--latent_dir", required=True, help="directory holding latent.pth")
@@ -36,23 +38,19 @@ def parse_args(argv=None):
     ap.add_argument("--discount", type=float, default=0.99)
     ap.add_argument("--mean", action="store_true", help="roll the means: no noise in the posterior or the rollout")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--bf16", action="store_true", help="bf16 conv stack of the encoder")
-    ap.add_argument("--fused_chain", action="store_true", help="every chain as one launch (bitwise the same result)")
+    add_chain_options(ap, bf16_help="bf16 conv stack of the encoder", fused_chain="every chain as one launch (bitwise the same result)")
     ap.add_argument("--bootstrap", action="store_true", help="add discount^H min(qf1, qf2)(z(H), pi(z(H))) from critic.pth")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.context < 1:
         ap.error("--context >= 1")
     if a.windows < 1 or a.batch < 1 or (a.stride is not None and a.stride < 1):
         ap.error("--windows, --batch and --stride are at least 1")
     return a
-
-
-def net_shape(sd, prefix=""):
-    """(hidden sizes, input size, output size) of the MLP under `prefix` of a state_dict."""
-    hidden = []
-    while "%sfc%d.weight" % (prefix, len(hidden)) in sd:
-        hidden.append(int(sd["%sfc%d.weight" % (prefix, len(hidden))].shape[0]))
-    return hidden, int(sd[prefix + "fc0.weight"].shape[1]), int(sd[prefix + "last_fc.weight"].shape[0])
 
 
 def mean_se(x):
@@ -66,7 +64,6 @@ def main(argv=None):
         raise SystemExit("--horizon is at least 1")
     from s2p_amd.data import load_arrays
     from s2p_amd.offline_rl import CriticSLAC, Qfunction, TanhGaussianPolicy, Vfunction
-    from s2p_amd.slac import LatentModel
     from s2p_amd.slac_imagine import behaviour, imagined_returns
     from s2p_amd.slac_predict import gather, windows
     data = load_arrays(a.data)
@@ -81,8 +78,7 @@ def main(argv=None):
                          "would need decoded frames in the loop, which is not built" % (obs_dim, Z))
     if A != int(np.asarray(data["actions"]).shape[1]):
         raise SystemExit("policy.pth has %d actions, the dataset %d" % (A, int(np.asarray(data["actions"]).shape[1])))
-    if not torch.cuda.is_available():
-        raise SystemExit("imagine_policy.py needs a HIP device (no CPU fallback)")
+    need_device("imagine_policy.py")
     torch.manual_seed(a.seed)
     torch.cuda.manual_seed(a.seed)
     policy = TanhGaussianPolicy(hidden_sizes=hidden, obs_dim=obs_dim, action_dim=A).load_state_dict(sd, strict=True)
@@ -93,9 +89,7 @@ def main(argv=None):
         q = [Qfunction(hidden_sizes=qh, output_size=1, input_size=qin) for _ in range(4)]
         critic = CriticSLAC(q[0], q[1], q[2], q[3], vf=Vfunction(hidden_sizes=qh, output_size=1, input_size=net_shape(csd, "vf.")[1]))
         critic.load_state_dict(csd, strict=True)
-    latent = LatentModel((3, 100, 100), (A,), dtype=torch.bfloat16 if a.bf16 else torch.float32, device="cuda:0")
-    latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
-    latent.fused_chain = a.fused_chain
+    latent = load_latent(a, (3, 100, 100), A)
     parts = {}
     for lo in range(0, len(starts), a.batch):
         st = starts[lo:lo + a.batch]

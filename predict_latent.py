@@ -13,15 +13,16 @@ those columns (`psnr`, `ssim`, `baseline_psnr`, `baseline_ssim`, `reward_abs_err
 `frames` as uint8 [n,H,100,100,3].  --mean rolls the means (no noise anywhere); --fused_chain runs every chain as one launch
 (bitwise the same result); --bf16_chain gives those launches bf16 operands (SPEC.md N3m: mixed precision, not the same numbers)."""
 import argparse
-import os
 
 import numpy as np
 import torch
 
+from s2p_amd.latent_cli import add_chain_options, check_chain_options, load_latent, need_device
+
 COLUMNS = ("psnr", "ssim", "baseline_psnr", "baseline_ssim", "reward_abs_err")
 
 
-def parse_args(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", required=True, help="dataset file (.npz / .hdf5) with image_observations, image_observations_tp1, actions, rewards, timeouts")
     ap.add_argument("--latent_dir", required=True, help="directory holding latent.pth")
@@ -33,15 +34,16 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=64, help="windows per device batch")
     ap.add_argument("--mean", action="store_true", help="roll the means: no noise in the posterior or the rollout")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--bf16", action="store_true", help="bf16 conv stacks of the encoder and the decoder")
-    ap.add_argument("--fused_chain", action="store_true", help="posterior and prior chain as one launch each (bitwise the same result)")
-    ap.add_argument("--bf16_chain", action="store_true",
-                    help="with --fused_chain: bf16 matrix-core compute inside the fused no-grad latent chain (SPEC.md N3m), independent of --bf16 and "
-                         "--bf16_mlp: weights and LDS activations rounded to bf16, fp32 sums, heads and outputs; mixed precision, not the same numbers")
+    add_chain_options(ap, bf16_help="bf16 conv stacks of the encoder and the decoder", bf16_chain=True,
+                      fused_chain="posterior and prior chain as one launch each (bitwise the same result)")
     ap.add_argument("--frames", action="store_true", help="also write the predicted frames")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
-    if a.bf16_chain and not a.fused_chain:
-        ap.error("--bf16_chain needs --fused_chain: the bf16 compute mode exists only in the fused chain kernels")
+    check_chain_options(ap, a)
     if a.horizon < 1 or a.context < 1:
         ap.error("--horizon >= 1 and --context >= 1")
     if a.windows < 1 or a.batch < 1 or (a.stride is not None and a.stride < 1):
@@ -51,10 +53,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("predict_latent.py needs a HIP device (no CPU fallback)")
+    need_device("predict_latent.py")
     from s2p_amd.data import load_arrays
-    from s2p_amd.slac import LatentModel
     from s2p_amd.slac_predict import gather, open_loop, windows
     data = load_arrays(a.data)
     length = a.context + a.horizon
@@ -64,11 +64,7 @@ def main(argv=None):
         raise SystemExit("%s: %s" % (a.data, e))
     torch.manual_seed(a.seed)
     torch.cuda.manual_seed(a.seed)
-    A = int(np.asarray(data["actions"]).shape[1])
-    latent = LatentModel((3, 100, 100), (A,), dtype=torch.bfloat16 if a.bf16 else torch.float32, device="cuda:0")
-    latent.load_state_dict(torch.load(os.path.join(a.latent_dir, "latent.pth"), map_location="cpu"), strict=True)
-    latent.fused_chain = a.fused_chain
-    latent.chain_compute = "bf16" if a.bf16_chain else "fp32"
+    latent = load_latent(a, (3, 100, 100), int(np.asarray(data["actions"]).shape[1]))
     keep = ("z", "reward_mean", "reward_std") + COLUMNS + (("frames",) if a.frames else ())
     parts = {k: [] for k in keep}
     for lo in range(0, len(starts), a.batch):

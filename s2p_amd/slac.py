@@ -337,7 +337,7 @@ def _mlp_tail_wgrad(g, pk, draw, h2, dh2, h1, dev):
 
 
 def _mlp_fwd(g, pk, x, M, dev):
-    h1, h2, raw = _f32((M, HID), dev), _f32((M, HID), dev), _f32((M, g.Npad), dev)
+    h1, h2, raw = _head_state([g], (M,), dev)[0]
     ops.linear_fwd_into(x, pk["g1"][0][0], pk["b1"], HID, h1, ACT_LRELU, SLOPE)
     _mlp_tail_fwd(g, pk, h1, h2, raw)
     return h1, h2, raw
@@ -409,50 +409,74 @@ class _GaussFn(torch.autograd.Function):
         return (dx, None) + tuple(grads)
 
 
+def _head_state(gs, lead, dev):
+    """The posterior chain's backward state of the Gaussian heads `gs`, uninitialised: per head (h1, h2, raw) on rows of the leading
+    shape `lead` -- (B,) for the two t = 0 heads, (Tn, B) for the two chain heads -- in the order `ops.chain_state` and
+    `_PosteriorFn.backward` read them, whichever forward form fills them."""
+    return [(_f32(lead + (HID,), dev), _f32(lead + (HID,), dev), _f32(lead + (g.Npad,), dev)) for g in gs]
+
+
+def _chain_mlps(packs):
+    return [ops.chain_mlp(p) for p in packs]
+
+
+def _chain_mlps_bf16(heads):
+    return [ops.chain_mlp_bf16(g.packed_bf16()) for g in heads]
+
+
 class _PosteriorFn(torch.autograd.Function):
     """The reparameterised posterior chain (latent.py:250-281) as ONE autograd node over HIP launches.
     feat [B,T,256], action [B,T-1,A], noise [B,T,288] (keep: the caller's grad mode; activations are saved only then) -> z1_mean [B,T,32], z1_std [B,T,32], z [B,T,288] (z1 | z2).
     Per time step the chain is 8 launches forward (2 x (3 layers + head)) and 8 backward (2 x (head + 3 dgrads)): the
     feature / action columns of the two first layers are one batched GEMM before the chain, every weight gradient and the
-    feature / action gradients are batched launches after it.  With `model.fused_chain` a call that keeps no backward state
-    (keep False) runs the hoisted GEMMs and then the whole chain as one launch (_fused; SPEC.md N3h), bitwise the same.  With
-    `model.fused_chain_grad` a call that does keep it runs the chain as one launch that also stores that state (_fused_save), and the
-    8 S sequential launches of the backward as one (SPEC.md N3k), bitwise the same again."""
+    feature / action gradients are batched launches after it.  `model.chain_form(keep)` names what the forward does with the chain
+    itself: "layers" runs those 8 launches per step; "fused" / "fused_bf16" (`model.fused_chain`, no backward state kept) run it as
+    one launch (SPEC.md N3h, bitwise the same; N3m, bf16 operands); "fused_save" (`model.fused_chain_grad`, state kept) as one launch
+    that also stores that state, with the 8 S sequential launches of the backward as one (SPEC.md N3k), bitwise the same again."""
 
     @staticmethod
     def forward(ctx, feat, action, noise, model, keep, *params):
         dev = feat.device
         B, T, _ = feat.shape
-        S, A = T - 1, action.shape[2]
-        gi1, gi2, g1, g2 = model.z1_posterior_init, model.z2_prior_init, model.z1_posterior, model.z2_prior
-        pi1, pi2, p1, p2 = gi1.packed(), gi2.packed(), g1.packed(), g2.packed()
-        Tn = max(S, 1) if keep else 1                                  # time slots of the saved activations
-        slot = (lambda t: t - 1) if keep else (lambda t: 0)
+        S = T - 1
+        form = model.chain_form(keep)
+        ctx.fused = form == "fused_save"                               # the backward follows what the forward did
+        gs = gi1, gi2, g1, g2 = model._chain_heads()
+        packs = pi1, pi2, p1, p2 = tuple(g.packed() for g in gs)
         z = _f32((B, T, Z1 + Z2), dev)
         mean, std = _f32((B, T, Z1), dev), _f32((B, T, Z1), dev)
-        if model.fused_chain and not keep:
-            return _PosteriorFn._fused(ctx, model, feat, action, noise, (pi1, pi2, p1, p2), mean, std, z)
-        ctx.fused = bool(keep and model.fused_chain_grad)                  # the backward follows what the forward did
-        if ctx.fused:
-            return _PosteriorFn._fused_save(ctx, model, feat, action, noise, (pi1, pi2, p1, p2), mean, std, z)
-        # t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
-        xz = _f32((Tn, B, Z1 + Z2), dev)                               # [slot(t)] = z1(t) | z2(t-1): the chain's input rows
-        a0 = _mlp_fwd(gi1, pi1, feat[:, 0], B, dev)
-        ops.gauss_head_fwd(a0[2], Z1, eps=noise[:, 0, :Z1], mean=mean[:, 0], std=std[:, 0], z=z[:, 0, :Z1])
-        b0 = _mlp_fwd(gi2, pi2, z[:, 0, :Z1], B, dev)
-        ops.gauss_head_fwd(b0[2], Z2, eps=noise[:, 0, Z1:], z=z[:, 0, Z1:], z2=xz[0][:, Z1:] if S > 0 else None)
-        sv = None
+        xz = a0 = b0 = chain = xa = xb = ra = rb = None
+        state = form in ("layers", "fused_save")                       # the forms that fill backward state: its one allocation
+        Tn = max(S, 1) if keep else 1                                  # time slots of that state: one when it is not kept
+        if state:
+            xz = _f32((Tn, B, Z1 + Z2), dev)                           # [slot(t)] = z1(t) | z2(t-1): the chain's input rows
+        if form == "fused_save":
+            a0, b0 = _head_state(gs[:2], (B,), dev)
+        elif form == "layers":                                         # t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
+            a0 = _mlp_fwd(gi1, pi1, feat[:, 0], B, dev)
+            ops.gauss_head_fwd(a0[2], Z1, eps=noise[:, 0, :Z1], mean=mean[:, 0], std=std[:, 0], z=z[:, 0, :Z1])
+            b0 = _mlp_fwd(gi2, pi2, z[:, 0, :Z1], B, dev)
+            ops.gauss_head_fwd(b0[2], Z2, eps=noise[:, 0, Z1:], z=z[:, 0, Z1:], z2=xz[0][:, Z1:] if S > 0 else None)
         if S > 0:
             xa, xb, ra, rb = _PosteriorFn._hoisted(feat, action, p1, p2)
-            h1a, h2a, rawa = _f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g1.Npad), dev)
-            h1b, h2b, rawb = _f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g2.Npad), dev)
+            if state:
+                chain = sum(_head_state(gs[2:], (Tn, B), dev), ())     # h1a, h2a, rawa, h1b, h2b, rawb
+        if form == "fused":                                            # the whole chain, t = 0 included, as ONE launch (SPEC.md N3h)
+            ops.posterior_chain_fwd(feat[:, 0], ra, rb, noise, _chain_mlps(packs), mean, std, z)
+        elif form == "fused_bf16":                                     # SPEC.md N3m: the same launch count, bf16 operands
+            ops.posterior_chain_fwd_bf16(feat[:, 0], ra, rb, noise, _chain_mlps_bf16(gs), mean, std, z)
+        elif form == "fused_save":                                     # one launch that also fills the state (SPEC.md N3k)
+            ops.posterior_chain_fwd_save(feat[:, 0], ra, rb, noise, _chain_mlps(packs), mean, std, z,
+                                         ops.chain_state(a0, b0, chain + (xz,) if chain else None))
+        else:
+            slot = (lambda t: t - 1) if keep else (lambda t: 0)
             for t in range(1, T):
                 s, r = slot(t), slice((t - 1) * B, t * B)
                 # q(z1(t) | feat(t), z2(t-1), a(t-1)), q(z2(t) | z1(t), z2(t-1), a(t-1))
-                _chain_step(g1, p1, g2, p2, (h1a[s], h2a[s], rawa[s]), (h1b[s], h2b[s], rawb[s]), ra[r], rb[r], noise, mean, std, z, t,
+                _chain_step(g1, p1, g2, p2, tuple(c[s] for c in chain[:3]), tuple(c[s] for c in chain[3:]), ra[r], rb[r], noise, mean, std, z, t,
                             xz[s], xz[slot(t + 1)] if t < S else None)
-            sv = (xa, xb, h1a, h2a, rawa, h1b, h2b, rawb)
-        ctx.model, ctx.packs, ctx.A = model, (pi1, pi2, p1, p2), A
+        sv = (xa, xb) + chain if keep and S > 0 else None             # every form leaves the same behind: operands, state, its bytes
+        ctx.model, ctx.packs, ctx.A = model, packs, action.shape[2]
         ctx.saved = (feat, noise, z, xz, a0, b0, sv) if keep else None
         model.chain_state_bytes = sum(t.numel() * 4 for t in (xz,) + a0 + b0 + (sv or ())) if keep else 0
         return mean, std, z
@@ -474,51 +498,10 @@ class _PosteriorFn(torch.autograd.Function):
         return xa, xb, ra, rb
 
     @staticmethod
-    def _fused(ctx, model, feat, action, noise, packs, mean, std, z):
-        """No backward state is wanted: the hoisted terms as in forward(), then the whole chain as ONE launch
-        (s2p_posterior_chain_fwd; bitwise the per-layer path) -- or, with `model.chain_compute == "bf16"`, its bf16-compute twin."""
-        pi1, pi2, p1, p2 = packs
-        ra = rb = None
-        if feat.shape[1] > 1:
-            _, _, ra, rb = _PosteriorFn._hoisted(feat, action, p1, p2)
-        if model.bf16_chain():                                         # SPEC.md N3m: the same launch count, bf16 operands
-            heads = (model.z1_posterior_init, model.z2_prior_init, model.z1_posterior, model.z2_prior)
-            ops.posterior_chain_fwd_bf16(feat[:, 0], ra, rb, noise, [ops.chain_mlp_bf16(g.packed_bf16()) for g in heads], mean, std, z)
-        else:
-            ops.posterior_chain_fwd(feat[:, 0], ra, rb, noise, [ops.chain_mlp(p) for p in packs], mean, std, z)
-        ctx.model, ctx.packs, ctx.A, ctx.saved = model, packs, action.shape[2], None
-        model.chain_state_bytes = 0
-        return mean, std, z
-
-    @staticmethod
-    def _fused_save(ctx, model, feat, action, noise, packs, mean, std, z):
-        """Backward state is wanted and `model.fused_chain_grad` is set: the hoisted terms, then the whole chain as ONE launch that
-        also fills the buffers forward() keeps (s2p_posterior_chain_fwd_save; SPEC.md N3k) -- the same tensors in the same layout,
-        bitwise."""
-        dev = feat.device
-        B, T, _ = feat.shape
-        S, Tn = T - 1, max(T - 1, 1)
-        gs = (model.z1_posterior_init, model.z2_prior_init, model.z1_posterior, model.z2_prior)
-        xz = _f32((Tn, B, Z1 + Z2), dev)
-        a0, b0 = [(_f32((B, HID), dev), _f32((B, HID), dev), _f32((B, g.Npad), dev)) for g in gs[:2]]
-        sv = ra = rb = None
-        if S > 0:
-            xa, xb, ra, rb = _PosteriorFn._hoisted(feat, action, packs[2], packs[3])
-            (h1a, h2a, rawa), (h1b, h2b, rawb) = [(_f32((Tn, B, HID), dev), _f32((Tn, B, HID), dev), _f32((Tn, B, g.Npad), dev))
-                                                  for g in gs[2:]]
-            sv = (xa, xb, h1a, h2a, rawa, h1b, h2b, rawb)
-        ops.posterior_chain_fwd_save(feat[:, 0], ra, rb, noise, [ops.chain_mlp(p) for p in packs], mean, std, z,
-                                     ops.chain_state(a0, b0, sv[2:] + (xz,) if sv else None))
-        ctx.model, ctx.packs, ctx.A = model, packs, action.shape[2]
-        ctx.saved = (feat, noise, z, xz, a0, b0, sv)
-        model.chain_state_bytes = sum(t.numel() * 4 for t in (xz,) + a0 + b0 + (sv or ()))
-        return mean, std, z
-
-    @staticmethod
     def backward(ctx, dmean, dstd, dz):
         model, A = ctx.model, ctx.A
         pi1, pi2, p1, p2 = ctx.packs
-        gi1, gi2, g1, g2 = model.z1_posterior_init, model.z2_prior_init, model.z1_posterior, model.z2_prior
+        gi1, gi2, g1, g2 = model._chain_heads()
         feat, noise, z, xz, a0, b0, sv = ctx.saved
         dev = feat.device
         B, T, _ = feat.shape
@@ -679,16 +662,24 @@ class LatentModel(nn.Module):
     def device(self):
         return self.encoder.device
 
-    def bf16_chain(self):
-        """Whether a fused no-grad chain that is about to run multiplies in bf16 (SPEC.md N3m); ValueError for an unknown `chain_compute`.
-        Read only there: with grad, on the per-layer path and in `imagine` the attribute changes nothing."""
+    def chain_form(self, keep):
+        """How a posterior or prior chain that is about to run does its steps, from the three switches.  keep (backward state is
+        wanted): "fused_save" with `fused_chain_grad`, else "layers".  Without: "layers" unless `fused_chain`; then "fused", or
+        "fused_bf16" when the launch multiplies in bf16 (SPEC.md N3m).  `chain_compute` is read, and an unknown value is a ValueError,
+        only there: with grad, on the per-layer path and in `imagine` the attribute changes nothing."""
+        if keep:
+            return "fused_save" if self.fused_chain_grad else "layers"
+        if not self.fused_chain:
+            return "layers"
         if self.chain_compute not in ("fp32", "bf16"):
             raise ValueError("chain_compute is 'fp32' or 'bf16', not %r" % (self.chain_compute,))
-        return self.chain_compute == "bf16"
+        return "fused_bf16" if self.chain_compute == "bf16" else "fused"
+
+    def _chain_heads(self):
+        return self.z1_posterior_init, self.z2_prior_init, self.z1_posterior, self.z2_prior
 
     def _chain_params(self):
-        return (self.z1_posterior_init.layer_params() + self.z2_prior_init.layer_params() + self.z1_posterior.layer_params() +
-                self.z2_prior.layer_params())
+        return sum((g.layer_params() for g in self._chain_heads()), [])
 
     def _posterior(self, features_, actions_, noise):
         dev = self.device
@@ -764,12 +755,13 @@ class LatentModel(nn.Module):
             return mean, std, z
         g1, g2, p1, p2, wc, wb, xz = st
         rc, rb = _action_term(actions_, wc)[1], _action_term(actions_, wb)[1]
-        if self.fused_chain:
-            if self.bf16_chain():
-                ops.prior_chain_fwd_bf16(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp_bf16(g1.packed_bf16(k1=Z2)),
-                                                                     ops.chain_mlp_bf16(g2.packed_bf16())], mean, std, z)
-            else:
-                ops.prior_chain_fwd(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], mean, std, z)
+        form = self.chain_form(False)
+        if form == "fused_bf16":
+            ops.prior_chain_fwd_bf16(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp_bf16(g1.packed_bf16(k1=Z2)),
+                                                                 ops.chain_mlp_bf16(g2.packed_bf16())], mean, std, z)
+            return mean, std, z
+        if form == "fused":
+            ops.prior_chain_fwd(xz[:, Z1:], rc, rb, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], mean, std, z)
             return mean, std, z
         h1, h2 = _f32((B, HID), self.device), _f32((B, HID), self.device)
         bufa, bufb = (h1, h2, _f32((B, g1.Npad), self.device)), (h1, h2, _f32((B, g2.Npad), self.device))
