@@ -436,6 +436,24 @@ int s2p_posterior_chain_fwd_bf16(const float* feat, int feat_pitch, const float*
 int s2p_prior_chain_fwd_bf16(const float* z2_0, int z2_0_pitch, const float* rc, const float* rb, const float* eps, int eps_pitch,
                              const s2p_chain_mlp_bf16* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
                              int z_pitch, int B, int H, void* stream);
+/* The closed-loop rollout in bf16 compute (SPEC.md N3n; csrc/gauss_chain_bf16.hip): the arguments, no-ops and refusals of
+ * s2p_imagine_chain_fwd, ONE launch.  Every tensor stays fp32 (z0, eps, wc, wb, act, mean, std, z, the biases) except the weight
+ * operands: mlps as for s2p_prior_chain_fwd_bf16 (z1_prior: the pack of its 256 z2 columns, k1 == 256; z2_prior: k1 == 288), and
+ * s2p_policy_mlp_bf16 holds w1 [W][w1_row >= 288], w2 [W][W], w3 [>= A][W] (the last_fc rows first) as bf16 bits, each the fp32
+ * parameter rounded to nearest even, 16-byte aligned, w1_row in bf16 elements and a multiple of 8.  The latent half follows the rule
+ * above.  The policy's first layer reads z(h) as the kernel holds it in bf16; its two hidden activations are rounded to bf16 where
+ * they are written to LDS; per layer acc = the fp32 sum of the exact products on v_mfma_f32_16x16x32_bf16, k ascending in steps of 32,
+ * K never split, then relu(acc + bias) resp. tanh(acc + bias) in fp32.  a(h) is NOT rounded: the two action terms are bitwise
+ * s2p_linear_fwd of a(h) [B][pad4(A)] on wc / wb without bias, the first layers (acc + add) + bias.  A row's values do not depend on B;
+ * two identical calls are bitwise equal.  Nothing but act (exactly A columns), mean, std and z is written.                          */
+typedef struct {
+  const uint16_t* w1; const float* b1; const uint16_t* w2; const float* b2; const uint16_t* w3; const float* b3;
+  int32_t w1_row, width;
+} s2p_policy_mlp_bf16;
+int s2p_imagine_chain_fwd_bf16(const float* z0, int z0_pitch, const float* eps, int eps_pitch, const s2p_chain_mlp_bf16* mlps,
+                               const float* wc, int wc_row, const float* wb, int wb_row, int A, const s2p_policy_mlp_bf16* policy,
+                               float* act, int act_pitch, float* mean, int mean_pitch, float* std, int std_pitch, float* z, int z_pitch,
+                               int B, int H, void* stream);
 /* KL(p || q) of diagonal Gaussians, value and all four gradients in one pass (slac/utils.py:66-69):
  *   loss[0] += scale * sum 0.5 ((sp/sq)^2 + ((mp-mq)/sq)^2 - 1 - log (sp/sq)^2),  d* = scale * dKL/d*  (overwritten; any NULL).
  * p: [B][T][p_pitch >= D].  const_first == 0: q is [B][T][q_pitch]; const_first != 0: q is [B][T-1][q_pitch] and holds the

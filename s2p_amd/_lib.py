@@ -94,6 +94,11 @@ class PolicyMlp(ctypes.Structure):
                 ("w1_row", ctypes.c_int32), ("width", ctypes.c_int32)]
 
 
+class PolicyMlpBf16(ctypes.Structure):
+    """s2p_policy_mlp_bf16: PolicyMlp with the three weight operands as bf16 bits (w1_row in bf16 elements); the biases stay fp32."""
+    _fields_ = PolicyMlp._fields_
+
+
 class MlpBwdGroup(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("dpre", c_void_p), ("w", c_void_p), ("dw", c_void_p), ("db", c_void_p), ("pre_prev", c_void_p),
                 ("dprev", c_void_p), ("x_pitch", ctypes.c_int32), ("dpre_pitch", ctypes.c_int32), ("prev_pitch", ctypes.c_int32),
@@ -164,6 +169,8 @@ SIGNATURES = {
                                  _P],
     "s2p_imagine_chain_fwd": [_P, c_int, _P, c_int, ctypes.POINTER(ChainMlp), _P, c_int, _P, c_int, c_int, ctypes.POINTER(PolicyMlp),
                               _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
+    "s2p_imagine_chain_fwd_bf16": [_P, c_int, _P, c_int, ctypes.POINTER(ChainMlpBf16), _P, c_int, _P, c_int, c_int,
+                                   ctypes.POINTER(PolicyMlpBf16), _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
     "s2p_linear_add_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int, _P, _P,
                            c_int, c_int, _P, c_int, _P],
     "s2p_gauss_kl": [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int, _P, _P, c_int, _P],

@@ -1,5 +1,6 @@
 // The two fused no-grad latent chains of gauss_chain.hip -- the posterior chain (SPEC.md N3h) and the open-loop prior chain (N3i) -- in
-// bf16 compute (SPEC.md N3m): s2p_posterior_chain_fwd_bf16, s2p_prior_chain_fwd_bf16.  Ordinary mixed precision: every tensor the
+// bf16 compute (SPEC.md N3m): s2p_posterior_chain_fwd_bf16, s2p_prior_chain_fwd_bf16; further down the closed-loop imagination chain
+// (N3j) in the same mode (N3n): s2p_imagine_chain_fwd_bf16.  Ordinary mixed precision: every tensor the
 // caller sees stays fp32; the WEIGHT operand of each layer is a bf16 pack the host made once (round to nearest even), the ACTIVATION
 // operand is rounded to bf16 where it is written to LDS (feat(0), z1(t), z2(t-1), h1, h2), the products are summed in fp32 on
 // v_mfma_f32_16x16x32_bf16 with k ascending in steps of 32 and K never split, and everything after the sum -- (acc + add) + bias or
@@ -21,6 +22,15 @@
 //     file with halved pitches; as there, the 16-lane groups a ds_read_b128 is served in still leave one lane pair per group colliding).
 // A row of a tile depends on that row's operands alone, so a row's values do not depend on B or on which rows share its tile; rows >= B
 // are zero operands and are never stored.
+//
+// The closed-loop IMAGINATION chain (SPEC.md N3j) in the same mode (SPEC.md N3n; s2p_imagine_chain_fwd_bf16) puts the deterministic tanh
+// policy in front of cb_step(): the policy's three layers multiply in bf16 as every layer here does (weights: a bf16 pack; first layer:
+// xz as it stands; hidden activations: rounded where they are written to two [16][W + 8] bf16 tiles, whose heads h1 / h2 of the latent
+// half alias -- the halves never overlap in time), a(h) stays fp32 (global memory and a 16 x 8 fp32 LDS tile), and the two action terms
+// are the fp32 MFMA chunk of the hoisted GEMM with its operands exchanged, so that a lane's four results are the four additive values of
+// CbHidden (CbActionTerm): they never leave the registers and are bitwise the hoisted GEMM's.  A policy layer is up to 64 column tiles,
+// so a wave takes its tiles one at a time and streams the weights in k-blocks with the next block in flight (ib_gemm).
+// LDS: xz 9 472 + 2 x 33 024 + action tile 512 = 76 032 bytes, static.
 #include "gauss_dev.h"
 
 namespace {
@@ -92,6 +102,13 @@ __device__ __forceinline__ void cb_gemm(const __bf16* xr, const bf16x8 (&wv)[NT]
   }
 }
 
+// The additive term of a CbHidden first layer that the closed-loop chain makes itself (SPEC.md N3n): ONE k-chunk of a(h) [16][pad4(A)]
+// x the action columns w[256][w_row], zero-filled past kp = pad4(A), from a zero accumulator, then + 0 -- s2p_linear_fwd without bias.
+// `at`: the fp32 LDS tile [16][CB_AT_P] of a(h), columns >= A and rows >= B zeros.  CbHidden::ask evaluates it where it takes its operands.
+// `tid`: threadIdx.x as the step's own value (ib_tid), so that the term's addresses are made where they are used.
+constexpr int CB_AT_P = 8;
+struct CbActionTerm { const float* at; const float* w; int w_row, kp, tid; };
+
 // A hidden layer: ys[16][CB_H_P] = bf16(lrelu(xs[16][K] . w[256][w_row]^T (+ add) + bias)); wave v owns the column tiles v and v + 8.
 // ask(): everything that does not depend on the previous layer -- the weights, the bias, the additive term; run() after the barrier.
 template <int K, bool ADD>
@@ -115,6 +132,32 @@ struct CbHidden {
     }
     cb_load_w<K, NT>(wr, wv);
     __builtin_amdgcn_sched_barrier(0);                     // (the loads stay here: hipcc would sink them to their first use)
+  }
+
+  // The same with the action term of the closed-loop chain as the additive values.  The chunk is lin_mfma_chunk with its operands
+  // exchanged -- the same four products per element and MFMA -- so that a lane's four results are the columns 16 tile + 4 j .. + 3 of
+  // row i: they are `av` and never leave the registers.
+  __device__ __forceinline__ void ask(const uint16_t* w, int w_row, const float* bias, const CbActionTerm& add, int, int, bool vec) {
+    static_assert(ADD, "an additive term for a layer without one");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    const uint16_t* wr[NT];
+    const int ti = add.tid & 15, tj = (add.tid >> 4) & 3, tw = add.tid >> 6;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const bool kok = 4 * tj < add.kp;
+    const f32x4 xv = kok ? *(const f32x4*)(add.at + ti * CB_AT_P + 4 * tj) : zero;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int t0 = 16 * (wave + q * CB_WAVES);
+      wr[q] = w + (size_t)(t0 + i) * w_row + 8 * j;
+      cb_load4(bias + t0 + 4 * j, vec, bv[q]);
+      const f32x4 tv = kok ? *(const f32x4*)(add.w + (size_t)(16 * (tw + q * CB_WAVES) + ti) * add.w_row + 4 * tj) : zero;
+      const f32x4 acc = lin_mfma_chunk(tv, xv, zero);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) av[q][r] = acc[r] + 0.f;
+    }
+    cb_load_w<K, NT>(wr, wv);
+    __builtin_amdgcn_sched_barrier(0);
   }
 
   // Where a step does NOT ask for the next one (the last step): the operands hold nothing.  Without this the old ones stay live
@@ -238,10 +281,11 @@ __device__ __forceinline__ void cb_mlp(const ChainArgsB& a, const s2p_chain_mlp_
 
 // One chain step, shared by the posterior chain (t >= 1) and the prior chain (every step): the z1 MLP `ma` on xz[:, 32:288] =
 // z2(t-1) with its first layer `a1` already asked for, then the z2 MLP `mb` on xz = z1(t) | z2(t-1) with the additive term `add_b`.
-// Results go to slot t of eps / mean / std / z.  `next()` asks for whatever follows the step.
-template <typename Next>
+// (a pointer to the hoisted term [B][256] of this step, or a CbActionTerm).  Results go to slot t of eps / mean / std / z.  `next()` asks
+// for whatever follows the step.
+template <typename AddB, typename Next>
 __device__ __forceinline__ void cb_step(const ChainArgsB& a, const s2p_chain_mlp_bf16& ma, const s2p_chain_mlp_bf16& mb,
-                                        CbHidden<CB_Z2, true>& a1, CbHidden<CB_Z, true>& b1, const float* add_b, int t, int row0, __bf16* xz,
+                                        CbHidden<CB_Z2, true>& a1, CbHidden<CB_Z, true>& b1, const AddB add_b, int t, int row0, __bf16* xz,
                                         __bf16* h1, __bf16* h2, Next next) {
   cb_mlp<CB_Z1>(a, ma, a1, xz + CB_Z1, t, 0, row0, xz, h1, h2, [&] { b1.ask(mb.w1, mb.w1_row, mb.b1, add_b, row0, a.B, a.vec_in); });
   cb_mlp<CB_Z2>(a, mb, b1, xz, t, CB_Z1, row0, xz, h1, h2, next);
@@ -294,6 +338,120 @@ __global__ __launch_bounds__(CB_THREADS) void prior_chain_bf16_kernel(const Chai
   cb_load_rows<CB_Z1, CB_Z2>(a.feat, a.feat_pitch, row0, a.B, xz);
   for (int s = 0; s < a.T; ++s)
     cb_step(a, a.m[0], a.m[1], a1, b1, a.rb + (size_t)s * a.B * CB_HID, s, row0, xz, h1, h2, [&] { ask_a1(s + 1); });
+}
+
+// ---- the closed-loop imagination chain in bf16 compute (SPEC.md N3n) -----------------------------------------------------------------
+constexpr int IB_WMAX = 1024, IB_AP = CB_AT_P;             // widest policy hidden layer; columns of the fp32 LDS action tile (A <= 8)
+constexpr int IB_P_MAX = IB_WMAX + CB_PAD;
+
+struct ImagineArgsB {
+  ChainArgsB c;                                            // feat / ra / rb unused; m[0] / m[1] = z1_prior / z2_prior; T = H
+  const float* z0; const float* wc; const float* wb; float* act;
+  int z0_pitch, wc_row, wb_row, act_pitch, A;
+  s2p_policy_mlp_bf16 p;
+};
+
+// One 16 x 16 tile of w[16 columns][32 nc] . x[16 rows][32 nc]^T: the MFMA over the k-steps 0 .. nc - 1 in ascending order from a zero
+// accumulator.  nc is a run-time value (the policy's width): blocks of 8 k-steps, the next block's operands load while this one is
+// multiplied (policy_gemm of the fp32 file).  xr / wr: this lane's LDS activation row and weight row at k = 8 j; wok false (a column
+// past N): zero weights.
+__device__ __forceinline__ f32x4 ib_gemm(const __bf16* xr, const uint16_t* wr, int nc, bool wok) {
+  constexpr int U = 8;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  bf16x8 xa[U], wa[U], xb[U], wb[U];
+  auto load = [&](bf16x8 (&xv)[U], bf16x8 (&wv)[U], int c0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (c0 + u < nc) {
+        xv[u] = *(const bf16x8*)(xr + 32 * (c0 + u));
+        wv[u] = wok ? *(const bf16x8*)(wr + 32 * (c0 + u)) : (bf16x8){};
+      }
+  };
+  auto mul = [&](const bf16x8 (&xv)[U], const bf16x8 (&wv)[U], int c0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (c0 + u < nc) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[u], xv[u], acc, 0, 0, 0);
+  };
+  load(xa, wa, 0);
+  for (int c0 = 0; c0 < nc; c0 += 2 * U) {
+    load(xb, wb, c0 + U);
+    __builtin_amdgcn_sched_barrier(0);
+    mul(xa, wa, c0);
+    __builtin_amdgcn_sched_barrier(0);
+    load(xa, wa, c0 + 2 * U);
+    __builtin_amdgcn_sched_barrier(0);
+    mul(xb, wb, c0 + U);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return acc;
+}
+
+// threadIdx.x as a value of the step it is asked in.  The policy half's per-lane addresses (weight rows, biases, act, the action columns)
+// are launch constants; hipcc computes them before the step loop and, at the register ceiling of the latent half, keeps them in scratch
+// that every step reloads.  Made from this value they are a few VALU instructions per step instead.
+__device__ __forceinline__ int ib_tid() {
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  return tid;
+}
+
+// A policy hidden layer: ys[16][yp] = bf16(relu(xs[16][32 nc] . w[W][w_row]^T + bias)); wave v owns the column tiles v, v + 8, ... one at a time
+__device__ __forceinline__ void ib_hidden(const __bf16* xs, int xp, int nc, const uint16_t* w, int w_row, const float* bias, int W, int row0,
+                                          int B, bool vec, int tid, __bf16* ys, int yp) {
+  const int lane = tid & 63, wave = tid >> 6, i = lane & 15, j = lane >> 4;
+  const bool ok = row0 + i < B;
+  for (int t = wave; t < W / 16; t += CB_WAVES) {
+    float bv[4], v[4];
+    cb_load4(bias + 16 * t + 4 * j, vec, bv);
+    const f32x4 acc = ib_gemm(xs + i * xp + 8 * j, w + (size_t)(16 * t + i) * w_row + 8 * j, nc, true);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float s = act_fwd(acc[r] + bv[r], S2P_ACT_RELU, 0.f);
+      v[r] = ok ? s : 0.f;
+    }
+    cb_store4(ys + i * yp + 16 * t + 4 * j, v);
+  }
+}
+
+// a(h) = tanh(last_fc(hs)): one column tile (A <= 8 of its 16 columns), wave 0; a lane holds the columns 4 j .. + 3 of row i.  -> act
+// slot h, unrounded, and the fp32 LDS tile at[16][IB_AP], whose columns >= A and rows >= B are zeros.
+__device__ __forceinline__ void ib_last(const ImagineArgsB& g, const __bf16* hs, int hp, int h, int row0, int tid, float* at) {
+  const int lane = tid & 63, wave = tid >> 6, i = lane & 15, j = lane >> 4;
+  if (wave != 0) return;
+  const bool nok = i < g.A;
+  const int W = g.p.width, gm = row0 + i;
+  const f32x4 acc = ib_gemm(hs + i * hp + 8 * j, g.p.w3 + (size_t)(nok ? i : 0) * W + 8 * j, W / 32, nok);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = 4 * j + r;
+    const bool ok = n < g.A && gm < g.c.B;
+    const float v = ok ? act_fwd(acc[r] + g.p.b3[n < g.A ? n : 0], S2P_ACT_TANH, 0.f) : 0.f;
+    if (n < IB_AP) at[i * IB_AP + n] = v;
+    if (ok) g.act[((size_t)gm * g.c.T + h) * g.act_pitch + n] = v;
+  }
+}
+
+// z(0) -> xz, then H times: a(h) = policy(z(h)), the two action terms, cb_step.  Slot h holds a(h) and z(h+1).
+__global__ __launch_bounds__(CB_THREADS) void imagine_chain_bf16_kernel(const ImagineArgsB g) {
+  __shared__ __attribute__((aligned(16))) __bf16 xz[CB_ROWS * CB_XZ_P], pa[CB_ROWS * IB_P_MAX], pb[CB_ROWS * IB_P_MAX];
+  __shared__ __attribute__((aligned(16))) float at[CB_ROWS * IB_AP];
+  const ChainArgsB& a = g.c;
+  const int row0 = blockIdx.x * CB_ROWS, W = g.p.width, pp = W + CB_PAD, kp = (g.A + 3) / 4 * 4;
+  CbHidden<CB_Z2, true> a1;
+  CbHidden<CB_Z, true> b1;
+  cb_load_rows<0, CB_Z>(g.z0, g.z0_pitch, row0, a.B, xz);
+  for (int s = 0; s < a.T; ++s) {
+    const int tid = ib_tid();
+    __syncthreads();                                       // xz = z(s); the latent half is done with h1 / h2 (= pa / pb)
+    ib_hidden(xz, CB_XZ_P, CB_Z / 32, g.p.w1, g.p.w1_row, g.p.b1, W, row0, a.B, a.vec_in, tid, pa, pp);
+    __syncthreads();
+    ib_hidden(pa, pp, W / 32, g.p.w2, W, g.p.b2, W, row0, a.B, a.vec_in, tid, pb, pp);
+    __syncthreads();
+    ib_last(g, pb, pp, s, row0, tid, at);
+    __syncthreads();
+    a1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, CbActionTerm{at, g.wc, g.wc_row, kp, tid}, row0, a.B, a.vec_in);
+    cb_step(a, a.m[0], a.m[1], a1, b1, CbActionTerm{at, g.wb, g.wb_row, kp, tid}, s, row0, xz, pa, pb, [] {});
+  }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
@@ -362,5 +520,36 @@ extern "C" int s2p_prior_chain_fwd_bf16(const float* z2_0, int z2_0_pitch, const
   a.ra = rc; a.rb = rb; a.vec_in &= s2p_al16(rc) && s2p_al16(rb);
   hipLaunchKernelGGL(prior_chain_bf16_kernel, dim3(cdiv(B, CB_ROWS)), dim3(CB_THREADS), 0, (hipStream_t)stream, a);
   S2P_CHECK_LAUNCH("prior_chain_bf16_kernel");
+  return 0;
+}
+
+extern "C" int s2p_imagine_chain_fwd_bf16(const float* z0, int z0_pitch, const float* eps, int eps_pitch, const s2p_chain_mlp_bf16* mlps,
+                                          const float* wc, int wc_row, const float* wb, int wb_row, int A,
+                                          const s2p_policy_mlp_bf16* policy, float* act, int act_pitch, float* mean, int mean_pitch,
+                                          float* std, int std_pitch, float* z, int z_pitch, int B, int H, void* stream) {
+  const char* who = "s2p_imagine_chain_fwd_bf16";
+  S2P_REQUIRE(B >= 0 && H >= 0, "%s: negative size", who);
+  if (B == 0 || H == 0) return 0;
+  S2P_REQUIRE(z0 && mlps && wc && wb && policy && act, "%s: null pointer (z0, mlps, wc, wb, policy and act are required)", who);
+  S2P_REQUIRE(A >= 1 && A <= IB_AP, "%s: action width %d, 1 .. 8 is built", who, A);
+  const int kp = (A + 3) / 4 * 4;
+  S2P_REQUIRE(z0_pitch >= CB_Z && act_pitch >= A, "%s: a pitch is below its row (z0 288, act A)", who);
+  ImagineArgsB g{};
+  if (int e = cb_take_views(who, "z0", z0, z0_pitch, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, H, g.c)) return e;
+  S2P_REQUIRE(wc_row >= kp && wc_row % 4 == 0 && wb_row >= kp && wb_row % 4 == 0,
+              "%s: wc_row and wb_row must be multiples of 4 floats and at least A padded to 4", who);
+  S2P_REQUIRE(s2p_al16(wc) && s2p_al16(wb), "%s: wc and wb must be 16-byte aligned", who);
+  if (int e = cb_take_mlps(who, mlps, CB_PRIOR_HEADS, 2, g.c)) return e;
+  const s2p_policy_mlp_bf16& p = *policy;
+  S2P_REQUIRE(p.w1 && p.b1 && p.w2 && p.b2 && p.w3 && p.b3, "%s: policy: null operand", who);
+  S2P_REQUIRE(p.width >= 128 && p.width <= IB_WMAX && p.width % 128 == 0,
+              "%s: policy: hidden width %d, multiples of 128 from 128 to 1024 are built", who, (int)p.width);
+  S2P_REQUIRE(p.w1_row >= CB_Z && p.w1_row % 8 == 0, "%s: policy: w1_row must be a multiple of 8 bf16 elements and at least K", who);
+  S2P_REQUIRE(s2p_al16(p.w1) && s2p_al16(p.w2) && s2p_al16(p.w3), "%s: policy: the weights must be 16-byte aligned", who);
+  g.c.vec_in &= s2p_al16(p.b1) && s2p_al16(p.b2);
+  g.p = p; g.z0 = z0; g.z0_pitch = z0_pitch; g.wc = wc; g.wc_row = wc_row; g.wb = wb; g.wb_row = wb_row; g.A = A; g.act = act;
+  g.act_pitch = act_pitch;
+  hipLaunchKernelGGL(imagine_chain_bf16_kernel, dim3(cdiv(B, CB_ROWS)), dim3(CB_THREADS), 0, (hipStream_t)stream, g);
+  S2P_CHECK_LAUNCH("imagine_chain_bf16_kernel");
   return 0;
 }

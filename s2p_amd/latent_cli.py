@@ -1,5 +1,5 @@
 """What the command lines of the latent pipeline share (train_latent.py, train_iql.py, train_cql.py, evaluate_policy.py,
-predict_latent.py, imagine_policy.py): the dataset and chain options, the rule between them, and the way from parsed options to a loaded
+predict_latent.py, imagine_policy.py, select_policy.py): the dataset and chain options, the rule between them, and the way from parsed options to a loaded
 `LatentModel`, a filled `SlacAlgorithm` and a finished offline-RL run.  A new switch of the chains is threaded here, once: its option
 in `add_chain_options`, its rule in `check_chain_options`, its way into the model in `chain_settings`."""
 import os

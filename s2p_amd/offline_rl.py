@@ -197,6 +197,7 @@ class TanhGaussianPolicy(Mlp):
         self._sd["last_fc_log_std.bias"] = torch.empty(self.action_dim).uniform_(-init_w, init_w)
         self.packed = Packed(self.dims())
         self.n = self.packed.end
+        self._bf16_key, self._bf16 = None, None
         if self.device is None:
             return
         self.flat = torch.zeros(self.n, dtype=torch.float32, device=self.device)
@@ -218,6 +219,19 @@ class TanhGaussianPolicy(Mlp):
 
     def grads(self):
         return _export(self, self.packed, self.grad)
+
+    def packed_bf16(self):
+        """The weight operands of the bf16-compute imagination chain (SPEC.md N3n), beside `packed` and under the key rule of
+        `Gaussian.packed_bf16`: w[li] = the packed fp32 layer [N][Kpad] `.to(torch.bfloat16)` (round to nearest even; the last one
+        holds the `last_fc` rows first), b[li] = the fp32 bias in place.  Re-made only when `flat` changed: its (data_ptr, _version),
+        which `load_state_dict` and the trainers' optimizer step move."""
+        key = (self.flat.data_ptr(), self.flat._version)
+        if key != self._bf16_key:
+            n = len(self.packed.dims)
+            with torch.no_grad():
+                w = [self.packed.w(self.flat, li).to(torch.bfloat16).contiguous() for li in range(n)]
+            self._bf16_key, self._bf16 = key, dict(w=w, b=[self.packed.b(self.flat, li) for li in range(n)])
+        return self._bf16
 
     @torch.no_grad()
     def act(self, policy_input):
@@ -251,6 +265,7 @@ class _Adam:
     def step(self):
         check(lib().s2p_adam_step_dev(ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v), self.flat.numel(), self.lr,
                                       self.betas[0], self.betas[1], self.eps, ptr(self.t), 1.0, stream()), "s2p_adam_step_dev")
+        torch.autograd.graph.increment_version(self.flat)   # the launch wrote `flat` behind torch's back: packs keyed on _version follow
 
     def state_dict(self, tensors, all_names):
         """torch.optim.Adam's format; `tensors(flat)` -> name -> tensor in the reference layout, `all_names` the optimizer's

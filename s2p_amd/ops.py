@@ -752,16 +752,34 @@ def prior_chain_fwd_bf16(z2_0, rc, rb, eps, mlps, mean, std, z):
     check(lib().s2p_prior_chain_fwd_bf16(zp, zs, ptr(rc), ptr(rb), ptr(eps), eps.stride(1), arr, *tail), "s2p_prior_chain_fwd_bf16")
 
 
-def policy_mlp(policy):
-    """The s2p_policy_mlp of a two-hidden-layer TanhGaussianPolicy: its packed layers in place (the last layer's first A rows are
-    `last_fc`).  ValueError for a shape outside what s2p_imagine_chain_fwd is built for."""
-    pk, hs = policy.packed, policy.hidden_sizes
+def _policy_built(policy):
+    """ValueError for a policy outside the shapes s2p_imagine_chain_fwd and s2p_imagine_chain_fwd_bf16 are built for."""
+    hs = policy.hidden_sizes
     if policy.obs_dim != 288 or len(hs) != 2 or hs[0] != hs[1] or hs[0] % 128 or not 128 <= hs[0] <= 1024 or not 1 <= policy.action_dim <= 8:
         raise ValueError("the fused imagination chain is built for obs_dim 288, two hidden layers of one width W (a multiple of 128, "
                          "128 <= W <= 1024) and 1 <= action_dim <= 8; got obs_dim %d, hidden_sizes %s, action_dim %d"
                          % (policy.obs_dim, hs, policy.action_dim))
+
+
+def policy_mlp(policy):
+    """The s2p_policy_mlp of a two-hidden-layer TanhGaussianPolicy: its packed layers in place (the last layer's first A rows are
+    `last_fc`).  ValueError for a shape outside what s2p_imagine_chain_fwd is built for."""
+    _policy_built(policy)
+    pk, hs = policy.packed, policy.hidden_sizes
     w, b = [pk.w(policy.flat, li) for li in range(3)], [pk.b(policy.flat, li) for li in range(3)]
     return _lib.PolicyMlp(ptr(w[0]), ptr(b[0]), ptr(w[1]), ptr(b[1]), ptr(w[2]), ptr(b[2]), w[0].shape[1], hs[0])
+
+
+def policy_mlp_bf16(policy):
+    """The s2p_policy_mlp_bf16 of a two-hidden-layer TanhGaussianPolicy: the weights of its `packed_bf16()`, the fp32 biases in place.
+    ValueError for a shape outside what s2p_imagine_chain_fwd_bf16 is built for (those of policy_mlp)."""
+    _policy_built(policy)
+    pk = policy.packed_bf16()
+    w, b = pk["w"], pk["b"]
+    for t in w:
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError("the weight operands of a bf16 chain are contiguous torch.bfloat16 packs")
+    return _lib.PolicyMlpBf16(ptr(w[0]), ptr(b[0]), ptr(w[1]), ptr(b[1]), ptr(w[2]), ptr(b[2]), w[0].shape[1], policy.hidden_sizes[0])
 
 
 def imagine_chain_fwd(z0, eps, mlps, wc, wb, A, policy, act, mean, std, z):
@@ -771,6 +789,14 @@ def imagine_chain_fwd(z0, eps, mlps, wc, wb, A, policy, act, mean, std, z):
     (zp, zs), arr, tail = _chain_operands(z0, eps, mlps, 2, mean, std, z, more=(act,))
     check(lib().s2p_imagine_chain_fwd(zp, zs, ptr(eps), eps.stride(1), arr, ptr(wc), wc.shape[1], ptr(wb), wb.shape[1], A,
                                       ctypes.byref(policy), ptr(act), act.stride(1), *tail), "s2p_imagine_chain_fwd")
+
+
+def imagine_chain_fwd_bf16(z0, eps, mlps, wc, wb, A, policy, act, mean, std, z):
+    """imagine_chain_fwd in bf16 compute (s2p_imagine_chain_fwd_bf16; SPEC.md N3n): the same fp32 tensors (wc, wb included), mlps: the
+    chain_mlp_bf16() structs of z1_prior (its z2-column pack) and z2_prior; policy: a policy_mlp_bf16() struct."""
+    (zp, zs), arr, tail = _chain_operands(z0, eps, mlps, 2, mean, std, z, more=(act,), mlp_type=_lib.ChainMlpBf16)
+    check(lib().s2p_imagine_chain_fwd_bf16(zp, zs, ptr(eps), eps.stride(1), arr, ptr(wc), wc.shape[1], ptr(wb), wb.shape[1], A,
+                                           ctypes.byref(policy), ptr(act), act.stride(1), *tail), "s2p_imagine_chain_fwd_bf16")
 
 
 def posterior_chain_fwd(feat0, ra, rb, eps, mlps, mean, std, z):

@@ -656,7 +656,7 @@ class LatentModel(nn.Module):
         self.chain_state_bytes = 0              # bytes the last sample_posterior kept for its backward (0 under no_grad)
         self.fused_chain = False                # True: a no-grad sample_posterior, predict and imagine run their chain as ONE launch (SPEC.md N3h-N3j)
         self.fused_chain_grad = False           # True: a grad-mode sample_posterior runs its chain as ONE launch forward, ONE backward (SPEC.md N3k)
-        self.chain_compute = "fp32"             # "bf16": the fused no-grad chains of sample_posterior and predict multiply in bf16 (SPEC.md N3m)
+        self.chain_compute = "fp32"             # "bf16": the fused no-grad chains of sample_posterior and predict multiply in bf16 (SPEC.md N3m; imagine: its `compute` keyword)
 
     @property
     def device(self):
@@ -771,13 +771,20 @@ class LatentModel(nn.Module):
         return mean, std, z
 
     @torch.no_grad()
-    def imagine(self, policy, z0, horizon, noise=None, sample=True):
+    def imagine(self, policy, z0, horizon, noise=None, sample=True, compute="fp32"):
         """Closed-loop rollout (SPEC.md N3j): the deterministic policy tanh(mean) reads z(h) and the generative model steps on its
         action.  policy: a `TanhGaussianPolicy` with obs_dim 288 and two hidden layers; z0 [B,288] = z1(0) | z2(0) (z1(0) IS read);
         noise [B,H,288] as in `predict` -> (actions [B,H,A], z1_mean [B,H,32], z1_std [B,H,32], z [B,H,288]); slot h holds a(h) and
         z(h+1).  Always without grad.  With `fused_chain` the H steps are one launch (s2p_imagine_chain_fwd; ValueError for a policy
         outside its built shapes), else 13 per step; the two are bitwise equal, and `predict(z0, actions, noise)` returns bitwise
-        this z1_mean, z1_std and z."""
+        this z1_mean, z1_std and z.  `compute`: "fp32" is all of the above whatever `chain_compute` says; "bf16" (SPEC.md N3n) runs the
+        one launch with bf16 operands (s2p_imagine_chain_fwd_bf16): mixed precision, not the same numbers, and `predict` with
+        `fused_chain` and `chain_compute == "bf16"` returns bitwise ITS z1_mean, z1_std and z.  The mode exists only in the fused
+        kernel: without `fused_chain` it is a ValueError, as is any other value."""
+        if compute not in ("fp32", "bf16"):
+            raise ValueError("compute is 'fp32' or 'bf16', not %r" % (compute,))
+        if compute == "bf16" and not self.fused_chain:
+            raise ValueError("compute='bf16' needs fused_chain: the bf16 compute mode exists only in the fused imagination kernel")
         dev, A, H = self.device, self.action_dim, int(horizon)
         hs = getattr(policy, "hidden_sizes", None)
         if getattr(policy, "obs_dim", None) != Z1 + Z2 or getattr(policy, "action_dim", None) != A or hs is None or len(hs) != 2:
@@ -790,6 +797,10 @@ class LatentModel(nn.Module):
         if st is None:
             return act[..., :A], mean, std, z
         g1, g2, p1, p2, wc, wb, xz = st
+        if compute == "bf16":
+            ops.imagine_chain_fwd_bf16(xz, noise, [ops.chain_mlp_bf16(g1.packed_bf16(k1=Z2)), ops.chain_mlp_bf16(g2.packed_bf16())], wc, wb,
+                                       A, ops.policy_mlp_bf16(policy), act, mean, std, z)
+            return act[..., :A], mean, std, z
         if self.fused_chain:
             ops.imagine_chain_fwd(xz, noise, [ops.chain_mlp(p1, k1=Z2), ops.chain_mlp(p2)], wc, wb, A, ops.policy_mlp(policy), act,
                                   mean, std, z)
