@@ -7,7 +7,10 @@
 
 Takes up to --windows stretches of --context + --horizon transitions from the trajectories of --data (`s2p_amd.slac_predict.windows`),
 filters the first --context + 1 frames of each with the posterior and, from z(context), (1) lets the deterministic policy (tanh of
-its mean, input `latent_z`: z [288]) act in the model for --horizon steps, (2) rolls the model under the dataset's recorded actions.
+its mean) act in the model for --horizon steps, (2) rolls the model under the dataset's recorded actions.  The policy's input type is
+read off its obs_dim and printed: 288 is `latent_z` (the policy reads z); S * 256 + (S - 1) * A is `feature_action` (SPEC.md N3o: the
+policy reads the last S encoder features and S - 1 actions, so every imagined step decodes z, quantises the frame to uint8 and encodes
+it again; --context + 1 >= S is needed).
 Prints mean +- standard error over the windows of the policy's imagined return, the model's return under the dataset's actions and
 the dataset's true discounted reward sum over the same rows, and the mean |a| of the policy against the data.  --out holds those per
 window (`policy_return`, `behaviour_return`, `data_return`; with --bootstrap also `bootstrap` and `policy_value` = return +
@@ -19,9 +22,7 @@ import os
 import numpy as np
 import torch
 
-from s2p_amd.latent_cli import add_chain_options, load_latent, need_device, net_shape
-
-Z = 288
+from s2p_amd.latent_cli import add_chain_options, input_type_name, load_latent, need_device, net_shape, policy_input_type
 
 
 def build_parser():
@@ -73,11 +74,10 @@ def main(argv=None):
         raise SystemExit("%s: %s" % (a.data, e))
     sd = torch.load(os.path.join(a.policy_dir, "policy.pth"), map_location="cpu")
     hidden, obs_dim, A = net_shape(sd)
-    if obs_dim != Z:
-        raise SystemExit("policy.pth reads %d inputs: imagined returns need a latent_z policy (obs_dim %d); a feature_action policy "
-                         "would need decoded frames in the loop, which is not built" % (obs_dim, Z))
     if A != int(np.asarray(data["actions"]).shape[1]):
         raise SystemExit("policy.pth has %d actions, the dataset %d" % (A, int(np.asarray(data["actions"]).shape[1])))
+    S = policy_input_type(obs_dim, A, a.context)
+    print("policy.pth: input type %s, obs_dim %d" % (input_type_name(S), obs_dim))
     need_device("imagine_policy.py")
     torch.manual_seed(a.seed)
     torch.cuda.manual_seed(a.seed)

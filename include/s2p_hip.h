@@ -521,6 +521,19 @@ int s2p_nhwc_to_u8(int dtype, const void* x, int x_pitch, int64_t pixels, int C,
  * with dword loads and 16-byte stores.  x must be 16-byte aligned.  B * T == 0 is a successful no-op.                  */
 int s2p_window_gather_u8(int dtype, const void* pool, int64_t n_slots, int64_t frame_pixels, int C, const int32_t* table, int T,
                          const int64_t* win, int B, void* x, int x_pitch, void* u8_out, void* stream);
+/* Decoded frame -> observed frame (SPEC.md N3o): the hand-off from the decoder to the encoder inside an imagined rollout.
+ *   y      dtype [pixels_total][y_pitch]  the decoder's NHWC output; channels < C are read, each as float v
+ *   x      dtype [pixels_total][x_pitch]  the encoder's NHWC input; channels C..x_pitch are exactly 0.  Nullable.
+ *   u8_out uint8 [pixels_total][C]        the frame an environment would hand out.  Nullable (not both).
+ * The byte is q = min(max(rintf(v * 255.0f), 0), 255): one fp32 multiply, ties to even, a NaN gives 0.  u8_out always holds q.
+ * quantize != 0: x holds from_f32((float)q / 255.0f), a true IEEE division -- the value s2p_window_gather_u8 writes for the byte q.
+ * quantize == 0: x holds from_f32(min(max(v, 0), 1)); a NaN and -0.0 give +0.
+ * Every source element is read once for both outputs; all offsets are 64-bit.  Any C >= 1 with C <= y_pitch (and <= x_pitch where x
+ * is given) is accepted; C == 3 with pixels_total % 4 == 0, both pitches whole numbers of 16-byte chunks, 16-byte aligned y and 4-byte
+ * aligned u8_out moves 4 pixels per thread step with 16-byte loads and stores and three dword stores.  x must be 16-byte aligned, y
+ * aligned to its element.  pixels_total == 0 is a successful no-op that looks at no pointer.                                        */
+int s2p_decoded_to_frames(int dtype, const void* y, int y_pitch, int64_t pixels_total, int C, int quantize, void* x, int x_pitch,
+                          void* u8_out, void* stream);
 /* Cached encoder features of the replay buffer (SPEC.md N3g): with a frozen encoder a frame's feature row is a constant, kept in a
  * table beside the frame pool; one launch turns B sampled window ids into everything an RL step on a frozen latent model reads.
  *   feat        fp32  [n_slots][feat_pitch]    feature row of every pool slot, F floats used

@@ -188,6 +188,7 @@ SIGNATURES = {
     "s2p_u8_to_nhwc": [c_int, _P, c_int64, c_int, _P, c_int, _P],
     "s2p_nhwc_to_u8": [c_int, _P, c_int, c_int64, c_int, _P, _P],
     "s2p_window_gather_u8": [c_int, _P, c_int64, c_int64, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P],
+    "s2p_decoded_to_frames": [c_int, _P, c_int, c_int64, c_int, c_int, _P, c_int, _P, _P],
     "s2p_feature_window_gather": [_P, c_int64, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, c_int,
                                   _P, _P, _P],
     "s2p_frame_pair_gather": [_P, c_int64, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P],

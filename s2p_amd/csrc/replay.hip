@@ -105,6 +105,105 @@ extern "C" int s2p_window_gather_u8(int dtype, const void* pool, int64_t n_slots
   return 0;
 }
 
+// Decoded frame -> observed frame (SPEC.md N3o): the decoder's NHWC output becomes the frame an environment would have handed out, in
+// the two forms the gather above writes -- the encoder's NHWC input and the uint8 frame -- so an imagined frame reaches the encoder
+// with the bits the same frame has coming out of the replay buffer.  One value: the byte is clamp(rintf(v * 255), 0, 255) (one fp32
+// multiply, ties to even; NaN and -0.0 give byte 0), x holds that byte / 255.0f as the gather forms it or, clamp-only, min(max(v, 0), 1)
+// with NaN and -0.0 as +0.
+__device__ __forceinline__ unsigned decoded_byte(float v) {
+  const float r = rintf(v * 255.0f);
+  const float lo = r > 0.f ? r : 0.f;                         // (NaN compares false: 0)
+  return (unsigned)(lo < 255.f ? lo : 255.f);
+}
+__device__ __forceinline__ float decoded_value(float v, unsigned q, bool quantize) {
+  if (quantize) return (float)q / 255.0f;                     // true division: 255 -> exactly 1.0
+  const float lo = v > 0.f ? v : 0.f;
+  return lo < 1.f ? lo : 1.f;
+}
+
+// C == 3, pixels % 4 == 0, both pitches whole numbers of 16-byte chunks, y / x 16-byte and u8_out 4-byte aligned: a thread step moves
+// 4 pixels = 4 16-byte loads (the chunk that holds the three channels), 4 * chunks 16-byte stores (x) and 3 dwords (u8_out).
+template <typename T>
+__global__ __launch_bounds__(256) void decoded_frames_rgb4_kernel(const T* y, int ychunks, long long quads, int quantize, T* x, int xchunks,
+                                                                  unsigned char* u8o) {
+  constexpr int CE = DT<T>::CE;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < quads; q += (long long)gridDim.x * 256) {
+    Chunk<T> in[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) in[k].raw = *(const u32x4*)(y + (size_t)(4 * q + k) * ychunks * CE);
+    unsigned d[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                             // pixel k: bytes 3k .. 3k+2 of the 12
+      float v[CE];
+#pragma unroll
+      for (int e = 0; e < CE; ++e) v[e] = 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float s = in[k].get(c);
+        const unsigned b = decoded_byte(s);
+        const int byte = 3 * k + c;
+        d[byte >> 2] |= b << (8 * (byte & 3));
+        v[c] = decoded_value(s, b, quantize != 0);
+      }
+      if (x) {
+        Chunk<T> o; o.pack(v);
+        T* px = x + (size_t)(4 * q + k) * xchunks * CE;
+        *(u32x4*)px = o.raw;
+        for (int ch = 1; ch < xchunks; ++ch) *(u32x4*)(px + ch * CE) = (u32x4){0u, 0u, 0u, 0u};
+      }
+    }
+    if (u8o) {
+      unsigned* d8 = (unsigned*)(u8o + (size_t)q * 12);
+      d8[0] = d[0]; d8[1] = d[1]; d8[2] = d[2];
+    }
+  }
+}
+
+// any C, any pixel count, any pitches, any alignment of u8_out: one thread per pixel, elements in, elements and bytes out
+template <typename T>
+__global__ __launch_bounds__(256) void decoded_frames_kernel(const T* y, int y_pitch, long long pixels, int C, int quantize, T* x,
+                                                             int x_pitch, unsigned char* u8o) {
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (long long)gridDim.x * 256) {
+    for (int c = 0; c < C; ++c) {
+      const float s = to_f32(y[(size_t)p * y_pitch + c]);
+      const unsigned b = decoded_byte(s);
+      if (u8o) u8o[(size_t)p * C + c] = (unsigned char)b;
+      if (x) x[(size_t)p * x_pitch + c] = from_f32<T>(decoded_value(s, b, quantize != 0));
+    }
+    if (x) for (int c = C; c < x_pitch; ++c) x[(size_t)p * x_pitch + c] = from_f32<T>(0.f);
+  }
+}
+
+extern "C" int s2p_decoded_to_frames(int dtype, const void* y, int y_pitch, int64_t pixels_total, int C, int quantize, void* x,
+                                     int x_pitch, void* u8_out, void* stream) {
+  S2P_REQUIRE(s2p_is_dtype(dtype), "s2p_decoded_to_frames: bad dtype");
+  S2P_REQUIRE(y_pitch >= 0 && pixels_total >= 0 && x_pitch >= 0, "s2p_decoded_to_frames: negative size");
+  S2P_REQUIRE(C >= 1, "s2p_decoded_to_frames: C < 1");
+  if (pixels_total == 0) return 0;                                     // nothing to convert: no pointer is looked at
+  S2P_REQUIRE(y, "s2p_decoded_to_frames: null y");
+  S2P_REQUIRE(x || u8_out, "s2p_decoded_to_frames: both outputs are null");
+  S2P_REQUIRE(C <= y_pitch && (!x || C <= x_pitch), "s2p_decoded_to_frames: channels exceed pitch");
+  S2P_REQUIRE(s2p_al16(x), "s2p_decoded_to_frames: x must be 16-byte aligned");
+  const int ce = s2p_chunk_elems(dtype);
+  S2P_REQUIRE(((uintptr_t)y & (uintptr_t)(16 / ce - 1)) == 0, "s2p_decoded_to_frames: y must be aligned to its element size");
+  const bool fast = C == 3 && pixels_total % 4 == 0 && y_pitch % ce == 0 && (!x || x_pitch % ce == 0) && s2p_al16(y) &&
+                    ((uintptr_t)u8_out & 3) == 0;
+  const long long items = fast ? pixels_total / 4 : pixels_total;     // thread steps
+  long long gx = (items + 255) / 256; if (gx > (1 << 20)) gx = 1 << 20;
+  hipStream_t st = (hipStream_t)stream;
+  s2p_with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (fast)
+      hipLaunchKernelGGL(decoded_frames_rgb4_kernel<T>, dim3((unsigned)gx), dim3(256), 0, st, (const T*)y, y_pitch / ce, items, quantize,
+                         (T*)x, x_pitch / ce, (unsigned char*)u8_out);
+    else
+      hipLaunchKernelGGL(decoded_frames_kernel<T>, dim3((unsigned)gx), dim3(256), 0, st, (const T*)y, y_pitch, (long long)pixels_total, C,
+                         quantize, (T*)x, x_pitch, (unsigned char*)u8_out);
+  });
+  S2P_CHECK_LAUNCH("decoded_frames_kernel");
+  return 0;
+}
+
 // Cached encoder features (SPEC.md N3g): sampled window ids -> everything a frozen-encoder RL step reads, out of a feature table
 // that holds one row of F floats per pool slot.  Row (b, t) is block-uniform as above (blockIdx.y = t, blockIdx.z strides over b):
 // the table lookup and the slot check are scalar work, a lane owns one 16-byte chunk of the row, reads it once and stores it to up

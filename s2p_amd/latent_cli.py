@@ -88,6 +88,24 @@ def net_shape(sd, prefix=""):
     return hidden, int(sd[prefix + "fc0.weight"].shape[1]), int(sd[prefix + "last_fc.weight"].shape[0])
 
 
+def policy_input_type(obs_dim, action_dim, context, where="policy.pth", feature_dim=256, z_dim=288):
+    """The input type an imagined rollout finds in a `policy.pth` by its obs_dim: None for `latent_z` (z_dim), else S of a
+    `feature_action` input S feature_dim + (S - 1) A.  Exits where no integer S >= 2 fits, or --context + 1 < S."""
+    if obs_dim == z_dim:
+        return None
+    S, rem = divmod(obs_dim + action_dim, feature_dim + action_dim)
+    if rem or S < 2:
+        raise SystemExit("%s reads %d inputs: neither a latent_z policy (obs_dim %d) nor a feature_action policy (obs_dim S * %d + (S - 1) * %d "
+                         "for an integer S >= 2)" % (where, obs_dim, z_dim, feature_dim, action_dim))
+    if context + 1 < S:
+        raise SystemExit("%s is a feature_action policy of %d frames: --context + 1 >= %d is needed, not --context %d" % (where, S, S, context))
+    return S
+
+
+def input_type_name(S):
+    return "latent_z" if S is None else "feature_action (%d frames)" % S
+
+
 def policy_input_dim(a, action_dim, feature_dim=256, z_dim=288):
     """finetune_rl.py:204: S features and S - 1 actions, or the latent."""
     return a.num_sequences * feature_dim + (a.num_sequences - 1) * action_dim if a.slac_policy_input_type == "feature_action" else z_dim

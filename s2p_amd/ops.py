@@ -588,6 +588,35 @@ def window_gather_u8(pool, table, win, dtype, pitch=None, want_x=True, want_u8=T
     return x, u8
 
 
+def decoded_to_frames(y, C, quantize, x=None, u8_out=None):
+    """The decoder's NHWC output y [N,H,W,y_pitch] -> the frames an environment would hand out (csrc/replay.hip, SPEC.md N3o), in one
+    launch: x [N,H,W,x_pitch] in y's dtype = the encoder's input (byte / 255 with `quantize`, else the value clamped to [0,1]; pad
+    channels zero) and u8_out uint8 [N,H,W,C] = clamp(round(v * 255), 0, 255).  Both are caller-owned and contiguous; one may be
+    None.  -> (x, u8_out)."""
+    N, H, W, yp = y.shape
+    if not y.is_contiguous():
+        raise ValueError("y must be contiguous")
+    if x is not None and (x.dtype != y.dtype or x.dim() != 4 or tuple(x.shape[:3]) != (N, H, W) or not x.is_contiguous()):
+        raise ValueError("x is contiguous [N,H,W,x_pitch] in y's dtype")
+    if u8_out is not None and (u8_out.dtype != torch.uint8 or tuple(u8_out.shape) != (N, H, W, C) or not u8_out.is_contiguous()):
+        raise ValueError("u8_out is contiguous uint8 [N,H,W,C]")
+    check(lib().s2p_decoded_to_frames(dtype_id(y.dtype), ptr(y), yp, N * H * W, C, int(bool(quantize)), ptr(x),
+                                      x.shape[3] if x is not None else 0, ptr(u8_out), stream()), "s2p_decoded_to_frames")
+    return x, u8_out
+
+
+def feature_action_push(src, dst, S, F, A, feat, action):
+    """dst row n = src row n shifted left by one feature and one action, with feat[n] and action[n] last (csrc/actor.hip,
+    `SlacObservation.append`): src / dst fp32 [N,pitch] with pitch a multiple of 4 at least S F + (S - 1) A (pad columns written as
+    zeros), feat / action 2-D fp32 views.  src and dst may not overlap: the caller ping-pongs two buffers.  No reset code is set."""
+    (sp, ss), (dp, ds), (fp, fs), (ap, as_) = _view2(src), _view2(dst), _view2(feat), _view2(action)
+    N = src.shape[0]
+    if ss != ds or dst.shape[0] != N or src.shape[1] != ss or dst.shape[1] != ds or feat.shape[0] != N or action.shape[0] != N:
+        raise ValueError("src and dst are dense [N,pitch]; feat and action have N rows")
+    check(lib().s2p_feature_action_push(sp, dp, ss, N, S, F, A, fp, fs, ap, as_, None, None, stream()), "s2p_feature_action_push")
+    return dst
+
+
 def feature_window_gather(feat, table, win, action_, reward_, done_):
     """Cached encoder features of the windows `win` (int64 [B], ids into `table` int32 [n_windows,T]) out of the feature table `feat`
     fp32 [n_slots,F] (row pitch = its stride), with the windows' actions [n_windows,T-1,A], rewards and terminals [n_windows,T-1,1], in

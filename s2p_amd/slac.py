@@ -821,6 +821,80 @@ class LatentModel(nn.Module):
             _chain_step(g1, p1, g2, p2, bufa, bufb, rc, rb, noise, mean, std, z, s, xz, xz)
         return act[..., :A], mean, std, z
 
+    @staticmethod
+    def feature_action_frames(obs_dim, action_dim):
+        """S of a `feature_action` policy input: obs_dim = S 256 + (S - 1) A -> S = (obs_dim + A) / (256 + A); None where no integer
+        S >= 2 fits."""
+        S, rem = divmod(int(obs_dim) + int(action_dim), FEAT + int(action_dim))
+        return S if rem == 0 and S >= 2 else None
+
+    @torch.no_grad()
+    def imagine_feature_action(self, policy, z0, window, horizon, noise=None, sample=True, quantize=True, final_obs=False,
+                               keep_frames=False):
+        """Closed-loop rollout of a `feature_action` policy (SPEC.md N3o): the policy reads the window of the last S encoder features
+        and S - 1 actions, so every step decodes z(h+1), turns the decoded frame into the frame an environment would hand out
+        (s2p_decoded_to_frames), encodes it and shifts it into the window.  policy: a `TanhGaussianPolicy` with two hidden layers and
+        obs_dim = S 256 + (S - 1) A, S >= 2; window [B,obs_dim]: the policy-input row at the start, `SlacAlgorithm.preprocess`'s layout
+        [f_0 .. f_{S-1} | a_0 .. a_{S-2}]; z0, noise, sample as in `imagine`.  Step h: a(h) = policy.act(window(h)); the prior step of
+        the per-layer `imagine` path gives z(h+1); unless h = H - 1 and not `final_obs`, decoder -> hand-off -> encoder -> push give
+        window(h+1).  `quantize`: the encoder sees the uint8 frame / 255 (what it was trained on; bitwise the replay buffer's gather of
+        that frame); False: the decoded frame clamped to [0,1].  -> (actions [B,H,A], z1_mean, z1_std [B,H,32], z [B,H,288] as `imagine`
+        returns them, obs [B,H (+1 with final_obs),obs_dim] the rows the policy read (the last one of `final_obs`: window(H)),
+        frames_u8 [B,H-1 (+1 with final_obs),100,100,3] with `keep_frames`, else None: slot h is the frame behind window(h+1)).
+        Always without grad; `fused_chain` and `chain_compute` are not read; the conv stacks run in the model's dtype."""
+        dev, A, H = self.device, self.action_dim, int(horizon)
+        hs = getattr(policy, "hidden_sizes", None)
+        P = getattr(policy, "obs_dim", None)
+        S = self.feature_action_frames(P, A) if P is not None else None
+        if S is None or getattr(policy, "action_dim", None) != A or hs is None or len(hs) != 2:
+            raise ValueError("a TanhGaussianPolicy with obs_dim S * %d + (S - 1) * %d for an integer S >= 2, action_dim %d and two hidden "
+                             "layers is needed" % (FEAT, A, A))
+        if policy.device is None or policy.device.type != dev.type:
+            raise ValueError("the policy and the latent model share a HIP device")
+        noise, (mean, std, z), st = self._rollout_start(z0, H, noise, sample)
+        B = z.shape[0]
+        window = torch.as_tensor(window).to(dev, torch.float32)
+        if window.dim() != 2 or window.shape[1] != P or window.shape[0] != B:
+            raise ValueError("window [B,%d], one policy-input row per row of z0, is needed" % P)
+        if B > 65535:
+            raise ValueError("at most 65535 rows (s2p_feature_action_push)")
+        n_obs = H + 1 if final_obs else H
+        n_fr = max(n_obs - 1, 0)
+        act = _f32((B, H, pad_to(A, 4)), dev, True)
+        obs = _f32((B, n_obs, P), dev)
+        frames = torch.empty((n_fr, B, 100, 100, 3), dtype=torch.uint8, device=dev) if keep_frames else None
+        if st is None:
+            if n_obs and B:
+                obs[:, 0] = window
+            return act[..., :A], mean, std, z, obs, frames.transpose(0, 1) if keep_frames else None
+        g1, g2, p1, p2, wc, wb, xz = st
+        dt = self.decoder.dtype
+        win = [_f32((B, pad_to(P, 4)), dev, True) for _ in range(2)]
+        win[0][:, :P] = window
+        rc, rb = _f32((B, HID), dev), _f32((B, HID), dev)
+        h1, h2 = _f32((B, HID), dev), _f32((B, HID), dev)
+        bufa, bufb = (h1, h2, _f32((B, g1.Npad), dev)), (h1, h2, _f32((B, g2.Npad), dev))
+        zin = torch.empty((B, 1, 1, Z1 + Z2), dtype=dt, device=dev)
+        xin = torch.empty((B, 100, 100, chunk_elems(dt)), dtype=dt, device=dev)
+        for s in range(H):
+            cur, nxt = win[s % 2], win[1 - s % 2]
+            obs[:, s] = cur[:, :P]
+            a = act[:, s]                                                                # [B, pad4(A)] view, pitch H * pad4(A)
+            a[:, :A] = policy.act(cur[:, :P])
+            ops.linear_fwd_into(a, wc, None, HID, rc)
+            ops.linear_fwd_into(a, wb, None, HID, rb)
+            _chain_step(g1, p1, g2, p2, bufa, bufb, rc, rb, noise, mean, std, z, s, xz, xz)
+            if s == H - 1 and not final_obs:
+                break
+            zin.view(B, Z1 + Z2).copy_(z[:, s])
+            y = self.decoder.run(zin)                                                    # [B,100,100,pitch]
+            ops.decoded_to_frames(y, 3, quantize, x=xin, u8_out=frames[s] if keep_frames else None)
+            f = self.encoder.run(xin).reshape(B, -1).float()
+            ops.feature_action_push(cur, nxt, S, FEAT, A, f, a)
+        if final_obs:
+            obs[:, H] = win[H % 2][:, :P]
+        return act[..., :A], mean, std, z, obs, frames.transpose(0, 1) if keep_frames else None
+
     def predict_reward(self, z0, z, actions_):
         """Reward head on [z(h-1) | a(h-1) | z(h)], h = 1..H, with z(0) = z0 [B,288], z [B,H,288] (predict's), actions_ [B,H,A] ->
         (mean [B,H], std [B,H])."""

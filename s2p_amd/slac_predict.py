@@ -55,10 +55,11 @@ def _nchw01(u8):
     return (x.float() / 255.0).contiguous()
 
 
-def filter_context(latent, frames_u8_nhwc, actions, context, sample, posterior_noise):
+def filter_context(latent, frames_u8_nhwc, actions, context, sample, posterior_noise, with_feat=False):
     """The filtering pass before a rollout: the encoder and `sample_posterior` see the first `context` + 1 frames and `context`
     actions (longer ones are cut).  `posterior_noise` [B,context+1,288] fixes the pass (None: drawn, or zeros when `sample` is False,
-    so that a mean rollout is a function of its inputs alone).  -> z0 = z(context) [B,288] and the actions on the device."""
+    so that a mean rollout is a function of its inputs alone).  -> z0 = z(context) [B,288] and the actions on the device; with
+    `with_feat` also the encoder's features of the context frames [B,context+1,256] (what a `feature_action` window is cut from)."""
     dev = latent.device
     frames = torch.as_tensor(frames_u8_nhwc)
     actions = torch.as_tensor(actions).to(dev, torch.float32)
@@ -71,7 +72,8 @@ def filter_context(latent, frames_u8_nhwc, actions, context, sample, posterior_n
     if posterior_noise is None and not sample:
         posterior_noise = torch.zeros((B, context + 1, Z1 + Z2), dtype=torch.float32, device=dev)
     _, _, z1, z2 = latent.sample_posterior(feat, actions[:, :context], posterior_noise)
-    return torch.cat([z1[:, -1], z2[:, -1]], dim=-1), actions
+    z0 = torch.cat([z1[:, -1], z2[:, -1]], dim=-1)
+    return (z0, actions, feat) if with_feat else (z0, actions)
 
 
 @torch.no_grad()

@@ -3,27 +3,31 @@ discounted reward inside the model `latent.pth`, and is the difference to the be
 
   python select_policy.py --data FILE --latent_dir DIR --policy_dirs DIR [DIR ...] --out sel.npz [--context 8] [--horizon 16]
                           [--windows 256] [--stride N] [--batch 256] [--discount 0.99] [--mean] [--seed 0] [--bf16] [--bootstrap]
-                          [--fused_chain] [--bf16_chain]
+                          [--fused_chain] [--bf16_chain] [--float_frames] [--frames FILE.npy]
 
 The windows, the filtering pass and the rollout are those of imagine_policy.py, but the model is loaded once, every batch of windows is
 encoded and filtered ONCE, and every policy rolls from the same start states under the same rollout noise
-(`s2p_amd.slac_imagine.compare_policies`).  The returns of two policies on one window then differ by their actions alone, and the
+(`s2p_amd.slac_imagine.compare_rollouts`).  The returns of two policies on one window then differ by their actions alone, and the
 table prints, per policy in the order of their means, mean +- standard error over the windows and the PAIRED difference to the best
 policy +- its standard error (`s2p_amd.slac_imagine.paired`): a difference of several standard errors is a real one.  The model's
 return under the dataset's recorded actions and the dataset's true discounted reward sum over the same rows are printed once.
 --out holds `returns` [P,n], `order` [P], `starts` [n], `policy_dirs` [P], `behaviour_return` and `data_return` [n], and with
 --bootstrap `value` [P,n] = return + discount^H min(qf1, qf2)(z(H), pi(z(H))) from each directory's `critic.pth` (the table then
 ranks by it).  --mean rolls the means; --fused_chain runs every chain as one launch (bitwise the same); --bf16_chain, which needs
---fused_chain, multiplies in bf16 inside the filtering chain (SPEC.md N3m) AND the rollout (N3n): mixed precision, not the same numbers."""
+--fused_chain, multiplies in bf16 inside the filtering chain (SPEC.md N3m) AND the rollout (N3n): mixed precision, not the same numbers.
+Each policy's input type is read off its obs_dim and printed: 288 is `latent_z`; S * 256 + (S - 1) * A is `feature_action` (SPEC.md
+N3o: every imagined step decodes z, quantises the frame to uint8 and encodes it again; --context + 1 >= S is needed).  Both kinds may
+be mixed.  For `feature_action` policies --float_frames keeps the decoded frame as floats clamped to [0,1] instead of quantising it,
+and --frames writes the imagined uint8 frames [n,H-1,100,100,3] of the best policy; --bf16_chain with such a policy is refused (its
+rollout has no fused chain)."""
 import argparse
 import os
 
 import numpy as np
 import torch
 
-from s2p_amd.latent_cli import add_chain_options, check_chain_options, load_latent, need_device, net_shape
-
-Z = 288
+from s2p_amd.latent_cli import (add_chain_options, check_chain_options, input_type_name, load_latent, need_device, net_shape,
+                                policy_input_type)
 
 
 def build_parser():
@@ -43,11 +47,14 @@ def build_parser():
     add_chain_options(ap, bf16_help="bf16 conv stack of the encoder")
     ap.add_argument("--bootstrap", action="store_true", help="rank by return + discount^H min(qf1, qf2)(z(H), pi(z(H))) from each critic.pth")
     add_chain_options(ap, fused_chain="every chain as one launch (bitwise the same result)", bf16_chain=True)
+    ap.add_argument("--float_frames", action="store_true", help="feature_action policies: the encoder sees the decoded frame clamped to [0,1], "
+                    "not quantised to uint8")
+    ap.add_argument("--frames", help="feature_action policies: write the imagined uint8 frames [n,H-1,100,100,3] of the best policy to this .npy")
     return ap
 
 
-def parse_args(argv=None):
-    ap = build_parser()
+def parse_args(argv=None, parser=None):
+    ap = parser if parser is not None else build_parser()
     a = ap.parse_args(argv)
     check_chain_options(ap, a)
     if a.context < 1:
@@ -57,17 +64,25 @@ def parse_args(argv=None):
     return a
 
 
-def load_policy(directory, data_actions, bootstrap):
-    """(policy, critic or None) of one --policy_dirs entry, loaded and refused as imagine_policy.py does."""
-    from s2p_amd.offline_rl import CriticSLAC, Qfunction, TanhGaussianPolicy, Vfunction
+def check_policy(number, directory, data_actions, context, ap, bf16_chain):
+    """What needs no device of --policy_dirs entry `number`: its `policy.pth` read, refused as imagine_policy.py does, its input type
+    printed (by its number: the table names the directories).  -> (state_dict, hidden sizes, obs_dim, action_dim)."""
     sd = torch.load(os.path.join(directory, "policy.pth"), map_location="cpu")
     hidden, obs_dim, A = net_shape(sd)
-    if obs_dim != Z:
-        raise SystemExit("%s: policy.pth reads %d inputs: imagined returns need a latent_z policy (obs_dim %d); a feature_action policy "
-                         "would need decoded frames in the loop, which is not built" % (directory, obs_dim, Z))
     if A != data_actions:
         raise SystemExit("%s: policy.pth has %d actions, the dataset %d" % (directory, A, data_actions))
-    need_device("select_policy.py")
+    S = policy_input_type(obs_dim, A, context, "%s: policy.pth" % directory)
+    if S is not None and bf16_chain:
+        ap.error("--bf16_chain with the feature_action policy of %s: the bf16 mode exists only in the fused latent_z rollout kernel "
+                 "(a feature_action rollout has no fused chain)" % directory)
+    print("policy %d: input type %s, obs_dim %d" % (number, input_type_name(S), obs_dim))
+    return sd, hidden, obs_dim, A
+
+
+def load_policy(directory, checked, bootstrap):
+    """(policy, critic or None) of one --policy_dirs entry on the device, from what `check_policy` read."""
+    from s2p_amd.offline_rl import CriticSLAC, Qfunction, TanhGaussianPolicy, Vfunction
+    sd, hidden, obs_dim, A = checked
     policy = TanhGaussianPolicy(hidden_sizes=hidden, obs_dim=obs_dim, action_dim=A).load_state_dict(sd, strict=True)
     critic = None
     if bootstrap:
@@ -80,11 +95,12 @@ def load_policy(directory, data_actions, bootstrap):
 
 
 def main(argv=None):
-    a = parse_args(argv)
+    ap = build_parser()
+    a = parse_args(argv, ap)
     if a.horizon < 1:
         raise SystemExit("--horizon is at least 1")
     from s2p_amd.data import load_arrays
-    from s2p_amd.slac_imagine import behaviour, compare_policies, paired
+    from s2p_amd.slac_imagine import behaviour, compare_rollouts, paired
     from s2p_amd.slac_predict import gather, windows
     data = load_arrays(a.data)
     try:
@@ -92,17 +108,28 @@ def main(argv=None):
     except ValueError as e:
         raise SystemExit("%s: %s" % (a.data, e))
     A = int(np.asarray(data["actions"]).shape[1])
-    loaded = [load_policy(d, A, a.bootstrap) for d in a.policy_dirs]
+    checked = [check_policy(i + 1, d, A, a.context, ap, a.bf16_chain) for i, d in enumerate(a.policy_dirs)]
+    need_device("select_policy.py")
+    loaded = [load_policy(d, c, a.bootstrap) for d, c in zip(a.policy_dirs, checked)]
     policies, critics = [p for p, _ in loaded], [c for _, c in loaded] if a.bootstrap else None
     torch.manual_seed(a.seed)
     torch.cuda.manual_seed(a.seed)
     latent = load_latent(a, (3, 100, 100), A)
     compute = "bf16" if a.bf16_chain else "fp32"
-    parts = {}
+    # the modes of the feature_action rollout; left out, compare_rollouts runs its defaults (quantised frames, none kept)
+    fa_mode = dict(quantize=False) if a.float_frames else {}
+    if a.frames:
+        fa_mode["keep_frames"] = True
+    parts, imagined = {}, {}
     for lo in range(0, len(starts), a.batch):
         st = starts[lo:lo + a.batch]
         frames, actions, _ = gather(data, st, a.context)
-        cp = compare_policies(latent, policies, frames, actions, a.horizon, a.discount, critics, a.context, sample=not a.mean, compute=compute)
+        cp = compare_rollouts(latent, policies, frames, actions, a.horizon, a.discount, critics, a.context, sample=not a.mean, compute=compute,
+                              **fa_mode)
+        if a.frames:
+            for p, fr in enumerate(cp["frames_u8"]):
+                if fr is not None:
+                    imagined.setdefault(p, []).append(fr[:, :a.horizon - 1].cpu().numpy())
         be = behaviour(latent, data, st, a.context, a.horizon, a.discount, sample=not a.mean)
         row = dict(returns=cp["returns"], behaviour_return=be["returns"], data_return=be["data_returns"])
         if a.bootstrap:
@@ -125,6 +152,13 @@ def main(argv=None):
     save = dict(res, order=st["order"], starts=starts, policy_dirs=np.array(a.policy_dirs))
     np.savez(a.out, **save)
     print("wrote", a.out)
+    if a.frames:
+        best = int(st["order"][0])
+        if best in imagined:
+            np.save(a.frames, np.concatenate(imagined[best]))
+            print("wrote", a.frames, "(the imagined frames of %s)" % a.policy_dirs[best])
+        else:
+            print("--frames: the best policy, %s, is a latent_z policy and imagines no frames" % a.policy_dirs[best])
     return save
 
 
