@@ -17,7 +17,7 @@ DIAG_SRCS=""
 if [ "$1" = "diag" ]; then OUT=libs2p_hip_diag.so; SUF=".diag"; EXTRA="-DS2P_DIAG_BUILD"; DIAG_SRCS="diag_probe.hip"; shift; fi
 SRCS="conv_igemm.hip conv_plane.hip conv_planeg.hip wgrad_igemm.hip wgrad_slab.hip wgrad_slabg.hip wgrad_head.hip linear_small.hip gauss.hip gauss_chain.hip gauss_chain_bf16.hip norm.hip misc.hip thin_conv.hip thin_rows.hip metrics.hip spectral.hip ensemble_train.hip mlp.hip iql.hip cql.hip replay.hip transition.hip actor.hip"
 NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops"
-newest=$(ls -t $SRCS $DIAG_SRCS s2p_common.h conv_plane.h conv_planeg.h conv_plane_epi.h norm_stats.h wgrad_slab_core.h ens_tile.h ens_tile_bf16.h rl_head.h gauss_dev.h ../../include/s2p_hip.h build.sh | head -1)
+newest=$(ls -t $SRCS $DIAG_SRCS s2p_common.h conv_plane.h conv_planeg.h conv_plane_epi.h norm_stats.h wgrad_slab_core.h ens_tile.h ens_tile_bf16.h rl_head.h gauss_dev.h gauss_chain_common.h ../../include/s2p_hip.h build.sh | head -1)
 if [ -z "$FORCE" ] && [ -f "$OUT" ] && [ "$OUT" -nt "$newest" ]; then echo "up to date: $(pwd)/$OUT"; exit 0; fi
 pids=(); objs=""
 for s in $SRCS $DIAG_SRCS; do

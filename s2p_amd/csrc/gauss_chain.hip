@@ -30,7 +30,7 @@
 // all 16 rows start on one bank, with +4 floats row i starts on bank 4 i (mod 64).  (The 16-lane groups a ds_read_b128 is served in
 // are not the j groups, so one lane pair per group still collides; +8 removes that and measures the same: the LDS is not the limit.)
 //
-// The open-loop PRIOR chain (SPEC.md N3i; s2p_prior_chain_fwd) is the same kernel design around the same step: chain_step() below is
+// The open-loop PRIOR chain (SPEC.md N3i; s2p_prior_chain_fwd) is the same kernel design around the same step: chain_step() is
 // the posterior chain's t >= 1 body, and the prior chain runs it H times from z2(0) with z1_prior's weights in place of
 // z1_posterior's and the action term rc in place of ra.  It is bitwise its own per-layer path for the same reason.
 //
@@ -44,46 +44,22 @@
 // MLP -- h1, h2, raw = acc + bias and the chain's input rows go to global memory as the per-layer path keeps them -- in a kernel of
 // its own, so that the three kernels above keep their generated code; s2p_posterior_chain_bwd (further down) is the sequential part
 // of the backward, per step two head backwards and six input gradients, on the same 16-rows-per-workgroup design.
-#include "gauss_dev.h"
+//
+// WHERE THINGS LIVE.  Here: the fp32 layers (chain_load_w, chain_gemm, ChainHidden, ChainHead, ChainAddRegs, chain_action_term), the
+// policy layers' epilogues, the five kernels, the whole backward and the five entry points.  In gauss_chain_common.h, shared with the
+// bf16 mode of gauss_chain_bf16.hip: the dimensions and knobs, ChainLane, ChainSaveT, chain_mlp / chain_step / chain_load_rows,
+// chain_stream_gemm, and the host side (head tables, operand checks, launch frame).
+#include "gauss_chain_common.h"
 
 namespace {
-constexpr int CH_Z1 = 32, CH_Z2 = 256, CH_Z = CH_Z1 + CH_Z2, CH_HID = 256, CH_FEAT = 256;
-#ifndef S2P_CHAIN_THREADS
-#define S2P_CHAIN_THREADS 512
-#endif
-#ifndef S2P_CHAIN_INFLIGHT
-#define S2P_CHAIN_INFLIGHT 8                               // weight loads (16 bytes per lane) a wave asks for per block of k-chunks
-#endif
-constexpr int CH_THREADS = S2P_CHAIN_THREADS, CH_WAVES = CH_THREADS / 64, CH_ROWS = 16;
 constexpr int ch_u(int nt) { return S2P_CHAIN_INFLIGHT / nt > 0 ? S2P_CHAIN_INFLIGHT / nt : 1; }
-#ifndef S2P_CHAIN_PAD
-#define S2P_CHAIN_PAD 4                                    // floats added to the LDS row pitch of the activation tiles
-#endif
 constexpr int CH_XZ_P = CH_Z + S2P_CHAIN_PAD, CH_H_P = CH_HID + S2P_CHAIN_PAD;
-constexpr float CH_SLOPE = 0.2f;
 
 struct ChainArgs {
   const float* feat; const float* ra; const float* rb; const float* eps; float* mean; float* std; float* z;
   int feat_pitch, eps_pitch, mean_pitch, std_pitch, z_pitch, B, T;
   s2p_chain_mlp m[4];                                      // z1_posterior_init, z2_prior_init, z1_posterior, z2_prior
 };                                                         // (prior chain: feat = z2(0), ra = rc, T = H, m = z1_prior, z2_prior)
-
-// What the training form of the posterior chain (SPEC.md N3k) stores of one MLP at one time step, beside what every chain stores:
-// h1, h2 [B][256], raw [B][2 D] = acc + bias of the last layer, and the sample at its place in the saved input rows xz ([B][288] rows
-// of the step that reads it; nullptr: no step does).  ChainSaveT<false> holds nothing and every use of it is compiled out.
-template <bool SAVE>
-struct ChainSaveT {
-  static constexpr bool on = false;
-  __device__ __forceinline__ ChainSaveT() {}
-  __device__ __forceinline__ ChainSaveT(float*, float*, float*, float*) {}
-};
-template <>
-struct ChainSaveT<true> {
-  static constexpr bool on = true;
-  float *h1, *h2, *raw, *xz;
-  __device__ __forceinline__ ChainSaveT(float* h1_, float* h2_, float* raw_, float* xz_) : h1(h1_), h2(h2_), raw(raw_), xz(xz_) {}
-};
-using ChainNoSave = ChainSaveT<false>;
 
 // The weights of NT column tiles for one block of k-chunks; wr: this lane's weight rows, already at k = 4 j.
 template <int K, int NT, int U>
@@ -141,8 +117,9 @@ struct ChainHidden {
   f32x4 w0[NT][U];
   float av[NT][4], bv[NT];
 
-  __device__ __forceinline__ void ask(const float* w, int w_row, const float* bias, const float* add, int row0, int B) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+  __device__ __forceinline__ void ask(const ChainArgs& a, const float* w, int w_row, const float* bias, const float* add, int row0) {
+    const int B = a.B;
+    const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
       const int n = 16 * (wave + q * CH_WAVES) + i;
@@ -158,9 +135,9 @@ struct ChainHidden {
   }
 
   // the same with the additive values handed over in registers (the closed-loop chain's action term)
-  __device__ __forceinline__ void ask(const float* w, int w_row, const float* bias, const ChainAddRegs<NT>& add, int, int) {
+  __device__ __forceinline__ void ask(const ChainArgs&, const float* w, int w_row, const float* bias, const ChainAddRegs<NT>& add, int) {
     static_assert(ADD, "an additive term for a layer without one");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
       const int n = 16 * (wave + q * CH_WAVES) + i;
@@ -172,10 +149,12 @@ struct ChainHidden {
     chain_load_w<K, NT, U>(wr, 0, w0);
   }
 
+  __device__ __forceinline__ void forget() {}              // (the bf16 layer drops its operands here; these are refilled block by block)
+
   // gy (the SAVE variant): the layer's output of the rows < B also to global memory, [B][256]
   template <bool SAVE = false>
   __device__ __forceinline__ void run(const float* xs, int xp, int row0, int B, float* ys, float* gy = nullptr) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
     f32x4 acc[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -208,7 +187,7 @@ struct ChainHead {
   static __device__ __forceinline__ bool idle() { return (int)(threadIdx.x >> 6) >= PAIRS; }   // (wave-uniform; the 64-wide head has two pairs)
 
   __device__ __forceinline__ void ask(const ChainArgs& a, const float* w, const float* bias, int t, int off, int row0) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
     if (idle()) return;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
@@ -227,7 +206,7 @@ struct ChainHead {
 
   template <typename Save = ChainNoSave>
   __device__ __forceinline__ void run(const ChainArgs& a, const float* hs, int t, int off, int row0, float* xz, const Save sv = Save()) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
     if (idle()) return;
     f32x4 acc[NT];
 #pragma unroll
@@ -256,168 +235,36 @@ struct ChainHead {
   }
 };
 
-// Layers 2 and 3 of a Gaussian MLP whose first layer `l1` has been asked for: input xs, output z(t)[:, off : off + D].  Before its
-// last barrier it asks for the first layer of the NEXT MLP through `next()`.
-// `sv`: where the SAVE variant stores this MLP's h1, h2, raw and sample (ChainNoSave: nowhere).
-template <int D, typename L1, typename Next, typename Save = ChainNoSave>
-__device__ __forceinline__ void chain_mlp(const ChainArgs& a, const s2p_chain_mlp& m, L1& l1, const float* xs, int t, int off, int row0,
-                                          float* xz, float* h1, float* h2, Next next, const Save sv = Save()) {
-  ChainHidden<CH_HID, false> l2;
-  ChainHead<D> l3;
-  __syncthreads();
-  if constexpr (Save::on) l1.template run<true>(xs, CH_XZ_P, row0, a.B, h1, sv.h1);
-  else l1.run(xs, CH_XZ_P, row0, a.B, h1);
-  l2.ask(m.w2, CH_HID, m.b2, nullptr, row0, a.B);
-  __syncthreads();
-  if constexpr (Save::on) l2.template run<true>(h1, CH_H_P, row0, a.B, h2, sv.h2);
-  else l2.run(h1, CH_H_P, row0, a.B, h2);
-  l3.ask(a, m.w3, m.b3, t, off, row0);
-  __syncthreads();
-  l3.run(a, h2, t, off, row0, xz, sv);
-  next();
-}
-
-// One chain step, shared by the posterior chain (t >= 1) and the prior chain (every step): the z1 MLP `ma` on xz[:, 32:288] =
-// z2(t-1) with its first layer `a1` already asked for, then the z2 MLP `mb` on xz = z1(t) | z2(t-1) with the additive term `add_b`.
-// Results go to slot t of eps / mean / std / z.  `next()` asks for whatever follows the step, before the step's last barrier.
-// `add_b`: a global pointer ([B][256] rows of this step) or the values in registers (ChainAddRegs).
-// `sa` / `sb`: the two MLPs' ChainSaveT.
-template <typename Add, typename Next, typename Save = ChainNoSave>
-__device__ __forceinline__ void chain_step(const ChainArgs& a, const s2p_chain_mlp& ma, const s2p_chain_mlp& mb, ChainHidden<CH_Z2, true>& a1,
-                                           ChainHidden<CH_Z, true>& b1, const Add add_b, int t, int row0, float* xz, float* h1, float* h2,
-                                           Next next, const Save sa = Save(), const Save sb = Save()) {
-  chain_mlp<CH_Z1>(a, ma, a1, xz + CH_Z1, t, 0, row0, xz, h1, h2, [&] { b1.ask(mb.w1, mb.w1_row, mb.b1, add_b, row0, a.B); }, sa);
-  chain_mlp<CH_Z2>(a, mb, b1, xz, t, CH_Z1, row0, xz, h1, h2, next, sb);
-}
-
-// src[16 rows][W] -> xz[:, C0 : C0 + W]; rows >= B are zeros, and so is every activation row derived from them
-template <int C0, int W>
-__device__ __forceinline__ void chain_load_rows(const float* src, int pitch, int row0, int B, float* xz) {
-  for (int idx = threadIdx.x; idx < CH_ROWS * (W / 4); idx += CH_THREADS) {
-    const int row = idx / (W / 4), c4 = idx % (W / 4), gm = row0 + row;
-    const f32x4 v = gm < B ? *(const f32x4*)(src + (size_t)gm * pitch + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    *(f32x4*)(xz + row * CH_XZ_P + C0 + 4 * c4) = v;
-  }
-}
-
-__global__ __launch_bounds__(CH_THREADS) void posterior_chain_kernel(const ChainArgs a) {
-  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
-  const int row0 = blockIdx.x * CH_ROWS;
-  ChainHidden<CH_FEAT, false> i1;
-  ChainHidden<CH_Z1, false> j1;
-  ChainHidden<CH_Z2, true> a1;
-  ChainHidden<CH_Z, true> b1;
-  i1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, nullptr, row0, a.B);
-  chain_load_rows<CH_Z1, CH_FEAT>(a.feat, a.feat_pitch, row0, a.B, xz);      // feat(0) -> xz[:, 32:]
-  auto ask_a1 = [&](int t) {
-    if (t < a.T) a1.ask(a.m[2].w1, a.m[2].w1_row, a.m[2].b1, a.ra + (size_t)(t - 1) * a.B * CH_HID, row0, a.B);
-  };
-  // t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
-  chain_mlp<CH_Z1>(a, a.m[0], i1, xz + CH_Z1, 0, 0, row0, xz, h1, h2, [&] { j1.ask(a.m[1].w1, a.m[1].w1_row, a.m[1].b1, nullptr, row0, a.B); });
-  chain_mlp<CH_Z2>(a, a.m[1], j1, xz, 0, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(1); });
-  // q(z1(t) | feat(t), z2(t-1), a(t-1)), q(z2(t) | z1(t), z2(t-1), a(t-1)): the feat / action columns arrive as ra / rb
-  for (int t = 1; t < a.T; ++t)
-    chain_step(a, a.m[2], a.m[3], a1, b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, t, row0, xz, h1, h2, [&] { ask_a1(t + 1); });
-}
-
-// The training form of the posterior chain (SPEC.md N3k): the kernel above, every MLP with a ChainSaveT<true> that names where its
-// h1, h2, raw and sample go in `s` -- everything _PosteriorFn.backward reads.  A kernel of its own and not a template of the one
-// above: that one sits at the register ceiling and keeps its generated code.
-__global__ __launch_bounds__(CH_THREADS) void posterior_chain_save_kernel(const ChainArgs a, const s2p_chain_state s) {
-  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
-  using Sv = ChainSaveT<true>;
-  const int row0 = blockIdx.x * CH_ROWS;
-  const size_t B = a.B;
-  ChainHidden<CH_FEAT, false> i1;
-  ChainHidden<CH_Z1, false> j1;
-  ChainHidden<CH_Z2, true> a1;
-  ChainHidden<CH_Z, true> b1;
-  i1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, nullptr, row0, a.B);
-  chain_load_rows<CH_Z1, CH_FEAT>(a.feat, a.feat_pitch, row0, a.B, xz);
-  auto ask_a1 = [&](int t) {
-    if (t < a.T) a1.ask(a.m[2].w1, a.m[2].w1_row, a.m[2].b1, a.ra + (size_t)(t - 1) * a.B * CH_HID, row0, a.B);
-  };
-  chain_mlp<CH_Z1>(a, a.m[0], i1, xz + CH_Z1, 0, 0, row0, xz, h1, h2, [&] { j1.ask(a.m[1].w1, a.m[1].w1_row, a.m[1].b1, nullptr, row0, a.B); },
-                   Sv(s.a0_h1, s.a0_h2, s.a0_raw, nullptr));
-  chain_mlp<CH_Z2>(a, a.m[1], j1, xz, 0, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(1); },
-                   Sv(s.b0_h1, s.b0_h2, s.b0_raw, a.T > 1 ? s.xz : nullptr));          // z2(0) -> xz[0][:, 32:]
-  for (int t = 1; t < a.T; ++t) {
-    const size_t r = (size_t)(t - 1) * B;                  // the first row of slot t - 1 in the time-major state
-    chain_step(a, a.m[2], a.m[3], a1, b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, t, row0, xz, h1, h2, [&] { ask_a1(t + 1); },
-               Sv(s.h1a + r * CH_HID, s.h2a + r * CH_HID, s.rawa + r * 2 * CH_Z1, s.xz + r * CH_Z),      // z1(t) -> xz[t-1][:, :32]
-               Sv(s.h1b + r * CH_HID, s.h2b + r * CH_HID, s.rawb + r * 2 * CH_Z2, t + 1 < a.T ? s.xz + (r + B) * CH_Z : nullptr));
-  }
-}
-
-// The open-loop prior chain (SPEC.md N3i): z2(0) -> xz[:, 32:], then H steps of p(z1(h) | z2(h-1), a(h-1)), p(z2(h) | z1(h), z2(h-1),
-// a(h-1)) on the model's own samples.  a.feat is z2(0), a.ra / a.rb the action terms of the two first layers, a.T the horizon H,
-// a.m[0] / a.m[1] z1_prior / z2_prior; step h writes slot h - 1.  xz[:, :32] is written by the first z1 head before b1 reads it.
-__global__ __launch_bounds__(CH_THREADS) void prior_chain_kernel(const ChainArgs a) {
-  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
-  const int row0 = blockIdx.x * CH_ROWS;
-  ChainHidden<CH_Z2, true> a1;
-  ChainHidden<CH_Z, true> b1;
-  auto ask_a1 = [&](int s) {
-    if (s < a.T) a1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, a.ra + (size_t)s * a.B * CH_HID, row0, a.B);
-  };
-  ask_a1(0);
-  chain_load_rows<CH_Z1, CH_Z2>(a.feat, a.feat_pitch, row0, a.B, xz);
-  for (int s = 0; s < a.T; ++s)
-    chain_step(a, a.m[0], a.m[1], a1, b1, a.rb + (size_t)s * a.B * CH_HID, s, row0, xz, h1, h2, [&] { ask_a1(s + 1); });
-}
-// ---- the closed-loop imagination chain (SPEC.md N3j) ---------------------------------------------------------------------------------
-constexpr int IM_WMAX = 1024, IM_AP = 8;                   // widest policy hidden layer; columns of the LDS action tile (A <= 8)
-constexpr int IM_P_MAX = IM_WMAX + S2P_CHAIN_PAD;
-
-struct ImagineArgs {
-  ChainArgs c;                                             // feat / ra / rb unused; m[0] / m[1] = z1_prior / z2_prior; T = H
-  const float* z0; const float* wc; const float* wb; float* act;
-  int z0_pitch, wc_row, wb_row, act_pitch, A;
-  s2p_policy_mlp p;
+// The fp32 mode of the chains (gauss_chain_common.h): the layers above, [16][K + S2P_CHAIN_PAD] fp32 activation tiles, layer 2 asked for
+// after layer 1 has run.
+struct ChainF32 {
+  using Args = ChainArgs; using Mlp = s2p_chain_mlp; using Elem = float;
+  template <int K, bool ADD> using Hidden = ChainHidden<K, ADD>;
+  template <int D> using Head = ChainHead<D>;
+  static constexpr int XZ_P = CH_XZ_P, H_P = CH_H_P, PAD = S2P_CHAIN_PAD;
+  static constexpr bool AHEAD = false;
+  static __device__ __forceinline__ void put4(float* dst, const f32x4 v) { *(f32x4*)dst = v; }
 };
 
-// One 16 x 16 tile of x[16][16 nc] . w^T: lin_mfma_chunk over the chunks 0 .. nc - 1 in ascending order from 0 (what lin_fwd_kernel
-// does for an element; its zero chunks past K add nothing).  nc is a run-time value (the policy's width): blocks of 8 chunks, the
-// next block's operands load while this one is multiplied.  xr / wr: this lane's LDS activation row and weight row at k = 4 j;
-// wok false (a column past N): zero weights, as lin_fwd_kernel feeds them.
-__device__ __forceinline__ f32x4 policy_gemm(const float* xr, const float* wr, int nc, bool wok) {
-  constexpr int U = 8;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f}, xa[U], wa[U], xb[U], wb[U];
-  auto load = [&](f32x4 (&xv)[U], f32x4 (&wv)[U], int c0) {
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (c0 + u < nc) {
-        xv[u] = *(const f32x4*)(xr + 16 * (c0 + u));
-        wv[u] = wok ? *(const f32x4*)(wr + 16 * (c0 + u)) : (f32x4){0.f, 0.f, 0.f, 0.f};
-      }
-  };
-  auto mul = [&](const f32x4 (&xv)[U], const f32x4 (&wv)[U], int c0) {
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (c0 + u < nc) acc = lin_mfma_chunk(xv[u], wv[u], acc);
-  };
-  load(xa, wa, 0);
-  for (int c0 = 0; c0 < nc; c0 += 2 * U) {
-    load(xb, wb, c0 + U);
-    __builtin_amdgcn_sched_barrier(0);
-    mul(xa, wa, c0);
-    __builtin_amdgcn_sched_barrier(0);
-    load(xa, wa, c0 + 2 * U);
-    __builtin_amdgcn_sched_barrier(0);
-    mul(xb, wb, c0 + U);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  return acc;
-}
+using ImagineArgs = ImagineArgsT<ChainArgs, s2p_policy_mlp>;
+constexpr int IM_P_MAX = IM_WMAX + S2P_CHAIN_PAD;
 
+// The operands of chain_stream_gemm: lin_mfma_chunk on 16 k of fp32, a lane holds 4 of them.
+struct ChainOpsF32 {
+  using Vec = f32x4; using X = float; using W = float;
+  static constexpr int KSTEP = 16;
+  static __device__ __forceinline__ f32x4 mma(const f32x4 xv, const f32x4 wv, const f32x4 acc) { return lin_mfma_chunk(xv, wv, acc); }
+};
+
+// ---- the policy half of the closed-loop imagination chain (SPEC.md N3j) ---------------------------------------------------------------
 // A policy hidden layer: ys[16][yp] = relu(xs[16][16 nc] . w[W][w_row]^T + bias); wave v owns the column tiles v, v + 8, ... one at a time
 __device__ __forceinline__ void policy_hidden(const float* xs, int xp, int nc, const float* w, int w_row, const float* bias, int W, int row0,
                                               int B, float* ys, int yp) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+  const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
   for (int t = wave; t < W / 16; t += CH_WAVES) {
     const int n = 16 * t + i;
     const float b = bias[n];
-    const f32x4 acc = policy_gemm(xs + i * xp + 4 * j, w + (size_t)n * w_row + 4 * j, nc, true);
+    const f32x4 acc = chain_stream_gemm<ChainOpsF32>(xs + i * xp + 4 * j, w + (size_t)n * w_row + 4 * j, nc, true);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 4 * j + r;
@@ -430,12 +277,12 @@ __device__ __forceinline__ void policy_hidden(const float* xs, int xp, int nc, c
 // a(h) = tanh(last_fc(hs)): one column tile (A <= 8 of its 16 columns), wave 0.  -> act slot h and the LDS tile at[16][IM_AP], whose
 // columns >= A and rows >= B are zeros.
 __device__ __forceinline__ void policy_last(const ImagineArgs& g, const float* hs, int hp, int h, int row0, float* at) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+  const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
   if (wave != 0) return;
   const bool nok = i < g.A;
   const int W = g.p.width;
   const float b = nok ? g.p.b3[i] : 0.f;
-  const f32x4 acc = policy_gemm(hs + i * hp + 4 * j, g.p.w3 + (size_t)(nok ? i : 0) * W + 4 * j, W / 16, nok);
+  const f32x4 acc = chain_stream_gemm<ChainOpsF32>(hs + i * hp + 4 * j, g.p.w3 + (size_t)(nok ? i : 0) * W + 4 * j, W / 16, nok);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = 4 * j + r, gm = row0 + row;
@@ -450,7 +297,7 @@ __device__ __forceinline__ void policy_last(const ImagineArgs& g, const float* h
 // action columns w[256][w_row], zero-filled past pad4(A), from a zero accumulator, then + 0 (s2p_linear_fwd without bias).
 template <int NT>
 __device__ __forceinline__ void chain_action_term(const float* at, const float* w, int w_row, int kp, ChainAddRegs<NT>& out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+  const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const bool kok = 4 * j < kp;
   const f32x4 xv = kok ? *(const f32x4*)(at + i * IM_AP + 4 * j) : zero;
@@ -464,14 +311,79 @@ __device__ __forceinline__ void chain_action_term(const float* at, const float* 
   }
 }
 
-// z(0) -> xz, then H times: a(h) = policy(z(h)), the two action terms, chain_step.  Slot h holds a(h) and z(h+1).
+__global__ __launch_bounds__(CH_THREADS) void posterior_chain_kernel(const ChainArgs a) {
+  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
+  const int row0 = blockIdx.x * CH_ROWS;
+  ChainF32::Hidden<CH_FEAT, false> i1;
+  ChainF32::Hidden<CH_Z1, false> j1;
+  ChainF32::Hidden<CH_Z2, true> a1;
+  ChainF32::Hidden<CH_Z, true> b1;
+  i1.ask(a, a.m[0].w1, a.m[0].w1_row, a.m[0].b1, nullptr, row0);
+  chain_load_rows<ChainF32, CH_Z1, CH_FEAT>(a.feat, a.feat_pitch, row0, a.B, xz);      // feat(0) -> xz[:, 32:]
+  auto ask_a1 = [&](int t) {
+    if (t < a.T) a1.ask(a, a.m[2].w1, a.m[2].w1_row, a.m[2].b1, a.ra + (size_t)(t - 1) * a.B * CH_HID, row0);
+    else a1.forget();
+  };
+  // t = 0: q(z1(0) | feat(0)), q(z2(0) | z1(0))
+  chain_mlp<ChainF32, CH_Z1>(a, a.m[0], i1, xz + CH_Z1, 0, 0, row0, xz, h1, h2, [&] { j1.ask(a, a.m[1].w1, a.m[1].w1_row, a.m[1].b1, nullptr, row0); });
+  chain_mlp<ChainF32, CH_Z2>(a, a.m[1], j1, xz, 0, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(1); });
+  // q(z1(t) | feat(t), z2(t-1), a(t-1)), q(z2(t) | z1(t), z2(t-1), a(t-1)): the feat / action columns arrive as ra / rb
+  for (int t = 1; t < a.T; ++t)
+    chain_step<ChainF32>(a, a.m[2], a.m[3], a1, b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, t, row0, xz, h1, h2, [&] { ask_a1(t + 1); });
+}
+
+// The training form of the posterior chain (SPEC.md N3k): the kernel above, every MLP with a ChainSaveT<true> that names where its
+// h1, h2, raw and sample go in `s` -- everything _PosteriorFn.backward reads.  Written out a second time and not one body with a SAVE
+// flag: a body that a kernel only calls is inlined in another order, both kernels get another instruction stream, and this one then
+// measured 0.3 % slower at B 256.
+__global__ __launch_bounds__(CH_THREADS) void posterior_chain_save_kernel(const ChainArgs a, const s2p_chain_state s) {
+  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
+  using Sv = ChainSaveT<true>;
+  const int row0 = blockIdx.x * CH_ROWS;
+  const size_t B = a.B;
+  ChainF32::Hidden<CH_FEAT, false> i1;
+  ChainF32::Hidden<CH_Z1, false> j1;
+  ChainF32::Hidden<CH_Z2, true> a1;
+  ChainF32::Hidden<CH_Z, true> b1;
+  i1.ask(a, a.m[0].w1, a.m[0].w1_row, a.m[0].b1, nullptr, row0);
+  chain_load_rows<ChainF32, CH_Z1, CH_FEAT>(a.feat, a.feat_pitch, row0, a.B, xz);
+  auto ask_a1 = [&](int t) {
+    if (t < a.T) a1.ask(a, a.m[2].w1, a.m[2].w1_row, a.m[2].b1, a.ra + (size_t)(t - 1) * a.B * CH_HID, row0);
+  };
+  chain_mlp<ChainF32, CH_Z1>(a, a.m[0], i1, xz + CH_Z1, 0, 0, row0, xz, h1, h2, [&] { j1.ask(a, a.m[1].w1, a.m[1].w1_row, a.m[1].b1, nullptr, row0); },
+                      Sv(s.a0_h1, s.a0_h2, s.a0_raw, nullptr));
+  chain_mlp<ChainF32, CH_Z2>(a, a.m[1], j1, xz, 0, CH_Z1, row0, xz, h1, h2, [&] { ask_a1(1); },
+                      Sv(s.b0_h1, s.b0_h2, s.b0_raw, a.T > 1 ? s.xz : nullptr));       // z2(0) -> xz[0][:, 32:]
+  for (int t = 1; t < a.T; ++t) {
+    const size_t r = (size_t)(t - 1) * B;                  // the first row of slot t - 1 in the time-major state
+    chain_step<ChainF32>(a, a.m[2], a.m[3], a1, b1, a.rb + (size_t)(t - 1) * a.B * CH_HID, t, row0, xz, h1, h2, [&] { ask_a1(t + 1); },
+                  Sv(s.h1a + r * CH_HID, s.h2a + r * CH_HID, s.rawa + r * 2 * CH_Z1, s.xz + r * CH_Z),      // z1(t) -> xz[t-1][:, :32]
+                  Sv(s.h1b + r * CH_HID, s.h2b + r * CH_HID, s.rawb + r * 2 * CH_Z2, t + 1 < a.T ? s.xz + (r + B) * CH_Z : nullptr));
+  }
+}
+
+__global__ __launch_bounds__(CH_THREADS) void prior_chain_kernel(const ChainArgs a) {
+  __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], h1[CH_ROWS * CH_H_P], h2[CH_ROWS * CH_H_P];
+  const int row0 = blockIdx.x * CH_ROWS;
+  ChainF32::Hidden<CH_Z2, true> a1;
+  ChainF32::Hidden<CH_Z, true> b1;
+  auto ask_a1 = [&](int s) {
+    if (s < a.T) a1.ask(a, a.m[0].w1, a.m[0].w1_row, a.m[0].b1, a.ra + (size_t)s * a.B * CH_HID, row0);
+    else a1.forget();
+  };
+  ask_a1(0);
+  chain_load_rows<ChainF32, CH_Z1, CH_Z2>(a.feat, a.feat_pitch, row0, a.B, xz);
+  for (int s = 0; s < a.T; ++s)
+    chain_step<ChainF32>(a, a.m[0], a.m[1], a1, b1, a.rb + (size_t)s * a.B * CH_HID, s, row0, xz, h1, h2, [&] { ask_a1(s + 1); });
+}
+
 __global__ __launch_bounds__(CH_THREADS) void imagine_chain_kernel(const ImagineArgs g) {
   __shared__ __attribute__((aligned(16))) float xz[CH_ROWS * CH_XZ_P], pa[CH_ROWS * IM_P_MAX], pb[CH_ROWS * IM_P_MAX], at[CH_ROWS * IM_AP];
   const ChainArgs& a = g.c;
-  const int row0 = blockIdx.x * CH_ROWS, W = g.p.width, pp = W + S2P_CHAIN_PAD, kp = (g.A + 3) / 4 * 4;
-  ChainHidden<CH_Z2, true> a1;
-  ChainHidden<CH_Z, true> b1;
-  chain_load_rows<0, CH_Z>(g.z0, g.z0_pitch, row0, a.B, xz);
+  const int row0 = blockIdx.x * CH_ROWS, W = g.p.width, pp = W + ChainF32::PAD, kp = (g.A + 3) / 4 * 4;
+  ChainF32::Hidden<CH_Z2, true> a1;
+  ChainF32::Hidden<CH_Z, true> b1;
+  chain_load_rows<ChainF32, 0, CH_Z>(g.z0, g.z0_pitch, row0, a.B, xz);
   for (int s = 0; s < a.T; ++s) {
     __syncthreads();                                       // xz = z(s); the latent half is done with h1 / h2 (= pa / pb)
     policy_hidden(xz, CH_XZ_P, CH_Z / 16, g.p.w1, g.p.w1_row, g.p.b1, W, row0, a.B, pa, pp);
@@ -484,8 +396,8 @@ __global__ __launch_bounds__(CH_THREADS) void imagine_chain_kernel(const Imagine
     ChainAddRegs<ChainHidden<CH_Z, true>::NT> tb;
     chain_action_term(at, g.wc, g.wc_row, kp, ta);
     chain_action_term(at, g.wb, g.wb_row, kp, tb);
-    a1.ask(a.m[0].w1, a.m[0].w1_row, a.m[0].b1, ta, row0, a.B);
-    chain_step(a, a.m[0], a.m[1], a1, b1, tb, s, row0, xz, pa, pb, [] {});
+    a1.ask(a, a.m[0].w1, a.m[0].w1_row, a.m[0].b1, ta, row0);
+    chain_step<ChainF32>(a, a.m[0], a.m[1], a1, b1, tb, s, row0, xz, pa, pb, [] {});
   }
 }
 // ---- the backward of the posterior chain's steps (SPEC.md N3k) -----------------------------------------------------------------------
@@ -520,7 +432,7 @@ struct ChainDgrad {
   static __device__ __forceinline__ bool has(int q) { return (int)(threadIdx.x >> 6) + q * CH_WAVES < TILES; }   // (wave-uniform)
 
   __device__ __forceinline__ void ask(const float* w, int w_row, const float* ya, int row0, int B) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
       const int n = 16 * (has(q) ? wave + q * CH_WAVES : wave) + i;            // (a wave without tile q multiplies tile 0 again, unused)
@@ -535,7 +447,7 @@ struct ChainDgrad {
   }
 
   __device__ __forceinline__ void run(const float* xs, int xp, int row0, int B, float* go, int gp, float* os, int op) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, j = lane >> 4;
+    const auto [lane, wave, i, j] = ChainLane(threadIdx.x);
     f32x4 acc[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -622,49 +534,17 @@ __global__ __launch_bounds__(CH_THREADS) void posterior_chain_bwd_kernel(const C
     __syncthreads();
   }
 }
-// ---- host side ---------------------------------------------------------------------------------------------------------------------------
-struct ChainHeadSpec { int k1; const char* name; };        // the chain columns of a head's first layer, and the head's name in messages
-const ChainHeadSpec CH_POSTERIOR_HEADS[4] = {{CH_FEAT, "z1_posterior_init"}, {CH_Z1, "z2_prior_init"}, {CH_Z2, "z1_posterior"}, {CH_Z, "z2_prior"}};
-const ChainHeadSpec CH_PRIOR_HEADS[2] = {{CH_Z2, "z1_prior"}, {CH_Z, "z2_prior"}};
-
-// Checks `n` s2p_chain_mlps against `spec` and copies them into a.m.  0, or S2P_REQUIRE's value with the error text set.
-int chain_take_mlps(const char* who, const s2p_chain_mlp* mlps, const ChainHeadSpec* spec, int n, ChainArgs& a) {
-  for (int g = 0; g < n; ++g) {
-    const s2p_chain_mlp& m = mlps[g];
-    const char* name = spec[g].name;
-    S2P_REQUIRE(m.w1 && m.b1 && m.w2 && m.b2 && m.w3 && m.b3, "%s: %s: null operand", who, name);
-    S2P_REQUIRE(m.k1 == spec[g].k1, "%s: %s: the first layer's K is %d, %d is built", who, name, (int)m.k1, spec[g].k1);
-    S2P_REQUIRE(m.w1_row >= m.k1 && m.w1_row % 4 == 0, "%s: %s: w1_row must be a multiple of 4 floats and at least K", who, name);
-    S2P_REQUIRE(s2p_al16(m.w1) && s2p_al16(m.w2) && s2p_al16(m.w3), "%s: %s: the weights must be 16-byte aligned", who, name);
-    a.m[g] = m;
-  }
-  return 0;
-}
-
-// Checks the [B, T, C] views every chain reads (eps) and writes (mean, std, z) and fills them, B and T into `a`.  Returns as above.
-int chain_take_views(const char* who, const float* eps, int eps_pitch, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
-                     int z_pitch, int B, int T, ChainArgs& a) {
-  S2P_REQUIRE(eps && mean && std && z, "%s: null pointer (eps, mean, std and z are required)", who);
-  S2P_REQUIRE(eps_pitch >= CH_Z && mean_pitch >= CH_Z1 && std_pitch >= CH_Z1 && z_pitch >= CH_Z,
-              "%s: a pitch is below its row (eps 288, mean 32, std 32, z 288)", who);
-  a.eps = eps; a.eps_pitch = eps_pitch; a.mean = mean; a.mean_pitch = mean_pitch; a.std = std; a.std_pitch = std_pitch; a.z = z;
-  a.z_pitch = z_pitch; a.B = B; a.T = T;
-  return 0;
-}
-
-// The operand checks of the posterior chain, for both of its forms.  0 with `a` filled, or S2P_REQUIRE's value with the error text set.
-int posterior_chain_take(const char* who, const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
-                         int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
-                         int z_pitch, int B, int T, ChainArgs& a) {
-  S2P_REQUIRE(feat && mlps, "%s: null pointer (feat and mlps are required)", who);
-  S2P_REQUIRE(T == 1 || (ra && rb), "%s: ra and rb are required when T > 1", who);
-  if (int e = chain_take_views(who, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a)) return e;
-  S2P_REQUIRE(feat_pitch >= CH_FEAT, "%s: the pitch of feat is below its row of 256", who);
-  S2P_REQUIRE(s2p_al16(feat) && feat_pitch % 4 == 0, "%s: feat must be 16-byte aligned, its pitch a multiple of 4 floats", who);
-  if (int e = chain_take_mlps(who, mlps, CH_POSTERIOR_HEADS, T > 1 ? 4 : 2, a)) return e;
-  a.feat = feat; a.feat_pitch = feat_pitch; a.ra = ra; a.rb = rb;
-  return 0;
-}
+// ---- host side: the operand checks and the launch frame are gauss_chain_common.h's ----------------------------------------------------
+// The transposed packs of the backward, read by chain_take_mlps: all three given and aligned, a w1t row holds the 256 hidden columns.
+template <>
+struct ChainMlpFields<s2p_chain_mlp_bwd> {
+  using Unit = ChainRowUnit<float>;
+  static constexpr const char *row_name = "w1t_row", *least_name = "256";
+  static bool given(const s2p_chain_mlp_bwd& m) { return m.w1t && m.w2t && m.w3t; }
+  static bool aligned(const s2p_chain_mlp_bwd& m) { return s2p_al16(m.w1t) && s2p_al16(m.w2t) && s2p_al16(m.w3t); }
+  static int row(const s2p_chain_mlp_bwd& m) { return m.w1t_row; }
+  static int least(const s2p_chain_mlp_bwd&) { return CH_HID; }
+};
 
 // every buffer of `n` is given and 16-byte aligned
 bool chain_bufs_ok(float* const* p, int n) {
@@ -679,8 +559,7 @@ extern "C" int s2p_posterior_chain_fwd_save(const float* feat, int feat_pitch, c
                                             int std_pitch, float* z, int z_pitch, const s2p_chain_state* state, int B, int T,
                                             void* stream) {
   const char* who = "s2p_posterior_chain_fwd_save";
-  S2P_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
-  if (B == 0 || T == 0) return 0;
+  if (int e = chain_sizes(who, B, T); e <= 0) return e;
   ChainArgs a{};
   if (int e = posterior_chain_take(who, feat, feat_pitch, ra, rb, eps, eps_pitch, mlps, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a))
     return e;
@@ -688,73 +567,49 @@ extern "C" int s2p_posterior_chain_fwd_save(const float* feat, int feat_pitch, c
   float* const bufs[13] = {state->a0_h1, state->a0_h2, state->a0_raw, state->b0_h1, state->b0_h2, state->b0_raw, state->h1a,
                            state->h2a, state->rawa, state->h1b, state->h2b, state->rawb, state->xz};
   S2P_REQUIRE(chain_bufs_ok(bufs, T > 1 ? 13 : 6), "%s: state: a buffer is NULL or not 16-byte aligned", who);
-  hipLaunchKernelGGL(posterior_chain_save_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a, *state);
-  S2P_CHECK_LAUNCH("posterior_chain_save_kernel");
-  return 0;
+  return chain_launch("posterior_chain_save_kernel", posterior_chain_save_kernel, B, stream, a, *state);
 }
 
 extern "C" int s2p_posterior_chain_bwd(const float* eps, int eps_pitch, const float* dmean, int dmean_pitch, const float* dstd,
                                        int dstd_pitch, const float* dz, int dz_pitch, const s2p_chain_mlp_bwd* mlps,
                                        const s2p_chain_state* state, const s2p_chain_grads* grads, int B, int T, void* stream) {
   const char* who = "s2p_posterior_chain_bwd";
-  S2P_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
-  if (B == 0 || T < 2) return 0;                           // (T == 1: the chain has no step)
+  if (int e = chain_sizes(who, B, T, 2); e <= 0) return e;    // (T == 1: the chain has no step)
   S2P_REQUIRE(eps && dmean && dstd && dz && mlps && state && grads,
               "%s: null pointer (eps, dmean, dstd, dz, mlps, state and grads are required)", who);
   S2P_REQUIRE(eps_pitch >= CH_Z && dz_pitch >= CH_Z && dmean_pitch >= CH_Z1 && dstd_pitch >= CH_Z1,
               "%s: a pitch is below its row (eps 288, dz 288, dmean 32, dstd 32)", who);
   ChainBwdArgs a{};
-  for (int g = 0; g < 2; ++g) {
-    const s2p_chain_mlp_bwd& m = mlps[g];
-    const char* name = CH_POSTERIOR_HEADS[2 + g].name;
-    S2P_REQUIRE(m.w1t && m.w2t && m.w3t, "%s: %s: null operand", who, name);
-    S2P_REQUIRE(m.k1 == CH_POSTERIOR_HEADS[2 + g].k1, "%s: %s: the first layer's K is %d, %d is built", who, name, (int)m.k1,
-                CH_POSTERIOR_HEADS[2 + g].k1);
-    S2P_REQUIRE(m.w1t_row >= CH_HID && m.w1t_row % 4 == 0, "%s: %s: w1t_row must be a multiple of 4 floats and at least 256", who, name);
-    S2P_REQUIRE(s2p_al16(m.w1t) && s2p_al16(m.w2t) && s2p_al16(m.w3t), "%s: %s: the weights must be 16-byte aligned", who, name);
-    a.m[g] = m;
-  }
+  if (int e = chain_take_mlps(who, mlps, CH_POSTERIOR_HEADS + 2, 2, a)) return e;
   float* const sb[6] = {state->h1a, state->h2a, state->rawa, state->h1b, state->h2b, state->rawb};
   S2P_REQUIRE(chain_bufs_ok(sb, 6), "%s: state: a chain buffer is NULL or not 16-byte aligned", who);
   float* const gb[7] = {grads->drawa, grads->dh2a, grads->dh1a, grads->drawb, grads->dh2b, grads->dh1b, grads->dxz};
   S2P_REQUIRE(chain_bufs_ok(gb, 7), "%s: grads: a buffer is NULL or not 16-byte aligned", who);
   a.eps = eps; a.eps_pitch = eps_pitch; a.dmean = dmean; a.dmean_pitch = dmean_pitch; a.dstd = dstd; a.dstd_pitch = dstd_pitch; a.dz = dz;
   a.dz_pitch = dz_pitch; a.B = B; a.T = T; a.s = *state; a.g = *grads;
-  hipLaunchKernelGGL(posterior_chain_bwd_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
-  S2P_CHECK_LAUNCH("posterior_chain_bwd_kernel");
-  return 0;
+  return chain_launch("posterior_chain_bwd_kernel", posterior_chain_bwd_kernel, B, stream, a);
 }
 
 extern "C" int s2p_posterior_chain_fwd(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
                                        int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std,
                                        int std_pitch, float* z, int z_pitch, int B, int T, void* stream) {
   const char* who = "s2p_posterior_chain_fwd";
-  S2P_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
-  if (B == 0 || T == 0) return 0;
+  if (int e = chain_sizes(who, B, T); e <= 0) return e;
   ChainArgs a{};
   if (int e = posterior_chain_take(who, feat, feat_pitch, ra, rb, eps, eps_pitch, mlps, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a))
     return e;
-  hipLaunchKernelGGL(posterior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
-  S2P_CHECK_LAUNCH("posterior_chain_kernel");
-  return 0;
+  return chain_launch("posterior_chain_kernel", posterior_chain_kernel, B, stream, a);
 }
 
 extern "C" int s2p_prior_chain_fwd(const float* z2_0, int z2_0_pitch, const float* rc, const float* rb, const float* eps, int eps_pitch,
                                    const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
                                    int z_pitch, int B, int H, void* stream) {
   const char* who = "s2p_prior_chain_fwd";
-  S2P_REQUIRE(B >= 0 && H >= 0, "%s: negative size", who);
-  if (B == 0 || H == 0) return 0;
-  S2P_REQUIRE(z2_0 && rc && rb && mlps, "%s: null pointer (z2_0, rc, rb and mlps are required)", who);
+  if (int e = chain_sizes(who, B, H); e <= 0) return e;
   ChainArgs a{};
-  if (int e = chain_take_views(who, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, H, a)) return e;
-  S2P_REQUIRE(z2_0_pitch >= CH_Z2, "%s: the pitch of z2_0 is below its row of 256", who);
-  S2P_REQUIRE(s2p_al16(z2_0) && z2_0_pitch % 4 == 0, "%s: z2_0 must be 16-byte aligned, its pitch a multiple of 4 floats", who);
-  if (int e = chain_take_mlps(who, mlps, CH_PRIOR_HEADS, 2, a)) return e;
-  a.feat = z2_0; a.feat_pitch = z2_0_pitch; a.ra = rc; a.rb = rb;
-  hipLaunchKernelGGL(prior_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, a);
-  S2P_CHECK_LAUNCH("prior_chain_kernel");
-  return 0;
+  if (int e = prior_chain_take(who, z2_0, z2_0_pitch, rc, rb, eps, eps_pitch, mlps, mean, mean_pitch, std, std_pitch, z, z_pitch, B, H, a))
+    return e;
+  return chain_launch("prior_chain_kernel", prior_chain_kernel, B, stream, a);
 }
 
 extern "C" int s2p_imagine_chain_fwd(const float* z0, int z0_pitch, const float* eps, int eps_pitch, const s2p_chain_mlp* mlps,
@@ -762,28 +617,10 @@ extern "C" int s2p_imagine_chain_fwd(const float* z0, int z0_pitch, const float*
                                      float* act, int act_pitch, float* mean, int mean_pitch, float* std, int std_pitch, float* z,
                                      int z_pitch, int B, int H, void* stream) {
   const char* who = "s2p_imagine_chain_fwd";
-  S2P_REQUIRE(B >= 0 && H >= 0, "%s: negative size", who);
-  if (B == 0 || H == 0) return 0;
-  S2P_REQUIRE(z0 && mlps && wc && wb && policy && act, "%s: null pointer (z0, mlps, wc, wb, policy and act are required)", who);
-  S2P_REQUIRE(A >= 1 && A <= IM_AP, "%s: action width %d, 1 .. 8 is built", who, A);
-  const int kp = (A + 3) / 4 * 4;
+  if (int e = chain_sizes(who, B, H); e <= 0) return e;
   ImagineArgs g{};
-  if (int e = chain_take_views(who, eps, eps_pitch, mean, mean_pitch, std, std_pitch, z, z_pitch, B, H, g.c)) return e;
-  S2P_REQUIRE(z0_pitch >= CH_Z && act_pitch >= A, "%s: a pitch is below its row (z0 288, act A)", who);
-  S2P_REQUIRE(s2p_al16(z0) && z0_pitch % 4 == 0, "%s: z0 must be 16-byte aligned, its pitch a multiple of 4 floats", who);
-  S2P_REQUIRE(wc_row >= kp && wc_row % 4 == 0 && wb_row >= kp && wb_row % 4 == 0,
-              "%s: wc_row and wb_row must be multiples of 4 floats and at least A padded to 4", who);
-  S2P_REQUIRE(s2p_al16(wc) && s2p_al16(wb), "%s: wc and wb must be 16-byte aligned", who);
-  if (int e = chain_take_mlps(who, mlps, CH_PRIOR_HEADS, 2, g.c)) return e;
-  const s2p_policy_mlp& p = *policy;
-  S2P_REQUIRE(p.w1 && p.b1 && p.w2 && p.b2 && p.w3 && p.b3, "%s: policy: null operand", who);
-  S2P_REQUIRE(p.width >= 128 && p.width <= IM_WMAX && p.width % 128 == 0,
-              "%s: policy: hidden width %d, multiples of 128 from 128 to 1024 are built", who, (int)p.width);
-  S2P_REQUIRE(p.w1_row >= CH_Z && p.w1_row % 4 == 0, "%s: policy: w1_row must be a multiple of 4 floats and at least K", who);
-  S2P_REQUIRE(s2p_al16(p.w1) && s2p_al16(p.w2) && s2p_al16(p.w3), "%s: policy: the weights must be 16-byte aligned", who);
-  g.p = p; g.z0 = z0; g.z0_pitch = z0_pitch; g.wc = wc; g.wc_row = wc_row; g.wb = wb; g.wb_row = wb_row; g.A = A; g.act = act;
-  g.act_pitch = act_pitch;
-  hipLaunchKernelGGL(imagine_chain_kernel, dim3(cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, (hipStream_t)stream, g);
-  S2P_CHECK_LAUNCH("imagine_chain_kernel");
-  return 0;
+  if (int e = imagine_chain_take(who, z0, z0_pitch, eps, eps_pitch, mlps, wc, wc_row, wb, wb_row, A, policy, act, act_pitch, mean, mean_pitch,
+                                 std, std_pitch, z, z_pitch, B, H, g))
+    return e;
+  return chain_launch("imagine_chain_kernel", imagine_chain_kernel, B, stream, g);
 }

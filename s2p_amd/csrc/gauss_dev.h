@@ -1,4 +1,5 @@
-// Device functions shared by the kernels of the SLAC Gaussian heads (linear_small.hip, gauss.hip, gauss_chain.hip).  The fused
+// Device functions shared by the kernels of the SLAC Gaussian heads (linear_small.hip, gauss.hip, and through gauss_chain_common.h
+// gauss_chain.hip and gauss_chain_bf16.hip).  The fused
 // posterior chain returns bitwise what the per-layer launches return BECAUSE both are made of these: the same MFMA sequence per
 // k-chunk, the same softplus, the same sample -- and, for the backward chain, the same head gradient.
 #pragma once

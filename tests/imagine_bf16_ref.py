@@ -9,6 +9,7 @@ evaluation's rounding flips do not travel down the chain."""
 import torch
 
 import chain_bf16_ref as C
+import chain_refusals as CR
 import slac_imagine_ref as IM
 
 Z = C.Z
@@ -80,68 +81,17 @@ def assert_exact_premises(pol, z0):
         assert float(x.max()) > 0
 
 
-# ---- the C ABI of s2p_imagine_chain_fwd_bf16: refusals happen before any launch, so fake addresses serve ------------------------------
+# ---- the C ABI of s2p_imagine_chain_fwd_bf16: its rows of the table of every chain entry point (tests/chain_refusals.py) ----------------
 NAME = "s2p_imagine_chain_fwd_bf16"
-P = 4096                                               # a non-NULL, 16-byte aligned address
+P = CR.P
+REFUSALS = tuple(CR.cases(NAME))                       # (the edit, a piece of the message)
 
 
 def abi_args(_lib, **edit):
-    """The 22 arguments of a valid call (B 17, H 2, A 6, W 256) on fake addresses, with `edit` applied: an argument by its name, or
-    `mlp=(index, field, value)` / `policy=(field, value)` for a field of the host structs."""
-    a = dict(z0=P, z0_pitch=288, eps=P, eps_pitch=288, wc=P, wc_row=8, wb=P, wb_row=8, A=6, act=P, act_pitch=8, mean=P, mean_pitch=32,
-             std=P, std_pitch=32, z=P, z_pitch=288, B=17, H=2)
-    mlps = (_lib.ChainMlpBf16 * 2)(_lib.ChainMlpBf16(P, P, P, P, P, P, 256, 256), _lib.ChainMlpBf16(P, P, P, P, P, P, 288, 288))
-    pol = _lib.PolicyMlpBf16(P, P, P, P, P, P, 288, 256)
-    mlps_arg, pol_arg = mlps, pol
-    for k, v in edit.items():
-        if k == "mlp":
-            setattr(mlps[v[0]], v[1], v[2])
-        elif k == "policy":
-            setattr(pol, v[0], v[1])
-        elif k == "mlps":
-            mlps_arg = v
-        elif k == "policy_ptr":
-            pol_arg = v
-        else:
-            assert k in a, k
-            a[k] = v
-    return (a["z0"], a["z0_pitch"], a["eps"], a["eps_pitch"], mlps_arg, a["wc"], a["wc_row"], a["wb"], a["wb_row"], a["A"], pol_arg, a["act"],
-            a["act_pitch"], a["mean"], a["mean_pitch"], a["std"], a["std_pitch"], a["z"], a["z_pitch"], a["B"], a["H"], None)
-
-
-REFUSALS = (                                           # (the edit, a piece of the message)
-    (dict(B=-1), "negative size"), (dict(H=-1), "negative size"),
-    (dict(z0=None), "null pointer"), (dict(wc=None), "null pointer"), (dict(wb=None), "null pointer"), (dict(act=None), "null pointer"),
-    (dict(mlps=None), "null pointer"), (dict(policy_ptr=None), "null pointer"),
-    (dict(eps=None), "null pointer"), (dict(mean=None), "null pointer"), (dict(std=None), "null pointer"), (dict(z=None), "null pointer"),
-    (dict(mlp=(0, "w2", None)), "z1_prior: null operand"), (dict(policy=("b2", None)), "policy: null operand"),
-    (dict(mlp=(0, "k1", 288)), "z1_prior: the first layer's K is 288, 256 is built"),
-    (dict(mlp=(1, "k1", 256)), "z2_prior: the first layer's K is 256, 288 is built"),
-    (dict(policy=("width", 192)), "hidden width 192"), (dict(policy=("width", 64)), "hidden width 64"),
-    (dict(policy=("width", 1152)), "hidden width 1152"), (dict(A=0), "action width 0"), (dict(A=9), "action width 9"),
-    (dict(z0_pitch=287), "a pitch is below its row (z0 288, act A)"), (dict(act_pitch=5), "a pitch is below its row (z0 288, act A)"),
-    (dict(eps_pitch=287), "a pitch is below its row"), (dict(mean_pitch=31), "a pitch is below its row"),
-    (dict(std_pitch=31), "a pitch is below its row"), (dict(z_pitch=287), "a pitch is below its row"),
-    (dict(z0_pitch=290), "z0 must be 16-byte aligned, its pitch a multiple of 4 floats"),
-    (dict(z0=P + 4), "z0 must be 16-byte aligned"),
-    (dict(wc_row=4), "wc_row and wb_row"), (dict(wb_row=10), "wc_row and wb_row"),
-    (dict(wc=P + 8), "wc and wb must be 16-byte aligned"), (dict(wb=P + 4), "wc and wb must be 16-byte aligned"),
-    (dict(mlp=(1, "w1_row", 280)), "z2_prior: w1_row"), (dict(mlp=(1, "w1_row", 292)), "z2_prior: w1_row"),
-    (dict(mlp=(0, "w3", P + 2)), "z1_prior: the weights must be 16-byte aligned"),
-    (dict(policy=("w1_row", 280)), "policy: w1_row"), (dict(policy=("w1_row", 292)), "policy: w1_row"),
-    (dict(policy=("w1", P + 2)), "policy: the weights must be 16-byte aligned"),
-    (dict(policy=("w3", P + 8)), "policy: the weights must be 16-byte aligned"),
-)
+    """The 22 arguments of a valid call (B 17, H 2, A 6, W 256) on fake addresses, with `edit` applied (chain_refusals.args)."""
+    return CR.args(_lib, NAME, **edit)
 
 
 def check_refusals(_lib):
     """Every case of REFUSALS returns a negative value with its message, and the no-ops return 0 looking at no pointer."""
-    L = _lib.lib()
-    fn = getattr(L, NAME)
-    for edit, text in REFUSALS:
-        rc = fn(*abi_args(_lib, **edit))
-        msg = L.s2p_last_error().decode()
-        assert rc < 0 and NAME in msg and text in msg, (edit, rc, msg)
-    nothing = (None, 0, None, 0, None, None, 0, None, 0, 0, None, None, 0, None, 0, None, 0, None, 0)
-    assert fn(*nothing, 0, 5, None) == 0 and fn(*nothing, 5, 0, None) == 0
-    return len(REFUSALS)
+    return CR.check(_lib, NAME)
