@@ -454,6 +454,40 @@ int s2p_imagine_chain_fwd_bf16(const float* z0, int z0_pitch, const float* eps, 
                                const float* wc, int wc_row, const float* wb, int wb_row, int A, const s2p_policy_mlp_bf16* policy,
                                float* act, int act_pitch, float* mean, int mean_pitch, float* std, int std_pitch, float* z, int z_pitch,
                                int B, int H, void* stream);
+/* The posterior chain under grad in bf16 compute (SPEC.md N3p; csrc/gauss_chain_bf16.hip): ordinary mixed precision for
+ * s2p_posterior_chain_fwd_save / s2p_posterior_chain_bwd, ONE launch each.  Every tensor the caller sees, the state and the
+ * gradients stay fp32; only the chain's own GEMMs multiply bf16 operands on v_mfma_f32_16x16x32_bf16.
+ * s2p_posterior_chain_fwd_save_bf16: the arguments of s2p_posterior_chain_fwd_save with the mlps of s2p_posterior_chain_fwd_bf16.
+ *   mean, std and z are BITWISE those of s2p_posterior_chain_fwd_bf16; the 13 state buffers get the UNROUNDED fp32 values (h1, h2
+ *   after LeakyReLU, raw = acc + bias, xz[t-1] = z1(t) | z2(t-1)) in the fp32 form's layout, rows >= B never stored.  No-ops and
+ *   refusals: those of s2p_posterior_chain_fwd_bf16, then the state refusals of the fp32 save form.
+ * s2p_chain_mlp_bwd_bf16: w1t [k1][w1t_row >= 256], w2t [256][256], w3t [256][2 D] as bf16 bits, the TRANSPOSES of the forward's
+ *   bf16 packs (the same rounded values), 16-byte aligned, w1t_row in bf16 elements and a multiple of 8.
+ * s2p_posterior_chain_bwd_bf16: the arguments, no-ops (B == 0, T < 2) and refusals of s2p_posterior_chain_bwd.  A head backward is
+ *   the fp32 one on fp32 inputs.  An input gradient is acc = sum_n bf16(g[m][n]) * bf16(wt[k][n]), g = draw for a last layer, else
+ *   dh * act'(h) (one fp32 multiply, rounded where it is written to LDS), fp32 sums with n ascending in steps of 32, the reduction
+ *   (512, 256 or 64) never split, then acc + 0, or (acc + dx_old) + 0 for the accumulating one.  The carried gradient at z1(t) |
+ *   z2(t-1) stays fp32.  The seven buffers of `grads` are written in fp32, unrounded, and nothing else is.
+ * s2p_chain_pack_bf16: ONE launch makes bf16 packs of `n_jobs` fp32 matrices.  A job reads src [rows][cols] (row pitch src_pitch
+ *   floats; the pointer may stand at a column group of a wider matrix) and writes dst [rows][dst_pitch] and / or its transpose
+ *   dst_t [cols][dst_t_pitch] as bf16 bits (pitches in elements; a NULL output is not made, one of the two is required).  Rounding
+ *   is to nearest even, bit for bit a cast of the fp32 value for every finite value, +-0 and +-inf; NaN stays NaN.  Elements past
+ *   `cols` / `rows` of a pitch are not written.  n_jobs == 0 and a job with rows == 0 or cols == 0 are no-ops that look at no
+ *   pointer; a negative size, a NULL jobs / src, no output, or a pitch below its row are refused before the launch.
+ * A row's values do not depend on B; two identical calls are bitwise equal.                                                      */
+typedef struct { const uint16_t* w1t; const uint16_t* w2t; const uint16_t* w3t; int32_t k1, w1t_row; } s2p_chain_mlp_bwd_bf16;
+typedef struct {
+  const float* src; uint16_t* dst; uint16_t* dst_t;
+  int32_t rows, cols, src_pitch, dst_pitch, dst_t_pitch;
+} s2p_bf16_pack_job;
+int s2p_posterior_chain_fwd_save_bf16(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
+                                      int eps_pitch, const s2p_chain_mlp_bf16* mlps, float* mean, int mean_pitch, float* std,
+                                      int std_pitch, float* z, int z_pitch, const s2p_chain_state* state, int B, int T,
+                                      void* stream);
+int s2p_posterior_chain_bwd_bf16(const float* eps, int eps_pitch, const float* dmean, int dmean_pitch, const float* dstd,
+                                 int dstd_pitch, const float* dz, int dz_pitch, const s2p_chain_mlp_bwd_bf16* mlps,
+                                 const s2p_chain_state* state, const s2p_chain_grads* grads, int B, int T, void* stream);
+int s2p_chain_pack_bf16(const s2p_bf16_pack_job* jobs, int n_jobs, void* stream);
 /* KL(p || q) of diagonal Gaussians, value and all four gradients in one pass (slac/utils.py:66-69):
  *   loss[0] += scale * sum 0.5 ((sp/sq)^2 + ((mp-mq)/sq)^2 - 1 - log (sp/sq)^2),  d* = scale * dKL/d*  (overwritten; any NULL).
  * p: [B][T][p_pitch >= D].  const_first == 0: q is [B][T][q_pitch]; const_first != 0: q is [B][T-1][q_pitch] and holds the

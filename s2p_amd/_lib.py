@@ -88,6 +88,17 @@ class ChainMlpBwd(ctypes.Structure):
     _fields_ = [("w1t", c_void_p), ("w2t", c_void_p), ("w3t", c_void_p), ("k1", ctypes.c_int32), ("w1t_row", ctypes.c_int32)]
 
 
+class ChainMlpBwdBf16(ctypes.Structure):
+    """s2p_chain_mlp_bwd_bf16: ChainMlpBwd with the three transposed packs as bf16 bits (w1t_row in bf16 elements)."""
+    _fields_ = ChainMlpBwd._fields_
+
+
+class Bf16PackJob(ctypes.Structure):
+    """s2p_bf16_pack_job: fp32 src [rows][cols] -> bf16 dst [rows][dst_pitch] and / or its transpose dst_t [cols][dst_t_pitch]."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("dst_t", c_void_p), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
+                ("src_pitch", ctypes.c_int32), ("dst_pitch", ctypes.c_int32), ("dst_t_pitch", ctypes.c_int32)]
+
+
 class PolicyMlp(ctypes.Structure):
     """s2p_policy_mlp: the packed layers of a two-hidden-layer tanh policy for the closed-loop chain (w3 / b3: the last_fc rows first)."""
     _fields_ = [("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("w3", c_void_p), ("b3", c_void_p),
@@ -171,6 +182,11 @@ SIGNATURES = {
                               _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
     "s2p_imagine_chain_fwd_bf16": [_P, c_int, _P, c_int, ctypes.POINTER(ChainMlpBf16), _P, c_int, _P, c_int, c_int,
                                    ctypes.POINTER(PolicyMlpBf16), _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P],
+    "s2p_posterior_chain_fwd_save_bf16": [_P, c_int, _P, _P, _P, c_int, ctypes.POINTER(ChainMlpBf16), _P, c_int, _P, c_int, _P, c_int,
+                                          ctypes.POINTER(ChainState), c_int, c_int, _P],
+    "s2p_posterior_chain_bwd_bf16": [_P, c_int, _P, c_int, _P, c_int, _P, c_int, ctypes.POINTER(ChainMlpBwdBf16),
+                                     ctypes.POINTER(ChainState), ctypes.POINTER(ChainGrads), c_int, c_int, _P],
+    "s2p_chain_pack_bf16": [ctypes.POINTER(Bf16PackJob), c_int, _P],
     "s2p_linear_add_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int, _P, _P,
                            c_int, c_int, _P, c_int, _P],
     "s2p_gauss_kl": [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int, _P, _P, c_int, _P],

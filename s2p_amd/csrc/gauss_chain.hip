@@ -534,25 +534,8 @@ __global__ __launch_bounds__(CH_THREADS) void posterior_chain_bwd_kernel(const C
     __syncthreads();
   }
 }
-// ---- host side: the operand checks and the launch frame are gauss_chain_common.h's ----------------------------------------------------
-// The transposed packs of the backward, read by chain_take_mlps: all three given and aligned, a w1t row holds the 256 hidden columns.
-template <>
-struct ChainMlpFields<s2p_chain_mlp_bwd> {
-  using Unit = ChainRowUnit<float>;
-  static constexpr const char *row_name = "w1t_row", *least_name = "256";
-  static bool given(const s2p_chain_mlp_bwd& m) { return m.w1t && m.w2t && m.w3t; }
-  static bool aligned(const s2p_chain_mlp_bwd& m) { return s2p_al16(m.w1t) && s2p_al16(m.w2t) && s2p_al16(m.w3t); }
-  static int row(const s2p_chain_mlp_bwd& m) { return m.w1t_row; }
-  static int least(const s2p_chain_mlp_bwd&) { return CH_HID; }
-};
-
-// every buffer of `n` is given and 16-byte aligned
-bool chain_bufs_ok(float* const* p, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!p[i] || !s2p_al16(p[i])) return false;
-  return true;
-}
 }  // namespace
+// ---- host side: the operand checks and the launch frame are gauss_chain_common.h's ----------------------------------------------------
 
 extern "C" int s2p_posterior_chain_fwd_save(const float* feat, int feat_pitch, const float* ra, const float* rb, const float* eps,
                                             int eps_pitch, const s2p_chain_mlp* mlps, float* mean, int mean_pitch, float* std,
@@ -563,10 +546,7 @@ extern "C" int s2p_posterior_chain_fwd_save(const float* feat, int feat_pitch, c
   ChainArgs a{};
   if (int e = posterior_chain_take(who, feat, feat_pitch, ra, rb, eps, eps_pitch, mlps, mean, mean_pitch, std, std_pitch, z, z_pitch, B, T, a))
     return e;
-  S2P_REQUIRE(state, "%s: null pointer (state is required)", who);
-  float* const bufs[13] = {state->a0_h1, state->a0_h2, state->a0_raw, state->b0_h1, state->b0_h2, state->b0_raw, state->h1a,
-                           state->h2a, state->rawa, state->h1b, state->h2b, state->rawb, state->xz};
-  S2P_REQUIRE(chain_bufs_ok(bufs, T > 1 ? 13 : 6), "%s: state: a buffer is NULL or not 16-byte aligned", who);
+  if (int e = chain_check_state(who, state, T)) return e;
   return chain_launch("posterior_chain_save_kernel", posterior_chain_save_kernel, B, stream, a, *state);
 }
 
@@ -575,18 +555,9 @@ extern "C" int s2p_posterior_chain_bwd(const float* eps, int eps_pitch, const fl
                                        const s2p_chain_state* state, const s2p_chain_grads* grads, int B, int T, void* stream) {
   const char* who = "s2p_posterior_chain_bwd";
   if (int e = chain_sizes(who, B, T, 2); e <= 0) return e;    // (T == 1: the chain has no step)
-  S2P_REQUIRE(eps && dmean && dstd && dz && mlps && state && grads,
-              "%s: null pointer (eps, dmean, dstd, dz, mlps, state and grads are required)", who);
-  S2P_REQUIRE(eps_pitch >= CH_Z && dz_pitch >= CH_Z && dmean_pitch >= CH_Z1 && dstd_pitch >= CH_Z1,
-              "%s: a pitch is below its row (eps 288, dz 288, dmean 32, dstd 32)", who);
   ChainBwdArgs a{};
-  if (int e = chain_take_mlps(who, mlps, CH_POSTERIOR_HEADS + 2, 2, a)) return e;
-  float* const sb[6] = {state->h1a, state->h2a, state->rawa, state->h1b, state->h2b, state->rawb};
-  S2P_REQUIRE(chain_bufs_ok(sb, 6), "%s: state: a chain buffer is NULL or not 16-byte aligned", who);
-  float* const gb[7] = {grads->drawa, grads->dh2a, grads->dh1a, grads->drawb, grads->dh2b, grads->dh1b, grads->dxz};
-  S2P_REQUIRE(chain_bufs_ok(gb, 7), "%s: grads: a buffer is NULL or not 16-byte aligned", who);
-  a.eps = eps; a.eps_pitch = eps_pitch; a.dmean = dmean; a.dmean_pitch = dmean_pitch; a.dstd = dstd; a.dstd_pitch = dstd_pitch; a.dz = dz;
-  a.dz_pitch = dz_pitch; a.B = B; a.T = T; a.s = *state; a.g = *grads;
+  if (int e = posterior_bwd_take(who, eps, eps_pitch, dmean, dmean_pitch, dstd, dstd_pitch, dz, dz_pitch, mlps, state, grads, B, T, a))
+    return e;
   return chain_launch("posterior_chain_bwd_kernel", posterior_chain_bwd_kernel, B, stream, a);
 }
 

@@ -1,5 +1,5 @@
 // What the fused SLAC latent chains share between their two compute modes: gauss_chain.hip (fp32; SPEC.md N3h, N3i, N3j, N3k) and
-// gauss_chain_bf16.hip (bf16 operands, fp32 sums; N3m, N3n).  Both are one design -- a workgroup owns 16 batch rows and every output column
+// gauss_chain_bf16.hip (bf16 operands, fp32 sums; N3m, N3n, N3p).  Both are one design -- a workgroup owns 16 batch rows and every output column
 // of every layer, workgroup barriers only (the head of gauss_chain.hip has the reasoning) -- and differ in how a LAYER multiplies.  A file
 // keeps its layers, its kernels and its entry points and names the layers in a MODE type (ChainF32, ChainBf16):
 //   Args, Mlp, Elem            the kernel-argument struct, the host struct of one MLP's operands, the element of the LDS activation tiles
@@ -177,7 +177,7 @@ template <> struct ChainRowUnit<uint16_t> { static constexpr int mult = 8; stati
 template <typename S> using ChainRowOf = ChainRowUnit<std::remove_cv_t<std::remove_pointer_t<decltype(S::w1)>>>;
 
 // How chain_take_mlps reads a host struct of one MLP's operands: s2p_chain_mlp and s2p_chain_mlp_bf16 here, the transposed packs of
-// s2p_chain_mlp_bwd in gauss_chain.hip.
+// the two backwards below.
 template <typename Mlp>
 struct ChainMlpFields {
   using Unit = ChainRowOf<Mlp>;
@@ -188,7 +188,21 @@ struct ChainMlpFields {
   static int least(const Mlp& m) { return m.k1; }
 };
 
-// Checks `n` host structs against `spec` and copies them into a.m.  0, or S2P_REQUIRE's value with the error text set.
+// The transposed packs of the backward (s2p_chain_mlp_bwd: fp32; s2p_chain_mlp_bwd_bf16: bf16 bits): all three given and aligned, a
+// w1t row holds the 256 hidden columns.
+template <typename Mlp, typename W>
+struct ChainMlpBwdFields {
+  using Unit = ChainRowUnit<W>;
+  static constexpr const char *row_name = "w1t_row", *least_name = "256";
+  static bool given(const Mlp& m) { return m.w1t && m.w2t && m.w3t; }
+  static bool aligned(const Mlp& m) { return s2p_al16(m.w1t) && s2p_al16(m.w2t) && s2p_al16(m.w3t); }
+  static int row(const Mlp& m) { return m.w1t_row; }
+  static int least(const Mlp&) { return CH_HID; }
+};
+template <> struct ChainMlpFields<s2p_chain_mlp_bwd> : ChainMlpBwdFields<s2p_chain_mlp_bwd, float> {};
+template <> struct ChainMlpFields<s2p_chain_mlp_bwd_bf16> : ChainMlpBwdFields<s2p_chain_mlp_bwd_bf16, uint16_t> {};
+
+// Checks `n` host structs against `spec` and copies them into a.m. 0, or S2P_REQUIRE's value with the error text set.
 template <typename Mlp, typename Args>
 int chain_take_mlps(const char* who, const Mlp* mlps, const ChainHeadSpec* spec, int n, Args& a) {
   using F = ChainMlpFields<Mlp>;
@@ -280,6 +294,42 @@ int imagine_chain_take(const char* who, const float* z0, int z0_pitch, const flo
   if (int e = chain_check_policy(who, *policy)) return e;
   g.p = *policy; g.z0 = z0; g.z0_pitch = z0_pitch; g.wc = wc; g.wc_row = wc_row; g.wb = wb; g.wb_row = wb_row; g.A = A; g.act = act;
   g.act_pitch = act_pitch;
+  return 0;
+}
+
+// every buffer of `n` is given and 16-byte aligned
+inline bool chain_bufs_ok(float* const* p, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!p[i] || !s2p_al16(p[i])) return false;
+  return true;
+}
+
+// The state buffers of the save forms of the posterior chain (fp32 and bf16 compute): the six of t = 0 and, with T > 1, the chain's seven
+inline int chain_check_state(const char* who, const s2p_chain_state* state, int T) {
+  S2P_REQUIRE(state, "%s: null pointer (state is required)", who);
+  float* const bufs[13] = {state->a0_h1, state->a0_h2, state->a0_raw, state->b0_h1, state->b0_h2, state->b0_raw, state->h1a,
+                           state->h2a, state->rawa, state->h1b, state->h2b, state->rawb, state->xz};
+  S2P_REQUIRE(chain_bufs_ok(bufs, T > 1 ? 13 : 6), "%s: state: a buffer is NULL or not 16-byte aligned", who);
+  return 0;
+}
+
+// The operand checks of the posterior chain's backward, for both compute modes (Mlp: s2p_chain_mlp_bwd or s2p_chain_mlp_bwd_bf16).
+// 0 with `a` filled, or S2P_REQUIRE's value with the error text set.
+template <typename Mlp, typename Args>
+int posterior_bwd_take(const char* who, const float* eps, int eps_pitch, const float* dmean, int dmean_pitch, const float* dstd,
+                       int dstd_pitch, const float* dz, int dz_pitch, const Mlp* mlps, const s2p_chain_state* state,
+                       const s2p_chain_grads* grads, int B, int T, Args& a) {
+  S2P_REQUIRE(eps && dmean && dstd && dz && mlps && state && grads,
+              "%s: null pointer (eps, dmean, dstd, dz, mlps, state and grads are required)", who);
+  S2P_REQUIRE(eps_pitch >= CH_Z && dz_pitch >= CH_Z && dmean_pitch >= CH_Z1 && dstd_pitch >= CH_Z1,
+              "%s: a pitch is below its row (eps 288, dz 288, dmean 32, dstd 32)", who);
+  if (int e = chain_take_mlps(who, mlps, CH_POSTERIOR_HEADS + 2, 2, a)) return e;
+  float* const sb[6] = {state->h1a, state->h2a, state->rawa, state->h1b, state->h2b, state->rawb};
+  S2P_REQUIRE(chain_bufs_ok(sb, 6), "%s: state: a chain buffer is NULL or not 16-byte aligned", who);
+  float* const gb[7] = {grads->drawa, grads->dh2a, grads->dh1a, grads->drawb, grads->dh2b, grads->dh1b, grads->dxz};
+  S2P_REQUIRE(chain_bufs_ok(gb, 7), "%s: grads: a buffer is NULL or not 16-byte aligned", who);
+  a.eps = eps; a.eps_pitch = eps_pitch; a.dmean = dmean; a.dmean_pitch = dmean_pitch; a.dstd = dstd; a.dstd_pitch = dstd_pitch; a.dz = dz;
+  a.dz_pitch = dz_pitch; a.B = B; a.T = T; a.s = *state; a.g = *grads;
   return 0;
 }
 

@@ -882,6 +882,52 @@ def posterior_chain_bwd(eps, dmean, dstd, dz, mlps, state, grads):
                                         ctypes.byref(_lib.ChainGrads(*_dense(grads))), B, T, stream()), "s2p_posterior_chain_bwd")
 
 
+def posterior_chain_fwd_save_bf16(feat0, ra, rb, eps, mlps, mean, std, z, state):
+    """posterior_chain_fwd_save in bf16 compute (s2p_posterior_chain_fwd_save_bf16; SPEC.md N3p): mean, std, z bitwise those of
+    posterior_chain_fwd_bf16, `state` filled with the unrounded fp32 values; mlps: four chain_mlp_bf16() structs."""
+    (fp, fs), arr, tail = _chain_operands(feat0, eps, mlps, 4, mean, std, z, terms=(ra, rb), steps=eps.shape[1] - 1,
+                                          mlp_type=_lib.ChainMlpBf16)
+    check(lib().s2p_posterior_chain_fwd_save_bf16(fp, fs, ptr(ra), ptr(rb), ptr(eps), eps.stride(1), arr, *tail[:6], ctypes.byref(state),
+                                                  *tail[6:]), "s2p_posterior_chain_fwd_save_bf16")
+
+
+def chain_mlp_bwd_bf16(pk):
+    """The s2p_chain_mlp_bwd_bf16 of a Gaussian.packed_bf16_grad() dict: the transposes of its three bf16 packs."""
+    w1t = pk["w1t"]
+    for w in (w1t, pk["w2t"], pk["w3t"]):
+        if w.dtype != torch.bfloat16 or not w.is_contiguous():
+            raise ValueError("the weight operands of a bf16 chain are contiguous torch.bfloat16 packs")
+    return _lib.ChainMlpBwdBf16(ptr(w1t), ptr(pk["w2t"]), ptr(pk["w3t"]), w1t.shape[0], w1t.shape[1])
+
+
+def posterior_chain_bwd_bf16(eps, dmean, dstd, dz, mlps, state, grads):
+    """posterior_chain_bwd in bf16 compute (s2p_posterior_chain_bwd_bf16; SPEC.md N3p): the same fp32 tensors, mlps: the
+    chain_mlp_bwd_bf16() of z1_posterior and z2_prior."""
+    B, T = eps.shape[:2]
+    _chain_views(B, T, eps, dmean, dstd, dz)
+    check(lib().s2p_posterior_chain_bwd_bf16(ptr(eps), eps.stride(1), ptr(dmean), dmean.stride(1), ptr(dstd), dstd.stride(1), ptr(dz),
+                                             dz.stride(1), (_lib.ChainMlpBwdBf16 * 2)(*mlps), ctypes.byref(state),
+                                             ctypes.byref(_lib.ChainGrads(*_dense(grads))), B, T, stream()),
+          "s2p_posterior_chain_bwd_bf16")
+
+
+def chain_pack_bf16(jobs):
+    """bf16 packs of fp32 matrices in ONE launch (s2p_chain_pack_bf16).  jobs: (src, dst, dst_t) with src a 2-D fp32 view with unit
+    stride in its last dimension (a column slice of a wider matrix is read in place), dst [rows, >= cols] and dst_t [cols, >= rows]
+    torch.bfloat16 views of the same kind, either None: dst = src rounded to nearest even, dst_t its transpose.  Columns past the
+    shape of src are not written."""
+    arr = (_lib.Bf16PackJob * len(jobs))()
+    for job, (src, dst, dst_t) in zip(arr, jobs):
+        rows, cols = src.shape
+        for t, shape in ((dst, (rows, cols)), (dst_t, (cols, rows))):
+            if t is not None and (t.dim() != 2 or t.dtype != torch.bfloat16 or tuple(t.shape) != shape or (shape[1] > 1 and t.stride(1) != 1)):
+                raise ValueError("a pack is a 2-D torch.bfloat16 view of the shape of src (dst) or of its transpose (dst_t)")
+        pitch = lambda t: 0 if t is None else t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+        job.src, job.src_pitch = _view2(src)
+        job.dst, job.dst_t, job.rows, job.cols, job.dst_pitch, job.dst_t_pitch = ptr(dst), ptr(dst_t), rows, cols, pitch(dst), pitch(dst_t)
+    check(lib().s2p_chain_pack_bf16(arr, len(jobs), stream()), "s2p_chain_pack_bf16")
+
+
 def gauss_head_bwd(raw, D, draw, eps=None, dmean=None, dstd=None, dz=None, dz2=None):
     """draw[:, :2D] = [dmean + dz + dz2 | (dstd + (dz + dz2) * eps) * sigmoid(raw_std)]."""
     views = [_view2(t) for t in (raw, eps, dmean, dstd, dz, dz2, draw)]

@@ -235,6 +235,7 @@ class Gaussian(nn.Module):
         self._pack_key, self._packed = None, None
         self._cols_key, self._cols = None, {}
         self._bf16_key, self._bf16 = None, {}
+        self._bf16g_key, self._bf16g = None, None
 
     def layer_params(self):
         out = []
@@ -288,6 +289,33 @@ class Gaussian(nn.Module):
                 bf = lambda t: t.to(torch.bfloat16).contiguous()
                 self._bf16[k1] = dict(w1=bf(w), b1=pk["b1"], w2=bf(w2), b2=pk["b2"], w3=bf(w3), b3=pk["b3"])
         return self._bf16[k1]
+
+    def packed_bf16_grad(self):
+        """The operands of the bf16-compute chain under grad (SPEC.md N3p), beside packed_bf16() and under its key rule: its w1 (the
+        first column group), w2, w3 and their transposes w1t [k1][256], w2t [256][256], w3t [256][2 D] -- the same rounded values --
+        made from the fp32 parameters in place by ONE launch (ops.chain_pack_bf16): under training the parameters change every step.
+        The biases are packed()'s fp32 ones."""
+        ps = self.layer_params()
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if key != self._bf16g_key:
+            pk = self.packed()
+            with torch.no_grad():
+                w1, _, w2, _, w3, _ = [p.detach() for p in ps]
+                if any(w.dtype != torch.float32 for w in (w1, w2, w3)):
+                    raise ValueError("the bf16 chain packs are made from fp32 parameters")
+                k1 = sum(b - a for a, b in self.groups[0])
+                if k1 % 8:
+                    raise ValueError("a bf16 chain operand has a multiple of 8 columns, not %d" % k1)
+                bf = lambda *shape: torch.empty(shape, dtype=torch.bfloat16, device=w1.device)
+                out = dict(w1=bf(HID, k1), w1t=bf(k1, HID), b1=pk["b1"], w2=bf(HID, HID), w2t=bf(HID, HID), b2=pk["b2"],
+                           w3=bf(self.N, HID), w3t=bf(HID, self.N), b3=pk["b3"])
+                jobs, o = [(w2, out["w2"], out["w2t"]), (w3, out["w3"], out["w3t"])], 0
+                for a, b in self.groups[0]:
+                    jobs.append((w1[:, a:b], out["w1"][:, o:o + b - a], out["w1t"][o:o + b - a]))
+                    o += b - a
+                ops.chain_pack_bf16(jobs)
+            self._bf16g_key, self._bf16g = key, out
+        return self._bf16g
 
     def packed_cols(self, lo, hi):
         """net.0.weight[:, lo:hi] as a GEMM operand of its own, [256][(hi - lo) padded to 4] with a zero pad, beside packed() and
@@ -424,6 +452,14 @@ def _chain_mlps_bf16(heads):
     return [ops.chain_mlp_bf16(g.packed_bf16()) for g in heads]
 
 
+def _chain_grad_compute(model):
+    """`model.chain_grad_compute`, read where a fused chain under grad is about to run: "fp32" or "bf16" (SPEC.md N3p)."""
+    mode = getattr(model, "chain_grad_compute", "fp32")
+    if mode not in ("fp32", "bf16"):
+        raise ValueError("chain_grad_compute is 'fp32' or 'bf16', not %r" % (mode,))
+    return mode
+
+
 class _PosteriorFn(torch.autograd.Function):
     """The reparameterised posterior chain (latent.py:250-281) as ONE autograd node over HIP launches.
     feat [B,T,256], action [B,T-1,A], noise [B,T,288] (keep: the caller's grad mode; activations are saved only then) -> z1_mean [B,T,32], z1_std [B,T,32], z [B,T,288] (z1 | z2).
@@ -432,7 +468,9 @@ class _PosteriorFn(torch.autograd.Function):
     feature / action gradients are batched launches after it.  `model.chain_form(keep)` names what the forward does with the chain
     itself: "layers" runs those 8 launches per step; "fused" / "fused_bf16" (`model.fused_chain`, no backward state kept) run it as
     one launch (SPEC.md N3h, bitwise the same; N3m, bf16 operands); "fused_save" (`model.fused_chain_grad`, state kept) as one launch
-    that also stores that state, with the 8 S sequential launches of the backward as one (SPEC.md N3k), bitwise the same again."""
+    that also stores that state, with the 8 S sequential launches of the backward as one (SPEC.md N3k), bitwise the same again.
+    With "fused_save", `model.chain_grad_compute == "bf16"` (SPEC.md N3p) gives those two launches bf16 operands: mixed precision, not
+    the same numbers; the state, every weight gradient and the t = 0 backward stay the fp32 launches on unrounded tensors."""
 
     @staticmethod
     def forward(ctx, feat, action, noise, model, keep, *params):
@@ -441,6 +479,9 @@ class _PosteriorFn(torch.autograd.Function):
         S = T - 1
         form = model.chain_form(keep)
         ctx.fused = form == "fused_save"                               # the backward follows what the forward did
+        ctx.bf16_packs = None                                          # SPEC.md N3p: the packs the forward multiplied with
+        if ctx.fused and _chain_grad_compute(model) == "bf16":
+            ctx.bf16_packs = [g.packed_bf16_grad() for g in model._chain_heads()]
         gs = gi1, gi2, g1, g2 = model._chain_heads()
         packs = pi1, pi2, p1, p2 = tuple(g.packed() for g in gs)
         z = _f32((B, T, Z1 + Z2), dev)
@@ -465,6 +506,9 @@ class _PosteriorFn(torch.autograd.Function):
             ops.posterior_chain_fwd(feat[:, 0], ra, rb, noise, _chain_mlps(packs), mean, std, z)
         elif form == "fused_bf16":                                     # SPEC.md N3m: the same launch count, bf16 operands
             ops.posterior_chain_fwd_bf16(feat[:, 0], ra, rb, noise, _chain_mlps_bf16(gs), mean, std, z)
+        elif form == "fused_save" and ctx.bf16_packs:                  # SPEC.md N3p: the same launch count, bf16 operands
+            ops.posterior_chain_fwd_save_bf16(feat[:, 0], ra, rb, noise, [ops.chain_mlp_bf16(p) for p in ctx.bf16_packs], mean, std, z,
+                                              ops.chain_state(a0, b0, chain + (xz,) if chain else None))
         elif form == "fused_save":                                     # one launch that also fills the state (SPEC.md N3k)
             ops.posterior_chain_fwd_save(feat[:, 0], ra, rb, noise, _chain_mlps(packs), mean, std, z,
                                          ops.chain_state(a0, b0, chain + (xz,) if chain else None))
@@ -517,7 +561,11 @@ class _PosteriorFn(torch.autograd.Function):
             drawa, dh2a, dh1a = _f32((S, B, g1.Npad), dev), _f32((S, B, HID), dev), _f32((S, B, HID), dev)
             drawb, dh2b, dh1b = _f32((S, B, g2.Npad), dev), _f32((S, B, HID), dev), _f32((S, B, HID), dev)
             steps = range(S, 0, -1)
-            if ctx.fused:                                              # the loop below as ONE launch (s2p_posterior_chain_bwd)
+            if ctx.fused and ctx.bf16_packs:                           # the loop below as ONE launch in bf16 compute (SPEC.md N3p)
+                ops.posterior_chain_bwd_bf16(noise, dmean, dstd, dz, [ops.chain_mlp_bwd_bf16(p) for p in ctx.bf16_packs[2:]],
+                                             ops.chain_state(a0, b0, sv[2:] + (xz,)), (drawa, dh2a, dh1a, drawb, dh2b, dh1b, dxz))
+                steps = ()
+            elif ctx.fused:                                            # the loop below as ONE launch (s2p_posterior_chain_bwd)
                 ops.posterior_chain_bwd(noise, dmean, dstd, dz, [ops.chain_mlp_bwd(p1), ops.chain_mlp_bwd(p2)],
                                         ops.chain_state(a0, b0, sv[2:] + (xz,)), (drawa, dh2a, dh1a, drawb, dh2b, dh1b, dxz))
                 steps = ()
@@ -657,6 +705,7 @@ class LatentModel(nn.Module):
         self.fused_chain = False                # True: a no-grad sample_posterior, predict and imagine run their chain as ONE launch (SPEC.md N3h-N3j)
         self.fused_chain_grad = False           # True: a grad-mode sample_posterior runs its chain as ONE launch forward, ONE backward (SPEC.md N3k)
         self.chain_compute = "fp32"             # "bf16": the fused no-grad chains of sample_posterior and predict multiply in bf16 (SPEC.md N3m; imagine: its `compute` keyword)
+        self.chain_grad_compute = "fp32"        # "bf16": with fused_chain_grad, the chain's forward and backward launches multiply in bf16 (SPEC.md N3p)
 
     @property
     def device(self):

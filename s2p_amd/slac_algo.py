@@ -90,7 +90,7 @@ class SlacAlgorithm:
     def __init__(self, state_shape, action_shape, action_repeat, device, seed, gamma=0.99, batch_size_sac=256, batch_size_latent=32,
                  buffer_size=10 ** 5, num_sequences=8, lr_sac=3e-4, lr_latent=1e-4, feature_dim=256, z1_dim=32, z2_dim=256,
                  hidden_units=(256, 256), tau=5e-3, image_size=100, use_seperate_buffer=False, dtype=torch.float32,
-                 frame_capacity=None, fused_chain=False, fused_chain_grad=False, chain_compute="fp32"):
+                 frame_capacity=None, fused_chain=False, fused_chain_grad=False, chain_compute="fp32", chain_grad_compute="fp32"):
         np.random.seed(seed)
         torch.manual_seed(seed)
         torch.cuda.manual_seed(seed)
@@ -105,6 +105,7 @@ class SlacAlgorithm:
         self.latent.fused_chain = bool(fused_chain)         # no-grad posterior chains (prepare_batch, the actor) as one launch each
         self.latent.fused_chain_grad = bool(fused_chain_grad)         # update_latent's chain: one launch forward, one backward
         self.latent.chain_compute = chain_compute            # "bf16": the fused no-grad chains multiply in bf16 (SPEC.md N3m)
+        self.latent.chain_grad_compute = chain_grad_compute  # "bf16": update_latent's fused chain multiplies in bf16 (SPEC.md N3p)
         self.target_entropy = -float(action_shape[0])
         self.optim_latent = Adam(self.latent.parameters(), lr=lr_latent)
         self.learning_steps_sac = 0
